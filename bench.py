@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the Frenet sampling-and-evaluation hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 Default workload (BASELINE.json configs[2], the largest single-GPU configuration): single agent, dense grid 19 x 51 x 52 =
 50 388 candidates x 31 samples (30-step horizon), 20 predicted obstacles (obstacle 0 a slow lead vehicle so that the cheapest
@@ -12,15 +12,15 @@ weights, SoA TrajectoryBundle materialised ("Mode B": every candidate's 14 plane
 
 A step = one plan step of the hot path: evaluation kernel + selection kernel + (N > 1) ONE RCCL all-gather of the per-GPU
 survivors, finished on the host (the winner is in host memory when the step ends).  The contract's timed region -- `value`,
-`ms_per_step` -- runs K such steps with the inputs resident in HBM.  A second region of K steps feeds every step a NEW ego
-state and NEW predictions from host buffers (fx_update_step: tables re-packed into the pinned staging block, one host-to-device
-copy, evaluation, result): `plan_step_p50_ms` / `value_with_upload` are that PCIe-inclusive plan step.  For N > 1 the global
-grid is N x 50 388 candidates (the velocity range is sampled N times denser) and each rank evaluates a contiguous shard:
-weak scaling.
+`ms_per_step` -- runs K such steps with the inputs resident in HBM.  For N > 1 the global grid is N x 50 388 candidates (the
+velocity range is sampled N times denser) and each rank evaluates a contiguous shard: weak scaling.
 
-In the same run, same JSON line (`north_star`): the target workload of BASELINE.json -- 1 005 100 candidates x 31 samples x
-20 obstacles, select-only (FP64-issue-bound: executed-work roofline) and 1 005 100 x 31 with the 3.49 GB bundle materialised
-(HBM-bound).
+A plain run does only that: set-up, preheat, W warm-up steps, the K timed steps, the line.  What needs runs of its own is
+measured with `--full` only: a second region of K steps that feeds every step a NEW ego state and NEW predictions from host
+buffers (fx_update_step: tables re-packed into the pinned staging block, one host-to-device copy, evaluation, result):
+`plan_step_p50_ms` / `value_with_upload` are that PCIe-inclusive plan step; and in the same run, same JSON line (`north_star`),
+the target workload of BASELINE.json -- 1 005 100 candidates x 31 samples x 20 obstacles, select-only (FP64-issue-bound:
+executed-work roofline) and 1 005 100 x 31 with the 3.49 GB bundle materialised (HBM-bound).
 
 `python bench.py --gpus N` without a launcher starts its own N ranks (torch.distributed.run on 127.0.0.1) before anything
 touches the GPU and relays rank 0's line.
@@ -37,7 +37,15 @@ Other workloads (parity-test configurations of BASELINE.json, measured on reques
 Timing.  Before the W warm-up steps the engine runs untimed steps for `--preheat` seconds (default 0.3; reported as
 `clock_preheat_s`): an idle GPU spends its first milliseconds at a lower clock and W = 5 steps are half a millisecond.  The
 K timed steps carry no instrumentation; the kernel durations of `roofline` come from an instrumented repeat of the same K
-steps (HIP events attached to every evaluation launch), because an instrumented launch costs 6 - 9 us of host time.
+steps (HIP events attached to every evaluation launch), because an instrumented launch costs 6 - 9 us of host time
+(`--full`).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed -- the arrays a caller of that path
+receives -- as DIR/<name>.npy (float64; flag words and indices are exact in float64): the winner record, every candidate's
+cost and flag word, the raw partial costs, and the planes of a fixed seeded sample of candidates plus the winner (the whole
+bundle of config 3 is 175 MB).  The inputs are seeded, so two builds run with the same arguments can be compared array by
+array.  Rank 0 writes: with several ranks the candidate arrays are rank 0's shard, the winner record leads with the global
+winner.
 
 Prints ONE JSON line (rank 0).  `value` = candidates evaluated by all ranks / wall time of the K timed steps.
 """
@@ -153,6 +161,61 @@ def make_workload(args, world, grid=GRID, n_obst=None, select_only=None):
                                  write_bundle=not select_only, write_costmap=not select_only,
                                  draw_traj_set=False, kinematic_debug=False,
                                  hull_builder=build_obstacle_hulls if n_obst else None)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 2048             # candidates whose planes --dump-outputs writes (fixed seed)
+RESULT_FIELDS = ("best_index", "best_cost", "n_returned", "n_feasible", "n_infeasible", "n_collisions", "feasible_percentage")
+
+
+def result_record(res):
+    """One step result (dict or FxResult view) as floats in RESULT_FIELDS order (the global winner first with several ranks)."""
+    return [float(res.get("global_best_index", res["best_index"])), float(res.get("global_best_cost", res["best_cost"]))] + \
+           [float(res[k]) for k in RESULT_FIELDS]
+
+
+def sample_index(n, k, best=-1):
+    """A fixed seeded sample of k of n candidates, sorted, with the winner added."""
+    idx = np.random.default_rng(20240601).choice(n, min(n, k), replace=False)
+    return np.union1d(idx, np.array([best] if best >= 0 else [], dtype=idx.dtype))
+
+
+def engine_outputs(eng, inp, res, agent=0):
+    """What one agent's step left on the device for its caller: costs and flag words of every candidate, the raw partial
+    costs, and the planes [n, 14, S] of a seeded sample of candidates and the winner (when the bundle is materialised)."""
+    from frenetix_motion_planner_amd import _abi
+    cost, flags = eng.costs(agent)
+    out = {"result": result_record(res), "reason_hist": res["reason_hist"], "cost": cost, "flags": flags}
+    if inp.write_costmap and len(inp.cost_names):
+        out["costmap"] = eng.costmap(agent)
+    if inp.write_bundle:
+        idx = sample_index(inp.n_candidates, DUMP_SAMPLE, int(res["best_index"]))
+        out["bundle_sample_index"] = idx
+        out["bundle_sample"] = np.stack([eng.plane(p, agent)[:, idx] for p in range(_abi.FX_NUM_PLANES)]).transpose(2, 0, 1)
+    return out
+
+
+def stress_outputs(eng, agents, res, surv):
+    """Config 5: every agent's result record, the gathered per-agent top-k survivors, and the costs and flag words of a seeded
+    sample of each agent's candidates (all of them would be 26 MB per 32 agents and array)."""
+    idx = sample_index(agents[0].n_candidates, 4 * DUMP_SAMPLE)
+    cf = [eng.costs(a) for a in range(len(agents))]
+    out = {"result": [result_record(r) for r in res], "cost_sample": [c[idx] for c, _ in cf],
+           "flags_sample": [f[idx] for _, f in cf], "sample_index": idx}
+    if surv is not None:
+        out["survivor_cost"], out["survivor_index"] = surv
+    return out
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: DIR/<name>.npy, float64."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
 
 
 def _host_threads():
@@ -401,6 +464,11 @@ def main():
     ap.add_argument("--preheat", type=float, default=0.3,
                     help="seconds of untimed steps before the W warm-up steps (clock ramp of an idle GPU; 0 = none)")
     ap.add_argument("--dry-launch", action="store_true", help="CPU-only check of the multi-rank launch path (gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: kernel times and rooflines, the host-fed plan step, the "
+                         "north-star workloads, the CPU baseline, the multi-rank agent-sharding showcase, config 1's C++-style step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
     if args.timing_every <= 0:
         args.timing_every = 1 if args.steps < 64 else 8
@@ -484,6 +552,61 @@ def main():
             gc.enable()
     if os.environ.get("FX_BENCH_LAT") and rank == 0:   # the K host latencies themselves (microseconds), for looking at outliers
         print("step latencies us:", " ".join(f"{x * 1e6:.1f}" for x in lat), file=sys.stderr)
+    winner = {"index": int(res.get("global_best_index", res["best_index"])),
+              "cost": float(res.get("global_best_cost", res["best_cost"])), "n_feasible_local": int(res["n_feasible"]),
+              "n_collisions": int(res["n_collisions"])}
+    dump_error = None
+    if args.dump_outputs and rank == 0:   # (`res` views the engine's result buffer: read before any further step)
+        try:
+            dump_outputs(args.dump_outputs, engine_outputs(eng, inp, res))
+        except Exception as e:   # raised once every rank knows (below): no peer is left waiting inside a collective
+            dump_error = e
+    rank_ms = [elapsed / args.steps * 1e3]
+    if world > 1:
+        # every rank's time and whether rank 0's dump failed, in one all-gather
+        t = torch.tensor([elapsed, float(dump_error is not None)], dtype=torch.float64, device="cuda")
+        allr = torch.empty(2 * world, dtype=torch.float64, device="cuda")
+        dist.all_gather_into_tensor(allr, t)
+        allr = allr.cpu().view(world, 2)
+        rank_ms = [float(x) / args.steps * 1e3 for x in allr[:, 0].tolist()]
+        elapsed = float(allr[:, 0].max().item())   # the contract's time: MAX over the ranks
+        if allr[:, 1].any() and dump_error is None:
+            dist.destroy_process_group()
+            sys.exit("bench.py: --dump-outputs failed on rank 0")
+    if dump_error is not None:
+        if world > 1:
+            dist.destroy_process_group()
+        raise dump_error
+    ms_per_step = elapsed / args.steps * 1e3
+    line = {
+        "metric": "candidate trajectories/sec (30-step horizon)",
+        "value": C_global * args.steps / elapsed, "unit": "trajectories/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "clock_preheat_s": args.preheat,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"BASELINE {args.workload}: single agent, {C_local} candidates/GPU x {S} samples "
+                               f"({GRID[0]}x{GRID[1]}x{GRID[2] + 1} grid per GPU), "
+                               f"{'20 predicted obstacles (prediction cost + OBB collision)' if n_obst else 'no obstacles'}, "
+                               f"{'select-only (Mode A)' if args.select_only else 'SoA TrajectoryBundle materialised (Mode B)'}",
+                   "candidates_global": C_global, "candidates_per_gpu": C_local, "samples": S,
+                   "reference_knots": int(inp.coordinate_system.ref_pos.shape[0]), "obstacles": n_obst,
+                   "parallelism": f"candidate-shard x{world}, all-gather top-{args.topk}" if world > 1 else "single GPU",
+                   "exchange": exchange_note},
+        # how stable the timed region was: K steps are a few milliseconds of wall time
+        "ms_per_step_min": float(np.min(lat) * 1e3), "ms_per_step_stdev": float(np.std(lat) * 1e3),
+        "steps_timed_wall_ms": elapsed * 1e3,
+        "resident_step_p50_ms": float(np.percentile(lat, 50) * 1e3), "resident_step_p95_ms": float(np.percentile(lat, 95) * 1e3),
+        "ms_per_step_rank_min": min(rank_ms), "ms_per_step_rank_max": max(rank_ms), "ms_per_step_ranks": rank_ms,
+        "winner": winner,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        eng.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # Kernel durations: the same K steps once more, now with HIP events attached to EVERY evaluation launch (an instrumented
     # launch costs 6 - 9 us of host time, which has no place in `value`; the events live in a ring and are read afterwards)
     eng.set_timing(args.timing, every=1)
@@ -494,16 +617,6 @@ def main():
     evalk, kern = eng.kernel_times(n_timed)
     obstk = eng.obstacle_kernel_times(n_timed)
     info = eng.step_info()
-    winner = {"index": int(res.get("global_best_index", res["best_index"])),
-              "cost": float(res.get("global_best_cost", res["best_cost"])), "n_feasible_local": int(res["n_feasible"]),
-              "n_collisions": int(res["n_collisions"])}
-    rank_ms = [elapsed / args.steps * 1e3]
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
-        allr = torch.empty(world, dtype=torch.float64, device="cuda")
-        dist.all_gather_into_tensor(allr, t)
-        rank_ms = [float(x) / args.steps * 1e3 for x in allr.cpu().tolist()]
-        elapsed = float(allr.max().item())   # the contract's time: MAX over the ranks
     comm = None
     try:
         if world > 1 and ev.uses_library_exchange():
@@ -558,6 +671,7 @@ def main():
         try:
             sub = argparse.Namespace(**vars(args))
             sub.steps, sub.warmup, sub.preheat, sub.no_cpu_baseline = min(args.steps, 50), min(args.warmup, 5), 0.0, True
+            sub.dump_outputs = None
             sc = bench_stress(sub, world, rank, local_rank, torch, dist, emit=False)
             if rank != 0 or sc is None:
                 return None
@@ -574,8 +688,6 @@ def main():
     showcase = run_showcase() if (world == 1 and sc_env == "force") else None
 
     if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        value = C_global * args.steps / elapsed
         walk_ms = float(np.mean(evalk))
         obst_ms = float(np.mean(obstk)) if info["obstacle_kernel"] else 0.0
         eval_ms = walk_ms + obst_ms
@@ -609,26 +721,9 @@ def main():
             kernels = [roofline]
         else:
             roofline = hbm
-        out = {
-            "metric": "candidate trajectories/sec (30-step horizon)",
-            "value": value, "unit": "trajectories/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "clock_preheat_s": args.preheat,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"BASELINE {args.workload}: single agent, {C_local} candidates/GPU x {S} samples "
-                                   f"({GRID[0]}x{GRID[1]}x{GRID[2] + 1} grid per GPU), "
-                                   f"{'20 predicted obstacles (prediction cost + OBB collision)' if n_obst else 'no obstacles'}, "
-                                   f"{'select-only (Mode A)' if args.select_only else 'SoA TrajectoryBundle materialised (Mode B)'}",
-                       "candidates_global": C_global, "candidates_per_gpu": C_local, "samples": S,
-                       "reference_knots": int(inp.coordinate_system.ref_pos.shape[0]), "obstacles": n_obst,
-                       "parallelism": f"candidate-shard x{world}, all-gather top-{args.topk}" if world > 1 else "single GPU",
-                       "exchange": exchange_note},
-            # how stable the timed region was: K steps are a few milliseconds of wall time
-            "ms_per_step_min": float(np.min(lat) * 1e3), "ms_per_step_stdev": float(np.std(lat) * 1e3),
-            "steps_timed_wall_ms": elapsed * 1e3,
+        out = dict(line, **{
             # the step a planner really takes (new ego state + predictions from host buffers every step), next to `value`
             "plan_step_value": C_global * args.steps / elapsed_u, "plan_step_ms": elapsed_u / args.steps * 1e3,
-            "resident_step_p50_ms": float(np.percentile(lat, 50) * 1e3), "resident_step_p95_ms": float(np.percentile(lat, 95) * 1e3),
             "plan_step_p50_ms": float(np.percentile(lat_u, 50) * 1e3), "plan_step_p95_ms": float(np.percentile(lat_u, 95) * 1e3),
             "plan_step_note": "plan_step_* = the step fed a new ego state and new predictions from host buffers every time "
                               "(fx_update_step: re-packed tables, one host-to-device copy, evaluation, result on the host); "
@@ -640,11 +735,9 @@ def main():
             # a scaling record checks itself: the ranks RCCL reports for the library's communicator (ncclCommCount; the torch
             # group's size when the exchange ran through torch.distributed) and every rank's own time for the K steps
             "rccl_ranks": (comm["rccl_ranks"] if comm and comm["rccl_ranks"] > 0 else world) if world > 1 else 1,
-            "ms_per_step_rank_min": min(rank_ms), "ms_per_step_rank_max": max(rank_ms), "ms_per_step_ranks": rank_ms,
-            "winner": winner,
             "roofline": roofline,
             "kernels": kernels,
-        }
+        })
         if showcase is not None:
             out["agent_sharding"] = showcase
         if n_obst:
@@ -757,6 +850,8 @@ def bench_stress(args, world, rank, local_rank, torch, dist, emit=True):
         last["res"], last["surv"] = ev.step_agents_enqueued() if world == 1 else exit_on_timeout(ev.step_agents_enqueued)
 
     elapsed, lat = _timed(args, world, dist, torch, step, 5e-3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, stress_outputs(eng, agents, last["res"], last["surv"]))
     n_timed = min(256, (args.steps + args.timing_every - 1) // args.timing_every)
     evalk, kern = eng.kernel_times(n_timed)
     obstk = eng.obstacle_kernel_times(n_timed)
@@ -793,7 +888,7 @@ def bench_stress(args, world, rank, local_rank, torch, dist, emit=True):
                          "note": "select-only writes 12 B per candidate: this workload is FP64-issue-bound, see `compute`"},
             "compute": compute, "launch": info,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import oracle
             one = synthetic.stress_agents(1, grid=STRESS_GRID, hull_builder=oracle.build_obstacle_hulls)[0]
             out["cpu_baseline"] = cpu_baseline_of(one, f"agent 0 ({one.n_candidates} candidates x {S} samples, {K} obstacles)")
@@ -827,6 +922,8 @@ def bench_scenario_step(args, world, rank, local_rank, torch, dist):
         last["res"] = eng.finish()[0]
 
     elapsed, lat = _timed(args, world, dist, torch, step, 5e-5)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engine_outputs(eng, inp, last["res"]))
     n_timed = min(256, (args.steps + args.timing_every - 1) // args.timing_every)
     evalk, kern = eng.kernel_times(n_timed)
     obstk = eng.obstacle_kernel_times(n_timed)
@@ -835,7 +932,7 @@ def bench_scenario_step(args, world, rank, local_rank, torch, dist):
     # step in the form the reference's C++ adapter hands over, a C x 13 sampling matrix (reactive_planner_cpp.py:228-253)
     cpp_style = None
     res630 = dict(last["res"])
-    if world == 1:
+    if world == 1 and args.full:
         import copy
         from frenetix_motion_planner_amd.sampling import generate_sampling_matrix
         t = np.union1d(inp.t_samp, [inp.N * inp.dt]); v = np.union1d(inp.v_samp, [inp.x0_lon[1]]); d = np.union1d(inp.d_samp, [inp.x0_lat[0]])
@@ -876,7 +973,7 @@ def bench_scenario_step(args, world, rank, local_rank, torch, dist):
             "reference_python_path": "about 1.2e3 trajectories/s on one core (measured in the build container, BASELINE.md section 3)",
         }
         out["cpp_style_800"] = cpp_style
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import oracle
             from frenetix_motion_planner_amd.problem import pack_predictions
             inp.obstacles = pack_predictions(inp.predictions if hasattr(inp, "predictions") and inp.predictions else
@@ -913,6 +1010,8 @@ def bench_multiagent(args, world, rank, local_rank, torch, dist):
             counts["batch_ms"].append(sim.batch.last_batch_ms)
 
     elapsed, lat = _timed(args, world, dist, torch, step, None)
+    if args.dump_outputs and rank == 0:   # the planned trajectories of every agent [agents, S, fields], identical on every rank
+        dump_outputs(args.dump_outputs, {"plans": sim.plans})
     if rank == 0:
         n_agents = len(sim.agent_ids)
         ls = sim.batch.agents[0].planner.last_step

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,7 +49,7 @@ def test_dry_launch_at_the_node_size_and_workload_from_the_environment():
 
 @pytest.mark.gpu
 def test_default_line_is_config3_with_north_star():
-    d = run("--steps", "24", "--warmup", "4", "--no-cpu-baseline")
+    d = run("--full", "--steps", "24", "--warmup", "4", "--no-cpu-baseline")
     for k in REQUIRED:
         assert k in d, k
     for k in ROOFLINE:
@@ -92,8 +93,43 @@ def test_default_line_is_config3_with_north_star():
 
 
 @pytest.mark.gpu
+def test_plain_line_and_the_dumped_outputs_of_the_last_step(tmp_path):
+    """A plain run is the headline of the K timed steps and nothing measured beside it; --dump-outputs writes what the last
+    timed step computed, the same arrays whatever the number of steps (seeded inputs, resident in HBM)."""
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = run("--steps", "7", "--warmup", "2", "--dump-outputs", str(a))
+    assert d["n_gpus"] == 1 and d["steps"] == 7 and d["warmup"] == 2 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["metric"] == "candidate trajectories/sec (30-step horizon)" and d["unit"] == "trajectories/s"
+    assert d["value"] == pytest.approx(50388 / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    assert d["steps_timed_wall_ms"] == pytest.approx(7 * d["ms_per_step"], rel=1e-9)
+    for k in ("north_star", "cpu_baseline", "roofline", "kernels", "plan_step_ms", "pipelined_value", "eval_kernel_ms"):
+        assert k not in d, k
+    out = {f.stem: np.load(f) for f in a.glob("*.npy")}
+    assert set(out) == {"result", "reason_hist", "cost", "flags", "costmap", "bundle_sample_index", "bundle_sample"}
+    assert all(v.dtype == np.float64 for v in out.values()) and sum(v.nbytes for v in out.values()) <= 64 << 20
+    w = d["winner"]
+    assert out["result"][0] == w["index"] and out["result"][1] == w["cost"] and out["result"][7] == w["n_collisions"]
+    assert out["cost"].shape == out["flags"].shape == (50388,) and out["costmap"].shape[0] == 50388
+    assert out["cost"][w["index"]] == pytest.approx(w["cost"], rel=1e-12)
+    assert out["bundle_sample"].shape == (len(out["bundle_sample_index"]), 14, 31) and w["index"] in out["bundle_sample_index"]
+    run("--steps", "3", "--warmup", "1", "--dump-outputs", str(b))
+    for k, v in out.items():
+        assert np.array_equal(np.load(b / f"{k}.npy"), v, equal_nan=True), k
+
+
+def test_dump_outputs_writes_float64_within_64_mb(tmp_path):
+    import bench
+    bench.dump_outputs(str(tmp_path / "d"), {"flags": np.array([1, 2 ** 32 - 1], np.uint32), "index": np.arange(3)})
+    f = np.load(tmp_path / "d" / "flags.npy")
+    assert f.dtype == np.float64 and f.tolist() == [1.0, 2.0 ** 32 - 1] and np.load(tmp_path / "d" / "index.npy").tolist() == [0, 1, 2]
+    with pytest.raises(RuntimeError, match="limit"):
+        bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros((64 << 20) // 8 + 1)})
+    assert not (tmp_path / "big").exists()
+
+
+@pytest.mark.gpu
 def test_config2_line_keeps_the_hbm_roofline():
-    d = run("--workload", "config2", "--steps", "24", "--warmup", "4", "--no-cpu-baseline", "--no-north-star")
+    d = run("--full", "--workload", "config2", "--steps", "24", "--warmup", "4", "--no-cpu-baseline", "--no-north-star")
     rf = d["roofline"]
     assert "config2" in d["config"]["workload"] and rf["bound"] == "hbm" and rf["peak"] == 8000.0 and 0.2 < rf["frac"] < 1.0
     assert rf["achieved"] == pytest.approx(rf["algorithmic_bytes_per_launch"] / (rf["avg_launch_ms"] * 1e-3) / 1e9)
@@ -114,7 +150,7 @@ def test_reference_python_record_is_committed():
 
 @pytest.mark.gpu
 def test_cpu_baseline_object_and_other_workloads():
-    d = run("--workload", "config1", "--steps", "20", "--warmup", "2")
+    d = run("--full", "--workload", "config1", "--steps", "20", "--warmup", "2")
     cb = d["cpu_baseline"]
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in cb, k
@@ -136,7 +172,7 @@ def test_multi_rank_line_carries_the_agent_sharded_workload():
     """With several ranks the default line also reports BASELINE config 5 measured by the same ranks (`agent_sharding`); here the
     same code path forced with ONE rank (FX_BENCH_SHOWCASE=force), 8 agents per GPU to keep it short."""
     env = dict(os.environ, FX_BENCH_SHOWCASE="force")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--no-north-star",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--no-north-star",
                         "--agents-per-gpu", "8"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-1500:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1,5 +1,5 @@
-"""stdlib CommonRoad reader: a small authored scenario (always) and the reference's example
-scenario when /root/reference is present (build container)."""
+"""stdlib CommonRoad reader: a small authored scenario and the reference's example scenario (stored as data
+under tests/golden/)."""
 import os
 
 import numpy as np
@@ -8,7 +8,7 @@ import pytest
 from frenetix_motion_planner_amd import commonroad_xml as crx
 from frenetix_motion_planner_amd import ref_path
 
-EXAMPLE = "/root/reference/example_scenarios/ZAM_Tjunction-1_42_T-1.xml"
+EXAMPLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ZAM_Tjunction-1_42_T-1.xml")
 
 
 from tests.fixtures import tiny_commonroad_xml  # noqa: E402
@@ -74,7 +74,6 @@ def test_ground_truth_predictions(tiny):
     assert p9["pos_list"].shape == (27, 2) and np.all(p9["pos_list"] == [80.0, -1.0])  # range(3, min(33, 30))
 
 
-@pytest.mark.skipif(not os.path.exists(EXAMPLE), reason="reference example scenarios not present (GPU box)")
 def test_example_scenario_of_the_reference():
     sc = crx.read_scenario(EXAMPLE)
     assert sc.benchmark_id == "ZAM_Tjunction-1_42_T-1" and sc.dt == 0.1

@@ -14,7 +14,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "ZAM_Tjunction-1_42_T-1.scenario.json")
-XML = "/root/reference/example_scenarios/ZAM_Tjunction-1_42_T-1.xml"
+XML = os.path.join(ROOT, "tests", "golden", "ZAM_Tjunction-1_42_T-1.xml")   # the reference's example scenario (data)
 
 from frenetix_motion_planner_amd import commonroad_xml as crx  # noqa: E402
 from frenetix_motion_planner_amd import multiagent  # noqa: E402
@@ -29,7 +29,6 @@ def scenario():
     return crx.read_scenario_json(FIXTURE)
 
 
-@pytest.mark.skipif(not os.path.exists(XML), reason="reference example scenarios not present (GPU box)")
 def test_fixture_is_what_the_reader_extracts_from_the_xml():
     assert crx.scenario_to_dict(crx.read_scenario(XML)) == crx.scenario_to_dict(crx.read_scenario_json(FIXTURE))
 

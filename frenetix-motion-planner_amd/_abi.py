@@ -5,7 +5,7 @@ wrapper (oracle/oracle.py) can share the struct definitions.
 """
 import ctypes as C
 
-FX_ABI_VERSION = 9
+FX_ABI_VERSION = 10
 FX_LON_VELOCITY_KEEPING, FX_LON_STOP_POINT = 0, 1
 
 FX_OK = 0
@@ -121,3 +121,18 @@ class FxResult(C.Structure):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reason_hist"}
         d["reason_hist"] = list(self.reason_hist)
         return d
+
+
+# trajectory risk (fxplan.h FxRiskParams)
+FX_RISK_PROB_MVN, FX_RISK_PROB_MAHALANOBIS = 0, 1
+FX_RISK_HARM_LOGISTIC, FX_RISK_HARM_REF_SPEED = 0, 1
+FX_RISK_CLASS_UNPROTECTED, FX_RISK_CLASS_PROTECTED = 0, 1
+FX_RISK_MAX_EDGES = 6
+
+
+class FxRiskParams(C.Structure):
+    _fields_ = [("prob_mode", C.c_int32), ("prot_model", C.c_int32), ("unprot_ego_model", C.c_int32), ("n_edges", C.c_int32),
+                ("edges", C.c_double * FX_RISK_MAX_EDGES), ("coef_pos", C.c_double * FX_RISK_MAX_EDGES),
+                ("coef_neg", C.c_double * FX_RISK_MAX_EDGES)] + \
+               [(n, C.c_double) for n in ("coef_else", "prot_c", "prot_s", "prot_ref", "prot_exp", "uego_c", "uego_s", "uego_ref",
+                                          "uego_exp", "ped_c", "ped_s", "ego_length", "ego_width", "ego_mass")]

@@ -40,6 +40,7 @@ def exported_symbols():
         "fx_read_coeffs_agent", "fx_read_lat_tau_agent", "fx_read_sample", "fx_read_sample_agent", "fx_read_candidate_agent", "fx_read_plane", "fx_read_plane_agent",
         "fx_read_topk", "fx_read_topk_batch", "fx_topk_to_device", "fx_build_obstacle_hulls", "fx_device_bytes",
         "fx_last_kernel_ms", "fx_last_eval_kernel_ms", "fx_device_views",
+        "fx_set_risk_obstacles_agent", "fx_eval_risk_agent", "fx_last_risk_ms",
     ]
 
 
@@ -130,6 +131,10 @@ def lib():
         "fx_read_lat_tau_agent": ([vp, C.c_int32, C.c_int64, pd], C.c_int32),
         "fx_read_sample": ([vp, C.c_int64, pd], C.c_int32),
         "fx_read_sample_agent": ([vp, C.c_int32, C.c_int64, pd], C.c_int32),
+        "fx_set_risk_obstacles_agent": ([vp, C.c_int32, C.c_int32, C.c_int32, pd, pd, pd, pd, pd, pi32, pi32, pi32, pd, pd, pd, pi32],
+                                        C.c_int32),
+        "fx_eval_risk_agent": ([vp, C.c_int32, C.POINTER(_abi.FxRiskParams), C.c_int64, pi64, pd, pd, pi64], C.c_int32),
+        "fx_last_risk_ms": ([vp], C.c_double),
         "fx_read_candidate_agent": ([vp, C.c_int32, C.c_int64, pd, pd, pi32, pd, pd, pu32], C.c_int32),
         "fx_read_plane": ([vp, C.c_int32, pd], C.c_int32),
         "fx_read_plane_agent": ([vp, C.c_int32, C.c_int32, pd], C.c_int32),

@@ -160,6 +160,7 @@ int32_t fx_destroy(FxContext *c) {
                    c->d_part_cost, c->d_part_idx, c->d_counters, c->d_topk_cost, c->d_topk_idx, c->d_topk_scr_cost,
                    c->d_topk_scr_idx};
     for (void *p : dev) if (p) (void)hipFree(p);
+    fx_risk_release(c);
     if (c->d_bstep) (void)hipFree(c->d_bstep);
     if (c->d_obs_part) (void)hipFree(c->d_obs_part);
     if (c->d_obs_colm) (void)hipFree(c->d_obs_colm);

@@ -237,7 +237,10 @@ struct FxContext {
     uint32_t tail_step = 0;           // FX_TAIL_* of the last evaluation
     size_t gen_rec_lds = 0;           // generic kernel, >= 4 lanes per candidate: bytes of the staged obstacle records + step masks
     int64_t dev_bytes = 0;
+    struct FxRiskState *risk = nullptr;    // trajectory risk (fx_api_risk.hip): obstacle tables and buffers, created on first use
 };
+
+void fx_risk_release(FxContext *c);   // (fx_api_risk.hip)
 
 extern "C" int32_t fx_wait_word(const volatile unsigned long long *word, unsigned long long expected, int32_t timeout_ms);   // (fx_api.hip)
 

@@ -29,6 +29,7 @@
 #include "fx_eval_grid_kernel.h"
 #include "fx_obstacle_kernel.h"
 #include "fx_step_kernel.h"
+#include "fx_risk_kernel.h"
 
 using fxk::wave_count;
 
@@ -589,5 +590,20 @@ extern "C" hipError_t fx_launch_topk(const DevProblem *d_probs, int n_agents, in
         hipLaunchKernelGGL(fx_topk_merge_wave_kernel, dim3(n_agents), dim3(64), 0, stream, k, scr_cost, scr_idx, out_cost, out_idx);
     else
         hipLaunchKernelGGL(fx_topk_merge_kernel, dim3(n_agents), dim3(256), 0, stream, k, scr_cost, scr_idx, out_cost, out_idx);
+    return hipGetLastError();
+}
+
+// trajectory risk (fx_risk_kernel.h): the risk pass over n listed candidates, then the arg-min; ev_start / ev_stop (may be
+// null) bracket both
+extern "C" hipError_t fx_launch_risk(const double *planes, int64_t ld, int S, int64_t n, const int64_t *ids, const uint32_t *flags,
+                                     const double *rec, const double *obs, const double *pos, const double *yaw, const double *vo,
+                                     int K, int P, const FxRiskParams *params, double *out_ego, double *out_obst, long long *out_idx,
+                                     hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream) {
+    if (ev_start) { hipError_t e = hipEventRecord(ev_start, stream); if (e != hipSuccess) return e; }
+    if (n > 0)
+        hipLaunchKernelGGL(fxrisk::fx_risk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, planes, ld, S, n, ids, flags,
+                           rec, obs, pos, yaw, vo, K, P, *params, out_ego, out_obst);
+    hipLaunchKernelGGL(fxrisk::fx_risk_argmin_kernel, dim3(1), dim3(1024), 0, stream, out_ego, out_obst, n, ids, out_idx);
+    if (ev_stop) { hipError_t e = hipEventRecord(ev_stop, stream); if (e != hipSuccess) return e; }
     return hipGetLastError();
 }

@@ -1,0 +1,247 @@
+// fx_risk_kernel.h -- trajectory risk (risk_costs.py:20-118, crash_angle_simplified) over the materialised bundle, and the
+// arg-min of ego + obstacle risk (reactive_planner.py:262-269, reactive_planner_cpp.py:404-413).  DESIGN.md section 11.
+//
+// One lane per candidate.  Every lane walks the (obstacle, step) pairs in the same order, so everything indexed by them -- the
+// three obstacle means, the standardisation (sigma_x, sigma_y, rho), the |rho| branch of the bivariate normal and its node terms
+// -- is wave-uniform and comes from a record the host built once per call (fx_api_risk.hip).  Only the 5 m gate diverges.
+//
+// Bivariate normal upper probability BVNU(h, k, rho) = P(X > h, Y > k) after Genz (2004), Statistics and Computing 14:251-260:
+// Drezner-Wesolowsky Gauss-Legendre quadrature of the Plackett integral in asin(rho) with 6 / 12 / 20 nodes for |rho| < 0.3 /
+// 0.75 / 0.925, and for |rho| >= 0.925 the expansion around rho = +-1 plus 20-node quadrature of the remainder.  The rectangle
+// probability of `mvnun` is BVNU(a1, a2) - BVNU(b1, a2) - BVNU(a1, b2) + BVNU(b1, b2) on the standardised bounds.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "fx_select.h"
+
+// record of one (obstacle, ego step i): doubles
+#define FXR_M0X 0    // means: pos[i-1], pos[i-1] +- (cos, sin)(yaw[i]) length / 2
+#define FXR_SX 6
+#define FXR_SY 7
+#define FXR_RHO 8
+#define FXR_BRANCH 9  // 0: rho == 0, 1: |rho| < 0.925, 2: 0.925 <= |rho| < 1, 3: |rho| == 1
+#define FXR_NG 10     // Gauss-Legendre half nodes (3, 6, 10)
+#define FXR_VALID 11  // i < len(pos_list)
+#define FXR_IV 12     // inverse covariance (Mahalanobis mode)
+#define FXR_ASR 16    // branch 1: asin(rho) / 2; branch 2: 1 - rho^2
+#define FXR_A 17      // branch 2: sqrt(1 - rho^2)
+#define FXR_N1 18     // branch 1: sin(asr (1 - x_j)), then sin(asr (1 + x_j)); branch 2: xs_j = (a/2 (1 -+ x_j))^2
+#define FXR_N2 38     // branch 2: sqrt(1 - xs_j)
+#define FXR_STRIDE 58
+
+// per obstacle: doubles
+#define FXO_LEN 0
+#define FXO_WID 1
+#define FXO_MASS 2
+#define FXO_CLS 3
+#define FXO_NPOS 4
+#define FXO_STRIDE 8
+
+namespace fxrisk {
+
+// Gauss-Legendre weights on [-1, 1], positive half (the nodes live in the host's records)
+__constant__ double kW6[3] = {0.1713244923791705, 0.3607615730481384, 0.4679139345726904};
+__constant__ double kW12[6] = {0.04717533638651177, 0.1069393259953183, 0.1600783285433464,
+                               0.2031674267230659, 0.2334925365383547, 0.2491470458134029};
+__constant__ double kW20[10] = {0.01761400713915212, 0.04060142980038694, 0.06267204833410906, 0.08327674157670475,
+                                0.1019301198172404,  0.1181945319615184,  0.1316886384491766,  0.1420961093183821,
+                                0.1491729864726037,  0.1527533871307259};
+
+__device__ __forceinline__ double phid(double z) { return 0.5 * erfc(-z / 1.4142135623730951); }
+
+__device__ __forceinline__ double weight(int ng, int j) { return ng == 3 ? kW6[j] : (ng == 6 ? kW12[j] : kW20[j]); }
+
+// BVNU(h, k, rho) with the wave-uniform part of rho taken from the record q
+__device__ double bvnu(double h, double k, const double *__restrict__ q) {
+    const double r = q[FXR_RHO];
+    const int branch = (int)q[FXR_BRANCH];
+    if (branch == 0) return phid(-h) * phid(-k);
+    const double tp = 6.283185307179586;
+    const int ng = (int)q[FXR_NG];
+    double hk = h * k, bvn = 0.0;
+    if (branch == 1) {
+        const double hs = (h * h + k * k) / 2.0, asr = q[FXR_ASR];
+        for (int j = 0; j < 2 * ng; j++) {
+            const double sn = q[FXR_N1 + j];
+            bvn += weight(ng, j < ng ? j : j - ng) * exp((sn * hk - hs) / (1.0 - sn * sn));
+        }
+        bvn = bvn * asr / tp + phid(-h) * phid(-k);
+    } else {
+        if (r < 0.0) { k = -k; hk = -hk; }
+        if (branch == 2) {
+            const double as = q[FXR_ASR], a = q[FXR_A], bs = (h - k) * (h - k);
+            const double c = (4.0 - hk) / 8.0, d = (12.0 - hk) / 80.0;
+            double asr = -(bs / as + hk) / 2.0;
+            if (asr > -100.0) bvn = a * exp(asr) * (1.0 - c * (bs - as) * (1.0 - d * bs) / 3.0 + c * d * as * as);
+            if (hk > -100.0) {
+                const double b = sqrt(bs), sp = 2.5066282746310002 * phid(-b / a);
+                bvn = bvn - exp(-hk / 2.0) * sp * b * (1.0 - c * bs * (1.0 - d * bs) / 3.0);
+            }
+            const double ah = a / 2.0;
+            double sum = 0.0;
+            for (int j = 0; j < 2 * ng; j++) {
+                const double xs = q[FXR_N1 + j];
+                asr = -(bs / xs + hk) / 2.0;
+                if (asr > -100.0) {
+                    const double sp = 1.0 + c * xs * (1.0 + 5.0 * d * xs), rs = q[FXR_N2 + j];
+                    const double ep = exp(-(hk / 2.0) * xs / ((1.0 + rs) * (1.0 + rs))) / rs;
+                    sum += exp(asr) * (sp - ep) * weight(ng, j < ng ? j : j - ng);
+                }
+            }
+            bvn = (ah * sum - bvn) / tp;
+        }
+        if (r > 0.0) bvn = bvn + phid(-fmax(h, k));
+        else if (h >= k) bvn = -bvn;
+        else {
+            const double L = h < 0.0 ? phid(k) - phid(h) : phid(-h) - phid(-k);
+            bvn = L - bvn;
+        }
+    }
+    return fmax(0.0, fmin(1.0, bvn));
+}
+
+// impact-area coefficient of an (unwrapped) angle: the bins of logistic_regression_{a,}symmetrical.py
+__device__ __forceinline__ double angle_coef(const FxRiskParams &p, double a) {
+    if (p.n_edges == 0) return 0.0;
+    if (-p.edges[0] < a && a < p.edges[0]) return 0.0;
+#pragma unroll   // constant indices into the kernel-argument block: no private copy of FxRiskParams
+    for (int j = 1; j < FX_RISK_MAX_EDGES; j++) {
+        if (j >= p.n_edges) break;
+        if (p.edges[j - 1] <= a && a < p.edges[j]) return p.coef_pos[j];
+        if (-p.edges[j - 1] >= a && a > -p.edges[j]) return p.coef_neg[j];
+    }
+    return p.coef_else;
+}
+
+__device__ __forceinline__ double ref_speed(double dv, double ref, double ex) { return dv < ref ? pow(dv / ref, ex) : 1.0; }
+
+// probability of step i (ego point i) against the record q; (x, y, th) of ego point i
+__device__ __forceinline__ double step_probability(const FxRiskParams &p, const double *__restrict__ q, double x, double y, double th) {
+    if (q[FXR_VALID] == 0.0) return 0.0;
+    if (p.prob_mode == FX_RISK_PROB_MAHALANOBIS) {
+        const double d0 = x - q[FXR_M0X], d1 = y - q[FXR_M0X + 1];
+        const double r0 = d0 * q[FXR_IV] + d1 * q[FXR_IV + 2], r1 = d0 * q[FXR_IV + 1] + d1 * q[FXR_IV + 3];
+        const double m = r0 * d0 + r1 * d1;
+        return 1.0 / (m * m);
+    }
+    double dmin = INFINITY;
+#pragma unroll
+    for (int u = 0; u < 3; u++) {
+        const double dx = q[FXR_M0X + 2 * u] - x, dy = q[FXR_M0X + 2 * u + 1] - y;
+        dmin = fmin(dmin, sqrt(dx * dx + dy * dy));
+    }
+    if (dmin > 5.0) return 0.0;
+    // three axis-aligned rectangles of half extents (l/6, w/2) centred at c, c +- (l/2)(2/3)(cos th, sin th)
+    const double rx = (p.ego_length / 2.0) * (2.0 / 3.0), ox = p.ego_length / 6.0, oy = p.ego_width / 2.0;
+    const double ex = rx * cos(th), ey = rx * sin(th);
+    const double cx[3] = {x, x + ex, x - ex}, cy[3] = {y, y + ey, y - ey};
+    const double sx = q[FXR_SX], sy = q[FXR_SY];
+    double prob = 0.0;
+    for (int u = 0; u < 3; u++) {
+        const double mx = q[FXR_M0X + 2 * u], my = q[FXR_M0X + 2 * u + 1];
+        for (int c = 0; c < 3; c++) {
+            const double a1 = ((cx[c] - ox) - mx) / sx, a2 = ((cy[c] - oy) - my) / sy;
+            const double b1 = ((cx[c] + ox) - mx) / sx, b2 = ((cy[c] + oy) - my) / sy;
+            prob += ((bvnu(a1, a2, q) - bvnu(b1, a2, q)) - bvnu(a1, b2, q)) + bvnu(b1, b2, q);
+        }
+    }
+    return prob / 3.0;
+}
+
+// One lane per listed candidate: out_ego / out_obst [n] (NaN where the candidate is not selected)
+__global__ __launch_bounds__(256) void fx_risk_kernel(const double *__restrict__ planes, int64_t ld, int S, int64_t n,
+                                                      const int64_t *__restrict__ ids, const uint32_t *__restrict__ flags,
+                                                      const double *__restrict__ rec, const double *__restrict__ obs,
+                                                      const double *__restrict__ pos, const double *__restrict__ yaw,
+                                                      const double *__restrict__ vo, int K, int P, FxRiskParams p,
+                                                      double *__restrict__ out_ego, double *__restrict__ out_obst) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int64_t c = ids ? ids[j] : j;
+    const uint32_t need = FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED;
+    if (!ids && (flags[c] & need) != need) { out_ego[j] = NAN; out_obst[j] = NAN; return; }
+    const double *X = planes + c, *Y = planes + (size_t)S * ld + c, *TH = planes + 2 * (size_t)S * ld + c,
+                 *V = planes + 3 * (size_t)S * ld + c;
+    const double me = p.ego_mass;
+    double ego_best = -INFINITY, obst_best = -INFINITY;
+    bool any = false;
+    for (int k = 0; k < K; k++) {
+        const double *o = obs + (size_t)k * FXO_STRIDE;
+        const int npos = (int)o[FXO_NPOS];
+        const int pl = min(S - 1, npos);
+        if (pl <= 0) continue;
+        const bool prot = o[FXO_CLS] == (double)FX_RISK_CLASS_PROTECTED;
+        const double mo = o[FXO_MASS];
+        const double f_ego = mo / (me + mo), f_obs = me / (me + mo);
+        double e_max = -INFINITY, o_max = -INFINITY;
+        for (int t = 0; t < pl; t++) {
+            const int i = t + 1;
+            const double *q = rec + ((size_t)k * S + i) * FXR_STRIDE;
+            const double prob = step_probability(p, q, X[(size_t)i * ld], Y[(size_t)i * ld], TH[(size_t)i * ld]);
+            double re = 0.0, ro = 0.0;
+            if (prob != 0.0) {
+                // harm of ego point t against prediction t (harm_estimation.py:282-300)
+                const double x = X[(size_t)t * ld], y = Y[(size_t)t * ld], th = TH[(size_t)t * ld], v = V[(size_t)t * ld];
+                const size_t kt = (size_t)k * P + t;
+                const double yo = yaw[kt], vob = vo[kt], px = pos[2 * kt], py = pos[2 * kt + 1];
+                const double pdof = (yo - th) + 3.141592653589793;
+                const double rel = atan2(py - y, px - x);
+                const double dv = sqrt((v * v + vob * vob) + ((2.0 * v) * vob) * cos(pdof));
+                const double dve = f_ego * dv, dvo = f_obs * dv;
+                double he, ho;
+                if (prot) {
+                    if (p.prot_model == FX_RISK_HARM_LOGISTIC) {
+                        const double ae = angle_coef(p, rel - th), ao = angle_coef(p, (3.141592653589793 + rel) - yo);
+                        he = 1.0 / (1.0 + exp(((-p.prot_c) - p.prot_s * dve) - ae));
+                        ho = 1.0 / (1.0 + exp(((-p.prot_c) - p.prot_s * dvo) - ao));
+                    } else {
+                        he = ref_speed(dve, p.prot_ref, p.prot_exp);
+                        ho = ref_speed(dvo, p.prot_ref, p.prot_exp);
+                    }
+                } else {
+                    he = p.unprot_ego_model == FX_RISK_HARM_LOGISTIC ? 1.0 / (1.0 + exp((-p.uego_c) - p.uego_s * dve))
+                                                                     : ref_speed(dve, p.uego_ref, p.uego_exp);
+                    ho = 1.0 / (1.0 + exp(p.ped_c - p.ped_s * dvo));
+                }
+                re = he * prob;
+                ro = ho * prob;
+            }
+            e_max = fmax(e_max, re);
+            o_max = fmax(o_max, ro);
+        }
+        ego_best = fmax(ego_best, e_max);
+        obst_best = fmax(obst_best, o_max);
+        any = true;
+    }
+    out_ego[j] = any ? ego_best : 0.0;
+    out_obst[j] = any ? obst_best : 0.0;
+}
+
+// arg-min of ego + obst over the n entries (NaN = not selected), ties to the lower candidate index: ONE workgroup of 1024
+// lanes, the lexicographic (cost, index) reduction of fx_select.h
+__global__ __launch_bounds__(1024) void fx_risk_argmin_kernel(const double *__restrict__ ego, const double *__restrict__ obst, int64_t n,
+                                                              const int64_t *__restrict__ ids, long long *__restrict__ out) {
+    __shared__ double sc[16];
+    __shared__ long long si[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double bc = INFINITY;
+    long long bi = 0x7fffffffffffffffLL;
+    for (int64_t j = tid; j < n; j += blockDim.x) {
+        const double e = ego[j], o = obst[j];
+        if (e != e || o != o) continue;
+        const double s = e + o;
+        const long long c = ids ? (long long)ids[j] : (long long)j;
+        if (fx_lex_less(s, c, bc, bi)) { bc = s; bi = c; }
+    }
+    fx_lex_wave_min(bc, bi);
+    if (lane == 0) { sc[wave] = bc; si[wave] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < (int)(blockDim.x >> 6); w++)
+            if (fx_lex_less(sc[w], si[w], bc, bi)) { bc = sc[w]; bi = si[w]; }
+        out[0] = bi == 0x7fffffffffffffffLL ? -1LL : bi;
+    }
+}
+
+}  // namespace fxrisk

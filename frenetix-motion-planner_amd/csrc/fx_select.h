@@ -14,6 +14,18 @@
 // publishes the result block.  One workgroup scanning 50 000 candidates took ~30 us; the slices take ~5.
 // The number of slices grows with the candidate count (host: fx_launch_select): 32 for planner-sized and 50 000-candidate steps,
 // 256 at a million candidates -- with a fixed 32 every workgroup scanned 31 000 cost / flag pairs there while 224 CUs idled.
+// The lexicographic (cost, index) order of every arg-min here: the lower cost, then the lower index (Python's stable sort).
+__device__ __forceinline__ bool fx_lex_less(double c, long long i, double bc, long long bi) { return c < bc || (c == bc && i < bi); }
+// (cost, index) minimum across the 64 lanes of a wave; every lane ends with it
+__device__ __forceinline__ void fx_lex_wave_min(double &bc, long long &bi) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double oc = __shfl_xor(bc, off);
+        const long long oi = __shfl_xor(bi, off);
+        if (fx_lex_less(oc, oi, bc, bi)) { bc = oc; bi = oi; }
+    }
+}
+
 #define FX_SELECT_SLICES_MIN 32
 #define FX_SELECT_SLICES_MAX 512
 // The body, for workgroup `slice` of `n_slices` of agent `agent` (256 lanes).  COH (fx_step_kernel.h: the selection as the last
@@ -67,21 +79,16 @@ __device__ __forceinline__ void fx_select_body(const DevProblem &P, const int ag
             }
 #pragma unroll
             for (int u = 0; u < 4; u++)
-                if (c[u] < bc || (c[u] == bc && ix[u] < bi)) { bc = c[u]; bi = ix[u]; }
+                if (fx_lex_less(c[u], ix[u], bc, bi)) { bc = c[u]; bi = ix[u]; }
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double oc = __shfl_xor(bc, off);
-        const long long oi = __shfl_xor(bi, off);
-        if (oc < bc || (oc == bc && oi < bi)) { bc = oc; bi = oi; }
-    }
+    fx_lex_wave_min(bc, bi);
     if (lane == 0) { sc[wave] = bc; si[wave] = bi; }
     if (tid == 0) scnt = 0;
     __syncthreads();
     bc = sc[0]; bi = si[0];
     for (int w = 1; w < 4; w++)
-        if (sc[w] < bc || (sc[w] == bc && si[w] < bi)) { bc = sc[w]; bi = si[w]; }
+        if (fx_lex_less(sc[w], si[w], bc, bi)) { bc = sc[w]; bi = si[w]; }
     const bool none = bi == 0x7fffffffffffffffLL;
     // colliding selectable candidates ordered before the winner (all of them when nothing is collision-free)
     if (count_mode) {

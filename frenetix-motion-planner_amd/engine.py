@@ -707,6 +707,39 @@ class FrenetEngine:
         """[C, 14, S] whole bundle (D2H of every plane; debugging / logging only)."""
         return np.ascontiguousarray(np.stack([self.plane(p, agent) for p in range(_abi.FX_NUM_PLANES)]).transpose(2, 0, 1))
 
+    def set_risk_obstacles(self, tables: dict, agent: int = 0):
+        """Obstacle tables of the trajectory risk (risk.obstacle_tables) for the next `risk` calls of this agent."""
+        pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        t = {k: np.ascontiguousarray(v) for k, v in tables.items() if isinstance(v, np.ndarray)}
+        self._risk_tables = t    # (kept alive for the call; the library copies them)
+        f = lambda n: t[n].ctypes.data_as(pd)
+        i = lambda n: t[n].ctypes.data_as(pi)
+        check(lib().fx_set_risk_obstacles_agent(self._ctx, agent, int(tables["K"]), int(tables["P"]), f("pos"), f("cov"), f("cov_inv"),
+                                                f("yaw"), f("v"), i("n_pos"), i("n_yaw"), i("n_v"), f("length"), f("width"), f("mass"),
+                                                i("cls")))
+
+    def risk(self, params, ids=None, agent: int = 0):
+        """(ego_risk, obst_risk, min_risk_index) of the last plan step's candidates on the device (fx_eval_risk_agent).
+        ids None: every VALID & FEASIBLE & RETURNED candidate -- the arrays then have C entries, NaN for the others; the index is
+        the arg-min of ego + obst (ties to the lower index), -1 when there is none."""
+        inp = self._inputs[agent]
+        pd, pi64 = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        if ids is None:
+            n, idp = inp.n_candidates, None
+        else:
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            n, idp = len(ids), ids.ctypes.data_as(pi64)
+        ego, obst = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        idx = C.c_int64(-1)
+        check(lib().fx_eval_risk_agent(self._ctx, agent, C.byref(params), int(len(ids)) if ids is not None else 0, idp,
+                                       ego.ctypes.data_as(pd), obst.ctypes.data_as(pd), C.byref(idx)))
+        return ego[:n], obst[:n], int(idx.value)
+
+    @property
+    def last_risk_ms(self) -> float:
+        """device time of the last `risk` call (risk pass + arg-min)"""
+        return float(lib().fx_last_risk_ms(self._ctx))
+
     def topk(self, k: int):
         n = len(self._inputs)
         cost = np.zeros((n, k))

@@ -81,6 +81,8 @@ class PlannerConfig:
     # ReactivePlannerHip.set_fallback_selector / min_risk_selector below.  With neither configured a plan step whose feasible
     # candidates all collide returns None (plus the standstill trajectory at v <= 0.1, reactive_planner.py:105-109).
     emergency_selection: bool = False
+    # debug.log_risk: ego / obstacle risk of the chosen trajectory (reactive_planner.py:123-124) -- needs set_risk_model
+    log_risk: bool = False
     cost_weights: Dict[str, float] = field(default_factory=lambda: dict(DEFAULT_COST_WEIGHTS))
     draw_traj_set: bool = True       # debug.yaml:8
     kinematic_debug: bool = True     # debug.yaml:20
@@ -107,6 +109,7 @@ class ReactivePlannerHip:
         self._engine = engine
         self.road_boundary_check = road_boundary_check
         self.fallback_selector: Optional[Callable] = None   # last-level selection among colliding candidates (set_fallback_selector)
+        self._risk_model = None             # set_risk_model: (risk.json, harm_parameters.json, obstacle types, ego mass)
         self.occlusion_module = None       # planner.py:99 (set_occlusion_module)
         self.use_occ_model = False
         self.road_boundary = None          # segments [n][4]; checked on the GPU (set_road_boundary)
@@ -237,7 +240,43 @@ class ReactivePlannerHip:
         views over the step's device results (valid and feasible, every one of them colliding) -- and returns the chosen
         sample or None.  `min_risk_selector(risk)` builds the reference's rule from a per-trajectory risk function; the harm
         model that computes the reference's risk is outside this package (out of scope)."""
+        if isinstance(selector, str) and (selector != "min_risk" or self._risk_model is None):
+            raise ValueError("set_fallback_selector('min_risk') needs set_risk_model first" if selector == "min_risk"
+                             else f"unknown fallback selector {selector!r}")
         self.fallback_selector = selector
+
+    def set_risk_model(self, params_risk: dict, params_harm: dict, obstacle_types: dict, ego_mass: float):
+        """The reference's risk model (risk.json, harm_parameters.json; obstacle id -> CommonRoad type name; the ego's mass from
+        the caller's vehicle model) evaluated on the device.  With it set_fallback_selector("min_risk") is
+        the Python back-end's last-level rule, PlannerConfig.emergency_mode "min_risk" (with emergency_selection) the C++
+        back-end's, and PlannerConfig.log_risk fills _ego_risk / _obst_risk of the chosen trajectory."""
+        from . import risk
+        self._risk_model = dict(modes=dict(params_risk), types=dict(obstacle_types),
+                                params=risk.risk_params(params_risk, params_harm, self.vehicle_params.length,
+                                                        self.vehicle_params.width, ego_mass))
+
+    def _eval_risk(self, step, ids):
+        """(ego_risk, obst_risk, min_risk_index) of the step's candidates `ids` on the device under the risk model"""
+        from . import risk
+        if self._risk_model is None:
+            raise ValueError("no risk model: call set_risk_model first")
+        m = self._risk_model
+        tabs = risk.obstacle_tables(self.predictions or {}, m["types"], mahalanobis=bool(m["modes"].get("fast_prob_mahalanobis")))
+        risk.check_obstacle_classes(m["modes"], tabs["classes"])
+        step.engine.set_risk_obstacles(tabs, step.agent)
+        return step.engine.risk(m["params"], np.asarray(ids, np.int64), step.agent)
+
+    def _min_risk_sample(self, step):
+        ids = np.nonzero(step.mask(_abi.FX_FLAG_VALID) & step.mask(_abi.FX_FLAG_FEASIBLE) & step.mask(_abi.FX_FLAG_RETURNED))[0]
+        if len(ids) == 0:
+            return None
+        ego, obst, g = self._eval_risk(step, ids)
+        if g < 0:
+            return None
+        chosen = step.sample(int(g))
+        j = int(np.searchsorted(ids, g))
+        chosen._ego_risk, chosen._obst_risk = float(ego[j]), float(obst[j])
+        return chosen
 
     def set_occlusion_module(self, occ_module):
         """planner.py:271-273.  The occlusion module itself is outside this package (it is not in the reference
@@ -484,6 +523,20 @@ class ReactivePlannerHip:
                 self.msg_logger.warning("No optimal trajectory available. Select stopping trajectory!")
                 self.trajectory_pair = self._compute_trajectory_pair(optimal_trajectory)
                 self.ego_vehicle_history.append(self.trajectory_pair[0])
+        # the C++ back-end's other emergency mode: the feasible trajectory of the lowest ego + obstacle risk (reactive_planner_cpp.py:408-413)
+        if optimal_trajectory is None and self.config.emergency_mode == "min_risk" and self.config.emergency_selection \
+                and self.last_step is not None and self._risk_model is not None:
+            optimal_trajectory = self._min_risk_sample(self.last_step)
+            if optimal_trajectory is not None:
+                self.msg_logger.warning("No optimal trajectory available. Select lowest risk trajectory!")
+                self.trajectory_pair = self._compute_trajectory_pair(optimal_trajectory)
+                self.ego_vehicle_history.append(self.trajectory_pair[0])
+        # debug.log_risk (reactive_planner_cpp.py:427-428): risk of the chosen trajectory for the loggers
+        if optimal_trajectory is not None and self.config.log_risk and self._risk_model is not None \
+                and getattr(optimal_trajectory, "_step", None) is self.last_step and self.last_step is not None \
+                and optimal_trajectory._ego_risk is None:
+            ego, obst, _ = self._eval_risk(self.last_step, [optimal_trajectory.uniqueId])
+            optimal_trajectory._ego_risk, optimal_trajectory._obst_risk = float(ego[0]), float(obst[0])
         if optimal_trajectory is not None and hasattr(optimal_trajectory, "materialise"):
             optimal_trajectory.materialise()  # survives the next step's overwrite of the device bundle
         self.optimal_trajectory = optimal_trajectory
@@ -545,7 +598,10 @@ class ReactivePlannerHip:
         ids = np.nonzero(step.mask(_abi.FX_FLAG_VALID) & step.mask(_abi.FX_FLAG_FEASIBLE) & step.mask(_abi.FX_FLAG_RETURNED))[0]
         if len(ids) == 0:
             return None
-        chosen = self.fallback_selector(_LazySamples(step, ids))
+        if isinstance(self.fallback_selector, str) and self.fallback_selector == "min_risk":
+            chosen = self._min_risk_sample(step)    # the device's risk pass and arg-min (set_risk_model)
+        else:
+            chosen = self.fallback_selector(_LazySamples(step, ids))
         if chosen is not None:
             self.msg_logger.warning("No optimal trajectory available. Select lowest risk trajectory!")
         return chosen

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 9
+#define FX_ABI_VERSION 10
 
 /* ---- status codes (planner.py / reactive_planner_cpp.py raise Python exceptions; the shim maps
  *      <0 -> ValueError, >0 -> RuntimeError, see SURVEY 8b "Error conventions") ---- */
@@ -513,6 +513,48 @@ int32_t fx_set_timing_interval(FxContext *ctx, int32_t every);
 int32_t fx_read_kernel_times(FxContext *ctx, int32_t max_n, double *eval_ms, double *step_ms, int32_t *n_out);
 /* device self-test of the kernel's elementary functions (atan, sin, cos) on n host values */
 int32_t fx_math_selftest(int32_t n, const double *x, double *atan_out, double *sin_out, double *cos_out);
+
+/* ---- trajectory risk: collision probability x harm (risk_costs.py:20-118, crash_angle_simplified) -- DESIGN.md section 11 ----
+ * Nothing here runs unless called: the plan step, its launches and its buffers are unchanged.  The risk buffers are allocated
+ * on the first fx_eval_risk_agent. */
+enum { FX_RISK_PROB_MVN = 0, FX_RISK_PROB_MAHALANOBIS = 1 };            /* risk.json fast_prob_mahalanobis false / true */
+enum { FX_RISK_HARM_LOGISTIC = 0, FX_RISK_HARM_REF_SPEED = 1 };          /* model of a protected pair / of the ego vs. unprotected */
+enum { FX_RISK_CLASS_UNPROTECTED = 0, FX_RISK_CLASS_PROTECTED = 1 };     /* harm_estimation.py obstacle_protection */
+#define FX_RISK_MAX_EDGES 6
+typedef struct FxRiskParams {
+    int32_t prob_mode;       /* FX_RISK_PROB_* */
+    int32_t prot_model;      /* protected obstacle, ego and obstacle harm: FX_RISK_HARM_LOGISTIC 1/(1+exp(-c - s dv - bin(angle)))
+                                or FX_RISK_HARM_REF_SPEED dv < ref ? (dv/ref)^exp : 1 (ignore_angle only) */
+    int32_t unprot_ego_model;/* ego harm against an unprotected obstacle: FX_RISK_HARM_LOGISTIC (c, s) or FX_RISK_HARM_REF_SPEED */
+    int32_t n_edges;         /* impact-area bins of the protected logistic model: 6 (12 areas), 2 (4 areas), 0 (angle ignored) */
+    double edges[FX_RISK_MAX_EDGES];     /* ascending |angle| edges [rad]: (-e0, e0) is the front bin (coefficient 0) */
+    double coef_pos[FX_RISK_MAX_EDGES];  /* [j], j >= 1: angle in [e(j-1), e(j)) */
+    double coef_neg[FX_RISK_MAX_EDGES];  /* [j], j >= 1: angle in (-e(j), -e(j-1)] */
+    double coef_else;                    /* every other angle (rear; NaN; angles are not wrapped) */
+    double prot_c, prot_s;               /* protected logistic model: const, speed */
+    double prot_ref, prot_exp;           /* protected reference-speed model */
+    double uego_c, uego_s;               /* ego vs. unprotected, logistic: 1/(1+exp(-c - s dv)) */
+    double uego_ref, uego_exp;           /* ego vs. unprotected, reference speed */
+    double ped_c, ped_s;                 /* unprotected obstacle: 1/(1+exp(c - s dv)) */
+    double ego_length, ego_width, ego_mass;
+} FxRiskParams;
+/* Predictions of the K obstacles, once per plan step: pos [K][P][2], cov [K][P][4] (raw), cov_inv [K][P][4] (Mahalanobis mode;
+ * may be NULL otherwise), yaw [K][P], v [K][P]; n_pos [K] = len(pos_list) (<= P), n_yaw / n_v [K] the lengths of
+ * orientation_list / v_list; length, width, mass [K]; cls [K] FX_RISK_CLASS_*.  Checked at fx_eval_risk_agent against the
+ * step's horizon: yaw must cover min(S, n_pos) entries and v min(S - 1, n_pos) (collision_probability.py:180,
+ * harm_estimation.py:282-300).  K = 0 clears. */
+int32_t fx_set_risk_obstacles_agent(FxContext *ctx, int32_t agent, int32_t K, int32_t P, const double *pos, const double *cov,
+                                    const double *cov_inv, const double *yaw, const double *v, const int32_t *n_pos,
+                                    const int32_t *n_yaw, const int32_t *n_v, const double *length, const double *width,
+                                    const double *mass, const int32_t *cls);
+/* ego_risk / obst_risk of candidates of the last plan step (max over obstacles of max over steps of harm x probability) and the
+ * arg-min of ego + obst over them, ties to the lower candidate index (-1 when there is none).  ids NULL: every candidate whose
+ * flags hold VALID, FEASIBLE and RETURNED; ego_risk / obst_risk then have C entries, NaN for the others.  Otherwise the n_ids
+ * listed candidates, in that order.  Needs FX_MODE_WRITE_BUNDLE (FX_ERR_NOT_READY otherwise).  Synchronous. */
+int32_t fx_eval_risk_agent(FxContext *ctx, int32_t agent, const FxRiskParams *params, int64_t n_ids, const int64_t *ids,
+                           double *ego_risk, double *obst_risk, int64_t *min_risk_index);
+/* device time of the last fx_eval_risk_agent (risk pass + arg-min), ms */
+double fx_last_risk_ms(FxContext *ctx);
 
 #ifdef __cplusplus
 }

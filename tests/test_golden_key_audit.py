@@ -6,7 +6,8 @@ unnoticed.  This audit is static (it reads the test sources), so it holds for ev
 
   * plan-step fixtures (tests/golden/INDEX.json): every key of every .npz must be subscripted -- fx["key"], or named in the
     tuple of a `for k in ("a", "b"):` loop whose body reads fx[k] -- in a tests/test_*.py file (an expectation) or in
-    tests/fixtures.py (an input the scenario is rebuilt from);
+    tests/fixtures.py (an input the scenario is rebuilt from); and every expectation among them also on the device's side: in a
+    module that is gpu-marked as a whole or in a helper such a module imports (the CPU oracle's tests alone do not satisfy it);
   * refpath_golden.npz: every "<path>/<what>" key's <what> is read by tests/test_ref_path.py;
   * cpp_adapter_trace*.npz: every array is referenced by the recorded call trace next to it (tests/dropin/trace_recorder.replay
     resolves "@array" references), and the trace itself is replayed by a test;
@@ -68,6 +69,38 @@ def test_every_key_of_the_plan_step_fixtures_is_read():
     # the key whose absence prompted this audit is compared both on the oracle's side and on the HIP side
     assert "tau_lat" in _keys_read(_sources("test_oracle_golden.py")["test_oracle_golden.py"])
     assert "tau_lat" in _keys_read(_sources("test_hip_parity.py")["test_hip_parity.py"])
+
+
+def _gpu_side_sources():
+    """test modules that are `gpu`-marked as a whole, and the helper modules (tests/<name>.py, not tests themselves) they import"""
+    marked = {n: s for n, s in _sources("test_*.py").items() if re.search(r"^pytestmark\s*=\s*pytest\.mark\.gpu\s*$", s, re.M)}
+    helpers = {}
+    for src in marked.values():
+        for m in re.finditer(r"^\s*from\s+tests\.(\w+)\s+import|^\s*from\s+tests\s+import\s+(\w+)", src, re.M):
+            mod = (m.group(1) or m.group(2)) + ".py"
+            if not mod.startswith("test_") and os.path.exists(os.path.join(HERE, mod)):
+                helpers[mod] = open(os.path.join(HERE, mod)).read()
+    return marked, helpers
+
+
+def test_every_expectation_of_the_plan_step_fixtures_is_read_on_the_gpu_side():
+    """The audit above is satisfied by the CPU oracle's tests alone: a stored reference output can lose its last reader on the
+    device's side without anything turning red (cost, costmap, sorted_ids, reasons, hist, traj_len, coeff_lon, valid and costed
+    had none).  Every expectation key -- each key tests/fixtures.py does not read as an input -- must be read in a module that is
+    gpu-marked as a whole or in a helper module such a module imports (tests/reference_vectors.py)."""
+    names = sorted(json.load(open(os.path.join(GOLDEN, "INDEX.json"))))
+    marked, helpers = _gpu_side_sources()
+    assert "test_hip_parity.py" in marked and ME not in marked
+    inputs = _keys_read(_sources("fixtures.py")["fixtures.py"])
+    read = set()
+    for name, src in list(marked.items()) + list(helpers.items()):
+        if name != "fixtures.py":
+            read |= _keys_read(src)
+    unread = set()
+    for name in names:
+        with np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False) as z:
+            unread |= {k for k in z.files if k not in inputs and k not in read}
+    assert not unread, f"expectation keys of the plan-step fixtures no GPU test reads: {sorted(unread)}"
 
 
 def test_every_key_of_the_reference_path_fixture_is_read():

@@ -162,6 +162,8 @@ int32_t fx_destroy(FxContext *c) {
     for (void *p : dev) if (p) (void)hipFree(p);
     fx_risk_release(c);
     if (c->d_bstep) (void)hipFree(c->d_bstep);
+    if (c->d_cands) (void)hipFree(c->d_cands);
+    if (c->h_cands) (void)hipHostFree(c->h_cands);
     if (c->d_obs_part) (void)hipFree(c->d_obs_part);
     if (c->d_obs_colm) (void)hipFree(c->d_obs_colm);
     if (c->d_obs_ticket) (void)hipFree(c->d_obs_ticket);

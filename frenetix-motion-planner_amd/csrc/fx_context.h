@@ -53,6 +53,9 @@ extern "C" hipError_t fx_launch_topk(const DevProblem *d_probs, int n_agents, in
                                      double *out_cost, long long *out_idx, hipStream_t stream);
 
 
+extern "C" hipError_t fx_launch_gather_candidates(const GatherArgs *args, const int64_t *d_ids, int64_t n, unsigned long long *d_out,
+                                                  hipStream_t stream);
+
 extern thread_local char g_err[512];   // (defined in fx_api.hip)
 
 inline int set_err(int code, const char *fmt, ...) {
@@ -188,6 +191,9 @@ struct FxContext {
     bool package_enabled = false, pkg_step = false;
     double *h_cand = nullptr;  // pinned staging of fx_read_candidate_agent: planes | coeffs | raw costs | cost | traj_len | flags
     size_t h_cand_doubles = 0;
+    // chunk of fx_read_candidates_agent (FX_READ_CHUNK_BYTES each, allocated on its first call): ids | packed records, on the device
+    // and pinned
+    char *d_cands = nullptr, *h_cands = nullptr;
     long long *h_topk_idx = nullptr;
     int64_t total_ld = 0;  // capacity of per-candidate arrays (elements)
     int64_t max_blocks_total = 0;

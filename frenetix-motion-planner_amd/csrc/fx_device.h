@@ -278,6 +278,27 @@ struct StepArgs {
     int32_t walk_blocks;            // workgroups [0, walk_blocks) of every agent walk candidates
 };
 
+// arguments of fx_gather_candidates_kernel (fx_gather_kernel.h): one agent's structure-of-arrays outputs of the last step and which
+// of them that step produced.  A packed record is FX_GATHER_WORDS(S, n_cost) 8-byte words:
+//   planes[FX_NUM_PLANES][S] | lon[6] lat[6] tau_lat | raw_costs[n_cost] | cost | traj_len | flags | boundary_step
+// (the three integers sign- / zero-extended to 64 bits; words of parts the step did not produce are 0 and their arrays are not read)
+#define FX_GATHER_BUNDLE 1u
+#define FX_GATHER_COSTMAP 2u
+#define FX_GATHER_BOUNDARY 4u
+#define FX_GATHER_WORDS(S, n_cost) (FX_NUM_PLANES * (S) + FX_COEFF_ROWS + (n_cost) + 4)
+struct GatherArgs {
+    const double *planes;      // [FX_NUM_PLANES][S][ld]
+    const double *coeffs;      // [FX_COEFF_ROWS][ld]
+    const double *costmap;     // [n_cost][ld]
+    const double *cost;        // [ld]
+    const uint32_t *flags;     // [ld]
+    const int32_t *traj_len;   // [ld]
+    const int32_t *bound_step; // [ld]
+    int64_t ld, C;
+    int32_t S, n_cost;
+    uint32_t parts;            // FX_GATHER_*
+};
+
 // Pointers stored inside DevProblem are loaded from memory, so the compiler only knows them as generic ("flat")
 // pointers: every access would be a flat_load/flat_store and wave-uniform reads could not become scalar loads.
 // They all point into hipMalloc'ed memory -- say so.

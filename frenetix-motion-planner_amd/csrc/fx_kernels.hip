@@ -30,6 +30,7 @@
 #include "fx_obstacle_kernel.h"
 #include "fx_step_kernel.h"
 #include "fx_risk_kernel.h"
+#include "fx_gather_kernel.h"
 
 using fxk::wave_count;
 
@@ -605,5 +606,13 @@ extern "C" hipError_t fx_launch_risk(const double *planes, int64_t ld, int S, in
                            rec, obs, pos, yaw, vo, K, P, *params, out_ego, out_obst);
     hipLaunchKernelGGL(fxrisk::fx_risk_argmin_kernel, dim3(1), dim3(1024), 0, stream, out_ego, out_obst, n, ids, out_idx);
     if (ev_stop) { hipError_t e = hipEventRecord(ev_stop, stream); if (e != hipSuccess) return e; }
+    return hipGetLastError();
+}
+
+// batched candidate read-back (fx_gather_kernel.h): one workgroup per listed candidate
+extern "C" hipError_t fx_launch_gather_candidates(const GatherArgs *args, const int64_t *d_ids, int64_t n, unsigned long long *d_out,
+                                                  hipStream_t stream) {
+    if (n > 0)
+        hipLaunchKernelGGL(fx_gather_candidates_kernel, dim3((unsigned)n), dim3(FX_GATHER_BLOCK), 0, stream, *args, d_ids, n, d_out);
     return hipGetLastError();
 }

@@ -13,6 +13,7 @@ import numpy as np
 from . import _abi
 from ._lib import check, lib
 from .problem import PlanInputs
+from .trajectories import StepRegistry
 
 
 def build_obstacle_hulls(n_pred, pos, yaw, length, width) -> np.ndarray:
@@ -198,7 +199,7 @@ def device_count() -> int:
     return n.value
 
 
-class FrenetEngine:
+class FrenetEngine(StepRegistry):
     def __init__(self, max_candidates: int, max_steps: int = 30, max_ref_knots: int = 1024, max_obstacles: int = 32,
                  max_pred_steps: int = 64, device: int = 0, max_agents: int = 1):
         self._ctx = C.c_void_p()
@@ -214,8 +215,12 @@ class FrenetEngine:
     # -- lifetime --
     def close(self):
         if getattr(self, "_ctx", None) is not None and self._ctx.value:
-            lib().fx_destroy(self._ctx)
-            self._ctx = C.c_void_p()
+            try:
+                if self._steps:   # samples somebody still holds read this context's buffers: the last moment to bring them over
+                    self.rescue_steps()
+            finally:              # (a failed read must not leak the context)
+                lib().fx_destroy(self._ctx)
+                self._ctx = C.c_void_p()
 
     def __del__(self):
         try:
@@ -329,6 +334,8 @@ class FrenetEngine:
 
     # -- plan step, split so callers can overlap host work (upload/evaluate enqueue only) --
     def upload(self, inputs):
+        if self._steps:
+            self.rescue_steps()
         batch = list(inputs) if isinstance(inputs, (list, tuple)) else [inputs]
         self._inputs = batch
         self._resident_key = None
@@ -413,6 +420,8 @@ class FrenetEngine:
 
     def update_step_raw(self, update):
         """update_state(agent 0) + step_raw() in ONE call across the boundary"""
+        if self._steps:
+            self.rescue_steps()
         res = getattr(self, "_res_buf", None)
         if res is None or len(res) != len(self._inputs):
             res = self._res_buf = (_abi.FxResult * len(self._inputs))()
@@ -420,6 +429,8 @@ class FrenetEngine:
         return res
 
     def evaluate(self):
+        if self._steps:
+            self.rescue_steps()
         check(lib().fx_evaluate(self._ctx))
 
     def finish(self):
@@ -432,6 +443,8 @@ class FrenetEngine:
     def step_raw(self):
         """evaluate() + finish() for the resident inputs in ONE call across the boundary; returns the FxResult array
         (fields as attributes: best_index, best_cost, n_feasible, ...) without building Python dicts."""
+        if self._steps:
+            self.rescue_steps()
         n = len(self._inputs)
         res = getattr(self, "_res_buf", None)
         if res is None or len(res) != n:
@@ -440,6 +453,8 @@ class FrenetEngine:
         return res
 
     def plan_step(self, inputs: PlanInputs) -> dict:
+        if self._steps:
+            self.rescue_steps()
         self.upload(inputs)
         self.evaluate()
         return self.finish()[0]
@@ -449,6 +464,8 @@ class FrenetEngine:
         has the structure of `inputs` (PlanInputs.structure_key) only the ego state, sampling values and predictions are
         rewritten in place, else everything is uploaded; evaluation; result; the winner's arrays, which the device gathers
         into pinned host memory behind the selection.  Returns (result dict, WinnerPackage or None)."""
+        if self._steps:
+            self.rescue_steps()
         key = inputs.structure_key()
         upd = None
         h = _fxhost()
@@ -521,6 +538,8 @@ class FrenetEngine:
     def step_exchange_topk_raw(self, k: int):
         """evaluate + per-agent top-k + ONE all-gather + finish in one call (fx_step_exchange_topk):
         (FxResult array, cost [W, A, k], index [W, A, k]) with A = the communicator's agent rows (comm_set_agents)"""
+        if self._steps:
+            self.rescue_steps()
         n, A = len(self._inputs), self._comm_agents
         res = getattr(self, "_res_buf", None)
         if res is None or len(res) != n:
@@ -538,6 +557,8 @@ class FrenetEngine:
     def step_exchange_raw(self):
         """evaluate + all-gather of every rank's winner(s) + finish in ONE call: (FxResult array, cost [W, A], index [W, A]) with
         A = the communicator's agent rows (comm_set_agents; rows a rank does not fill say cost inf / index -1)"""
+        if self._steps:
+            self.rescue_steps()
         n, A = len(self._inputs), self._comm_agents
         res = getattr(self, "_res_buf", None)
         if res is None or len(res) != n:
@@ -565,6 +586,8 @@ class FrenetEngine:
         """One batched launch over the agents.  When the resident upload has the same agents' structures
         (PlanInputs.structure_key) only their states, sampling values and predictions are rewritten in place
         (fx_update_state per agent, one staging copy in front of the evaluation); otherwise everything is uploaded."""
+        if self._steps:
+            self.rescue_steps()
         inputs = list(inputs)
         keys = [inp.structure_key() if inp.sampling_matrix is None else None for inp in inputs]
         if self._resident_keys is not None and keys == self._resident_keys and None not in keys:
@@ -582,6 +605,8 @@ class FrenetEngine:
         `_fxhost.plan_batch`: the inputs' arrays are read in C, the results come back as dicts): ([result dict],
         [WinnerPackage or None]).  The general path -- different structures, a sampling matrix, horizons of different
         lengths, no extension -- is plan_batch() followed by package() per agent."""
+        if self._steps:
+            self.rescue_steps()
         inputs = list(inputs)
         n = len(inputs)
         keys = [inp.structure_key() if inp.sampling_matrix is None else None for inp in inputs]
@@ -609,6 +634,8 @@ class FrenetEngine:
         """First half of plan_batch_packaged: the agents' states rewritten in place (or everything uploaded) and the evaluation
         launched -- returns without waiting (fx_plan_batch_begin).  The token goes to plan_batch_end.  None when the batch
         cannot take the packaged path (see plan_batch_packaged): the caller then uses that one."""
+        if self._steps:
+            self.rescue_steps()
         inputs = list(inputs)
         n = len(inputs)
         h = _fxhost()
@@ -694,6 +721,41 @@ class FrenetEngine:
                                             raw.ctypes.data_as(pd) if have_c else None, C.byref(cost), C.byref(flags)))
         return dict(planes=planes if have_b else None, lon=co[:6].copy(), lat=co[6:12].copy(), tau_lat=float(co[12]), traj_len=tl.value,
                     raw_costs=raw[:len(inp.cost_names)] if have_c else None, cost=cost.value, flags=flags.value)
+
+    def candidates(self, ids, agent: int = 0) -> dict:
+        """candidate() for a list of indices in ONE call (fx_read_candidates_agent: a gather kernel behind the step, one copy and
+        one synchronisation per chunk of _abi.FX_READ_CHUNK_BYTES): planes [n, 14, S], lon / lat [n, 6], tau_lat [n], traj_len [n],
+        raw_costs [n, n_cost], cost [n], flags [n], boundary_step [n], rows in the order of `ids` (any order, duplicates allowed);
+        None for the parts the step did not produce."""
+        inp = self._inputs[agent]
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        n, n_cost = len(ids), len(inp.cost_names)
+        # ascending indices: neighbouring workgroups of the gather then touch neighbouring lines; the rows are permuted back here
+        order = None
+        if n > 1 and not bool((ids[1:] >= ids[:-1]).all()):
+            order = np.argsort(ids, kind="stable")
+            ids = ids[order]
+        have_b, have_c = bool(inp.write_bundle), bool(inp.write_costmap) and n_cost > 0
+        have_r = inp._bound is not None and inp._bound["n"] > 0
+        planes = np.empty((n, _abi.FX_NUM_PLANES, inp.n_samples)) if have_b else None
+        co = np.empty((n, 13)) if have_b else None
+        tl = np.empty(n, np.int32) if have_b else None
+        raw = np.empty((n, n_cost)) if have_c else None
+        cost, flags = np.empty(n), np.empty(n, np.uint32)
+        bst = np.empty(n, np.int32) if have_r else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(lib().fx_read_candidates_agent(self._ctx, int(agent), n, ptr(ids), ptr(planes), ptr(co), ptr(tl), ptr(raw), ptr(cost),
+                                             ptr(flags), ptr(bst)))
+        if order is not None:
+            def back(a):
+                if a is None:
+                    return None
+                out = np.empty_like(a)
+                out[order] = a
+                return out
+            planes, co, tl, raw, cost, flags, bst = (back(a) for a in (planes, co, tl, raw, cost, flags, bst))
+        return dict(planes=planes, lon=co[:, :6] if have_b else None, lat=co[:, 6:12] if have_b else None,
+                    tau_lat=co[:, 12] if have_b else None, traj_len=tl, raw_costs=raw, cost=cost, flags=flags, boundary_step=bst)
 
     def plane(self, name_or_index, agent: int = 0) -> np.ndarray:
         """[S, C] one plane of every candidate."""

@@ -206,6 +206,11 @@ def product_grid_of(m: np.ndarray):
 
 class TrajectoryHandler:
     detect_grid = True   # evaluate a sampling matrix that is a Cartesian product as ranges (grid kernel; identical results)
+    # TrajectorySample objects a caller still holds when the trajectories are reset or evaluated again keep answering: what they
+    # have not fetched yet is read in one batched call before the device buffers are overwritten (the reference keeps
+    # optimal_trajectory and all_traj across plan steps, reactive_planner_cpp.py:330, 430, 437).  False: nothing is read, such
+    # reads raise -- for callers that hold the whole list and never look at it again.
+    retain_samples = True
 
     def __init__(self, dt: float, engine=None, device: int = 0):
         self.dt = float(dt)
@@ -243,7 +248,7 @@ class TrajectoryHandler:
 
     def reset_Trajectories(self):
         if self._step is not None:
-            self._step.invalidate()
+            self._step.invalidate(rescue=True)   # (nothing has been launched yet: what is still held can be read)
         self._matrix, self._step, self._stop = None, None, None
 
     def generate_trajectories(self, sampling_matrix, low_vel_mode: bool):
@@ -348,7 +353,7 @@ class TrajectoryHandler:
             obstacles=pack_predictions(preds, N + 1, build_obstacle_hulls),
             dto_pos=dto.obstacle_positions if dto is not None else None, lanelets=lco.lanelets if lco is not None else None)
         if self._step is not None:
-            self._step.invalidate()
+            self._step.invalidate(rescue=True)
         if inputs.sampling_matrix is None and hasattr(self.engine, "plan_batch"):
             # same structure as the resident upload (the usual case from the second cycle on): only state, sampling values and
             # predictions are rewritten in place (fx_update_state) instead of a full upload
@@ -356,6 +361,7 @@ class TrajectoryHandler:
         else:
             res = self.engine.plan_step(inputs)
         self._step = PlanStepResult(self.engine, inputs, res)
+        self._step.retain = bool(self.retain_samples)
         return res
 
     def evaluate_all_current_functions(self, calculate_all_costs: bool = True):

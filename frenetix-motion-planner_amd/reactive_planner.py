@@ -87,6 +87,10 @@ class PlannerConfig:
     draw_traj_set: bool = True       # debug.yaml:8
     kinematic_debug: bool = True     # debug.yaml:20
     save_all_traj: bool = False
+    # samples a caller took from all_traj (visualisation, a logger, an occlusion module) keep answering after the next plan step /
+    # sampling level: what they have not fetched is read in one batched call before the device buffers are overwritten.
+    # False: only the chosen trajectory survives, other reads of an old step raise.
+    retain_samples: bool = True
     survivors: int = 16              # top-k kept for the host-side road-boundary walk
     # dense grid (n_t, n_v, n_d) in natural order instead of the reference's sampling levels (BASELINE configs 2 - 5): T from
     # t_min in steps of dt, V over the planner's velocity range, D over [d_min, d_max] plus the current d
@@ -582,7 +586,7 @@ class ReactivePlannerHip:
     def _get_optimal_trajectory(self, inputs: PlanInputs, samp_lvl: int):
         """reactive_planner.py:184-272: feasibility, costs, stable sort, collision walk -- one fused launch."""
         if self.last_step is not None:
-            self.last_step.invalidate()
+            self.last_step.invalidate(rescue=True)   # before the launch: samples still held are read first
         pkg = None
         if hasattr(self.engine, "plan_step_packaged"):
             # one call across the boundary: in-place update of the resident inputs, evaluation, result, the winner packaged
@@ -610,6 +614,7 @@ class ReactivePlannerHip:
         if self.last_step is not None:
             self.last_step.invalidate()
         step = PlanStepResult(engine, inputs, res, agent)
+        step.retain = self.config.retain_samples
         step.package = package
         lr = self.params_harm["log_reg"]["ignore_angle"]
         step.harm_coeff = (lr["const"], lr["speed"])

@@ -13,7 +13,12 @@ reads back; the 14 planes, the per-name cost map and the polynomial coefficients
 from device memory on first access and then cached, so the object stays valid after the next plan step
 overwrites the device buffers (the reference keeps `optimal_trajectory` alive across steps,
 reactive_planner_cpp.py:430,437 / frenet_interface.py:277).
+
+Samples a caller still holds when the next evaluation is about to overwrite the device buffers are *rescued*: the step reads
+what they have not fetched yet in ONE batched call (engine.candidates) into a host snapshot and answers them from it from
+then on (PlanStepResult.rescue, StepRegistry).
 """
+import weakref
 from typing import List, Optional
 
 import numpy as np
@@ -78,6 +83,22 @@ class TrajectorySample:
     # writable from Python (planner.py:325-326,381-382)
     _ego_risk = _obst_risk = _boundary_harm = None
     harm_occ_module = None
+    # A sample is a view the step holds WEAKLY (PlanStepResult._samples), so step.sample(g) may hand out a new object for a
+    # candidate whose earlier object nobody kept.  What anybody WROTE to a sample -- the planner's host walk (boundary_harm,
+    # _coll_detected), an occlusion module (cost, valid, harm_occ_module), the risk fields -- therefore lives with the step
+    # (PlanStepResult._written) and every object of that candidate starts from it: the state is the candidate's, not the view's.
+    # Everything that is assigned from outside is kept, except the view's own caches and the two properties that store under
+    # another name.
+    _UNKEPT = frozenset(("_planes", "_costmap", "_coeffs", "_pkg", "_sp", "_materialised", "cost", "boundary_harm", "__dict__"))
+
+    def __setattr__(self, name, value):
+        object.__setattr__(self, name, value)
+        if name not in self._UNKEPT:
+            step = self._step
+            w = step._written
+            if w is None:
+                w = step._written = {}
+            w.setdefault(self.uniqueId, {})[name] = value
 
     @classmethod
     def bulk(cls, step: "PlanStepResult", ids) -> list:
@@ -94,9 +115,8 @@ class TrajectorySample:
                 out.append(cls(step, g))
                 continue
             t = new(cls)
-            t._step, t.uniqueId, t.global_id, t._flags, t._cost = step, g, g + base, f, c
-            t.feasible, t.valid = bool(f & FEAS), bool(f & VALID)
-            t._coll_detected = bool(f & COLL) if (f & SEL) else None
+            t.__dict__.update(_step=step, uniqueId=g, global_id=g + base, _flags=f, _cost=c, feasible=bool(f & FEAS),
+                              valid=bool(f & VALID), _coll_detected=bool(f & COLL) if (f & SEL) else None)
             out.append(t)
         return out
 
@@ -109,33 +129,34 @@ class TrajectorySample:
         return self._step.inputs.N * self._step.inputs.dt
 
     def __init__(self, step: "PlanStepResult", index: int):
-        self._step = step
-        self.uniqueId = int(index)           # index within the evaluated shard (== creation order when nothing is sharded)
-        self.global_id = int(index) + step.inputs.shard_begin   # creation order in the whole grid (reactive_planner.py:172)
+        d = self.__dict__   # (the view's own fields are not "written from outside": they bypass __setattr__)
+        d["_step"] = step
+        d["uniqueId"] = int(index)           # index within the evaluated shard (== creation order when nothing is sharded)
+        d["global_id"] = int(index) + step.inputs.shard_begin   # creation order in the whole grid (reactive_planner.py:172)
         pkg = step.package
         if pkg is not None and pkg.index == int(index) + step.inputs.shard_begin:
             # the winner: the library has already delivered everything (fx_read_package), nothing is fetched
-            flags, self._cost = pkg.flags, pkg.cost
-            self._planes = pkg.planes
-            self._pkg = pkg   # (coefficients and the cost map are built from the package when they are asked for)
+            flags, d["_cost"] = pkg.flags, pkg.cost
+            d["_planes"] = pkg.planes
+            d["_pkg"] = pkg   # (coefficients and the cost map are built from the package when they are asked for)
         elif step.have_arrays:
             flags = int(step.flags[index])
-            self._cost = float(step.cost[index])
+            d["_cost"] = float(step.cost[index])
         else:
             # the step's cost / flag arrays have not been read back: fetch this candidate whole (one synchronisation)
             rec = step.fetch_candidate(index)
             flags = int(rec["flags"])
-            self._cost = float(rec["cost"])
+            d["_cost"] = float(rec["cost"])
             if rec["planes"] is not None:
-                self._planes = rec["planes"]
-                self._coeffs = (rec["lon"], rec["lat"], rec["traj_len"], rec["tau_lat"])
+                d["_planes"] = rec["planes"]
+                d["_coeffs"] = (rec["lon"], rec["lat"], rec["traj_len"], rec["tau_lat"])
             if rec["raw_costs"] is not None:
                 names, w = step.inputs.cost_names, step.inputs.cost_weights
-                self._costmap = {n: (float(rec["raw_costs"][k]), float(w[n] * rec["raw_costs"][k])) for k, n in enumerate(names)}
-        self._flags = flags
-        self.feasible = bool(flags & _abi.FX_FLAG_FEASIBLE)
-        self.valid = bool(flags & _abi.FX_FLAG_VALID)
-        self._coll_detected = bool(flags & _abi.FX_FLAG_COLLISION) if (flags & _abi.FX_FLAG_SELECTABLE) else None
+                d["_costmap"] = {n: (float(rec["raw_costs"][k]), float(w[n] * rec["raw_costs"][k])) for k, n in enumerate(names)}
+        d["_flags"] = flags
+        d["feasible"] = bool(flags & _abi.FX_FLAG_FEASIBLE)
+        d["valid"] = bool(flags & _abi.FX_FLAG_VALID)
+        d["_coll_detected"] = bool(flags & _abi.FX_FLAG_COLLISION) if (flags & _abi.FX_FLAG_SELECTABLE) else None
 
     # ---- cheap attributes ----
     @property
@@ -282,17 +303,72 @@ class StandstillSample:
         self.harm_occ_module = None
 
 
+_STALE_MSG = "this plan step's device data has been overwritten; materialise() samples you keep"
+
+
+class StepRegistry:
+    """Mix-in of an engine: the plan steps whose samples read this engine's buffers, held weakly.  Every method of the engine
+    that launches an evaluation into those buffers (and close()) calls `rescue_steps()` FIRST -- `if self._steps:
+    self.rescue_steps()`, one truthiness test when nothing is registered.  The rescue belongs here and not with the planner: a
+    batch launches first and consumes second (multiagent.AgentBatchHip.step), so a planner that rescued in its own
+    invalidate() would read the NEW step's data into the OLD samples."""
+    _steps = ()
+
+    def register_step(self, step):
+        if not self._steps:
+            self._steps = []
+        self._steps.append(weakref.ref(step))
+
+    def rescue_steps(self):
+        steps, self._steps = self._steps, ()
+        for ref in steps:
+            step = ref()
+            if step is not None:
+                step.invalidate(rescue=True)
+
+
+class _RescuedColumn:
+    """a per-candidate array of a stale step of which only the rescued entries exist: column[index]"""
+
+    def __init__(self, step, values):
+        self._step, self._values = step, values
+
+    def __getitem__(self, index):
+        if not isinstance(index, (int, np.integer)):
+            raise RuntimeError(_STALE_MSG)   # the whole array went with the device data: one rescued candidate at a time
+        return self._values[self._step._row(index)]
+
+    def __len__(self):
+        raise RuntimeError(_STALE_MSG)
+
+    def __array__(self, *args, **kwargs):
+        raise RuntimeError(_STALE_MSG)
+
+
 class PlanStepResult:
     """Everything one evaluated plan step produced; hands out TrajectorySample views."""
+
+    retain = True                        # rescue the samples still held when the next evaluation overwrites the buffers
+    _open = False                        # a sample that still needs the device has been handed out (the engine then knows this step)
+    _snap = _snap_ids = None             # rescue(): engine.candidates() of the rescued indices (ascending) and those indices
+    _written = None                      # index -> {attribute: value}: what was assigned to samples from outside (TrajectorySample.__setattr__)
 
     def __init__(self, engine, inputs, result: dict, agent: int = 0):
         self.engine, self.inputs, self.result, self.agent = engine, inputs, result, agent
         self.package = None               # engine.WinnerPackage of the step's winner when the library packaged it
         self._cost = self._flags = None   # [C] arrays, read back on first use (all_traj, masks, sorted lists)
         self._stale = False
-        self._samples = {}
+        self._samples = {}                # index -> weak reference: the step must be able to tell which samples a caller still holds
         self.harm_coeff = (-4.591, 0.185)  # log_reg.ignore_angle const / speed (configurations/harm_parameters.json)
         self._bsteps = None
+
+    def _opened(self):
+        """the first sample that is not complete on the host leaves: from now on the engine asks this step to rescue() before it
+        overwrites the buffers (a closed loop that only ever takes the packaged winner never gets here)"""
+        self._open = True
+        reg = getattr(self.engine, "register_step", None)
+        if reg is not None:
+            reg(self)
 
     @property
     def have_arrays(self) -> bool:
@@ -314,42 +390,128 @@ class PlanStepResult:
         return self._flags
 
     def fetch_candidate(self, index) -> dict:
-        self._check()
+        if self._stale:
+            k, sn = self._row(index), self._snap
+            one = lambda name: None if sn[name] is None else sn[name][k]
+            return dict(planes=one("planes"), lon=one("lon"), lat=one("lat"), tau_lat=one("tau_lat"), traj_len=one("traj_len"),
+                        raw_costs=one("raw_costs"), cost=sn["cost"][k], flags=sn["flags"][k])
         return self.engine.candidate(int(index), self.agent)
 
     @property
-    def boundary_steps(self) -> np.ndarray:
+    def boundary_steps(self):
+        """[C] first step outside the road per candidate; of a stale step only the rescued entries exist: index it with one
+        candidate (anything else raises the stale-step error)"""
         if self._bsteps is None:
+            if self._stale and self._snap is not None and self._snap["boundary_step"] is not None:
+                return _RescuedColumn(self, self._snap["boundary_step"])
             self._check()
             self._bsteps = self.engine.boundary_steps(self.agent)
         return self._bsteps
 
-    def invalidate(self):
-        """The engine is about to run another step: device buffers will be overwritten."""
+    # ---- life beyond the next evaluation ----
+    def live_samples(self) -> list:
+        """the samples handed out that somebody still references"""
+        return [t for t in (ref() for ref in self._samples.values()) if t is not None]
+
+    def rescue(self):
+        """The engine is about to overwrite this step's device data: read what the samples still held have not fetched yet --
+        ONE engine.candidates() call -- into a host snapshot; fetch_* answer the rescued indices from it once the step is
+        stale.  Samples that are complete (materialised, or carrying the winner package) need nothing.  A no-op on a stale
+        step; on a fresh one a later call replaces the snapshot by one of the samples held THEN."""
+        if self._stale or not self._open:
+            return
+        ids = set()
+        for ref in self._samples.values():
+            t = ref()
+            if t is not None and not t._materialised and t._pkg is None:
+                ids.add(t.uniqueId)
+        if not ids:
+            return
+        ids = np.array(sorted(ids), dtype=np.int64)
+        eng = self.engine
+        self._snap = eng.candidates(ids, self.agent) if hasattr(eng, "candidates") else self._read_per_sample(ids)
+        self._snap_ids = ids
+
+    def _read_per_sample(self, ids) -> dict:
+        """what engine.candidates(ids) returns, from the per-sample methods of an engine without it (duck-typed stand-ins)"""
+        eng, inp, a = self.engine, self.inputs, self.agent
+        planes = lon = lat = tau = tl = raw = bst = None
+        if inp.write_bundle:
+            planes = np.stack([eng.sample(int(g), a) for g in ids])
+            co = [eng.coeffs(int(g), a) for g in ids]
+            lon, lat = np.stack([c[0] for c in co]), np.stack([c[1] for c in co])
+            tl, tau = np.array([c[2] for c in co], np.int32), np.array([c[3] for c in co])
+        if inp.write_costmap and len(inp.cost_names) > 0:
+            if not hasattr(self, "_cm"):
+                self._cm = eng.costmap(a)
+            raw = self._cm[ids]
+        if inp._bound is not None and inp._bound["n"] > 0:
+            bst = self.boundary_steps[ids]
+        return dict(planes=planes, lon=lon, lat=lat, tau_lat=tau, traj_len=tl, raw_costs=raw, cost=self.cost[ids].copy(),
+                    flags=self.flags[ids].copy(), boundary_step=bst)
+
+    def invalidate(self, rescue: bool = False):
+        """This step's device data is gone -- rescue=False: already overwritten (the meaning this call always had); rescue=True:
+        ABOUT to be overwritten, the caller runs before the launch, so what is still held is read first (unless `retain` is off)."""
+        if self._stale:
+            return
+        if rescue and self._open and self.retain:
+            self.rescue()
         self._stale = True
 
     def _check(self):
         if self._stale:
-            raise RuntimeError("this plan step's device data has been overwritten; materialise() samples you keep")
+            raise RuntimeError(_STALE_MSG)
+
+    def _row(self, index) -> int:
+        """row of candidate `index` in the snapshot of a stale step; the stale-step error for an index that was not rescued"""
+        ids = self._snap_ids
+        if ids is not None:
+            k = int(np.searchsorted(ids, index))
+            if k < len(ids) and ids[k] == index:
+                return k
+        raise RuntimeError(_STALE_MSG)
+
+    def _rescued(self, name, index, missing):
+        part = self._snap[name] if self._snap is not None else None
+        k = self._row(index)
+        if part is None:   # the step did not produce it: what the library answers on a fresh step
+            raise ValueError(f"fxplan: plan step ran without {missing} (status {_abi.FX_ERR_NOT_READY})")
+        return part, k
 
     def fetch_sample(self, index):
-        self._check()
+        if self._stale:
+            part, k = self._rescued("planes", index, "FX_MODE_WRITE_BUNDLE")
+            return part[k]
         return self.engine.sample(index, self.agent)
 
     def fetch_costmap_row(self, index):
-        self._check()
+        if self._stale:
+            part, k = self._rescued("raw_costs", index, "FX_MODE_WRITE_COSTMAP")
+            return part[k]
         if not hasattr(self, "_cm"):
             self._cm = self.engine.costmap(self.agent)
         return self._cm[index]
 
     def fetch_coeffs(self, index):
-        self._check()
+        if self._stale:
+            lon, k = self._rescued("lon", index, "FX_MODE_WRITE_BUNDLE")
+            sn = self._snap
+            return lon[k], sn["lat"][k], int(sn["traj_len"][k]), float(sn["tau_lat"][k])
         return self.engine.coeffs(index, self.agent)
 
     def sample(self, index: int) -> TrajectorySample:
-        if index not in self._samples:
-            self._samples[index] = TrajectorySample(self, index)
-        return self._samples[index]
+        ref = self._samples.get(index)
+        t = ref() if ref is not None else None
+        if t is None:
+            t = TrajectorySample(self, index)
+            self._samples[index] = weakref.ref(t)
+            if t._pkg is None and not self._open:
+                self._opened()
+            w = self._written
+            if w is not None and index in w:   # an earlier object of this candidate was written to and dropped
+                t.__dict__.update(w[index])
+        return t
 
     # ---- views the planner needs ----
     @property
@@ -366,11 +528,20 @@ class PlanStepResult:
 
     def samples(self, ids) -> List[TrajectorySample]:
         """the samples of `ids` (indices within the shard), in that order"""
-        todo = [int(g) for g in ids if int(g) not in self._samples]
+        ids = [int(g) for g in ids]
+        known = self._samples
+        todo = [g for g in ids if g not in known or known[g]() is None]
+        made = {}
         if len(todo) > 8:   # many new samples at once (the adapter's sorted list): built from the arrays in one go
+            if not self._open:
+                self._opened()
+            w = self._written
             for t in TrajectorySample.bulk(self, todo):
-                self._samples[t.uniqueId] = t
-        return [self.sample(int(g)) for g in ids]
+                known[t.uniqueId] = weakref.ref(t)
+                made[t.uniqueId] = t
+                if w is not None and t.uniqueId in w:
+                    t.__dict__.update(w[t.uniqueId])
+        return [made.get(g) or self.sample(g) for g in ids]
 
     def sorted_trajectories(self, pool_bit=_abi.FX_FLAG_COSTED, limit: Optional[int] = None) -> List[TrajectorySample]:
         ids = self.sorted_ids(pool_bit)

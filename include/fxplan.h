@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 10
+#define FX_ABI_VERSION 11
 
 /* ---- status codes (planner.py / reactive_planner_cpp.py raise Python exceptions; the shim maps
  *      <0 -> ValueError, >0 -> RuntimeError, see SURVEY 8b "Error conventions") ---- */
@@ -438,6 +438,26 @@ int32_t fx_read_plane_agent(FxContext *ctx, int32_t agent, int32_t plane, double
  * cost and flag word.  Any output pointer may be NULL.  What the planner reads back for the chosen trajectory. */
 int32_t fx_read_candidate_agent(FxContext *ctx, int32_t agent, int64_t index, double *planes, double *coeffs13,
                                 int32_t *traj_len, double *raw_costs, double *cost, uint32_t *flags);
+/* fx_read_candidate_agent for n candidates of one agent in one call -- what the reference's adapter asks of every evaluated
+ * trajectory each plan step (reactive_planner_cpp.py:353-358) and what a planner keeps across steps (:430, 437: optimal_trajectory,
+ * all_traj) -- in the caller's order (unsorted lists and duplicates are legal).  A gather kernel behind the step packs one record
+ * per listed candidate (planes | lon lat tau_lat | raw costs | cost | traj_len | flags | boundary_step) into a device buffer, one
+ * asynchronous copy brings it to pinned memory, one stream synchronisation -- per chunk of FX_READ_CHUNK_BYTES (the indices travel
+ * in the same chunk: 8 bytes per candidate on top of its record), so the number of synchronisations is
+ * ceil(n / floor(FX_READ_CHUNK_BYTES / (record bytes + 8))): 1 for everything a planner-sized step holds (800 candidates x 3.7 KB).
+ * The two chunk buffers (device and pinned) are allocated on the first call.  Any output pointer may be NULL.  Same contract as
+ * fx_read_candidate_agent: FX_ERR_NOT_READY where a requested part was not produced by the step (boundary_step: FX_MODE_ROAD_BOUNDARY),
+ * FX_ERR_INVALID_ARGUMENT for n < 0, ids == NULL with n > 0 or any index outside [0, C) -- checked before anything is launched or
+ * written; n == 0 returns FX_OK without device work. */
+#define FX_READ_CHUNK_BYTES (8u << 20)
+int32_t fx_read_candidates_agent(FxContext *ctx, int32_t agent, int64_t n, const int64_t *ids,
+                                 double *planes        /* [n][FX_NUM_PLANES][S] or NULL */,
+                                 double *coeffs13      /* [n][13]: lon[6] | lat[6] | tau_lat, or NULL */,
+                                 int32_t *traj_len     /* [n] or NULL */,
+                                 double *raw_costs     /* [n][n_cost] or NULL */,
+                                 double *cost          /* [n] or NULL */,
+                                 uint32_t *flags       /* [n] or NULL */,
+                                 int32_t *boundary_step/* [n] or NULL */);
 int32_t fx_read_topk_batch(FxContext *ctx, int32_t k, double *cost /*[n_agents][k]*/, int64_t *index /*[n_agents][k]*/);
 
 /* ---- road boundary (replaces create_road_boundary_obstacle + trajectories_collision_static_obstacles,

@@ -5,7 +5,7 @@ wrapper (oracle/oracle.py) can share the struct definitions.
 """
 import ctypes as C
 
-FX_ABI_VERSION = 11
+FX_ABI_VERSION = 12
 FX_READ_CHUNK_BYTES = 8 << 20   # fx_read_candidates_agent: bytes per chunk (ids + packed records)
 FX_LON_VELOCITY_KEEPING, FX_LON_STOP_POINT = 0, 1
 
@@ -137,3 +137,21 @@ class FxRiskParams(C.Structure):
                 ("coef_neg", C.c_double * FX_RISK_MAX_EDGES)] + \
                [(n, C.c_double) for n in ("coef_else", "prot_c", "prot_s", "prot_ref", "prot_exp", "uego_c", "uego_s", "uego_ref",
                                           "uego_exp", "ped_c", "ped_s", "ego_length", "ego_width", "ego_mass")]
+
+
+# per-obstacle risk and harm, risk-cost principles, responsibility (fxplan.h FxRiskCostParams / FxRiskOutputs)
+FX_RISK_RESP_NONE, FX_RISK_RESP_ACTION_SPACE, FX_RISK_RESP_REACH_SET = 0, 1, 2
+FX_RISK_BOUNDARY_ZERO, FX_RISK_BOUNDARY_ARRAY, FX_RISK_BOUNDARY_STEP = 0, 1, 2
+RISK_COST_NAMES = ("bayes", "equality", "maximin", "ego", "responsibility")   # order of FxRiskCostParams.weights
+
+
+class FxRiskCostParams(C.Structure):
+    _fields_ = [("weights", C.c_double * 5), ("maximin_eps", C.c_double), ("maximin_scale", C.c_double),
+                ("boundary_mode", C.c_int32), ("responsibility_mode", C.c_int32), ("boundary_c", C.c_double),
+                ("boundary_s", C.c_double), ("boundary_harm", C.c_void_p), ("responsibility", C.c_void_p)]
+
+
+class FxRiskOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("ego_risk", "obst_risk", "obst_harm_occ", "ego_risk_max", "obst_risk_max", "ego_harm_max",
+                                          "obst_harm_max", "bayes", "equality", "maximin", "ego", "responsibility", "total",
+                                          "boundary_harm", "min_risk_index", "min_cost_index")]

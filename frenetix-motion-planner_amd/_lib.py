@@ -41,6 +41,7 @@ def exported_symbols():
         "fx_read_topk", "fx_read_topk_batch", "fx_topk_to_device", "fx_build_obstacle_hulls", "fx_device_bytes",
         "fx_last_kernel_ms", "fx_last_eval_kernel_ms", "fx_device_views",
         "fx_set_risk_obstacles_agent", "fx_eval_risk_agent", "fx_last_risk_ms",
+        "fx_set_reach_sets_agent", "fx_eval_risk_costs_agent",
     ]
 
 
@@ -135,6 +136,9 @@ def lib():
                                         C.c_int32),
         "fx_eval_risk_agent": ([vp, C.c_int32, C.POINTER(_abi.FxRiskParams), C.c_int64, pi64, pd, pd, pi64], C.c_int32),
         "fx_last_risk_ms": ([vp], C.c_double),
+        "fx_set_reach_sets_agent": ([vp, C.c_int32, C.c_int32, pi32, pi32, C.c_int32, pi32, pi32, C.c_int32, pd], C.c_int32),
+        "fx_eval_risk_costs_agent": ([vp, C.c_int32, C.POINTER(_abi.FxRiskParams), C.POINTER(_abi.FxRiskCostParams), C.c_int64, pi64,
+                                      C.POINTER(_abi.FxRiskOutputs)], C.c_int32),
         "fx_read_candidate_agent": ([vp, C.c_int32, C.c_int64, pd, pd, pi32, pd, pd, pu32], C.c_int32),
         "fx_read_candidates_agent": ([vp, C.c_int32, C.c_int64] + [vp] * 8, C.c_int32),   # (arrays: plain addresses)
         "fx_read_plane": ([vp, C.c_int32, pd], C.c_int32),

@@ -1,5 +1,7 @@
 // fx_risk_kernel.h -- trajectory risk (risk_costs.py:20-118, crash_angle_simplified) over the materialised bundle, and the
 // arg-min of ego + obstacle risk (reactive_planner.py:262-269, reactive_planner_cpp.py:404-413).  DESIGN.md section 11.
+// The same walk with calc_risk's per-obstacle results, and the risk-cost principles with the responsibility cost over them
+// (risk_costs.py:124-251, utility/responsibility.py).  DESIGN.md section 13.
 //
 // One lane per candidate.  Every lane walks the (obstacle, step) pairs in the same order, so everything indexed by them -- the
 // three obstacle means, the standardisation (sigma_x, sigma_y, rho), the |rho| branch of the bivariate normal and its node terms
@@ -13,6 +15,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "fx_risk_args.h"
 #include "fx_select.h"
 
 // record of one (obstacle, ego step i): doubles
@@ -149,38 +152,57 @@ __device__ __forceinline__ double step_probability(const FxRiskParams &p, const 
     return prob / 3.0;
 }
 
-// One lane per listed candidate: out_ego / out_obst [n] (NaN where the candidate is not selected)
-__global__ __launch_bounds__(256) void fx_risk_kernel(const double *__restrict__ planes, int64_t ld, int S, int64_t n,
-                                                      const int64_t *__restrict__ ids, const uint32_t *__restrict__ flags,
-                                                      const double *__restrict__ rec, const double *__restrict__ obs,
-                                                      const double *__restrict__ pos, const double *__restrict__ yaw,
-                                                      const double *__restrict__ vo, int K, int P, FxRiskParams p,
-                                                      double *__restrict__ out_ego, double *__restrict__ out_obst) {
+// The candidate walk of lane j.  DETAIL = false: ego / obstacle risk (max over obstacles of max over steps of harm x probability),
+// harm evaluated only where the probability is not zero.  DETAIL = true adds what calc_risk returns per
+// obstacle -- col [4][K][n] = ego_risk_max | obst_risk_max | ego_harm_max | obst_harm_max, obstacle-major, so that the 64 lanes of a
+// wave store 512 contiguous bytes per column -- and obst_harm_occ [n]; the harm is then evaluated at every t < pl
+// (risk_costs.py:109-112 take the maxima of the whole harm lists).  The products and their order are the same in both.
+template <bool DETAIL>
+__device__ __forceinline__ void risk_walk(const double *__restrict__ planes, int64_t ld, int S, int64_t n, const int64_t *__restrict__ ids,
+                                          const uint32_t *__restrict__ flags, const double *__restrict__ rec,
+                                          const double *__restrict__ obs, const double *__restrict__ pos,
+                                          const double *__restrict__ yaw, const double *__restrict__ vo, int K, int P,
+                                          const FxRiskParams &p, double *__restrict__ out_ego, double *__restrict__ out_obst,
+                                          double *__restrict__ col, double *__restrict__ out_occ) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const int64_t c = ids ? ids[j] : j;
     const uint32_t need = FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED;
-    if (!ids && (flags[c] & need) != need) { out_ego[j] = NAN; out_obst[j] = NAN; return; }
+    if (!ids && (flags[c] & need) != need) {
+        out_ego[j] = NAN;
+        out_obst[j] = NAN;
+        if (DETAIL) {
+            out_occ[j] = NAN;
+            for (int q = 0; q < 4 * K; q++) col[(size_t)q * n + j] = NAN;
+        }
+        return;
+    }
     const double *X = planes + c, *Y = planes + (size_t)S * ld + c, *TH = planes + 2 * (size_t)S * ld + c,
                  *V = planes + 3 * (size_t)S * ld + c;
     const double me = p.ego_mass;
-    double ego_best = -INFINITY, obst_best = -INFINITY;
+    double ego_best = -INFINITY, obst_best = -INFINITY, occ_best = -INFINITY;
     bool any = false;
     for (int k = 0; k < K; k++) {
         const double *o = obs + (size_t)k * FXO_STRIDE;
         const int npos = (int)o[FXO_NPOS];
         const int pl = min(S - 1, npos);
-        if (pl <= 0) continue;
+        if (pl <= 0) {   // (the detail entry point refuses such an obstacle: np.max of an empty list upstream)
+            if (DETAIL)
+                for (int q = 0; q < 4; q++) col[((size_t)q * K + k) * n + j] = 0.0;
+            continue;
+        }
         const bool prot = o[FXO_CLS] == (double)FX_RISK_CLASS_PROTECTED;
         const double mo = o[FXO_MASS];
         const double f_ego = mo / (me + mo), f_obs = me / (me + mo);
         double e_max = -INFINITY, o_max = -INFINITY;
+        double he_max = -INFINITY, ho_max = -INFINITY, p_max = -INFINITY, ho_at = 0.0;   // DETAIL
+        bool p_nan = false;
         for (int t = 0; t < pl; t++) {
             const int i = t + 1;
             const double *q = rec + ((size_t)k * S + i) * FXR_STRIDE;
             const double prob = step_probability(p, q, X[(size_t)i * ld], Y[(size_t)i * ld], TH[(size_t)i * ld]);
             double re = 0.0, ro = 0.0;
-            if (prob != 0.0) {
+            if (DETAIL || prob != 0.0) {
                 // harm of ego point t against prediction t (harm_estimation.py:282-300)
                 const double x = X[(size_t)t * ld], y = Y[(size_t)t * ld], th = TH[(size_t)t * ld], v = V[(size_t)t * ld];
                 const size_t kt = (size_t)k * P + t;
@@ -204,8 +226,15 @@ __global__ __launch_bounds__(256) void fx_risk_kernel(const double *__restrict__
                                                                      : ref_speed(dve, p.uego_ref, p.uego_exp);
                     ho = 1.0 / (1.0 + exp(p.ped_c - p.ped_s * dvo));
                 }
-                re = he * prob;
-                ro = ho * prob;
+                re = prob != 0.0 ? he * prob : 0.0;
+                ro = prob != 0.0 ? ho * prob : 0.0;
+                if (DETAIL) {
+                    he_max = fmax(he_max, he);
+                    ho_max = fmax(ho_max, ho);
+                    // np.argmax: the FIRST maximum of the probability list (the entries behind pl are zeros)
+                    p_nan = p_nan || prob != prob;
+                    if (prob > p_max) { p_max = prob; ho_at = ho; }
+                }
             }
             e_max = fmax(e_max, re);
             o_max = fmax(o_max, ro);
@@ -213,24 +242,133 @@ __global__ __launch_bounds__(256) void fx_risk_kernel(const double *__restrict__
         ego_best = fmax(ego_best, e_max);
         obst_best = fmax(obst_best, o_max);
         any = true;
+        if (DETAIL) {
+            col[((size_t)0 * K + k) * n + j] = e_max;
+            col[((size_t)1 * K + k) * n + j] = o_max;
+            col[((size_t)2 * K + k) * n + j] = he_max;
+            col[((size_t)3 * K + k) * n + j] = ho_max;
+            occ_best = fmax(occ_best, (!p_nan && p_max > 0.001) ? ho_at : 0.0);   // risk_costs.py:104-107
+        }
     }
     out_ego[j] = any ? ego_best : 0.0;
     out_obst[j] = any ? obst_best : 0.0;
+    if (DETAIL) out_occ[j] = any ? occ_best : 0.0;
 }
 
-// arg-min of ego + obst over the n entries (NaN = not selected), ties to the lower candidate index: ONE workgroup of 1024
-// lanes, the lexicographic (cost, index) reduction of fx_select.h
-__global__ __launch_bounds__(1024) void fx_risk_argmin_kernel(const double *__restrict__ ego, const double *__restrict__ obst, int64_t n,
-                                                              const int64_t *__restrict__ ids, long long *__restrict__ out) {
+// One lane per listed candidate: out_ego / out_obst [n] (NaN where the candidate is not selected)
+__global__ __launch_bounds__(256) void fx_risk_kernel(const double *__restrict__ planes, int64_t ld, int S, int64_t n,
+                                                      const int64_t *__restrict__ ids, const uint32_t *__restrict__ flags,
+                                                      const double *__restrict__ rec, const double *__restrict__ obs,
+                                                      const double *__restrict__ pos, const double *__restrict__ yaw,
+                                                      const double *__restrict__ vo, int K, int P, FxRiskParams p,
+                                                      double *__restrict__ out_ego, double *__restrict__ out_obst) {
+    risk_walk<false>(planes, ld, S, n, ids, flags, rec, obs, pos, yaw, vo, K, P, p, out_ego, out_obst, nullptr, nullptr);
+}
+
+// The same walk with the per-obstacle columns and obst_harm_occ (fx_eval_risk_costs_agent)
+__global__ __launch_bounds__(256) void fx_risk_detail_kernel(const double *__restrict__ planes, int64_t ld, int S, int64_t n,
+                                                             const int64_t *__restrict__ ids, const uint32_t *__restrict__ flags,
+                                                             const double *__restrict__ rec, const double *__restrict__ obs,
+                                                             const double *__restrict__ pos, const double *__restrict__ yaw,
+                                                             const double *__restrict__ vo, int K, int P, FxRiskParams p,
+                                                             double *__restrict__ out_ego, double *__restrict__ out_obst,
+                                                             double *__restrict__ col, double *__restrict__ out_occ) {
+    risk_walk<true>(planes, ld, S, n, ids, flags, rec, obs, pos, yaw, vo, K, P, p, out_ego, out_obst, col, out_occ);
+}
+
+// Risk-cost principles (risk_costs.py:124-251) over the columns of the detail pass: one lane per listed candidate streams the K
+// obstacles and accumulates as it goes -- no per-lane array, nothing in scratch.  Every lane walks the reach-set parts in the
+// same order, so the part tables and the vertices are wave-uniform loads; the crossing test has no branch.
+// out [7][n] = bayes | equality | maximin | ego | responsibility | total | boundary_harm (NaN where the candidate is not selected)
+__global__ __launch_bounds__(256) void fx_risk_cost_kernel(const RiskCostArgs a) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= a.n) return;
+    const size_t n = (size_t)a.n;
+    const int64_t c = a.ids ? a.ids[j] : j;
+    const uint32_t fl = a.flags[c];
+    const uint32_t need = FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED;
+    double *__restrict__ out = a.out + j;
+    if (!a.ids && (fl & need) != need) {
+#pragma unroll
+        for (int q = 0; q < 7; q++) out[q * n] = NAN;
+        return;
+    }
+    const int K = a.K, S = a.S;
+    const int64_t ld = a.ld;
+    // boundary harm: the caller's, or planner.py:369-375 on the first step outside the road
+    double bh = 0.0;
+    if (a.bh_in) {
+        bh = a.bh_in[j];
+    } else if (a.bstep && (fl & FX_FLAG_BOUNDARY)) {
+        const int st = a.bstep[c];
+        if (st >= 0 && st < S) bh = 1.0 / (1.0 + exp((-a.bh_c) - a.bh_s * a.planes[(3 * (size_t)S + st) * ld + c]));
+    }
+    const double *__restrict__ ce = a.col + j;
+    double se = 0.0, so = 0.0, sabs = 0.0, mx = bh, resp = 0.0;
+    for (int k = 0; k < K; k++) {
+        const double er = ce[((size_t)0 * K + k) * n], orr = ce[((size_t)1 * K + k) * n];
+        const double eh = ce[((size_t)2 * K + k) * n], oh = ce[((size_t)3 * K + k) * n];
+        se += er;
+        so += orr;
+        sabs += fabs(er - orr);
+        // get_maximin_costs: the harm is KEPT where the risk is below eps (upstream's gate, transcribed)
+        mx = fmax(mx, fmax(eh * (er < a.eps ? 1.0 : 0.0), oh * (orr < a.eps ? 1.0 : 0.0)));
+        if (a.resp_mode == FX_RISK_RESP_ACTION_SPACE) resp = resp - a.resp[k] * orr;
+    }
+    if (a.resp_mode == FX_RISK_RESP_REACH_SET) {
+        const double *X = a.planes + c, *Y = a.planes + (size_t)S * ld + c;
+        for (int e = 0; e < a.n_entries; e++) {
+            unsigned inside = 0u;
+            for (int pt = a.entry_off[e]; pt < a.entry_off[e + 1]; pt++) {
+                const int st = a.part_step[pt], v0 = a.vert_off[pt], v1 = a.vert_off[pt + 1];
+                if (v1 <= v0) continue;
+                const double px = X[(size_t)st * ld], py = Y[(size_t)st * ld];
+                double xj = a.verts[2 * (size_t)(v1 - 1)], yj = a.verts[2 * (size_t)(v1 - 1) + 1];
+                unsigned par = 0u;
+                for (int v = v0; v < v1; v++) {   // even-odd crossings of the ray towards +x; a horizontal edge never straddles
+                    const double xi = a.verts[2 * (size_t)v], yi = a.verts[2 * (size_t)v + 1];
+                    par ^= (unsigned)((yi > py) != (yj > py)) & (unsigned)(px < (xj - xi) * (py - yi) / (yj - yi) + xi);
+                    xj = xi;
+                    yj = yi;
+                }
+                inside |= par;
+            }
+            const double r = ce[((size_t)1 * K + a.entry_obs[e]) * n];
+            resp = inside ? resp : resp - r;
+        }
+    }
+    double bayes = 0.0, equal = 0.0, maximin = 0.0, ego = 0.0;
+    if (K > 0) {
+        bayes = ((se + so) + bh) / (double)(2 * K);
+        equal = sabs / (double)K;
+        maximin = pow(mx, a.scale);
+        ego = se + bh;
+    } else {
+        resp = 0.0;
+    }
+    out[0 * n] = bayes;
+    out[1 * n] = equal;
+    out[2 * n] = maximin;
+    out[3 * n] = ego;
+    out[4 * n] = resp;
+    out[5 * n] = (((a.w[0] * bayes + a.w[1] * equal) + a.w[2] * maximin) + a.w[3] * ego) + a.w[4] * resp;
+    out[6 * n] = bh;
+}
+
+// arg-min over the n entries of ego + obst (SUM) or of val = ego alone, NaN = not selected or not comparable, ties to the lower
+// candidate index, -1 when nothing is left: ONE workgroup of 1024 lanes, the lexicographic (cost, index) reduction of fx_select.h
+template <bool SUM>
+__device__ __forceinline__ void risk_argmin(const double *__restrict__ ego, const double *__restrict__ obst, int64_t n,
+                                            const int64_t *__restrict__ ids, long long *__restrict__ out) {
     __shared__ double sc[16];
     __shared__ long long si[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double bc = INFINITY;
     long long bi = 0x7fffffffffffffffLL;
     for (int64_t j = tid; j < n; j += blockDim.x) {
-        const double e = ego[j], o = obst[j];
+        const double e = ego[j], o = SUM ? obst[j] : 0.0;
         if (e != e || o != o) continue;
-        const double s = e + o;
+        const double s = SUM ? e + o : e;
         const long long c = ids ? (long long)ids[j] : (long long)j;
         if (fx_lex_less(s, c, bc, bi)) { bc = s; bi = c; }
     }
@@ -242,6 +380,17 @@ __global__ __launch_bounds__(1024) void fx_risk_argmin_kernel(const double *__re
             if (fx_lex_less(sc[w], si[w], bc, bi)) { bc = sc[w]; bi = si[w]; }
         out[0] = bi == 0x7fffffffffffffffLL ? -1LL : bi;
     }
+}
+
+__global__ __launch_bounds__(1024) void fx_risk_argmin_kernel(const double *__restrict__ ego, const double *__restrict__ obst, int64_t n,
+                                                              const int64_t *__restrict__ ids, long long *__restrict__ out) {
+    risk_argmin<true>(ego, obst, n, ids, out);
+}
+
+// the same over the total of the risk-cost pass
+__global__ __launch_bounds__(1024) void fx_risk_cost_argmin_kernel(const double *__restrict__ val, int64_t n, const int64_t *__restrict__ ids,
+                                                                   long long *__restrict__ out) {
+    risk_argmin<false>(val, nullptr, n, ids, out);
 }
 
 }  // namespace fxrisk

@@ -774,6 +774,7 @@ class FrenetEngine(StepRegistry):
         pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         t = {k: np.ascontiguousarray(v) for k, v in tables.items() if isinstance(v, np.ndarray)}
         self._risk_tables = t    # (kept alive for the call; the library copies them)
+        self._risk_K = {**getattr(self, "_risk_K", {}), agent: int(tables["K"])}   # (shape of risk_detail's columns)
         f = lambda n: t[n].ctypes.data_as(pd)
         i = lambda n: t[n].ctypes.data_as(pi)
         check(lib().fx_set_risk_obstacles_agent(self._ctx, agent, int(tables["K"]), int(tables["P"]), f("pos"), f("cov"), f("cov_inv"),
@@ -797,9 +798,64 @@ class FrenetEngine(StepRegistry):
                                        ego.ctypes.data_as(pd), obst.ctypes.data_as(pd), C.byref(idx)))
         return ego[:n], obst[:n], int(idx.value)
 
+    def set_reach_sets(self, tables: dict, agent: int = 0):
+        """Reach-set tables (risk.reach_set_tables) for the reach-set responsibility of the next `risk_costs` calls of this
+        agent.  Call it after set_risk_obstacles: the entries index that call's obstacles, and new obstacles clear them."""
+        pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        t = {k: np.ascontiguousarray(tables[k], dtype=np.int32) for k in ("entry_obs", "entry_part_off", "part_step", "part_vert_off")}
+        verts = np.ascontiguousarray(tables["verts"], dtype=np.float64).reshape(-1, 2)
+        i = lambda n: t[n].ctypes.data_as(pi)
+        check(lib().fx_set_reach_sets_agent(self._ctx, agent, len(t["entry_obs"]), i("entry_obs"), i("entry_part_off"), len(t["part_step"]),
+                                            i("part_step"), i("part_vert_off"), len(verts), verts.ctypes.data_as(pd)))
+
+    def _risk_costs(self, params, cost_params, ids, agent):
+        inp = self._inputs[agent]
+        K = getattr(self, "_risk_K", {}).get(agent, 0)
+        if ids is None:
+            n, idp = inp.n_candidates, None
+        else:
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            n, idp = len(ids), ids.ctypes.data_as(C.POINTER(C.c_int64))
+        if cost_params is not None:   # the arrays behind the structure's pointers must cover what the library reads
+            lens = getattr(cost_params, "_lengths", {})
+            if lens.get("boundary_harm", n) != n:
+                raise ValueError(f"boundary_harm has {lens['boundary_harm']} entries for {n} candidates")
+            if lens.get("responsibility", K) != K:
+                raise ValueError(f"responsibility has {lens['responsibility']} entries for {K} obstacles")
+        names = ["ego_risk", "obst_risk", "obst_harm_occ"]
+        cols = ["ego_risk_max", "obst_risk_max", "ego_harm_max", "obst_harm_max"]
+        cost_names = list(_abi.RISK_COST_NAMES) + ["total", "boundary_harm"] if cost_params is not None else []
+        res = {k: np.zeros(max(n, 1)) for k in names + cost_names}
+        res.update({k: np.zeros((K, max(n, 1))) for k in cols})
+        idx = np.full(2, -1, np.int64)
+        out = _abi.FxRiskOutputs()
+        for k, a in res.items():
+            setattr(out, k, a.ctypes.data)
+        out.min_risk_index, out.min_cost_index = idx.ctypes.data, idx.ctypes.data + 8
+        if n > 0:   # (an empty id list: nothing to evaluate, no arg-min)
+            check(lib().fx_eval_risk_costs_agent(self._ctx, agent, C.byref(params), C.byref(cost_params) if cost_params is not None else None,
+                                                 n if ids is not None else 0, idp, C.byref(out)))
+        res = {k: (a[:, :n].T if k in cols else a[:n]) for k, a in res.items()}   # [n, K] views of the obstacle-major columns
+        res["min_risk_index"] = int(idx[0])
+        if cost_params is not None:
+            res["min_cost_index"] = int(idx[1])
+        return res
+
+    def risk_detail(self, params, ids=None, agent: int = 0) -> dict:
+        """calc_risk's seven results of the last plan step's candidates on the device (fx_eval_risk_costs_agent, DESIGN.md section
+        13): ego_risk, obst_risk (bit for bit what `risk` returns), obst_harm_occ [n]; ego_risk_max, obst_risk_max, ego_harm_max,
+        obst_harm_max [n, K] (columns in the order of the obstacle tables' keys); min_risk_index.  ids as in `risk`."""
+        return self._risk_costs(params, None, ids, agent)
+
+    def risk_costs(self, params, cost_params, ids=None, agent: int = 0) -> dict:
+        """risk_detail plus the risk-cost principles of risk.risk_cost_params: bayes, equality, maximin, ego, responsibility, their
+        weighted total, the boundary_harm they used [n], and min_cost_index, the arg-min of the total (ties to the lower index, NaN
+        skipped, -1 when nothing is left)."""
+        return self._risk_costs(params, cost_params, ids, agent)
+
     @property
     def last_risk_ms(self) -> float:
-        """device time of the last `risk` call (risk pass + arg-min)"""
+        """device time of the last `risk` / `risk_detail` / `risk_costs` call (its kernels)"""
         return float(lib().fx_last_risk_ms(self._ctx))
 
     def topk(self, k: int):

@@ -114,6 +114,8 @@ class ReactivePlannerHip:
         self.road_boundary_check = road_boundary_check
         self.fallback_selector: Optional[Callable] = None   # last-level selection among colliding candidates (set_fallback_selector)
         self._risk_model = None             # set_risk_model: (risk.json, harm_parameters.json, obstacle types, ego mass)
+        self._risk_cost_weights = None      # set_risk_cost_weights: (weights, responsibility mode)
+        self.reach_set = None               # set_reach_set
         self.occlusion_module = None       # planner.py:99 (set_occlusion_module)
         self.use_occ_model = False
         self.road_boundary = None          # segments [n][4]; checked on the GPU (set_road_boundary)
@@ -244,7 +246,11 @@ class ReactivePlannerHip:
         views over the step's device results (valid and feasible, every one of them colliding) -- and returns the chosen
         sample or None.  `min_risk_selector(risk)` builds the reference's rule from a per-trajectory risk function; the harm
         model that computes the reference's risk is outside this package (out of scope)."""
-        if isinstance(selector, str) and (selector != "min_risk" or self._risk_model is None):
+        if isinstance(selector, str) and selector == "min_risk_cost":
+            # the arg-min of the weighted risk-cost total (DESIGN.md section 13) where "min_risk" takes that of ego + obstacle risk
+            if self._risk_model is None or self._risk_cost_weights is None:
+                raise ValueError("set_fallback_selector('min_risk_cost') needs set_risk_model and set_risk_cost_weights first")
+        elif isinstance(selector, str) and (selector != "min_risk" or self._risk_model is None):
             raise ValueError("set_fallback_selector('min_risk') needs set_risk_model first" if selector == "min_risk"
                              else f"unknown fallback selector {selector!r}")
         self.fallback_selector = selector
@@ -269,6 +275,66 @@ class ReactivePlannerHip:
         risk.check_obstacle_classes(m["modes"], tabs["classes"])
         step.engine.set_risk_obstacles(tabs, step.agent)
         return step.engine.risk(m["params"], np.asarray(ids, np.int64), step.agent)
+
+    def set_reach_set(self, reach_set):
+        """planner.py:219: the reachable-set module whose `reach_sets[x_0.time_step]` (obstacle id -> list of {time_t: polygon})
+        the reach-set responsibility reads.  Computing reach sets is outside this package."""
+        self.reach_set = reach_set
+
+    def set_risk_cost_weights(self, weights, responsibility_mode=None):
+        """Weights of the risk-cost total (bayes, equality, maximin, ego, responsibility: a dict by name or a sequence) and how
+        the responsibility cost is computed: None (0), "action_space" (assign_responsibility_by_action_space on the ego state of the
+        step) or "reach_set" (calc_responsibility_reach_set on set_reach_set's sets).  Upstream's `responsibility_costs` unpacks
+        six of calc_risk's seven values and reads `planner.reachset`, so it raises there; here the cost is a post-step evaluation
+        (risk_costs, the "min_risk_cost" fallback), not a weighted plan-step term.  DESIGN.md section 13."""
+        from . import risk
+        if responsibility_mode not in (None, "action_space", "reach_set"):
+            raise ValueError(f"responsibility_mode {responsibility_mode!r}: None, 'action_space' or 'reach_set'")
+        risk.risk_cost_params(weights)   # (validates names and count)
+        self._risk_cost_weights = (dict(weights) if isinstance(weights, dict) else list(weights), responsibility_mode)
+
+    def risk_costs(self, ids=None):
+        """FrenetEngine.risk_costs of the last plan step under set_risk_model / set_risk_cost_weights: per-obstacle risk and
+        harm, the five principles, their total and its arg-min, for the candidates `ids` (None: every valid, feasible and returned
+        one, NaN rows for the others).  The boundary harm comes from the step's road-boundary stage (0 without it)."""
+        if self.last_step is None:
+            raise ValueError("no plan step yet")
+        return self._risk_costs_on(self.last_step, ids)
+
+    def _risk_costs_on(self, step, ids):
+        from . import risk
+        if self._risk_model is None or self._risk_cost_weights is None:
+            raise ValueError("no risk model: call set_risk_model and set_risk_cost_weights first")
+        m = self._risk_model
+        weights, mode = self._risk_cost_weights
+        preds = self.predictions or {}
+        tabs = risk.obstacle_tables(preds, m["types"], mahalanobis=bool(m["modes"].get("fast_prob_mahalanobis")))
+        risk.check_obstacle_classes(m["modes"], tabs["classes"])
+        step.engine.set_risk_obstacles(tabs, step.agent)
+        resp = None
+        if mode == "action_space":
+            resp = risk.action_space_responsibility(preds, self.x_0.position, self.x_0.orientation)
+        elif mode == "reach_set":
+            if self.reach_set is None:
+                raise ValueError("responsibility_mode 'reach_set' needs set_reach_set first")
+            sets = self.reach_set.reach_sets[self.x_0.time_step]
+            step.engine.set_reach_sets(risk.reach_set_tables(sets, tabs["keys"], self.dT, step.inputs.n_samples), step.agent)
+            resp = "reach_set"
+        cp = risk.risk_cost_params(weights, boundary_harm="step", harm_coeff=step.harm_coeff, responsibility=resp)
+        return step.engine.risk_costs(m["params"], cp, None if ids is None else np.asarray(ids, np.int64), step.agent)
+
+    def _min_risk_cost_sample(self, step):
+        ids = np.nonzero(step.mask(_abi.FX_FLAG_VALID) & step.mask(_abi.FX_FLAG_FEASIBLE) & step.mask(_abi.FX_FLAG_RETURNED))[0]
+        if len(ids) == 0:
+            return None
+        res = self._risk_costs_on(step, ids)
+        g = res["min_cost_index"]
+        if g < 0:
+            return None
+        chosen = step.sample(int(g))
+        j = int(np.searchsorted(ids, g))
+        chosen._ego_risk, chosen._obst_risk = float(res["ego_risk"][j]), float(res["obst_risk"][j])
+        return chosen
 
     def _min_risk_sample(self, step):
         ids = np.nonzero(step.mask(_abi.FX_FLAG_VALID) & step.mask(_abi.FX_FLAG_FEASIBLE) & step.mask(_abi.FX_FLAG_RETURNED))[0]
@@ -604,6 +670,8 @@ class ReactivePlannerHip:
             return None
         if isinstance(self.fallback_selector, str) and self.fallback_selector == "min_risk":
             chosen = self._min_risk_sample(step)    # the device's risk pass and arg-min (set_risk_model)
+        elif isinstance(self.fallback_selector, str) and self.fallback_selector == "min_risk_cost":
+            chosen = self._min_risk_cost_sample(step)
         else:
             chosen = self.fallback_selector(_LazySamples(step, ids))
         if chosen is not None:

@@ -3,6 +3,9 @@
 `risk_params` turns the reference's `risk.json` / `harm_parameters.json` dicts into the FxRiskParams block the kernel reads,
 following `get_model` (harm_estimation.py) for every harm mode, protection class and angle variant; `obstacle_tables` packs
 the predictions dict of a plan step into the per-obstacle tables of `fx_set_risk_obstacles_agent`.  DESIGN.md section 11.
+
+`risk_cost_params`, `action_space_responsibility` and `reach_set_tables` prepare the risk-cost principles and the two
+responsibility modes (risk_costs.py:124-251, utility/responsibility.py) of `fx_eval_risk_costs_agent`.  DESIGN.md section 13.
 """
 import numpy as np
 
@@ -159,3 +162,97 @@ def obstacle_tables(predictions: dict, obstacle_types: dict, mahalanobis: bool =
         cls[k] = _abi.FX_RISK_CLASS_PROTECTED if PROTECTION[key] else _abi.FX_RISK_CLASS_UNPROTECTED
     return dict(K=K, P=P, pos=pos, cov=cov, cov_inv=cov_inv, yaw=yaw, v=vel, n_pos=n[0].copy(), n_yaw=n[1].copy(), n_v=n[2].copy(),
                 length=length, width=width, mass=mass, cls=cls, classes=classes, keys=keys)
+
+
+def action_space_responsibility(predictions: dict, ego_position, ego_orientation: float) -> np.ndarray:
+    """[K] 0 / 1 in the order of the predictions' keys, as assign_responsibility_by_action_space sets it: 0 for an obstacle whose
+    first predicted position lies within +-pi/4 of the ego's orientation (check_if_inside180view: no angle wrap), 1 otherwise."""
+    out = np.zeros(len(predictions))
+    for k, pr in enumerate(predictions.values()):
+        pos = np.asarray(pr["pos_list"], np.float64).reshape(-1, 2)
+        dx = pos[0, 0] - ego_position[0]
+        dy = pos[0, 1] - ego_position[1]
+        angle = np.arctan2(dy, dx)
+        inside = ego_orientation - (np.pi / 4) <= angle <= ego_orientation + (np.pi / 4)
+        out[k] = 0.0 if inside else 1.0
+    return out
+
+
+def reach_set_tables(reach_sets: dict, prediction_keys, dt: float, n_steps=None) -> dict:
+    """The arrays of fx_set_reach_sets_agent for `reach_set.reach_sets[time_step]`: obstacle id -> list of one-item dicts
+    {time_t: polygon vertices [m][2]} (calc_responsibility_reach_set).  The ego step of a part is the reference's own expression
+    np.array(time_t / dt - 1, dtype=int) -- its truncation kept: 0.3 / 0.1 - 1 -> 1; parts with time_t <= 0 are dropped (upstream
+    masks them).  An obstacle that is not among `prediction_keys` (KeyError upstream), a step index >= n_steps (IndexError
+    upstream) and a polygon of fewer than 3 vertices raise ValueError."""
+    index = {oid: k for k, oid in enumerate(prediction_keys)}
+    entry_obs, entry_off, part_step, part_obs, vert_off, verts, keys = [], [0], [], [], [0], [], []
+    for oid, rs in reach_sets.items():
+        if oid not in index:
+            raise ValueError(f"reach-set obstacle {oid} is not in the predictions")
+        if len(rs) == 0:
+            raise ValueError(f"reach-set obstacle {oid} has no parts")
+        time_t = np.array([list(part.keys())[0] for part in rs])
+        steps = np.array(time_t / dt - 1, dtype=int)
+        for part, t, st in zip(rs, time_t, steps):
+            if not t > 0:
+                continue
+            poly = np.asarray(list(part.values())[0], np.float64).reshape(-1, 2)
+            if len(poly) < 3:
+                raise ValueError(f"reach-set obstacle {oid}, time {t}: a polygon needs at least 3 vertices")
+            if st < 0 or (n_steps is not None and st >= n_steps):
+                raise ValueError(f"reach-set obstacle {oid}, time {t}: step index {st} outside the trajectory ({n_steps} points)")
+            part_step.append(int(st))
+            part_obs.append(index[oid])
+            verts.append(poly)
+            vert_off.append(vert_off[-1] + len(poly))
+        keys.append(oid)
+        entry_obs.append(index[oid])
+        entry_off.append(len(part_step))
+    i32 = lambda a: np.asarray(a, np.int32)
+    return dict(entry_obs=i32(entry_obs), entry_part_off=i32(entry_off), part_step=i32(part_step), part_obs=i32(part_obs),
+                part_vert_off=i32(vert_off), verts=np.concatenate(verts) if verts else np.zeros((0, 2)), keys=keys)
+
+
+def risk_cost_params(weights, boundary_harm=None, harm_coeff=None, responsibility=None, eps: float = 10e-10,
+                     scale: float = 10) -> _abi.FxRiskCostParams:
+    """FxRiskCostParams.  weights: the five weights of the total, a dict by _abi.RISK_COST_NAMES (missing: 0) or a sequence in that
+    order.  boundary_harm: None (0), an [n] array in the order of the evaluated candidates, or "step" with harm_coeff = (const,
+    speed) of harm_parameters.json log_reg.ignore_angle -- derived on the device from the step's road-boundary stage.
+    responsibility: None (the cost is 0), the [K] vector of action_space_responsibility, or "reach_set" (FrenetEngine.set_reach_sets).
+    eps / scale: get_maximin_costs' defaults."""
+    p = _abi.FxRiskCostParams()
+    if isinstance(weights, dict):
+        unknown = set(weights) - set(_abi.RISK_COST_NAMES)
+        if unknown:
+            raise ValueError(f"unknown risk-cost weights {sorted(unknown)}")
+        weights = [weights.get(n, 0.0) for n in _abi.RISK_COST_NAMES]
+    if len(weights) != 5:
+        raise ValueError("five weights: " + ", ".join(_abi.RISK_COST_NAMES))
+    for i, w in enumerate(weights):
+        p.weights[i] = float(w)
+    p.maximin_eps, p.maximin_scale = float(eps), float(scale)
+    p._keep, p._lengths = [], {}   # the arrays behind the structure's pointers live as long as it does
+    if boundary_harm is None:
+        p.boundary_mode = _abi.FX_RISK_BOUNDARY_ZERO
+    elif isinstance(boundary_harm, str):
+        if boundary_harm != "step" or harm_coeff is None:
+            raise ValueError('boundary_harm: None, an array, or "step" with harm_coeff=(const, speed)')
+        p.boundary_mode = _abi.FX_RISK_BOUNDARY_STEP
+        p.boundary_c, p.boundary_s = float(harm_coeff[0]), float(harm_coeff[1])
+    else:
+        a = np.ascontiguousarray(boundary_harm, dtype=np.float64).reshape(-1)
+        p._keep.append(a)
+        p._lengths["boundary_harm"] = len(a)
+        p.boundary_mode, p.boundary_harm = _abi.FX_RISK_BOUNDARY_ARRAY, a.ctypes.data
+    if responsibility is None:
+        p.responsibility_mode = _abi.FX_RISK_RESP_NONE
+    elif isinstance(responsibility, str):
+        if responsibility != "reach_set":
+            raise ValueError('responsibility: None, a [K] 0/1 vector, or "reach_set"')
+        p.responsibility_mode = _abi.FX_RISK_RESP_REACH_SET
+    else:
+        a = np.ascontiguousarray(responsibility, dtype=np.float64).reshape(-1)
+        p._keep.append(a)
+        p._lengths["responsibility"] = len(a)
+        p.responsibility_mode, p.responsibility = _abi.FX_RISK_RESP_ACTION_SPACE, a.ctypes.data
+    return p

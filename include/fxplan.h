@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 11
+#define FX_ABI_VERSION 12
 
 /* ---- status codes (planner.py / reactive_planner_cpp.py raise Python exceptions; the shim maps
  *      <0 -> ValueError, >0 -> RuntimeError, see SURVEY 8b "Error conventions") ---- */
@@ -573,8 +573,54 @@ int32_t fx_set_risk_obstacles_agent(FxContext *ctx, int32_t agent, int32_t K, in
  * listed candidates, in that order.  Needs FX_MODE_WRITE_BUNDLE (FX_ERR_NOT_READY otherwise).  Synchronous. */
 int32_t fx_eval_risk_agent(FxContext *ctx, int32_t agent, const FxRiskParams *params, int64_t n_ids, const int64_t *ids,
                            double *ego_risk, double *obst_risk, int64_t *min_risk_index);
-/* device time of the last fx_eval_risk_agent (risk pass + arg-min), ms */
+/* device time of the last fx_eval_risk_agent (risk pass + arg-min) or fx_eval_risk_costs_agent (all its kernels), ms */
 double fx_last_risk_ms(FxContext *ctx);
+
+/* ---- per-obstacle risk and harm, risk-cost principles, responsibility (risk_costs.py:20-251, utility/responsibility.py) --
+ *      DESIGN.md section 13; ABI 12.  Beside the plan step like the block above: nothing here runs unless called. ---- */
+enum { FX_RISK_RESP_NONE = 0, FX_RISK_RESP_ACTION_SPACE = 1, FX_RISK_RESP_REACH_SET = 2 };   /* get_responsibility_cost mode */
+enum { FX_RISK_BOUNDARY_ZERO = 0, FX_RISK_BOUNDARY_ARRAY = 1, FX_RISK_BOUNDARY_STEP = 2 };
+typedef struct FxRiskCostParams {
+    double weights[5];          /* total = sum w_i principle_i: bayes, equality, maximin, ego, responsibility */
+    double maximin_eps;         /* get_maximin_costs eps (upstream 10e-10) */
+    double maximin_scale;       /* ... and scale_factor (upstream 10) */
+    int32_t boundary_mode;      /* FX_RISK_BOUNDARY_ZERO; _ARRAY: boundary_harm below; _STEP: 1/(1+exp(-c - s v[first step outside the
+                                   road])) for candidates with FX_FLAG_BOUNDARY, 0 for the others and for a step that ran without
+                                   FX_MODE_ROAD_BOUNDARY (planner.py:369-375) */
+    int32_t responsibility_mode;/* FX_RISK_RESP_*; _REACH_SET reads the tables of fx_set_reach_sets_agent */
+    double boundary_c, boundary_s;   /* harm_parameters.json log_reg.ignore_angle const / speed (_STEP) */
+    const double *boundary_harm;     /* [n] (n = n_ids, or C with ids NULL), _ARRAY */
+    const double *responsibility;    /* [K] 0 / 1 per obstacle (_ACTION_SPACE): 0 inside the ego's +-pi/4 view (check_if_inside180view) */
+} FxRiskCostParams;
+/* Every pointer may be NULL.  n = n_ids, or C with ids NULL (NaN rows for the candidates that are not selected).  The per-obstacle
+ * results are obstacle-major, [K][n]: column k of candidate j at [k * n + j]. */
+typedef struct FxRiskOutputs {
+    double *ego_risk, *obst_risk;        /* [n] as fx_eval_risk_agent returns them, bit for bit */
+    double *obst_harm_occ;               /* [n] max over obstacles of: obstacle harm at the first arg-max of the probability list if
+                                            that maximum is > 0.001, else 0 */
+    double *ego_risk_max, *obst_risk_max, *ego_harm_max, *obst_harm_max;   /* [K][n] maxima over t */
+    double *bayes, *equality, *maximin, *ego, *responsibility, *total;     /* [n]; written with cost parameters only */
+    double *boundary_harm;               /* [n] the boundary harm the principles used; with cost parameters only */
+    int64_t *min_risk_index;             /* arg-min of ego_risk + obst_risk, as fx_eval_risk_agent */
+    int64_t *min_cost_index;             /* arg-min of total: ties to the lower candidate index, NaN totals skipped, -1 when nothing
+                                            is left or without cost parameters */
+} FxRiskOutputs;
+/* Reach sets of one agent for FX_RISK_RESP_REACH_SET (calc_responsibility_reach_set), after fx_set_risk_obstacles_agent (which
+ * clears them): entry e is a reach-set obstacle, entry_obs [n_entries] its index among the K prediction obstacles, its parts
+ * entry_part_off[e] .. entry_part_off[e + 1] (the host drops the parts with time_t <= 0); part p tests the ego point
+ * (x, y)[part_step[p]] against the polygon verts[part_vert_off[p] .. part_vert_off[p + 1]][2] (>= 3 vertices; closing or padding a
+ * ring with repeated vertices does not change the result): strict interior by the even-odd crossing rule.  The cost is
+ * -sum obst_risk_max[entry_obs[e]] over the entries none of whose parts contains its point.  Indices are checked against K and the
+ * horizon at fx_eval_risk_costs_agent.  n_entries = 0 clears. */
+int32_t fx_set_reach_sets_agent(FxContext *ctx, int32_t agent, int32_t n_entries, const int32_t *entry_obs,
+                                const int32_t *entry_part_off, int32_t n_parts, const int32_t *part_step,
+                                const int32_t *part_vert_off, int32_t n_verts, const double *verts);
+/* calc_risk's seven results for candidates of the last plan step and, with cost != NULL, the risk-cost principles and their
+ * weighted total with its arg-min.  ids as in fx_eval_risk_agent.  An obstacle with min(S - 1, n_pos) == 0 is refused
+ * (FX_ERR_INVALID_ARGUMENT: np.max of an empty list upstream).  Needs FX_MODE_WRITE_BUNDLE (FX_ERR_NOT_READY otherwise).
+ * Synchronous; its buffers are allocated on first use and counted in fx_device_bytes; fx_last_risk_ms covers it. */
+int32_t fx_eval_risk_costs_agent(FxContext *ctx, int32_t agent, const FxRiskParams *params, const FxRiskCostParams *cost /* NULL: detail only */,
+                                 int64_t n_ids, const int64_t *ids, const FxRiskOutputs *out);
 
 #ifdef __cplusplus
 }

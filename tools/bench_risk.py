@@ -4,6 +4,10 @@ risk call (median over --reps), gated (candidate, obstacle, step) triples and BV
 operation estimate with their shares of the MI355X peaks (8 TB/s HBM, 78.6 TFLOP/s FP64 vector, public specifications), and
 the reference calc_risk's CPU time per trajectory recorded by tests/golden/gen_risk_golden.py.
 
+--costs adds the per-obstacle detail pass and the risk-cost pass on the same step: device-event time of
+risk_detail (detail kernel + arg-min) and of risk_costs (detail, both arg-mins and the cost kernel, reach-set responsibility
+over six obstacles' polygons); the cost pass is their difference.
+
 Kernel time by rocprofv3, in a run of its own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/bench_risk.py
 """
 import argparse
@@ -30,6 +34,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--variant", default="log_reg_reduced_sym")
+    ap.add_argument("--costs", action="store_true", help="also time risk_detail and risk_costs (DESIGN.md section 13)")
     a = ap.parse_args()
     inp = synthetic.make_inputs(hull_builder=build_obstacle_hulls, ref_kind="arc", v0=10.0, grid=(19, 51, 51), n_obstacles=20)
     modes = dict(BASE)
@@ -47,6 +52,32 @@ def main():
         for _ in range(a.reps):
             eng.risk(params)
             ms.append(eng.last_risk_ms)
+        extra = {}
+        if a.costs:
+            ids_ = np.nonzero((flags & 0xB) == 0xB)[0]
+            keys = list(preds)
+            sets = {}
+            for n_, oid in enumerate(keys[:6]):   # polygons on the candidates' own points, growing with time
+                parts = []
+                for t_ in (0.3, 0.5, 1.0, 1.6, 2.2, 2.9):
+                    st = int(np.array(t_ / inp.dt - 1, dtype=int))
+                    c = np.array([np.median(planes["x"][ids_, st]), np.median(planes["y"][ids_, st])])
+                    ang = 0.2 * n_ + 2 * np.pi * np.arange(5 + n_) / (5 + n_)
+                    parts.append({t_: c + (1.0 + 0.8 * t_) * np.stack([np.cos(ang), np.sin(ang)], axis=1)})
+                sets[oid] = parts
+            eng.set_reach_sets(risk.reach_set_tables(sets, keys, inp.dt, inp.n_samples))
+            cp = risk.risk_cost_params([1.0, 0.5, 2.0, 0.25, 1.5], boundary_harm="step", harm_coeff=(-4.591, 0.185), responsibility="reach_set")
+            eng.risk_costs(params, cp)             # allocation, first launch
+            md, mc = [], []
+            for _ in range(a.reps):
+                eng.risk_detail(params)
+                md.append(eng.last_risk_ms)
+                out_c = eng.risk_costs(params, cp)
+                mc.append(eng.last_risk_ms)
+            extra = dict(detail_ms_median=float(np.median(md)), detail_ms_min=float(np.min(md)), detail_ms_max=float(np.max(md)),
+                         costs_ms_median=float(np.median(mc)), costs_ms_min=float(np.min(mc)), costs_ms_max=float(np.max(mc)),
+                         cost_pass_ms=float(np.median(mc) - np.median(md)), min_cost_index=out_c["min_cost_index"],
+                         reach_set_parts=sum(len(v) for v in sets.values()), device_bytes=eng.device_bytes)
     ids = np.nonzero((flags & 0xB) == 0xB)[0]
     S = planes["x"].shape[1]
     # gated triples, from the same means the kernel uses
@@ -67,11 +98,12 @@ def main():
     bytes_read = 4 * S * n * 8 + n * 4 + 2 * n * 8   # x, y, theta, v planes + flags + risk outputs
     t = float(np.median(ms)) * 1e-3
     g = np.load(os.path.join(ROOT, "tests", "golden", "risk_config3_obs20.npz"))
-    out = dict(metric="risk pass + arg-min, config 3", candidates=n, selected=int(len(ids)), obstacles=len(preds), steps=S,
+    out = dict(metric="risk pass + arg-min, config 3", ms_max=float(np.max(ms)), candidates=n, selected=int(len(ids)), obstacles=len(preds), steps=S,
                ms_median=float(np.median(ms)), ms_min=float(np.min(ms)), gated_triples=gated, bvn_evaluations=36 * gated,
                bytes_read=bytes_read, hbm_share=bytes_read / t / 8.0e12, fp64_ops_estimate=ops,
                fp64_share=ops / t / 78.6e12, us_per_candidate=t * 1e6 / max(len(ids), 1),
                reference_cpu_ms_per_trajectory=float(g["ref_seconds_per_trajectory"]) * 1e3)
+    out.update(extra)
     print(json.dumps(out))
 
 

@@ -594,17 +594,27 @@ extern "C" hipError_t fx_launch_topk(const DevProblem *d_probs, int n_agents, in
     return hipGetLastError();
 }
 
-// trajectory risk (fx_risk_kernel.h): the risk pass over n listed candidates, then the arg-min; ev_start / ev_stop (may be
-// null) bracket both
-extern "C" hipError_t fx_launch_risk(const double *planes, int64_t ld, int S, int64_t n, const int64_t *ids, const uint32_t *flags,
-                                     const double *rec, const double *obs, const double *pos, const double *yaw, const double *vo,
-                                     int K, int P, const FxRiskParams *params, double *out_ego, double *out_obst, long long *out_idx,
-                                     hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream) {
+// trajectory risk (fx_risk_kernel.h; DESIGN.md sections 11 and 13) over the w.n listed candidates: the walk -- the plain one, or
+// with col / out_occ the detail one -- and the arg-min of ego + obst into out_idx[0]; then, cost != null, the cost pass over the
+// columns and the arg-min of its total into out_idx[1].  ev_start / ev_stop (may be null) bracket all of them
+extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const FxRiskParams *params, double *out_ego, double *out_obst,
+                                     double *col, double *out_occ, const RiskCostArgs *cost, long long *out_idx, hipEvent_t ev_start,
+                                     hipEvent_t ev_stop, hipStream_t stream) {
+    const RiskWalkArgs &w = *walk;
     if (ev_start) { hipError_t e = hipEventRecord(ev_start, stream); if (e != hipSuccess) return e; }
-    if (n > 0)
-        hipLaunchKernelGGL(fxrisk::fx_risk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, planes, ld, S, n, ids, flags,
-                           rec, obs, pos, yaw, vo, K, P, *params, out_ego, out_obst);
-    hipLaunchKernelGGL(fxrisk::fx_risk_argmin_kernel, dim3(1), dim3(1024), 0, stream, out_ego, out_obst, n, ids, out_idx);
+    const dim3 grid((unsigned)((w.n + 255) / 256));
+    if (w.n > 0 && col)
+        hipLaunchKernelGGL(fxrisk::fx_risk_detail_kernel, grid, dim3(256), 0, stream, w.planes, w.ld, w.S, w.n, w.ids, w.flags, w.rec,
+                           w.obs, w.pos, w.yaw, w.vo, w.K, w.P, *params, out_ego, out_obst, col, out_occ);
+    else if (w.n > 0)
+        hipLaunchKernelGGL(fxrisk::fx_risk_kernel, grid, dim3(256), 0, stream, w.planes, w.ld, w.S, w.n, w.ids, w.flags, w.rec, w.obs,
+                           w.pos, w.yaw, w.vo, w.K, w.P, *params, out_ego, out_obst);
+    hipLaunchKernelGGL(fxrisk::fx_risk_argmin_kernel, dim3(1), dim3(1024), 0, stream, out_ego, out_obst, w.n, w.ids, out_idx);
+    if (cost) {
+        if (w.n > 0) hipLaunchKernelGGL(fxrisk::fx_risk_cost_kernel, grid, dim3(256), 0, stream, *cost);
+        hipLaunchKernelGGL(fxrisk::fx_risk_cost_argmin_kernel, dim3(1), dim3(1024), 0, stream, cost->out + 5 * (size_t)w.n, w.n, w.ids,
+                           out_idx + 1);
+    }
     if (ev_stop) { hipError_t e = hipEventRecord(ev_stop, stream); if (e != hipSuccess) return e; }
     return hipGetLastError();
 }
@@ -614,27 +624,5 @@ extern "C" hipError_t fx_launch_gather_candidates(const GatherArgs *args, const 
                                                   hipStream_t stream) {
     if (n > 0)
         hipLaunchKernelGGL(fx_gather_candidates_kernel, dim3((unsigned)n), dim3(FX_GATHER_BLOCK), 0, stream, *args, d_ids, n, d_out);
-    return hipGetLastError();
-}
-
-// per-obstacle risk and harm, risk-cost principles (fx_risk_kernel.h): the detail pass over n listed
-// candidates, the arg-min of ego + obst into out_idx[0], then -- cost != null -- the cost pass and the arg-min of its total into
-// out_idx[1]; ev_start / ev_stop (may be null) bracket all of them
-extern "C" hipError_t fx_launch_risk_costs(const double *planes, int64_t ld, int S, int64_t n, const int64_t *ids, const uint32_t *flags,
-                                           const double *rec, const double *obs, const double *pos, const double *yaw, const double *vo,
-                                           int K, int P, const FxRiskParams *params, double *out_ego, double *out_obst, double *col,
-                                           double *out_occ, const RiskCostArgs *cost, long long *out_idx, hipEvent_t ev_start,
-                                           hipEvent_t ev_stop, hipStream_t stream) {
-    if (ev_start) { hipError_t e = hipEventRecord(ev_start, stream); if (e != hipSuccess) return e; }
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (n > 0)
-        hipLaunchKernelGGL(fxrisk::fx_risk_detail_kernel, grid, dim3(256), 0, stream, planes, ld, S, n, ids, flags, rec, obs, pos, yaw, vo,
-                           K, P, *params, out_ego, out_obst, col, out_occ);
-    hipLaunchKernelGGL(fxrisk::fx_risk_argmin_kernel, dim3(1), dim3(1024), 0, stream, out_ego, out_obst, n, ids, out_idx);
-    if (cost) {
-        if (n > 0) hipLaunchKernelGGL(fxrisk::fx_risk_cost_kernel, grid, dim3(256), 0, stream, *cost);
-        hipLaunchKernelGGL(fxrisk::fx_risk_cost_argmin_kernel, dim3(1), dim3(1024), 0, stream, cost->out + 5 * (size_t)n, n, ids, out_idx + 1);
-    }
-    if (ev_stop) { hipError_t e = hipEventRecord(ev_stop, stream); if (e != hipSuccess) return e; }
     return hipGetLastError();
 }

@@ -1,10 +1,49 @@
-// fx_risk_args.h -- argument block of the risk-cost kernel (fx_risk_kernel.h), shared by the host code that fills it
-// (fx_api_risk.hip) and the launcher (fx_kernels.hip).  DESIGN.md section 13.
+// fx_risk_args.h -- what the host code of the trajectory risk (fx_api_risk.hip), its launcher (fx_kernels.hip) and its kernels
+// (fx_risk_kernel.h) share: the layout of the records the host builds and the kernels read, the arguments of the candidate walk
+// and the argument block of the risk-cost kernel.  DESIGN.md sections 11 and 13.
 #pragma once
 
 #include <stdint.h>
 
 #include "../../include/fxplan.h"
+
+// record of one (obstacle, ego step i): doubles
+#define FXR_M0X 0    // means: pos[i-1], pos[i-1] +- (cos, sin)(yaw[i]) length / 2
+#define FXR_SX 6
+#define FXR_SY 7
+#define FXR_RHO 8
+#define FXR_BRANCH 9  // 0: rho == 0, 1: |rho| < 0.925, 2: 0.925 <= |rho| < 1, 3: |rho| == 1
+#define FXR_NG 10     // Gauss-Legendre half nodes (3, 6, 10)
+#define FXR_VALID 11  // i < len(pos_list)
+#define FXR_IV 12     // inverse covariance (Mahalanobis mode)
+#define FXR_ASR 16    // branch 1: asin(rho) / 2; branch 2: 1 - rho^2
+#define FXR_A 17      // branch 2: sqrt(1 - rho^2)
+#define FXR_N1 18     // branch 1: sin(asr (1 - x_j)), then sin(asr (1 + x_j)); branch 2: xs_j = (a/2 (1 -+ x_j))^2
+#define FXR_N2 38     // branch 2: sqrt(1 - xs_j)
+#define FXR_STRIDE 58
+
+// per obstacle: doubles
+#define FXO_LEN 0
+#define FXO_WID 1
+#define FXO_MASS 2
+#define FXO_CLS 3
+#define FXO_NPOS 4
+#define FXO_STRIDE 8
+
+// arguments of the candidate walk (fx_risk_kernel / fx_risk_detail_kernel), device pointers
+struct RiskWalkArgs {
+    const double *planes;      // [FX_NUM_PLANES][S][ld] of the agent
+    int64_t ld;
+    int32_t S;
+    int64_t n;
+    const int64_t *ids;        // [n] or null: every candidate, NaN rows for the unselected ones
+    const uint32_t *flags;     // [ld] of the agent
+    const double *rec;         // [K][S][FXR_STRIDE]
+    const double *obs;         // [K][FXO_STRIDE]
+    const double *pos;         // [K][P][2]
+    const double *yaw, *vo;    // [K][P]
+    int32_t K, P;
+};
 
 struct RiskCostArgs {
     const double *col;         // [4][K][n]: ego_risk_max | obst_risk_max | ego_harm_max | obst_harm_max of the detail pass

@@ -5,7 +5,8 @@
 //
 // One lane per candidate.  Every lane walks the (obstacle, step) pairs in the same order, so everything indexed by them -- the
 // three obstacle means, the standardisation (sigma_x, sigma_y, rho), the |rho| branch of the bivariate normal and its node terms
-// -- is wave-uniform and comes from a record the host built once per call (fx_api_risk.hip).  Only the 5 m gate diverges.
+// -- is wave-uniform and comes from a record the host built once per call (fx_api_risk.hip; its layout, FXR_* / FXO_*, is in
+// fx_risk_args.h).  Only the 5 m gate diverges.
 //
 // Bivariate normal upper probability BVNU(h, k, rho) = P(X > h, Y > k) after Genz (2004), Statistics and Computing 14:251-260:
 // Drezner-Wesolowsky Gauss-Legendre quadrature of the Plackett integral in asin(rho) with 6 / 12 / 20 nodes for |rho| < 0.3 /
@@ -17,29 +18,6 @@
 
 #include "fx_risk_args.h"
 #include "fx_select.h"
-
-// record of one (obstacle, ego step i): doubles
-#define FXR_M0X 0    // means: pos[i-1], pos[i-1] +- (cos, sin)(yaw[i]) length / 2
-#define FXR_SX 6
-#define FXR_SY 7
-#define FXR_RHO 8
-#define FXR_BRANCH 9  // 0: rho == 0, 1: |rho| < 0.925, 2: 0.925 <= |rho| < 1, 3: |rho| == 1
-#define FXR_NG 10     // Gauss-Legendre half nodes (3, 6, 10)
-#define FXR_VALID 11  // i < len(pos_list)
-#define FXR_IV 12     // inverse covariance (Mahalanobis mode)
-#define FXR_ASR 16    // branch 1: asin(rho) / 2; branch 2: 1 - rho^2
-#define FXR_A 17      // branch 2: sqrt(1 - rho^2)
-#define FXR_N1 18     // branch 1: sin(asr (1 - x_j)), then sin(asr (1 + x_j)); branch 2: xs_j = (a/2 (1 -+ x_j))^2
-#define FXR_N2 38     // branch 2: sqrt(1 - xs_j)
-#define FXR_STRIDE 58
-
-// per obstacle: doubles
-#define FXO_LEN 0
-#define FXO_WID 1
-#define FXO_MASS 2
-#define FXO_CLS 3
-#define FXO_NPOS 4
-#define FXO_STRIDE 8
 
 namespace fxrisk {
 

@@ -781,21 +781,24 @@ class FrenetEngine(StepRegistry):
                                                 f("yaw"), f("v"), i("n_pos"), i("n_yaw"), i("n_v"), f("length"), f("width"), f("mass"),
                                                 i("cls")))
 
+    def _risk_ids(self, ids, agent):
+        """(rows of the result, n_ids and ids as the library takes them, the array behind ids) of a risk call: ids None is every
+        candidate"""
+        if ids is None:
+            return self._inputs[agent].n_candidates, 0, None, None
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        return len(ids), len(ids), ids.ctypes.data_as(C.POINTER(C.c_int64)), ids
+
     def risk(self, params, ids=None, agent: int = 0):
         """(ego_risk, obst_risk, min_risk_index) of the last plan step's candidates on the device (fx_eval_risk_agent).
         ids None: every VALID & FEASIBLE & RETURNED candidate -- the arrays then have C entries, NaN for the others; the index is
         the arg-min of ego + obst (ties to the lower index), -1 when there is none."""
-        inp = self._inputs[agent]
-        pd, pi64 = C.POINTER(C.c_double), C.POINTER(C.c_int64)
-        if ids is None:
-            n, idp = inp.n_candidates, None
-        else:
-            ids = np.ascontiguousarray(ids, dtype=np.int64)
-            n, idp = len(ids), ids.ctypes.data_as(pi64)
+        pd = C.POINTER(C.c_double)
+        n, n_ids, idp, ids = self._risk_ids(ids, agent)
         ego, obst = np.zeros(max(n, 1)), np.zeros(max(n, 1))
         idx = C.c_int64(-1)
-        check(lib().fx_eval_risk_agent(self._ctx, agent, C.byref(params), int(len(ids)) if ids is not None else 0, idp,
-                                       ego.ctypes.data_as(pd), obst.ctypes.data_as(pd), C.byref(idx)))
+        check(lib().fx_eval_risk_agent(self._ctx, agent, C.byref(params), n_ids, idp, ego.ctypes.data_as(pd), obst.ctypes.data_as(pd),
+                                       C.byref(idx)))
         return ego[:n], obst[:n], int(idx.value)
 
     def set_reach_sets(self, tables: dict, agent: int = 0):
@@ -809,13 +812,8 @@ class FrenetEngine(StepRegistry):
                                             i("part_step"), i("part_vert_off"), len(verts), verts.ctypes.data_as(pd)))
 
     def _risk_costs(self, params, cost_params, ids, agent):
-        inp = self._inputs[agent]
         K = getattr(self, "_risk_K", {}).get(agent, 0)
-        if ids is None:
-            n, idp = inp.n_candidates, None
-        else:
-            ids = np.ascontiguousarray(ids, dtype=np.int64)
-            n, idp = len(ids), ids.ctypes.data_as(C.POINTER(C.c_int64))
+        n, n_ids, idp, ids = self._risk_ids(ids, agent)
         if cost_params is not None:   # the arrays behind the structure's pointers must cover what the library reads
             lens = getattr(cost_params, "_lengths", {})
             if lens.get("boundary_harm", n) != n:
@@ -834,7 +832,7 @@ class FrenetEngine(StepRegistry):
         out.min_risk_index, out.min_cost_index = idx.ctypes.data, idx.ctypes.data + 8
         if n > 0:   # (an empty id list: nothing to evaluate, no arg-min)
             check(lib().fx_eval_risk_costs_agent(self._ctx, agent, C.byref(params), C.byref(cost_params) if cost_params is not None else None,
-                                                 n if ids is not None else 0, idp, C.byref(out)))
+                                                 n_ids, idp, C.byref(out)))
         res = {k: (a[:, :n].T if k in cols else a[:n]) for k, a in res.items()}   # [n, K] views of the obstacle-major columns
         res["min_risk_index"] = int(idx[0])
         if cost_params is not None:

@@ -265,16 +265,21 @@ class ReactivePlannerHip:
                                 params=risk.risk_params(params_risk, params_harm, self.vehicle_params.length,
                                                         self.vehicle_params.width, ego_mass))
 
-    def _eval_risk(self, step, ids):
-        """(ego_risk, obst_risk, min_risk_index) of the step's candidates `ids` on the device under the risk model"""
+    def _set_risk_obstacles(self, step):
+        """Hands the obstacle tables of the current predictions under the risk model to the step's engine; returns them"""
         from . import risk
-        if self._risk_model is None:
-            raise ValueError("no risk model: call set_risk_model first")
         m = self._risk_model
         tabs = risk.obstacle_tables(self.predictions or {}, m["types"], mahalanobis=bool(m["modes"].get("fast_prob_mahalanobis")))
         risk.check_obstacle_classes(m["modes"], tabs["classes"])
         step.engine.set_risk_obstacles(tabs, step.agent)
-        return step.engine.risk(m["params"], np.asarray(ids, np.int64), step.agent)
+        return tabs
+
+    def _eval_risk(self, step, ids):
+        """(ego_risk, obst_risk, min_risk_index) of the step's candidates `ids` on the device under the risk model"""
+        if self._risk_model is None:
+            raise ValueError("no risk model: call set_risk_model first")
+        self._set_risk_obstacles(step)
+        return step.engine.risk(self._risk_model["params"], np.asarray(ids, np.int64), step.agent)
 
     def set_reach_set(self, reach_set):
         """planner.py:219: the reachable-set module whose `reach_sets[x_0.time_step]` (obstacle id -> list of {time_t: polygon})
@@ -307,13 +312,10 @@ class ReactivePlannerHip:
             raise ValueError("no risk model: call set_risk_model and set_risk_cost_weights first")
         m = self._risk_model
         weights, mode = self._risk_cost_weights
-        preds = self.predictions or {}
-        tabs = risk.obstacle_tables(preds, m["types"], mahalanobis=bool(m["modes"].get("fast_prob_mahalanobis")))
-        risk.check_obstacle_classes(m["modes"], tabs["classes"])
-        step.engine.set_risk_obstacles(tabs, step.agent)
+        tabs = self._set_risk_obstacles(step)
         resp = None
         if mode == "action_space":
-            resp = risk.action_space_responsibility(preds, self.x_0.position, self.x_0.orientation)
+            resp = risk.action_space_responsibility(self.predictions or {}, self.x_0.position, self.x_0.orientation)
         elif mode == "reach_set":
             if self.reach_set is None:
                 raise ValueError("responsibility_mode 'reach_set' needs set_reach_set first")
@@ -323,8 +325,13 @@ class ReactivePlannerHip:
         cp = risk.risk_cost_params(weights, boundary_harm="step", harm_coeff=step.harm_coeff, responsibility=resp)
         return step.engine.risk_costs(m["params"], cp, None if ids is None else np.asarray(ids, np.int64), step.agent)
 
+    @staticmethod
+    def _fallback_ids(step):
+        """the candidates a risk fallback chooses among: VALID & FEASIBLE & RETURNED, ascending"""
+        return np.nonzero(step.mask(_abi.FX_FLAG_VALID) & step.mask(_abi.FX_FLAG_FEASIBLE) & step.mask(_abi.FX_FLAG_RETURNED))[0]
+
     def _min_risk_cost_sample(self, step):
-        ids = np.nonzero(step.mask(_abi.FX_FLAG_VALID) & step.mask(_abi.FX_FLAG_FEASIBLE) & step.mask(_abi.FX_FLAG_RETURNED))[0]
+        ids = self._fallback_ids(step)
         if len(ids) == 0:
             return None
         res = self._risk_costs_on(step, ids)
@@ -337,7 +344,7 @@ class ReactivePlannerHip:
         return chosen
 
     def _min_risk_sample(self, step):
-        ids = np.nonzero(step.mask(_abi.FX_FLAG_VALID) & step.mask(_abi.FX_FLAG_FEASIBLE) & step.mask(_abi.FX_FLAG_RETURNED))[0]
+        ids = self._fallback_ids(step)
         if len(ids) == 0:
             return None
         ego, obst, g = self._eval_risk(step, ids)

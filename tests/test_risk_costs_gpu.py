@@ -198,6 +198,75 @@ def test_boundary_harm_derived_from_the_step():
             assert _err(out["ego"], out["ego_risk_max"].sum(axis=1) + want) < 3e-12
 
 
+def _same(got, want):
+    if isinstance(want, dict):
+        return got.keys() == want.keys() and all(_same(got[k], want[k]) for k in want)
+    if isinstance(want, tuple):
+        return len(got) == len(want) and all(_same(a, b) for a, b in zip(got, want))
+    return np.array_equal(got, want, equal_nan=True) if isinstance(want, np.ndarray) else got == want
+
+
+def test_calls_share_one_block():
+    """risk(), risk_detail() and risk_costs() of an engine share one grow-only device block.  Whatever ran
+    before on it, every call returns bit for bit what it returns on a fresh engine that planned the same step and made only that
+    call; the block keeps the size of the first, largest call; the engine opened after close() starts from the same device_bytes.
+    Grid (6, 7, 3): 168 candidates, 74 of them selected -- the smallest synthetic grid with at least 65 selected candidates
+    ((3, 5, 9) has 150 and 32), both counts ragged in their last wave.  Found on the CPU: oracle.plan_step's flags of the grids
+    (a, b, c) with a in 2..6, b in 3..9, c in 3..13, in the order of their candidate counts a b (c + 1)."""
+    from frenetix_motion_planner_amd import synthetic, risk
+    from frenetix_motion_planner_amd.engine import FrenetEngine, build_obstacle_hulls
+    inp = synthetic.make_inputs(hull_builder=build_obstacle_hulls, ref_kind="arc", v0=10.0, grid=(6, 7, 3), n_obstacles=2)
+    params = risk.risk_params(BASE, HARM, **EGO)
+
+    def planned():
+        e = FrenetEngine(max_candidates=inp.n_candidates, device=0)
+        e.plan_step(inp)
+        return e
+
+    eng = planned()
+    bytes0 = eng.device_bytes
+    _, flags = eng.costs()
+    planes = {n: eng.plane(n).T.copy() for n in ("x", "y", "theta", "v")}
+    ids = np.nonzero((flags & 0xB) == 0xB)[0]
+    assert inp.n_candidates % 64 != 0 and len(ids) >= 65 and len(ids) % 64 != 0
+    preds, typ = _predictions(planes, flags, np.random.default_rng(11), n_obs=3)
+    keys = list(preds)
+    bh = np.linspace(0.0, 0.9, len(ids))
+
+    def tables(e, K):
+        e.set_risk_obstacles(risk.obstacle_tables({k: preds[k] for k in keys[:K]}, typ))
+        if K:
+            e.set_reach_sets(risk.reach_set_tables(_reach_sets(planes, keys[:K], ids, inp.dt), keys[:K], inp.dt, inp.n_samples))
+
+    def costs(e):
+        return e.risk_costs(params, risk.risk_cost_params(WEIGHTS, boundary_harm=bh, responsibility="reach_set"), ids)
+
+    calls = [(3, costs), (3, lambda e: e.risk(params, ids[::3])), (0, lambda e: e.risk_detail(params)), (0, lambda e: e.risk(params, ids)),
+             (1, costs), (3, costs)]
+    want = []
+    for j, (K, call) in enumerate(calls):
+        if j == 5:   # (the first call again)
+            want.append(want[0])
+            continue
+        with planned() as e:
+            assert e.device_bytes == bytes0
+            tables(e, K)
+            want.append(call(e))
+    assert np.nanmax(want[0]["obst_risk_max"]) > 0   # (not a comparison of zeros)
+
+    sizes, last = [], None
+    for (K, call), w in zip(calls, want):
+        if K != last:
+            tables(eng, K)
+        last = K
+        assert _same(call(eng), w), len(sizes)
+        sizes.append(eng.device_bytes)
+    assert sizes[0] > bytes0 and sizes == [sizes[0]] * len(calls)
+    eng.close()
+    with planned() as e:
+        assert e.device_bytes == bytes0
+
+
 @pytest.mark.parametrize("name", ["risk_costs_obs5", "risk_costs_mixed_obs6", "risk_costs_config3_obs20"])
 def test_device_matches_reference_golden(name):
     """as test_risk_golden.test_device_matches_reference_golden: the scenario planned on the device, 1e-7 on the candidates that

@@ -8,12 +8,16 @@ the reference calc_risk's CPU time per trajectory recorded by tests/golden/gen_r
 risk_detail (detail kernel + arg-min) and of risk_costs (detail, both arg-mins and the cost kernel, reach-set responsibility
 over six obstacles' polygons); the cost pass is their difference.
 
+--wall instead measures the host side, which at planner size the kernels no longer hide: wall-clock time around risk() and
+risk_costs() on an id list at grid (8, 16, 16) with 8 obstacles, after one warm-up call each, median over --reps.
+
 Kernel time by rocprofv3, in a run of its own:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/bench_risk.py
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -30,12 +34,40 @@ def bvn_ops(ng):
     return 2 * ng * (7 + 20) + 2 * 30 + 6
 
 
+def wall(reps):
+    inp = synthetic.make_inputs(hull_builder=build_obstacle_hulls, ref_kind="arc", v0=10.0, grid=(8, 16, 16), n_obstacles=4)
+    with FrenetEngine(max_candidates=inp.n_candidates, device=0) as eng:
+        eng.plan_step(inp)
+        _, flags = eng.costs()
+        planes = {n: eng.plane(n).T.copy() for n in ("x", "y", "theta", "v")}
+        preds, typ = _predictions(planes, flags, np.random.default_rng(7), n_obs=8)
+        eng.set_risk_obstacles(risk.obstacle_tables(preds, typ))
+        params = risk.risk_params(dict(BASE), HARM, **EGO)
+        ids = np.nonzero((flags & 0xB) == 0xB)[0]
+        cp = risk.risk_cost_params([1.0, 0.5, 2.0, 0.25, 1.5], boundary_harm="step", harm_coeff=(-4.591, 0.185))
+        out = dict(metric="wall time of the risk calls, grid (8, 16, 16), 8 obstacles", candidates=inp.n_candidates, listed=int(len(ids)),
+                   reps=reps)
+        for name, call in (("risk", lambda: eng.risk(params, ids)), ("risk_costs", lambda: eng.risk_costs(params, cp, ids))):
+            call()                             # allocation, first launch
+            ms = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                call()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            out.update({f"{name}_wall_ms_median": float(np.median(ms)), f"{name}_wall_ms_min": float(np.min(ms)),
+                        f"{name}_wall_ms_max": float(np.max(ms)), f"{name}_device_ms": eng.last_risk_ms})
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--variant", default="log_reg_reduced_sym")
     ap.add_argument("--costs", action="store_true", help="also time risk_detail and risk_costs (DESIGN.md section 13)")
+    ap.add_argument("--wall", action="store_true", help="wall-clock time of risk() and risk_costs() at planner size instead")
     a = ap.parse_args()
+    if a.wall:
+        return wall(a.reps)
     inp = synthetic.make_inputs(hull_builder=build_obstacle_hulls, ref_kind="arc", v0=10.0, grid=(19, 51, 51), n_obstacles=20)
     modes = dict(BASE)
     with FrenetEngine(max_candidates=inp.n_candidates, device=0) as eng:

@@ -42,6 +42,7 @@ def exported_symbols():
         "fx_last_kernel_ms", "fx_last_eval_kernel_ms", "fx_device_views",
         "fx_set_risk_obstacles_agent", "fx_eval_risk_agent", "fx_last_risk_ms",
         "fx_set_reach_sets_agent", "fx_eval_risk_costs_agent",
+        "fx_materialise_candidates_agent", "fx_read_materialised_agent", "fx_read_package_materialised", "fx_last_materialise_ms",
     ]
 
 
@@ -141,6 +142,10 @@ def lib():
                                       C.POINTER(_abi.FxRiskOutputs)], C.c_int32),
         "fx_read_candidate_agent": ([vp, C.c_int32, C.c_int64, pd, pd, pi32, pd, pd, pu32], C.c_int32),
         "fx_read_candidates_agent": ([vp, C.c_int32, C.c_int64] + [vp] * 8, C.c_int32),   # (arrays: plain addresses)
+        "fx_materialise_candidates_agent": ([vp, C.c_int32, C.c_int64, vp], C.c_int32),   # (ids: a plain address)
+        "fx_read_materialised_agent": ([vp, C.c_int32, C.c_int64] + [vp] * 8, C.c_int32),
+        "fx_read_package_materialised": ([vp, C.c_int32, C.c_int64, C.c_double, C.POINTER(_abi.FxPackage), vp], C.c_int32),
+        "fx_last_materialise_ms": ([vp], C.c_double),
         "fx_read_plane": ([vp, C.c_int32, pd], C.c_int32),
         "fx_read_plane_agent": ([vp, C.c_int32, C.c_int32, pd], C.c_int32),
         "fx_read_topk": ([vp, C.c_int32, pd, pi64, pi32], C.c_int32),

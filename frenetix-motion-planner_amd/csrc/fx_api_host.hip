@@ -246,6 +246,56 @@ int32_t fx_read_candidate_agent(FxContext *c, int32_t agent, int64_t index, doub
     return FX_OK;
 }
 
+} // extern "C"
+
+// The chunk loop of the batched read-back: `ids` index the columns of the arrays `ga` points at -- an agent's outputs of the last
+// step (fx_read_candidates_agent) or its sparse set (fx_read_materialised_agent, fx_api_materialise.hip).  The caller has validated
+// the list and set ga.parts.
+int fx_gather_rows(FxContext *c, const GatherArgs &ga, int64_t n, const int64_t *ids, double *planes, double *coeffs13, int32_t *traj_len,
+                   double *raw_costs, double *cost, uint32_t *flags, int32_t *boundary_step) {
+    int rc;
+    if (n == 0) return FX_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->d_cands) {
+        if (!c->h_cands) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_cands), FX_READ_CHUNK_BYTES, hipHostMallocDefault));
+        if ((rc = dev_alloc(c, &c->d_cands, (size_t)FX_READ_CHUNK_BYTES))) return rc;
+    }
+    const int S = ga.S, n_cost = ga.n_cost;
+    const size_t n_pl = (size_t)FX_NUM_PLANES * S;
+    const size_t W = (size_t)FX_GATHER_WORDS(S, n_cost);
+    // a chunk: ids [m] | records [m][W], 8-byte words all
+    const int64_t m_max = (int64_t)(FX_READ_CHUNK_BYTES / (sizeof(unsigned long long) * (W + 1)));
+    if (m_max < 1) return set_err(FX_ERR_CAPACITY, "candidate record larger than the read-back chunk");
+    for (int64_t at = 0; at < n; at += m_max) {
+        const int64_t m = std::min(m_max, n - at);
+        int64_t *h_ids = reinterpret_cast<int64_t *>(c->h_cands);
+        int64_t *d_ids = reinterpret_cast<int64_t *>(c->d_cands);
+        const unsigned long long *h_rec = reinterpret_cast<const unsigned long long *>(c->h_cands) + m_max;
+        unsigned long long *d_rec = reinterpret_cast<unsigned long long *>(c->d_cands) + m_max;
+        memcpy(h_ids, ids + at, sizeof(int64_t) * m);
+        HIP_TRY(hipMemcpyAsync(d_ids, h_ids, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(fx_launch_gather_candidates(&ga, d_ids, m, d_rec, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_cands + sizeof(int64_t) * m_max, d_rec, sizeof(unsigned long long) * W * m, hipMemcpyDeviceToHost,
+                               c->stream));
+        { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+        for (int64_t j = 0; j < m; j++) {
+            const unsigned long long *r = h_rec + (size_t)j * W;
+            const unsigned long long *t = r + n_pl + FX_COEFF_ROWS + n_cost;   // cost | traj_len | flags | boundary_step
+            const size_t k = (size_t)(at + j);
+            if (planes) memcpy(planes + k * n_pl, r, sizeof(double) * n_pl);
+            if (coeffs13) memcpy(coeffs13 + k * FX_COEFF_ROWS, r + n_pl, sizeof(double) * FX_COEFF_ROWS);
+            if (raw_costs && n_cost > 0) memcpy(raw_costs + k * n_cost, r + n_pl + FX_COEFF_ROWS, sizeof(double) * n_cost);
+            if (cost) memcpy(cost + k, t, sizeof(double));
+            if (traj_len) traj_len[k] = (int32_t)(long long)t[1];
+            if (flags) flags[k] = (uint32_t)t[2];
+            if (boundary_step) boundary_step[k] = (int32_t)(long long)t[3];
+        }
+    }
+    return FX_OK;
+}
+
+extern "C" {
+
 // fx_read_candidate_agent for n candidates at a time (fx_gather_kernel.h): per chunk of FX_READ_CHUNK_BYTES the listed indices go
 // to the device, the gather kernel packs their records behind the step on the context's stream, ONE asynchronous copy brings them
 // to the pinned block, ONE synchronisation, then the records are spread over the caller's arrays.  The two blocks are allocated
@@ -264,16 +314,6 @@ int32_t fx_read_candidates_agent(FxContext *c, int32_t agent, int64_t n, const i
     if (raw_costs && !cmap) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_COSTMAP");
     if (boundary_step && !bound) return set_err(FX_ERR_NOT_READY, "the step ran without FX_MODE_ROAD_BOUNDARY");
     if (n == 0) return FX_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->d_cands) {
-        if (!c->h_cands) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_cands), FX_READ_CHUNK_BYTES, hipHostMallocDefault));
-        if ((rc = dev_alloc(c, &c->d_cands, (size_t)FX_READ_CHUNK_BYTES))) return rc;
-    }
-    const size_t n_pl = (size_t)FX_NUM_PLANES * s.S;
-    const size_t W = (size_t)FX_GATHER_WORDS(s.S, s.n_cost);
-    // a chunk: ids [m] | records [m][W], 8-byte words all
-    const int64_t m_max = (int64_t)(FX_READ_CHUNK_BYTES / (sizeof(unsigned long long) * (W + 1)));
-    if (m_max < 1) return set_err(FX_ERR_CAPACITY, "candidate record larger than the read-back chunk");
     GatherArgs ga;
     ga.planes = c->h_probs[agent].planes;
     ga.coeffs = c->d_coeffs + (size_t)FX_COEFF_ROWS * s.cand_off;
@@ -286,32 +326,7 @@ int32_t fx_read_candidates_agent(FxContext *c, int32_t agent, int64_t n, const i
     // only what the caller asks for AND the step produced is read on the device
     ga.parts = ((planes || coeffs13 || traj_len) ? FX_GATHER_BUNDLE : 0u) | ((raw_costs && s.n_cost > 0) ? FX_GATHER_COSTMAP : 0u) |
                (boundary_step ? FX_GATHER_BOUNDARY : 0u);
-    for (int64_t at = 0; at < n; at += m_max) {
-        const int64_t m = std::min(m_max, n - at);
-        int64_t *h_ids = reinterpret_cast<int64_t *>(c->h_cands);
-        int64_t *d_ids = reinterpret_cast<int64_t *>(c->d_cands);
-        const unsigned long long *h_rec = reinterpret_cast<const unsigned long long *>(c->h_cands) + m_max;
-        unsigned long long *d_rec = reinterpret_cast<unsigned long long *>(c->d_cands) + m_max;
-        memcpy(h_ids, ids + at, sizeof(int64_t) * m);
-        HIP_TRY(hipMemcpyAsync(d_ids, h_ids, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(fx_launch_gather_candidates(&ga, d_ids, m, d_rec, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->h_cands + sizeof(int64_t) * m_max, d_rec, sizeof(unsigned long long) * W * m, hipMemcpyDeviceToHost,
-                               c->stream));
-        { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
-        for (int64_t j = 0; j < m; j++) {
-            const unsigned long long *r = h_rec + (size_t)j * W;
-            const unsigned long long *t = r + n_pl + FX_COEFF_ROWS + s.n_cost;   // cost | traj_len | flags | boundary_step
-            const size_t k = (size_t)(at + j);
-            if (planes) memcpy(planes + k * n_pl, r, sizeof(double) * n_pl);
-            if (coeffs13) memcpy(coeffs13 + k * FX_COEFF_ROWS, r + n_pl, sizeof(double) * FX_COEFF_ROWS);
-            if (raw_costs && s.n_cost > 0) memcpy(raw_costs + k * s.n_cost, r + n_pl + FX_COEFF_ROWS, sizeof(double) * s.n_cost);
-            if (cost) memcpy(cost + k, t, sizeof(double));
-            if (traj_len) traj_len[k] = (int32_t)(long long)t[1];
-            if (flags) flags[k] = (uint32_t)t[2];
-            if (boundary_step) boundary_step[k] = (int32_t)(long long)t[3];
-        }
-    }
-    return FX_OK;
+    return fx_gather_rows(c, ga, n, ids, planes, coeffs13, traj_len, raw_costs, cost, flags, boundary_step);
 }
 
 int32_t fx_read_plane_agent(FxContext *c, int32_t agent, int32_t plane, double *out) {

@@ -1,5 +1,6 @@
 // fx_api_risk.hip -- C-ABI of the trajectory risk (fx_risk_kernel.h): the obstacle tables of an agent and
-// the risk pass with its arg-min over the materialised bundle of the last plan step; the reach sets of an agent and the detail /
+// the risk pass with its arg-min over the materialised bundle of the last plan step (or, for listed candidates of a step that stored
+// none, over the agent's sparse set: fx_api_materialise.hip); the reach sets of an agent and the detail /
 // risk-cost pass.  The two evaluations share one host path (RiskPass) and one device block.  Nothing of
 // this runs in a plan step.
 #include <cmath>
@@ -168,6 +169,15 @@ struct RiskPass {
     bool maha;
     int64_t n;             // candidates evaluated: the listed ones, or all C
     const int64_t *ids;    // the caller's list, or null
+    // where the candidates' rows lie: the step's bundle, or -- a step that stored none -- the agent's sparse set
+    // (fx_api_materialise.hip), addressed by `pos`, the listed candidates' positions in it
+    bool sparse = false;
+    FxSparseView set;
+    std::vector<int64_t> pos;
+    const double *planes;
+    int64_t ld;
+    const uint32_t *flags;
+    const int32_t *bstep;
     std::vector<double> rec;
     size_t nE = 0, nP = 0, nV = 0;   // reach-set entries, parts and vertices of a cost pass in reach-set mode
     char *base;
@@ -194,7 +204,13 @@ static int risk_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskPara
     int rc = check_agent(c, agent);
     if (rc) return rc;
     const FxAgentSlot &s = c->slots[agent];
-    if (!(s.mode & FX_MODE_WRITE_BUNDLE)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_BUNDLE");
+    q.sparse = !(s.mode & FX_MODE_WRITE_BUNDLE);
+    if (q.sparse) {   // every listed candidate has been materialised since the step, or the pass has nothing to read
+        bool in_set = ids && n_ids >= 0 && fx_sparse_view(c, agent, &q.set);
+        for (int64_t j = 0; in_set && j < n_ids; j++) in_set = ids[j] >= 0 && ids[j] < s.C;
+        if (!in_set || !fx_sparse_positions(q.set, n_ids, ids, q.pos))
+            return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_BUNDLE");
+    }
     if (!params || (detail && !have_out)) return set_err(FX_ERR_INVALID_ARGUMENT, detail ? "params or out is NULL" : "params is NULL");
     const FxRiskParams &p = *params;
     if (p.prob_mode != FX_RISK_PROB_MVN && p.prob_mode != FX_RISK_PROB_MAHALANOBIS)
@@ -227,6 +243,10 @@ static int risk_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskPara
     q.c = c, q.agent = agent, q.s = &s, q.r = r, q.a = &a;
     q.S = S, q.K = K, q.P = a.P > 0 ? a.P : 1, q.maha = maha;
     q.n = ids ? n_ids : s.C, q.ids = ids;
+    q.planes = q.sparse ? q.set.planes : c->h_probs[agent].planes;
+    q.ld = q.sparse ? q.set.ld : s.ld;
+    q.flags = q.sparse ? q.set.flags : c->d_flags + s.cand_off;
+    q.bstep = q.sparse ? q.set.bound_step : c->d_bstep + s.cand_off;
     return FX_OK;
 }
 
@@ -271,7 +291,7 @@ static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost) {
         HIP_TRY(q.up(q.o_yaw, a.yaw.data(), sizeof(double) * a.yaw.size()));
         HIP_TRY(q.up(q.o_v, a.v.data(), sizeof(double) * a.v.size()));
     }
-    if (q.ids && q.n > 0) HIP_TRY(q.up(q.o_ids, q.ids, sizeof(int64_t) * q.n));
+    if (q.ids && q.n > 0) HIP_TRY(q.up(q.o_ids, q.sparse ? q.pos.data() : q.ids, sizeof(int64_t) * q.n));
     return FX_OK;
 }
 
@@ -279,7 +299,7 @@ static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost) {
 static int risk_run(RiskPass &q, const FxRiskParams &p, bool detail, const RiskCostArgs *ca, const FxRiskOutputs &out) {
     FxContext *c = q.c;
     FxRiskState *r = q.r;
-    const RiskWalkArgs w{c->h_probs[q.agent].planes, q.s->ld, q.S, q.n, q.d_ids(), c->d_flags + q.s->cand_off, q.D(q.o_rec), q.D(q.o_obs),
+    const RiskWalkArgs w{q.planes, q.ld, q.S, q.n, q.d_ids(), q.flags, q.D(q.o_rec), q.D(q.o_obs),
                          q.D(q.o_pos), q.D(q.o_yaw), q.D(q.o_v), q.K, q.P};
     long long *d_idx = reinterpret_cast<long long *>(q.base + q.o_idx);
     HIP_TRY(fx_launch_risk(&w, &p, q.D(q.o_ego), q.D(q.o_obst), detail ? q.D(q.o_col) : nullptr, detail ? q.D(q.o_occ) : nullptr, ca, d_idx,
@@ -300,6 +320,9 @@ static int risk_run(RiskPass &q, const FxRiskParams &p, bool detail, const RiskC
     HIP_TRY(hipMemcpyAsync(idx, d_idx, sizeof(long long) * (ca ? 2 : 1), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipEventElapsedTime(&r->last_ms, r->e0, r->e1));
+    // (sparse set: the arg-min ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
+    for (long long &i : idx)
+        if (q.sparse && i >= 0) i = (long long)q.set.ids[i];
     if (out.min_risk_index) *out.min_risk_index = (int64_t)idx[0];
     if (out.min_cost_index) *out.min_cost_index = (int64_t)idx[1];
     return FX_OK;
@@ -396,13 +419,13 @@ extern "C" int32_t fx_eval_risk_costs_agent(FxContext *c, int32_t agent, const F
         ca.col = q.D(q.o_col);
         ca.n = n;
         ca.ids = q.d_ids();
-        ca.flags = c->d_flags + s.cand_off;
-        ca.planes = c->h_probs[agent].planes;
-        ca.ld = s.ld;
+        ca.flags = q.flags;
+        ca.planes = q.planes;
+        ca.ld = q.ld;
         ca.S = S;
         ca.K = K;
         ca.bh_in = cost->boundary_mode == FX_RISK_BOUNDARY_ARRAY ? q.D(q.o_bh) : nullptr;
-        ca.bstep = (cost->boundary_mode == FX_RISK_BOUNDARY_STEP && (s.mode & FX_MODE_ROAD_BOUNDARY)) ? c->d_bstep + s.cand_off : nullptr;
+        ca.bstep = (cost->boundary_mode == FX_RISK_BOUNDARY_STEP && (s.mode & FX_MODE_ROAD_BOUNDARY)) ? q.bstep : nullptr;
         ca.bh_c = cost->boundary_c;
         ca.bh_s = cost->boundary_s;
         ca.resp_mode = cost->responsibility_mode;

@@ -2,6 +2,25 @@
 // updates, the winner package and the batched plan calls (header: include/fxplan.h; context: fx_context.h).
 #include "fx_context.h"
 
+// the derived columns of planner.py:394-447 (_compute_trajectory_pair) behind the FX_NUM_PLANES planes of a package block: yaw rate by
+// backward differences of the heading, steering angle of the kinematic single-track model, heading shifted into
+// [x0_orientation - pi, x0_orientation + pi]
+void fx_package_derive(const DevProblem &d, int S, double yaw_rate0, double *block) {
+    const double *theta = block + 2 * (size_t)S, *kappa = block + 5 * (size_t)S;
+    double *yaw = block + (size_t)FX_NUM_PLANES * S, *steer = yaw + S, *orient = steer + S;
+    const double lo = d.x0_orientation - M_PI, hi = d.x0_orientation + M_PI, wb = d.veh.wheelbase;
+    for (int i = 0; i < S; i++) {
+        yaw[i] = i == 0 ? yaw_rate0 : (theta[i] - theta[i - 1]) / d.dt;
+        steer[i] = std::atan2(wb * kappa[i], 1.0);
+        double o = theta[i];
+        for (int r = 0; r < 4; r++) {
+            if (o < lo) o += 2 * M_PI;
+            if (o > hi) o -= 2 * M_PI;
+        }
+        orient[i] = o;
+    }
+}
+
 extern "C" {
 
 // Stage n_agents problems.  Agent a's candidates occupy [cand_off, cand_off + ld) of every per-candidate array.
@@ -812,21 +831,7 @@ int32_t fx_read_package(FxContext *c, int32_t agent, double yaw_rate0, FxPackage
     pkg->tau_lat = tail[17 + FX_NUM_COSTS];
     if (!block) return FX_OK;
     memcpy(block, src, sizeof(double) * FX_NUM_PLANES * S);
-    // the derived columns of planner.py:394-447 (_compute_trajectory_pair): yaw rate by backward differences of the heading,
-    // steering angle of the kinematic single-track model, heading shifted into [x0_orientation - pi, x0_orientation + pi]
-    const double *theta = block + 2 * (size_t)S, *kappa = block + 5 * (size_t)S;
-    double *yaw = block + (size_t)FX_NUM_PLANES * S, *steer = yaw + S, *orient = steer + S;
-    const double lo = d.x0_orientation - M_PI, hi = d.x0_orientation + M_PI, wb = d.veh.wheelbase;
-    for (int i = 0; i < S; i++) {
-        yaw[i] = i == 0 ? yaw_rate0 : (theta[i] - theta[i - 1]) / d.dt;
-        steer[i] = std::atan2(wb * kappa[i], 1.0);
-        double o = theta[i];
-        for (int r = 0; r < 4; r++) {
-            if (o < lo) o += 2 * M_PI;
-            if (o > hi) o -= 2 * M_PI;
-        }
-        orient[i] = o;
-    }
+    fx_package_derive(d, S, yaw_rate0, block);
     return FX_OK;
 }
 

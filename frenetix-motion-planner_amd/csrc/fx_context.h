@@ -3,6 +3,8 @@
 //   fx_api_step.hip      upload, launch policy (fx_evaluate), results, state updates, winner package, batched plan calls
 //   fx_api_exchange.hip  survivor exchange inside the library (RCCL)
 //   fx_api_host.hip      host geometry of the callers either side of the path, read-back
+//   fx_api_risk.hip      trajectory risk and risk costs beside the plan step
+//   fx_api_materialise.hip  listed candidates of a step re-walked into a sparse set, its read-back and package
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -55,6 +57,8 @@ extern "C" hipError_t fx_launch_topk(const DevProblem *d_probs, int n_agents, in
 
 extern "C" hipError_t fx_launch_gather_candidates(const GatherArgs *args, const int64_t *d_ids, int64_t n, unsigned long long *d_out,
                                                   hipStream_t stream);
+extern "C" hipError_t fx_launch_eval_list(const DevProblem *d_prob, const int64_t *d_ids, int64_t n, size_t lds_bytes, bool obst, bool extra,
+                                          hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream);
 
 extern thread_local char g_err[512];   // (defined in fx_api.hip)
 
@@ -244,9 +248,29 @@ struct FxContext {
     size_t gen_rec_lds = 0;           // generic kernel, >= 4 lanes per candidate: bytes of the staged obstacle records + step masks
     int64_t dev_bytes = 0;
     struct FxRiskState *risk = nullptr;    // trajectory risk (fx_api_risk.hip): obstacle tables and buffers, created on first use
+    struct FxSparseState *sparse = nullptr;   // sparse sets of listed candidates (fx_api_materialise.hip), created on first use
 };
 
 void fx_risk_release(FxContext *c);   // (fx_api_risk.hip)
+void fx_sparse_release(FxContext *c);   // (fx_api_materialise.hip)
+
+// An agent's sparse set as its consumers see it (fx_api_materialise.hip): the structure-of-arrays rows of
+// the n listed candidates, column = position in the ascending, de-duplicated list `ids`
+struct FxSparseView {
+    const int64_t *ids;   // [n] host, ascending
+    int64_t n, ld;
+    const double *planes, *coeffs, *costmap, *cost;   // device
+    const uint32_t *flags;
+    const int32_t *traj_len, *bound_step;
+};
+// the valid set of `agent`, or false: none materialised since the last evaluation, upload or state update
+bool fx_sparse_view(FxContext *c, int32_t agent, FxSparseView *v);
+// positions of the listed candidates in the set; false when one of them is not in it
+bool fx_sparse_positions(const FxSparseView &v, int64_t n, const int64_t *ids, std::vector<int64_t> &pos);
+
+int fx_gather_rows(FxContext *c, const GatherArgs &ga, int64_t n, const int64_t *ids, double *planes, double *coeffs13, int32_t *traj_len,
+                   double *raw_costs, double *cost, uint32_t *flags, int32_t *boundary_step);   // (fx_api_host.hip)
+void fx_package_derive(const DevProblem &d, int S, double yaw_rate0, double *block);             // (fx_api_step.hip)
 
 extern "C" int32_t fx_wait_word(const volatile unsigned long long *word, unsigned long long expected, int32_t timeout_ms);   // (fx_api.hip)
 

@@ -1,0 +1,207 @@
+// fx_eval_list_kernel.h -- the list form of the generic evaluation kernel (fx_eval_kernel.h at one lane per candidate):
+// re-walks a caller's list of candidates of the last plan step and stores their bundle rows, coefficients, cost map, cost,
+// flags and boundary steps into a compact structure-of-arrays block, the agent's "sparse set" (fx_materialise_candidates_agent;
+// DESIGN.md section 14).
+//
+// Lane `pos` of the launch walks candidate ids[pos] -- the candidate's parameters come from ids[pos] + g_base, every output goes
+// to column pos of the problem's arrays.  The problem is a CLONE of the agent's DevProblem whose outputs (planes, coeffs,
+// traj_len, costmap, cost, flags, bound_step) and selection scratch (counters, part_cost, part_idx) address the sparse block,
+// with C = n, ld = n rounded up to 64, the bundle and the cost map on, FX_MODE_INT_DEFER_OBST off: nothing of the step is
+// written.  The arithmetic is the step's own -- row_at / lat_eval / walk_step / finish_candidate of the generic kernel, the
+// obstacle stage fused into the walk -- so a row equals the row the generic kernel stores for that candidate bit for bit.
+//
+// The launch passes no fused selection (FuseArgs.host_result == nullptr): finish_candidate stores the outputs, adds to the
+// clone's own counters, writes the workgroup's arg-min partial into the clone's scratch and returns.  No tail, no ticket, no
+// wait loop, no published word: like the gather kernel it cannot hang.
+//
+// grid = ceil(n / 256), block = 256, dynamic LDS as fx_eval_kernel: M * 64 B knots + FX_TP * S * 8 B time table + M arc lengths.
+#pragma once
+
+#include "fx_eval_kernel.h"
+
+//   OBST  : obstacles present and / or the road-boundary stage (prediction cost, OBB collision walk, boundary walk)
+//   EXTRA : windowed cost terms active (Simpson integrals, distance_to_obstacles, lane_center_offset)
+template <bool OBST, bool EXTRA>
+__global__ __launch_bounds__(FX_BLOCK, 2) void fx_eval_list_kernel(const DevProblem *__restrict__ prob, const int64_t *__restrict__ ids) {
+    using namespace fxk;
+    extern __shared__ __attribute__((aligned(16))) double lds_dyn[];  // [M][8] knots, the [S][FX_TP] time table, [M] arc lengths
+    __shared__ double red_cost[FX_BLOCK / 64];
+    __shared__ long long red_idx[FX_BLOCK / 64];
+    __shared__ unsigned int red_cnt[2 + FX_NUM_REASONS + 1];
+    __shared__ int32_t sh_cost_id[FX_NUM_COSTS];
+    __shared__ double sh_cost_w[FX_NUM_COSTS];
+
+    const DevProblem &Pg = prob[0];
+    const ProblemRegs P = ProblemRegs::load(Pg, sh_cost_id, sh_cost_w);
+    const int tid = threadIdx.x;
+    const int64_t n = P.C;   // (the clone's C is the length of the list)
+    if ((int64_t)blockIdx.x * FX_BLOCK >= n) return;
+    const int64_t pos_raw = (int64_t)blockIdx.x * FX_BLOCK + tid;
+    const bool active = pos_raw < n;
+    const int64_t g = active ? pos_raw : n - 1;            // output column
+    const int64_t gg = as_global(ids)[g] + P.g_base;       // global candidate index: the sampling row / grid point
+
+    const int M = P.M, S = P.S;
+    double *__restrict__ rpos = lds_dyn + (size_t)M * FX_REF_FIELDS + (size_t)FX_TP * S;
+    {
+        const FX_GLOBAL double *__restrict__ src = as_global(P.ref);
+        for (int i = tid; i < M * FX_REF_FIELDS; i += FX_BLOCK) {
+            const double v = src[i];
+            lds_dyn[i] = v;
+            if ((i & (FX_REF_FIELDS - 1)) == 0) rpos[i / FX_REF_FIELDS] = v;
+        }
+        const FX_GLOBAL double *__restrict__ tsrc = as_global(P.tpow);
+        for (int i = tid; i < S; i += FX_BLOCK)
+            fill_time_row(lds_dyn + M * FX_REF_FIELDS + i * FX_TP, tsrc[i], tsrc[S + i], tsrc[2 * S + i], tsrc[3 * S + i], tsrc[4 * S + i]);
+        if (tid < P.n_cost) { sh_cost_id[tid] = Pg.cost_id[tid]; sh_cost_w[tid] = Pg.cost_w[tid]; }
+    }
+    if (tid < 2 + FX_NUM_REASONS) red_cnt[tid] = 0;
+    __syncthreads();
+    const Knot *__restrict__ knots = reinterpret_cast<const Knot *>(lds_dyn);
+    const double *__restrict__ tp = lds_dyn + M * FX_REF_FIELDS;
+
+    const double dt = P.dt;
+    const bool low_vel = P.low_vel_mode != 0;
+    const bool D = (P.mode & FX_MODE_DRAW_TRAJ_SET) != 0;
+    const bool dbg = D || (P.mode & FX_MODE_KINEMATIC_DEBUG) != 0;
+    const bool do_collision = OBST && (P.mode & FX_MODE_COLLISION) != 0;
+    const bool bundle = (P.mode & FX_MODE_WRITE_BUNDLE) != 0;   // (the host sets it in the clone)
+    const double a_max = P.veh.a_max;
+    const int64_t ld = P.ld;
+
+    // ---- candidate parameters, polynomials, horizon length: fx_eval_kernel.h, the same expressions ----
+    double T, s0, ss0, sss0, v1, a1, d0, dd0, ddd0, d1, dd1, ddd1;
+    if (P.has_matrix) {
+        const FX_GLOBAL double *__restrict__ r = as_global(P.matrix) + 13 * gg;
+        T = r[1] - r[0];
+        s0 = r[2]; ss0 = r[3]; sss0 = r[4]; v1 = r[5]; a1 = r[6];
+        d0 = r[7]; dd0 = r[8]; ddd0 = r[9]; d1 = r[10]; dd1 = r[11]; ddd1 = r[12];
+    } else {
+        const int nD = P.nD, nV = P.nV;
+        const int64_t q = gg / nD;
+        const int id = (int)(gg - q * nD);
+        const int it = (int)(q / nV);
+        const int iv = (int)(q - (int64_t)it * nV);
+        T = as_global(P.t_samp)[it];
+        v1 = as_global(P.v_samp)[iv];
+        d1 = as_global(P.d_samp)[id];
+        s0 = P.x0_lon[0]; ss0 = P.x0_lon[1]; sss0 = P.x0_lon[2];
+        d0 = P.x0_lat[0]; dd0 = P.x0_lat[1]; ddd0 = P.x0_lat[2];
+        a1 = 0.0; dd1 = 0.0; ddd1 = 0.0;
+    }
+    double cl0 = s0, cl1 = ss0, cl2 = .5 * sss0, cl3, cl4, cl5;
+    lon_coeffs(P.has_matrix ? FX_LON_VELOCITY_KEEPING : P.lon_mode, s0, ss0, sss0, T, v1, a1, cl3, cl4, cl5);
+    double tau = T;
+    if (low_vel) {
+        double t2 = T * T, t3 = t2 * T, t4 = t2 * t2, t5 = t3 * t2;
+        double s_lon_goal = (cl0 + cl1 * T + cl2 * t2 + cl3 * t3 + cl4 * t4 + cl5 * t5) - s0;
+        if (s_lon_goal <= 0) s_lon_goal = T;
+        tau = s_lon_goal;
+    }
+    LatPoly L;
+    {
+        double T2 = tau * tau, T3 = T2 * tau, T4 = T3 * tau, T5 = T4 * tau;
+        double b0 = d1 - d0 - dd0 * tau - .5 * ddd0 * T2;
+        double b1 = dd1 - dd0 - ddd0 * tau;
+        double b2 = ddd1 - ddd0;
+        L.set(d0, dd0, .5 * ddd0, fdiv(10.0 * b0 - 4.0 * b1 * tau + .5 * b2 * T2, T3),
+              fdiv(-15.0 * b0 + 7.0 * b1 * tau - b2 * T2, T4), fdiv(6.0 * b0 - 3.0 * b1 * tau + .5 * b2 * T2, T5));
+    }
+    int traj_len = (int)ceil((T + dt) / dt);
+    traj_len = traj_len > S ? S : (traj_len < 1 ? 1 : traj_len);
+
+    if (bundle && active) {
+        FX_GLOBAL double *__restrict__ co = as_global(P.coeffs) + g;
+        const double cv[FX_COEFF_ROWS] = {cl0, cl1, cl2, cl3, cl4, cl5, L.c0, L.c1, L.c2, L.c3, L.c4, L.c5, tau};
+#pragma unroll
+        for (int q = 0; q < FX_COEFF_ROWS; q++) st_out(co + q * ld, cv[q], false);
+        st_out(as_global(P.traj_len) + g, (int32_t)traj_len, false);
+    }
+
+    const double rp_first = knots[0].pos, rp_last = knots[M - 1].pos;
+    const double guess_scale = fdiv((double)(M - 1), rp_last - rp_first);
+    const bool want_trig = OBST && ((do_collision && P.K > 0) || ((P.mode & FX_MODE_ROAD_BOUNDARY) && P.n_bound > 0));
+    auto row_at = [&](int i) {
+        return make_lon_row(i, S, M, dt, a_max, cl0, cl1, cl2, cl3, cl4, cl5, traj_len, tp, rp_first, rp_last, guess_scale,
+                            want_trig, [&](int k) { return knots[k]; }, [&](int k) { return rpos[k]; },
+                            (P.mode & FX_MODE_PROJ_PSEUDO_NORMAL) != 0);
+    };
+    auto lat_eval = [&](int i, double u_lowvel, double &d, double &dv, double &da) {
+        LatU U;
+        if (low_vel) U.from_parameter(u_lowvel);
+        else U.from_table(tp + i * FX_TP);
+        L.eval(U, d, dv, da);
+    };
+    double d_ext, dv_u, da_u;
+    {
+        const LonRow rl = row_at(traj_len - 1);
+        lat_eval(traj_len - 1, rl.u1, d_ext, dv_u, da_u);
+    }
+
+    StepConst K;
+    K.dt = dt; K.r_dt = 1.0 / dt; K.kappa_max = P.veh.kappa_max; K.a_max = a_max; K.v_switch = P.veh.v_switch;
+    K.av_switch = a_max * P.veh.v_switch; K.v_des = P.v_des; K.wb = P.veh.wb_rear_axle; K.half_len = P.veh.length / 2;
+    K.half_wid = P.veh.width / 2; K.S = S; K.half = S / 2; K.K = P.K; K.low_vel = low_vel; K.dbg = dbg;
+    K.do_collision = do_collision; K.store_wt = (P.mode & FX_MODE_INT_STORE_WT) != 0;
+    K.n_bound = (OBST && (P.mode & FX_MODE_ROAD_BOUNDARY)) ? P.n_bound : 0; K.bound_d_reach = P.bound_d_reach;
+    K.ox = P.hot_origin[0]; K.oy = P.hot_origin[1]; K.gap_margin = P.hot_gap_margin;
+    K.cull_r0 = (float)(1.41423 * sqrt(P.veh.length * P.veh.length + P.veh.width * P.veh.width) * 0.5);
+    K.atan_k = nullptr;
+    const BoundView Bv{as_global(P.bound_piece), as_global(P.bound_bin), as_global(P.bound_item)};
+    const FX_GLOBAL double *__restrict__ obs_rec = as_global(P.obs_rec);
+    const FX_GLOBAL unsigned long long *__restrict__ obs_pmask = as_global(P.obs_pmask);
+    const FX_GLOBAL unsigned long long *__restrict__ obs_hmask = as_global(P.obs_hmask);
+
+    StepCarry Cy;
+    Cy.th_prev = P.x0_orientation; Cy.kap_prev = 0.0; Cy.bx_prev = Cy.by_prev = Cy.ux_prev = Cy.uy_prev = 0.0;
+    StepAcc A;
+    A.neg = A.acc_viol = A.collided = false;
+    A.step_reasons = 0; A.first_key = 0xffffffffu; A.fail_step = 0x7fffffff; A.bound_step = 0x7fffffff;
+    A.sum_abs_d = A.sum_voff = A.pred = A.d_end = A.v_end = 0.0;
+    StepOut O;
+    Simpson sim_acc, sim_jerk, sim_orient, sim_path;
+    double a_prev = 0.0, thcl_prev = 0.0, dto = 0.0;
+    if (EXTRA) { sim_acc.init(); sim_jerk.init(); sim_orient.init(); sim_path.init(); }
+    const int n_dto = EXTRA ? P.n_dto : 0;
+    const FX_GLOBAL double *__restrict__ dto_pos = as_global(P.dto_pos);
+    bool lane_on = false;
+    if (EXTRA)
+        for (int q = 0; q < P.n_cost; q++) lane_on |= P.cost_id[q] == FX_COST_LANE_CENTER_OFFSET;
+    double lane_off = 0.0;
+    FX_GLOBAL double *__restrict__ planes = as_global(P.planes);
+    const int64_t ps = (int64_t)S * ld;
+
+#pragma unroll 1
+    for (int i = 0; i < S; i++) {
+        const LonRow r = row_at(i);
+        walk_step<OBST, true>(K, r, L, tp, i, traj_len, d_ext, true, bundle && active, planes + (int64_t)i * ld + g, 0u, ps, Cy, A, O,
+                              obs_rec, obs_pmask, obs_hmask, Bv, nullptr, -1, false, false);
+        if (EXTRA) {   // the windowed terms: fx_eval_kernel.h, partial_cost_functions.py
+            sim_acc.push(O.a * O.a, S);
+            sim_path.push(O.v, S);
+            if (i > 0) {
+                const double j = (O.a - a_prev) / dt;
+                const double w = (O.th_cl - thcl_prev) / dt;
+                sim_jerk.push(j * j, S - 1);
+                sim_orient.push(w * w, S - 1);
+            }
+            a_prev = O.a;
+            thcl_prev = O.th_cl;
+            for (int o = 0; o < n_dto; o++) {
+                const double ex = O.x - dto_pos[2 * o], ey = O.y - dto_pos[2 * o + 1];
+                const double dist = sqrt(ex * ex + ey * ey);
+                dto += 1.0 / (dist * dist);
+            }
+            if (lane_on) lane_off += lane_center_distance(P, O.x, O.y);
+        }
+    }
+
+    WalkResult W;
+    W.neg = A.neg; W.acc_viol = A.acc_viol; W.collided = A.collided;
+    W.step_reasons = A.step_reasons; W.first_key = A.first_key; W.fail_step = A.fail_step; W.bound_step = A.bound_step;
+    W.sum_abs_d = A.sum_abs_d; W.sum_voff = A.sum_voff; W.pred = A.pred; W.dto = dto; W.lane_off = lane_off; W.d_end = A.d_end; W.v_end = A.v_end;
+    W.cl3 = cl3; W.cl4 = cl4; W.cl5 = cl5; W.ct3 = L.c3; W.ct4 = L.c4; W.ct5 = L.c5;
+    if (EXTRA) { W.sim_acc = sim_acc; W.sim_jerk = sim_jerk; W.sim_orient = sim_orient; W.sim_path = sim_path; }
+    const FuseArgs no_fuse{nullptr, 0ULL, nullptr, 0};   // no fused selection, no tail: the outputs and the clone's own scratch only
+    finish_candidate<1, true, OBST, EXTRA>(P, Pg, W, g, active, 0, 0, S, bundle, do_collision, dbg, D, red_cost, red_idx, red_cnt, no_fuse);
+}

@@ -27,6 +27,7 @@
 
 #include "fx_eval_kernel.h"
 #include "fx_eval_grid_kernel.h"
+#include "fx_eval_list_kernel.h"
 #include "fx_obstacle_kernel.h"
 #include "fx_step_kernel.h"
 #include "fx_risk_kernel.h"
@@ -625,4 +626,30 @@ extern "C" hipError_t fx_launch_gather_candidates(const GatherArgs *args, const 
     if (n > 0)
         hipLaunchKernelGGL(fx_gather_candidates_kernel, dim3((unsigned)n), dim3(FX_GATHER_BLOCK), 0, stream, *args, d_ids, n, d_out);
     return hipGetLastError();
+}
+
+// list form of the generic kernel (fx_eval_list_kernel.h): the n = clone.C listed candidates of ONE agent into its sparse block;
+// d_prob is the clone of the agent's problem, lds_bytes as for fx_launch_eval
+extern "C" hipError_t fx_launch_eval_list(const DevProblem *d_prob, const int64_t *d_ids, int64_t n, size_t lds_bytes, bool obst, bool extra,
+                                          hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + FX_BLOCK - 1) / FX_BLOCK)), block(FX_BLOCK);
+#define FX_LAUNCH(O, E)                                                                                         \
+    do {                                                                                                        \
+        static std::atomic<size_t> lds_set_[FX_MAX_DEVICES];   /* per device, see fx_launch_eval */               \
+        std::atomic<size_t> &hw_ = lds_set_[fx_device_slot()];                                                  \
+        if (lds_bytes > 48 * 1024 && lds_bytes > hw_.load(std::memory_order_relaxed)) {                         \
+            hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&fx_eval_list_kernel<O, E>),     \
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);    \
+            if (e_ != hipSuccess) return e_;                                                                    \
+            hw_.store(lds_bytes, std::memory_order_relaxed);                                                    \
+        }                                                                                                       \
+        hipExtLaunchKernelGGL((fx_eval_list_kernel<O, E>), grid, block, lds_bytes, stream, ev_start, ev_stop, 0, d_prob, d_ids); \
+        return hipGetLastError();                                                                               \
+    } while (0)
+    if (obst && extra) FX_LAUNCH(true, true);
+    if (obst) FX_LAUNCH(true, false);
+    if (extra) FX_LAUNCH(false, true);
+    FX_LAUNCH(false, false);
+#undef FX_LAUNCH
 }

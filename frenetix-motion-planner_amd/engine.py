@@ -757,6 +757,44 @@ class FrenetEngine(StepRegistry):
         return dict(planes=planes, lon=co[:, :6] if have_b else None, lat=co[:, 6:12] if have_b else None,
                     tau_lat=co[:, 12] if have_b else None, traj_len=tl, raw_costs=raw, cost=cost, flags=flags, boundary_step=bst)
 
+    def materialise(self, ids, agent: int = 0) -> dict:
+        """The dict of `candidates(ids)` with EVERY part filled, whatever the step stored: the listed
+        candidates of the last step are re-walked with the step's own arithmetic into the agent's sparse set
+        (fx_materialise_candidates_agent) and read back (fx_read_materialised_agent).  Rows in the order of `ids` (any order,
+        duplicates allowed); boundary_step None unless the step ran the road-boundary stage.  The set stays on the device until
+        the next materialise of this agent or the next evaluation, upload or state update: `risk`, `risk_detail` and
+        `risk_costs` of a step without a bundle accept ids inside it, `materialised_package` packages one of its rows.  Nothing
+        the step wrote is touched (costs(), topk(), kept samples stay as they were), so no kept step is rescued here."""
+        inp = self._inputs[agent]
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        n, n_cost = len(ids), len(inp.cost_names)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(lib().fx_materialise_candidates_agent(self._ctx, int(agent), n, ptr(ids)))
+        have_r = inp._bound is not None and inp._bound["n"] > 0
+        planes, co, tl = np.empty((n, _abi.FX_NUM_PLANES, inp.n_samples)), np.empty((n, 13)), np.empty(n, np.int32)
+        raw = np.empty((n, n_cost))
+        cost, flags = np.empty(n), np.empty(n, np.uint32)
+        bst = np.empty(n, np.int32) if have_r else None
+        check(lib().fx_read_materialised_agent(self._ctx, int(agent), n, ptr(ids), ptr(planes), ptr(co), ptr(tl),
+                                               ptr(raw) if n_cost > 0 else None, ptr(cost), ptr(flags), ptr(bst)))
+        return dict(planes=planes, lon=co[:, :6], lat=co[:, 6:12], tau_lat=co[:, 12], traj_len=tl, raw_costs=raw, cost=cost, flags=flags,
+                    boundary_step=bst)
+
+    def materialised_package(self, index: int, yaw_rate: float = 0.0, agent: int = 0):
+        """The winner package of `package()` for candidate `index` of the agent's sparse set (fx_read_package_materialised)"""
+        pkg = _abi.FxPackage()
+        inp = self._inputs[agent]
+        block = np.empty((_abi.FX_PKG_ROWS, inp.n_samples))
+        check(lib().fx_read_package_materialised(self._ctx, int(agent), int(index), float(yaw_rate), C.byref(pkg), block.ctypes.data))
+        w = WinnerPackage(pkg, block, inp)
+        w._costmap = True   # (a set's rows carry their raw costs whatever the step stored)
+        return w
+
+    @property
+    def last_materialise_ms(self) -> float:
+        """device time of the last `materialise` call's list kernel"""
+        return float(lib().fx_last_materialise_ms(self._ctx))
+
     def plane(self, name_or_index, agent: int = 0) -> np.ndarray:
         """[S, C] one plane of every candidate."""
         inp = self._inputs[agent]

@@ -92,6 +92,11 @@ class PlannerConfig:
     # False: only the chosen trajectory survives, other reads of an old step raise.
     retain_samples: bool = True
     survivors: int = 16              # top-k kept for the host-side road-boundary walk
+    # k > 0: the plan step runs without the bundle and the cost map (the throughput mode) and the planner materialises the winner
+    # and the first k entries of the step's top-k beside it (at most 64, the top-k's bound); the host walk,
+    # the packaging, log_risk and the risk fallbacks then work on that set, every other sample answers as a select-only sample
+    # does.  0: the step stores everything, as ever.
+    sparse_bundle_k: int = 0
     # dense grid (n_t, n_v, n_d) in natural order instead of the reference's sampling levels (BASELINE configs 2 - 5): T from
     # t_min in steps of dt, V over the planner's velocity range, D over [d_min, d_max] plus the current d
     dense_grid: Optional[Tuple[int, int, int]] = None
@@ -279,6 +284,7 @@ class ReactivePlannerHip:
         if self._risk_model is None:
             raise ValueError("no risk model: call set_risk_model first")
         self._set_risk_obstacles(step)
+        step.materialise(ids)   # (a step without a bundle: the risk pass reads the listed candidates' rows from its sparse set)
         return step.engine.risk(self._risk_model["params"], np.asarray(ids, np.int64), step.agent)
 
     def set_reach_set(self, reach_set):
@@ -323,6 +329,8 @@ class ReactivePlannerHip:
             step.engine.set_reach_sets(risk.reach_set_tables(sets, tabs["keys"], self.dT, step.inputs.n_samples), step.agent)
             resp = "reach_set"
         cp = risk.risk_cost_params(weights, boundary_harm="step", harm_coeff=step.harm_coeff, responsibility=resp)
+        if ids is not None:
+            step.materialise(ids)   # (a step without a bundle: see _eval_risk)
         return step.engine.risk_costs(m["params"], cp, None if ids is None else np.asarray(ids, np.int64), step.agent)
 
     @staticmethod
@@ -508,8 +516,9 @@ class ReactivePlannerHip:
                              x0_orientation=self.x_0.orientation, v_des=self.desired_velocity, vehicle=self.vehicle_params,
                              coordinate_system=self.coordinate_system, t_samp=t, v_samp=v, d_samp=d,
                              stop_point=stop_point_s is not None, cost_weights=weights,
-                             draw_traj_set=self._draw_traj_set, kinematic_debug=self._kinematic_debug, write_bundle=True,
-                             write_costmap=True, collision=self.use_prediction, obstacles=self._packed_predictions,
+                             draw_traj_set=self._draw_traj_set, kinematic_debug=self._kinematic_debug,
+                             write_bundle=self.config.sparse_bundle_k <= 0, write_costmap=self.config.sparse_bundle_k <= 0,
+                             collision=self.use_prediction, obstacles=self._packed_predictions,
                              road_boundary=boundary, lanelets=self._packed_lanelets)
         self._prev_inputs = inp
         # (what the one-call path above needs to know of THIS step: its level, and that the level's time set came from this handler)
@@ -565,7 +574,7 @@ class ReactivePlannerHip:
         package: the winner as the batched call already packaged it (engine.plan_batch_packaged; None = nothing found);
         False: read it here."""
         if package is False:
-            package = engine.package(agent, self.x_0.yaw_rate) if getattr(engine, "packaging", False) else None
+            package = engine.package(agent, self.x_0.yaw_rate) if getattr(engine, "packaging", False) and inputs.write_bundle else None
         best = self._consume_result(inputs, res, engine, agent, package, self._sampling_min)
         if best is not None:
             best.materialise()
@@ -661,7 +670,7 @@ class ReactivePlannerHip:
         if self.last_step is not None:
             self.last_step.invalidate(rescue=True)   # before the launch: samples still held are read first
         pkg = None
-        if hasattr(self.engine, "plan_step_packaged"):
+        if hasattr(self.engine, "plan_step_packaged") and inputs.write_bundle:   # (the library packages a winner from the bundle)
             # one call across the boundary: in-place update of the resident inputs, evaluation, result, the winner packaged
             res, pkg = self.engine.plan_step_packaged(inputs, self.x_0.yaw_rate)
         else:
@@ -702,6 +711,12 @@ class ReactivePlannerHip:
         self._collision_counter = res["n_collisions"]
         if self._draw_traj_set or self.save_all_traj:
             self.all_traj = _LazySortedList(step)
+        if self.config.sparse_bundle_k > 0 and not inputs.write_bundle:
+            # the winner and the step's best survivors, re-walked into the agent's sparse set: what the code below reads of them
+            keep = [int(res["best_index"])] if res["best_index"] >= 0 else []
+            keep += [int(g) for g in engine.topk(min(int(self.config.sparse_bundle_k), 64))[1][agent] if g >= 0]
+            if keep:
+                step.materialise(np.asarray(keep, np.int64) - inputs.shard_begin)
         if self.occlusion_module is not None:
             return self._occlusion_walk(step, samp_lvl)
         best = step.best

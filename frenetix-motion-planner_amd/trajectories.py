@@ -352,6 +352,7 @@ class PlanStepResult:
     _open = False                        # a sample that still needs the device has been handed out (the engine then knows this step)
     _snap = _snap_ids = None             # rescue(): engine.candidates() of the rescued indices (ascending) and those indices
     _written = None                      # index -> {attribute: value}: what was assigned to samples from outside (TrajectorySample.__setattr__)
+    _mat = _mat_ids = None               # materialise(): engine.materialise() of the listed indices (ascending) and those indices
 
     def __init__(self, engine, inputs, result: dict, agent: int = 0):
         self.engine, self.inputs, self.result, self.agent = engine, inputs, result, agent
@@ -389,7 +390,35 @@ class PlanStepResult:
         self._load_arrays()
         return self._flags
 
+    # ---- listed candidates of a step that stored no bundle ----
+    def materialise(self, ids):
+        """Install the rows of the candidates `ids` (indices within the shard) of a step that ran without the bundle or the cost
+        map: engine.materialise re-walks them on the device and the host keeps its rows, from which sample(g), fetch_sample,
+        fetch_coeffs, fetch_costmap_row and fetch_candidate answer the listed candidates -- now and after the next evaluation;
+        unlisted candidates raise what they raise on such a step.  A later call adds to the set.  A step that stored everything
+        needs none of this and keeps answering from its own arrays."""
+        self._check()
+        if self.inputs.write_bundle and self.inputs.write_costmap:
+            return
+        ids = np.unique(np.asarray(ids, dtype=np.int64).reshape(-1))
+        if self._mat_ids is not None:
+            ids = np.union1d(self._mat_ids, ids)
+        self._mat = self.engine.materialise(ids, self.agent)
+        self._mat_ids = ids
+
+    def _mat_row(self, index):
+        """row of candidate `index` among the materialised ones, None when it is not listed"""
+        ids = self._mat_ids
+        if ids is not None:
+            k = int(np.searchsorted(ids, index))
+            if k < len(ids) and ids[k] == index:
+                return k
+        return None
+
     def fetch_candidate(self, index) -> dict:
+        k = self._mat_row(index)
+        if k is not None:
+            return {name: self._mat[name][k] for name in ("planes", "lon", "lat", "tau_lat", "traj_len", "raw_costs", "cost", "flags")}
         if self._stale:
             k, sn = self._row(index), self._snap
             one = lambda name: None if sn[name] is None else sn[name][k]
@@ -423,8 +452,8 @@ class PlanStepResult:
         ids = set()
         for ref in self._samples.values():
             t = ref()
-            if t is not None and not t._materialised and t._pkg is None:
-                ids.add(t.uniqueId)
+            if t is not None and not t._materialised and t._pkg is None and self._mat_row(t.uniqueId) is None:
+                ids.add(t.uniqueId)   # (a materialised candidate's rows are on the host already)
         if not ids:
             return
         ids = np.array(sorted(ids), dtype=np.int64)
@@ -480,12 +509,18 @@ class PlanStepResult:
         return part, k
 
     def fetch_sample(self, index):
+        k = self._mat_row(index)
+        if k is not None:
+            return self._mat["planes"][k]
         if self._stale:
             part, k = self._rescued("planes", index, "FX_MODE_WRITE_BUNDLE")
             return part[k]
         return self.engine.sample(index, self.agent)
 
     def fetch_costmap_row(self, index):
+        k = self._mat_row(index)
+        if k is not None:
+            return self._mat["raw_costs"][k]
         if self._stale:
             part, k = self._rescued("raw_costs", index, "FX_MODE_WRITE_COSTMAP")
             return part[k]
@@ -494,6 +529,10 @@ class PlanStepResult:
         return self._cm[index]
 
     def fetch_coeffs(self, index):
+        k = self._mat_row(index)
+        if k is not None:
+            sn = self._mat
+            return sn["lon"][k], sn["lat"][k], int(sn["traj_len"][k]), float(sn["tau_lat"][k])
         if self._stale:
             lon, k = self._rescued("lon", index, "FX_MODE_WRITE_BUNDLE")
             sn = self._snap

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 12
+#define FX_ABI_VERSION 13
 
 /* ---- status codes (planner.py / reactive_planner_cpp.py raise Python exceptions; the shim maps
  *      <0 -> ValueError, >0 -> RuntimeError, see SURVEY 8b "Error conventions") ---- */
@@ -460,6 +460,39 @@ int32_t fx_read_candidates_agent(FxContext *ctx, int32_t agent, int64_t n, const
                                  int32_t *boundary_step/* [n] or NULL */);
 int32_t fx_read_topk_batch(FxContext *ctx, int32_t k, double *cost /*[n_agents][k]*/, int64_t *index /*[n_agents][k]*/);
 
+/* ---- listed candidates of a plan step, materialised beside it -- DESIGN.md section 14; ABI 13 ----
+ *      A step without FX_MODE_WRITE_BUNDLE (the throughput mode) hands back cost, flag word and index per candidate.  What a planner
+ *      needs afterwards is a few dozen trajectories: the winner, the top-k survivors of its host walk (planner.py:362-390), the
+ *      samples it keeps.  fx_materialise_candidates_agent re-walks a list of candidates of the last evaluated step of `agent` with
+ *      the step's own arithmetic (the list form of the generic evaluation kernel, one lane per candidate, obstacle stage and road
+ *      boundary in the walk) and stores their bundle rows, coefficients, horizon lengths, raw costs, costs, flag words and boundary
+ *      steps in a compact block of the agent's own, the "sparse set".  It writes nothing a plan step wrote or published.
+ *      ids: local indices in [0, C), any order, duplicates legal; the library keeps the set ascending and de-duplicated.  The call
+ *      enqueues on the context's stream and returns; the readers below synchronise.  The set is valid until the next call for that
+ *      agent or the next evaluation, upload or state update of the context; n == 0 clears it without device work.  The block is
+ *      allocated on the first call and only grows: a context that never calls this owns what it always did (fx_device_bytes).
+ *      FX_ERR_INVALID_ARGUMENT for n < 0, ids == NULL with n > 0, an index outside [0, C); FX_ERR_NOT_READY before the first
+ *      evaluated step and when the resident inputs were rewritten since it (fx_upload*, or fx_update_state without an evaluation:
+ *      the re-walk would use another state); FX_ERR_CAPACITY for a reference whose knots do not fit the generic kernel's LDS --
+ *      all checked before anything is launched or written, a refused call leaves the previous set as it was. */
+int32_t fx_materialise_candidates_agent(FxContext *ctx, int32_t agent, int64_t n, const int64_t *ids);
+/* fx_read_candidates_agent on the sparse set: the same outputs, the same chunking, rows in the caller's order (unsorted lists and
+ * duplicates are legal).  Every part is there whatever the step's mode was, except boundary_step, which needs
+ * FX_MODE_ROAD_BOUNDARY.  FX_ERR_NOT_READY when a listed candidate is not in the agent's set (or there is no valid set). */
+int32_t fx_read_materialised_agent(FxContext *ctx, int32_t agent, int64_t n, const int64_t *ids,
+                                   double *planes        /* [n][FX_NUM_PLANES][S] or NULL */,
+                                   double *coeffs13      /* [n][13] or NULL */,
+                                   int32_t *traj_len     /* [n] or NULL */,
+                                   double *raw_costs     /* [n][n_cost] or NULL */,
+                                   double *cost          /* [n] or NULL */,
+                                   uint32_t *flags       /* [n] or NULL */,
+                                   int32_t *boundary_step/* [n] or NULL */);
+/* the package of fx_read_package for candidate `index` (local) of the sparse set: found = 1, pkg->index global, block as there */
+int32_t fx_read_package_materialised(FxContext *ctx, int32_t agent, int64_t index, double yaw_rate0, FxPackage *pkg,
+                                     double *block /*[FX_PKG_ROWS][S] or NULL*/);
+/* device time of the context's last list-kernel launch (events attached to the kernel), ms; -1 before the first.  Waits for it. */
+double fx_last_materialise_ms(FxContext *ctx);
+
 /* ---- road boundary (replaces create_road_boundary_obstacle + trajectories_collision_static_obstacles,
  *      planner.py:362-381,550-565; commonroad-drivability-checker, not in the reference tree) ----
  * fx_build_boundary_bins: host-side geometry, no GPU.  Splits the n_seg boundary segments seg[n_seg][4] =
@@ -570,7 +603,9 @@ int32_t fx_set_risk_obstacles_agent(FxContext *ctx, int32_t agent, int32_t K, in
 /* ego_risk / obst_risk of candidates of the last plan step (max over obstacles of max over steps of harm x probability) and the
  * arg-min of ego + obst over them, ties to the lower candidate index (-1 when there is none).  ids NULL: every candidate whose
  * flags hold VALID, FEASIBLE and RETURNED; ego_risk / obst_risk then have C entries, NaN for the others.  Otherwise the n_ids
- * listed candidates, in that order.  Needs FX_MODE_WRITE_BUNDLE (FX_ERR_NOT_READY otherwise).  Synchronous. */
+ * listed candidates, in that order.  Needs FX_MODE_WRITE_BUNDLE (FX_ERR_NOT_READY otherwise) -- or, ABI 13, a non-NULL ids all of which
+ * lie in the agent's sparse set (fx_materialise_candidates_agent): the pass then reads the set's rows, and the returned arg-min is a
+ * candidate index as ever.  Synchronous. */
 int32_t fx_eval_risk_agent(FxContext *ctx, int32_t agent, const FxRiskParams *params, int64_t n_ids, const int64_t *ids,
                            double *ego_risk, double *obst_risk, int64_t *min_risk_index);
 /* device time of the last fx_eval_risk_agent (risk pass + arg-min) or fx_eval_risk_costs_agent (all its kernels), ms */
@@ -617,7 +652,8 @@ int32_t fx_set_reach_sets_agent(FxContext *ctx, int32_t agent, int32_t n_entries
                                 const int32_t *part_vert_off, int32_t n_verts, const double *verts);
 /* calc_risk's seven results for candidates of the last plan step and, with cost != NULL, the risk-cost principles and their
  * weighted total with its arg-min.  ids as in fx_eval_risk_agent.  An obstacle with min(S - 1, n_pos) == 0 is refused
- * (FX_ERR_INVALID_ARGUMENT: np.max of an empty list upstream).  Needs FX_MODE_WRITE_BUNDLE (FX_ERR_NOT_READY otherwise).
+ * (FX_ERR_INVALID_ARGUMENT: np.max of an empty list upstream).  Needs FX_MODE_WRITE_BUNDLE (FX_ERR_NOT_READY otherwise), or listed
+ * candidates of the agent's sparse set as fx_eval_risk_agent does.
  * Synchronous; its buffers are allocated on first use and counted in fx_device_bytes; fx_last_risk_ms covers it. */
 int32_t fx_eval_risk_costs_agent(FxContext *ctx, int32_t agent, const FxRiskParams *params, const FxRiskCostParams *cost /* NULL: detail only */,
                                  int64_t n_ids, const int64_t *ids, const FxRiskOutputs *out);

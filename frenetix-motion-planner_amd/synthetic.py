@@ -102,17 +102,22 @@ def make_inputs(*, ref_kind="arc", n_knots=400, spacing=0.5, kappa=0.01, v0=10.0
                 write_bundle=True, write_costmap=True, collision=True, low_vel_threshold=2.0, hull_builder=None,
                 seed=SEED, vehicle=None, x0_orientation=None, as_matrix=False, stop_point_s=None, road_half_width=None,
                 obstacle_min_gap=0.0, lead_gap=0.0, knot_jitter=0.0, pseudo_normal=False, vertex_tangent="chord", lanelets=None,
-                heading0=0.0, wrap_x0_orientation=False):
+                heading0=0.0, wrap_x0_orientation=False, origin=(0.0, 0.0)):
     """One agent's PlanInputs on a synthetic reference.
 
     level: reference sampling level (set-ordered ranges, SamplingHandler) -- or
     grid=(n_t, n_v, n_d): dense grid (BASELINE configs 2/3/5).
     road_half_width: road boundary = the reference offset by +-road_half_width (two polylines of segments).
     stop_point_s: distance ahead of s0 of a stop point -> stop-point sampling (end positions in
-    [(s0 + s_stop) / 2, s_stop], reactive_planner.py:637) instead of end velocities."""
+    [(s0 + s_stop) / 2, s_stop], reactive_planner.py:637) instead of end velocities.
+    origin: where the first reference knot lies in the world (a CommonRoad map kilometres from its origin, UTM coordinates of an
+    OSM-derived one).  The polyline is translated AFTER heading0; ego state, predictions, road boundary and lanelets follow
+    through the CoordinateSystem.  (0, 0) adds nothing: the inputs are bit for bit what they were without the keyword."""
     veh = vehicle or VehicleParams()
-    cs = CoordinateSystem(reference_polyline(ref_kind, n_knots, spacing, kappa, knot_jitter, seed, heading0),
-                          pseudo_normal=pseudo_normal, vertex_tangent=vertex_tangent)
+    polyline = reference_polyline(ref_kind, n_knots, spacing, kappa, knot_jitter, seed, heading0)
+    if origin[0] != 0.0 or origin[1] != 0.0:
+        polyline = polyline + np.array([float(origin[0]), float(origin[1])])[None, :]
+    cs = CoordinateSystem(polyline, pseudo_normal=pseudo_normal, vertex_tangent=vertex_tangent)
     N = int(horizon / dt)
     s0 = float(cs.ref_pos[s_knot] + s_off)
     low_vel = v0 < low_vel_threshold

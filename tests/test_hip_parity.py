@@ -68,12 +68,16 @@ def settle_differing(ora, differ, flags, cost, limit=2000):
     return len(ids)
 
 
-def compare(eng, inp, out, res, *, check_planes=True, agent=0, ref_inp=None):
+def compare(eng, inp, out, res, *, check_planes=True, agent=0, ref_inp=None, xy_tol=None):
     """out = oracle.plan_step(ref_inp or inp) ; res = engine result of the same inputs.  EVERY candidate is checked:
       * decisions (flag word: masks + reasons) exactly, planes to STATE_TOL, costs to COST_RTOL -- where the reference itself
         loses digits (cos(arctan(d')) next to pi/2) the two tolerances grow with sec(theta_cl), tests/admissible.py;
       * candidates whose decisions the reference takes by the last ulp (oracle margin < FRAGILE) against every outcome those
-        decisions admit: the device result must equal ONE of them."""
+        decisions admit: the device result must equal ONE of them.
+    xy_tol (scenes far from the world origin, tests/test_frame_invariance_gpu.py): the planes are compared relative to 1 + their
+    peak, which at UTM coordinates (5e6 m) lets (x, y) move by 5 mm -- while no arithmetic meets an ABSOLUTE 1e-9 m where
+    np.spacing is 9.3e-10.  Given, xy_tol is the absolute bound in metres on the x and y planes of every stored candidate whose
+    conditioning is ordinary, on top of everything else; None (every other call): nothing changes."""
     from oracle import oracle
     from tests.admissible import (FRAGILE_STATE_TOL, KINEMATIC_PLANES, conditioning_many, kinematic_conditioning_many, matches_one_outcome,
                                   path_length_weight, signed_integral_slack)
@@ -160,6 +164,11 @@ def compare(eng, inp, out, res, *, check_planes=True, agent=0, ref_inp=None):
         got = eng.bundle(agent)
         refp = out["planes"]
         errs = np.abs(got - refp) / (1.0 + np.abs(refp).max(axis=2, keepdims=True))   # [C, 14, S]
+        if xy_tol is not None:
+            xy_err = np.abs(got[:, :2] - refp[:, :2]).max(axis=(1, 2))
+            ordinary = stored & (cond <= WELL_CONDITIONED)
+            print(f"(x, y) absolute error {xy_err[ordinary].max():.3e} m (bound {xy_tol:.3e}, {int(ordinary.sum())} candidates)")
+            assert (xy_err[ordinary] < xy_tol).all(), f"(x, y) off by {xy_err[ordinary].max()} m (bound {xy_tol})"
         # Steps that CRAWL (high-speed mode, s_dot between the "moving" literal 1e-3 and 1e-2 m/s): d'' = (d_ddot - d' s_ddot) / s_dot^2
         # divides the evaluation noise of two second derivatives -- sums of terms of order 1 .. 100 that cancel to 1e-4 at the end
         # of a stopping trajectory, 1e-15 .. 1e-14 absolute whatever their value -- by 1e-6 .. 1e-4.  The slowest sampled end

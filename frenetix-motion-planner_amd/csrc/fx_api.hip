@@ -55,11 +55,7 @@ int32_t fx_create_batch(FxContext **out, int32_t device, int32_t max_agents, int
     FxContext *c = new (std::nothrow) FxContext();
     if (!c) return set_err(FX_ERR_HIP, "out of host memory");
     c->device = device;
-    c->max_cand = max_candidates_total;
-    c->max_steps = max_steps;
-    c->max_knots = max_ref_knots;
-    c->max_obs = max_obstacles;
-    c->max_pred = std::max(max_pred_steps, 2);
+    c->caps = fx_caps_of(max_agents, max_candidates_total, max_steps, max_ref_knots, max_obstacles, max_pred_steps);
     c->max_agents = max_agents;
     *out = c;
     {   // FX_STREAM_PRIORITY=low|high: experiments with two contexts sharing the device (tools/ns_two_streams.py)
@@ -79,17 +75,15 @@ int32_t fx_create_batch(FxContext **out, int32_t device, int32_t max_agents, int
         HIP_TRY(hipEventCreate(&t.e_obs1));
     }
     const int S = max_steps + 1;
-    // every agent's leading dimension is rounded up to 64 candidates
-    c->total_ld = (int64_t)align_up((size_t)max_candidates_total, 64) + 64 * (int64_t)max_agents;
-    c->max_blocks_total = c->total_ld / 2 + max_agents + 1;  // 64-lane workgroups at G = 32: 2 candidates each
-    c->in_bytes = (size_t)max_agents * input_bytes_for(0, S, max_ref_knots, max_obstacles, c->max_pred, false) +
+    const int64_t total_ld = c->caps.total_ld;
+    c->in_bytes = (size_t)max_agents * input_bytes_for(0, S, max_ref_knots, max_obstacles, c->caps.max_pred, false) +
                   align_up(sizeof(double) * 13 * (size_t)max_candidates_total, 256) + 4096;
     c->probs_bytes = align_up(sizeof(DevProblem) * (size_t)max_agents, 256);
     c->in_bytes += c->probs_bytes;
     HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_in), c->in_bytes, hipHostMallocMapped));
     HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_in_dev), c->h_in, 0));
     if (const char *sm = getenv("FX_STAGE")) c->stage_mode = !strcmp(sm, "dma") ? 1 : (!strcmp(sm, "kernel") ? 2 : (!strcmp(sm, "bar") ? 3 : 0));
-    if (const char *of = getenv("FX_OBST_STAGE")) c->obst_force = std::max(0, std::min(2, atoi(of)));   // experiments: fx_set_obstacle_stage's first argument
+    if (const char *of = getenv("FX_OBST_STAGE")) c->force.obst_stage = std::max(0, std::min(2, atoi(of)));   // experiments: fx_set_obstacle_stage's first argument
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_in), c->in_bytes));
     c->dev_bytes += (int64_t)c->in_bytes;
     if (c->stage_mode == 3) {   // opt-in (see probe_host_writes)
@@ -101,15 +95,15 @@ int32_t fx_create_batch(FxContext **out, int32_t device, int32_t max_agents, int
     c->h_probs = reinterpret_cast<DevProblem *>(c->h_in);
     c->d_probs = reinterpret_cast<DevProblem *>(c->d_in);
     int rc;
-    if ((rc = dev_alloc(c, &c->d_cost, c->total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_cost_tail, c->total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_flags, c->total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_costmap, (size_t)FX_NUM_COSTS * c->total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_coeffs, (size_t)FX_COEFF_ROWS * c->total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_trajlen, c->total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_bstep, c->total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_part_cost, c->max_blocks_total))) return rc;
-    if ((rc = dev_alloc(c, &c->d_part_idx, c->max_blocks_total))) return rc;
+    if ((rc = dev_alloc(c, &c->d_cost, total_ld))) return rc;
+    if ((rc = dev_alloc(c, &c->d_cost_tail, total_ld))) return rc;
+    if ((rc = dev_alloc(c, &c->d_flags, total_ld))) return rc;
+    if ((rc = dev_alloc(c, &c->d_costmap, (size_t)FX_NUM_COSTS * total_ld))) return rc;
+    if ((rc = dev_alloc(c, &c->d_coeffs, (size_t)FX_COEFF_ROWS * total_ld))) return rc;
+    if ((rc = dev_alloc(c, &c->d_trajlen, total_ld))) return rc;
+    if ((rc = dev_alloc(c, &c->d_bstep, total_ld))) return rc;
+    if ((rc = dev_alloc(c, &c->d_part_cost, c->caps.max_blocks_total))) return rc;
+    if ((rc = dev_alloc(c, &c->d_part_idx, c->caps.max_blocks_total))) return rc;
     if ((rc = dev_alloc(c, &c->d_counters, (size_t)max_agents * FX_CNT_COUNT))) return rc;
     HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_counters), sizeof(unsigned long long) * max_agents * (FX_CNT_COUNT + 1),
                           hipHostMallocMapped | hipHostMallocCoherent));
@@ -121,7 +115,7 @@ int32_t fx_create_batch(FxContext **out, int32_t device, int32_t max_agents, int
     HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(unsigned long long) * max_agents * FX_CNT_COUNT, c->stream));
     if ((rc = dev_alloc(c, &c->d_bar, 2 * 16 * 65))) return rc;   // (two barrier blocks: fx_step_kernel.h, FX_BAR_WORDS)
     HIP_TRY(hipMemsetAsync(c->d_bar, 0, sizeof(unsigned long long) * 2 * 16 * 65, c->stream));
-    if (const char *e = getenv("FX_STEP_KERNEL")) c->step_kernel_force = atoi(e) ? 2 : 1;
+    if (const char *e = getenv("FX_STEP_KERNEL")) c->force.step_kernel = atoi(e) ? 2 : 1;
     HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_pub), sizeof(double) * (FX_PUB_MAX + 1), hipHostMallocMapped | hipHostMallocCoherent));
     memset(c->h_pub, 0, sizeof(double) * (FX_PUB_MAX + 1));
     HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_pub_dev), c->h_pub, 0));
@@ -141,6 +135,8 @@ int32_t fx_create_batch(FxContext **out, int32_t device, int32_t max_agents, int
     HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_cand), sizeof(double) * c->h_cand_doubles, hipHostMallocDefault));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_topk_idx), sizeof(long long) * max_agents * 64, hipHostMallocDefault));
     c->slots.resize(max_agents);
+    c->plan_rows.resize(max_agents);
+    c->plan.agents = c->plan_rows.data();
     return FX_OK;
 }
 
@@ -229,14 +225,14 @@ int32_t fx_set_winner_buffer(FxContext *c, void *d_winner) {
 int32_t fx_set_store_mode(FxContext *c, int32_t store_mode) {
     if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
     if (store_mode < 0 || store_mode > 2) return set_err(FX_ERR_INVALID_ARGUMENT, "store mode must be 0 (auto), 1 (write-back) or 2 (write-through)");
-    c->store_force = store_mode;
+    c->force.store = store_mode;
     return FX_OK;
 }
 
 int32_t fx_set_part_mapping(FxContext *c, int32_t mapping) {
     if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
     if (mapping < 0 || mapping > 2) return set_err(FX_ERR_INVALID_ARGUMENT, "mapping must be 0 (auto), 1 (lane split) or 2 (wave split)");
-    c->wsplit_force = mapping;
+    c->force.wsplit = mapping;
     return FX_OK;
 }
 
@@ -244,7 +240,7 @@ int32_t fx_set_block_size(FxContext *c, int32_t block_size) {
     if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
     if (block_size != 0 && block_size != 64 && block_size != 128 && block_size != 256)
         return set_err(FX_ERR_INVALID_ARGUMENT, "block_size must be 0 (auto), 64, 128 or 256");
-    c->block_force = block_size;
+    c->force.block = block_size;
     return FX_OK;
 }
 
@@ -256,9 +252,9 @@ int32_t fx_set_tuning(FxContext *c, int32_t lanes_per_candidate, int32_t waves_p
     if (waves_per_simd != 0 && (waves_per_simd < 2 || waves_per_simd > 4))
         return set_err(FX_ERR_INVALID_ARGUMENT, "waves_per_simd must be 0 (auto), 2, 3 or 4");
     if (kernel_variant < 0 || kernel_variant > 2) return set_err(FX_ERR_INVALID_ARGUMENT, "kernel_variant must be 0 (auto), 1 (generic) or 2 (grid)");
-    c->G_force = lanes_per_candidate;
-    c->wpe_force = waves_per_simd;
-    c->variant_force = kernel_variant;
+    c->force.G = lanes_per_candidate;
+    c->force.wpe = waves_per_simd;
+    c->force.variant = kernel_variant;
     return FX_OK;
 }
 
@@ -308,9 +304,9 @@ int32_t fx_set_timing_interval(FxContext *c, int32_t every) {
 // [9] dynamic LDS bytes
 int32_t fx_step_info(const FxContext *c, int64_t *out10) {
     if (!c || !out10) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_step_info: NULL argument");
-    const int64_t v[10] = {c->use_grid, c->G_step, c->wpe_step, c->block_step, c->wsplit_step, c->fused_step, c->max_blocks_step,
-                           c->n_agents, c->pkg_step, (int64_t)c->lds_step};
-    memcpy(out10, v, sizeof(v));
+    int64_t v[16];
+    fx_step_info_of(c->plan, c->launch, c->stage_path, v);
+    memcpy(out10, v, sizeof(int64_t) * 10);
     return FX_OK;
 }
 
@@ -319,7 +315,7 @@ int32_t fx_set_obstacle_stage(FxContext *c, int32_t stage, int32_t steps_per_ite
     if (stage < 0 || stage > 2) return set_err(FX_ERR_INVALID_ARGUMENT, "stage must be 0 (auto), 1 (fused into the walk) or 2 (own kernel)");
     if (steps_per_item != 0 && steps_per_item != 2 && steps_per_item != 3 && steps_per_item != 5)
         return set_err(FX_ERR_INVALID_ARGUMENT, "steps_per_item must be 0 (auto), 2, 3 or 5");
-    c->obst_force = stage; c->obst_CH = steps_per_item;
+    c->force.obst_stage = stage; c->force.obst_CH = steps_per_item;
     return FX_OK;
 }
 double fx_last_obstacle_kernel_ms(const FxContext *cc) {
@@ -347,29 +343,22 @@ int32_t fx_read_obstacle_kernel_times(FxContext *c, int32_t max_n, double *obst_
 // 2: winner package; fx_tail.h)
 int32_t fx_step_info_ex(const FxContext *c, int64_t *out16) {
     if (!c || !out16) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_step_info_ex: NULL argument");
-    int rc = fx_step_info(c, out16);
-    if (rc) return rc;
-    out16[10] = c->split_step; out16[11] = c->split_CH; out16[12] = c->obs_blocks_step; out16[13] = (int64_t)c->obs_lds_step;
-    out16[14] = c->obs_wg_step; out16[15] = c->tail_step | ((int64_t)c->stage_path << 8);
-    if (c->step_kernel_step) {   // the whole step in one launch: steps per item, waves, LDS of THAT kernel; bit 16 says so
-        out16[11] = c->step_CH; out16[12] = (int64_t)c->step_blocks * (FX_BLOCK / 64); out16[13] = (int64_t)c->step_lds; out16[14] = 0;
-        out16[15] |= 1 << 16;
-    }
+    fx_step_info_of(c->plan, c->launch, c->stage_path, out16);
     return FX_OK;
 }
 
 int32_t fx_set_step_kernel(FxContext *c, int32_t mode, int32_t steps_per_item) {
     if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
-    if (mode < 0 || mode > 2) return set_err(FX_ERR_INVALID_ARGUMENT, "mode must be 0 (auto), 1 (off: three launches) or 2 (on where applicable)");
+    if (mode < 0 || mode > 2) return set_err(FX_ERR_INVALID_ARGUMENT, "mode must be 0 / 1 (off: three launches) or 2 (on where applicable)");
     if (steps_per_item != 0 && steps_per_item != 3 && steps_per_item != 5 && steps_per_item != 8)
         return set_err(FX_ERR_INVALID_ARGUMENT, "steps_per_item must be 0 (auto), 3, 5 or 8");
-    c->step_kernel_force = mode; c->step_kernel_CH = steps_per_item;   // (the mode takes effect at the next upload)
+    c->force.step_kernel = mode; c->force.step_kernel_CH = steps_per_item;   // (the mode takes effect at the next upload)
     return FX_OK;
 }
 int32_t fx_set_fused_selection(FxContext *c, int32_t enabled) {
     if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
-    c->fuse_enabled = enabled != 0;
-    c->fuse_any_size = enabled == 2;   // (takes effect at the next upload)
+    c->force.fuse_enabled = enabled != 0;
+    c->force.fuse_any_size = enabled == 2;   // (takes effect at the next upload)
     return FX_OK;
 }
 int32_t fx_set_timing(FxContext *c, int32_t mode) {

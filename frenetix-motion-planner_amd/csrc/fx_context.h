@@ -1,6 +1,6 @@
 // fx_context.h -- what the translation units of the C-ABI share: the context, its helpers, the launchers' declarations.
 //   fx_api.hip           context life cycle, settings, measurement hooks
-//   fx_api_step.hip      upload, launch policy (fx_evaluate), results, state updates, winner package, batched plan calls
+//   fx_api_step.hip      upload, evaluation (launch policy: fx_policy.h), results, state updates, winner package, batched plan calls
 //   fx_api_exchange.hip  survivor exchange inside the library (RCCL)
 //   fx_api_host.hip      host geometry of the callers either side of the path, read-back
 //   fx_api_risk.hip      trajectory risk and risk costs beside the plan step
@@ -29,7 +29,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 
-#include "fx_device.h"
+#include "fx_policy.h"
 
 extern "C" hipError_t fx_launch_eval(const DevProblem *d_probs, int n_agents, int max_blocks, size_t lds_bytes, int G,
                                      bool bundle, bool obst, bool extra, int wpe, hipEvent_t ev_start, hipEvent_t ev_stop,
@@ -77,12 +77,6 @@ inline int set_err(int code, const char *fmt, ...) {
                                              __FILE__, __LINE__);                                           \
     } while (0)
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-
-// bundles up to this size use write-through plane stores.  tools/store_sweep.py on MI355X: write-through is faster up to
-// ~0.5 GB (41 vs 45 us at 175 MB) and equal beyond (740 vs 746 us at 3.5 GB), so there is no upper limit by default.
-#define FX_STORE_WT_MAX_BYTES (~(size_t)0)
 // state updates up to this many bytes are staged by a copy kernel reading the mapped pinned block, larger ones by the DMA engine
 #define FX_STAGE_KERNEL_MAX ((size_t)1 << 20)
 #define FX_STAGE_HOST_MAX ((size_t)4 << 20)     // host writes into the device arena (large BAR): ~50 GB/s of posted writes
@@ -120,8 +114,7 @@ struct FxContext {
     long long n_steps = 0;       // evaluations so far
     int timing_every = 1;        // time every n-th step
     // capacities
-    int64_t max_cand = 0;
-    int32_t max_steps = 0, max_knots = 0, max_obs = 0, max_pred = 0, max_agents = 1;
+    int32_t max_agents = 1;                // (the others: caps)
     // input arena
     size_t in_bytes = 0;
     char *h_in = nullptr;   // pinned + mapped
@@ -192,15 +185,13 @@ struct FxContext {
     double *h_pkg = nullptr, *h_pkg_dev = nullptr;
     int pkg_stride = 0, pkg_plane_rows = 0;
     double *d_winner_own = nullptr;        // [max_agents][2]: the winner stays device-resident for the package kernel
-    bool package_enabled = false, pkg_step = false;
+    bool package_enabled = false;
     double *h_cand = nullptr;  // pinned staging of fx_read_candidate_agent: planes | coeffs | raw costs | cost | traj_len | flags
     size_t h_cand_doubles = 0;
     // chunk of fx_read_candidates_agent (FX_READ_CHUNK_BYTES each, allocated on its first call): ids | packed records, on the device
     // and pinned
     char *d_cands = nullptr, *h_cands = nullptr;
     long long *h_topk_idx = nullptr;
-    int64_t total_ld = 0;  // capacity of per-candidate arrays (elements)
-    int64_t max_blocks_total = 0;
     // current step
     int n_agents = 0;
     std::vector<FxAgentSlot> slots;
@@ -208,44 +199,17 @@ struct FxContext {
     size_t in_used = 0;                    // bytes of the staging block the last upload filled
     size_t dirty_lo = (size_t)-1, dirty_hi = 0;  // staging range rewritten by fx_update_state, copied by the next evaluation
     bool probs_dirty = false;
-    int max_blocks_step = 0, M_max_step = 0, S_max_step = 0, K_max_step = 0;
-    int G_step = 1, wpe_step = 2;          // lanes per candidate / occupancy target of the current step
-    int G_force = 0, wpe_force = 0;        // fx_set_tuning overrides (0 = automatic)
-    int variant_force = 0;                 // 0 auto, 1 generic kernel, 2 grid kernel
-    int block_force = 0;                   // grid-kernel workgroup size override (0 auto)
-    int wsplit_force = 0;                  // 0 auto, 1 lane split, 2 wave split
-    int obst_force = 0;                    // obstacle stage: 0 auto, 1 fused into the walk, 2 its own kernel (fx_set_obstacle_stage)
-    int obst_CH = 0;                       // steps per work item of the obstacle kernel (0 auto)
-    bool split_step = false;               // current step runs fx_obstacle_kernel behind the walk
-    int split_CH = 3, obs_blocks_step = 0;
-    int obs_wg_waves = 0, obs_tiles_step = 0;   // obstacle kernel with one workgroup per tile: waves per workgroup (0: one wave per (tile, chunk) item), tiles
-    int obs_wg_step = 0;                        // waves per workgroup of the last obstacle-kernel launch (0: single-wave items)
-    size_t obs_lds_step = 0;
-    // the whole step in ONE launch (fx_step_kernel.h): walk | grid barrier | obstacle items | grid barrier | selection
-    int step_kernel_force = 0;             // 0 auto, 1 off, 2 on where applicable (fx_set_step_kernel; FX_STEP_KERNEL=0/1 in the environment)
-    int step_kernel_CH = 0;                // steps per obstacle item in that kernel (0 auto; 3, 5 or 8)
-    bool step_kernel_ok = false;           // the upload's step qualifies
-    bool step_kernel_step = false;         // the last evaluation ran it
-    int step_blocks = 0, step_CH = 0;      // workgroups per agent / steps per item of that launch
-    size_t step_lds = 0;
-    int64_t last_live = -1;                // costed candidates of the previous step's agents (max): sizes the obstacle items
-    unsigned long long *d_bar = nullptr;   // the two grid barriers' counter + release-flag blocks, monotonic
+    // launch policy (fx_policy.h): what callers and experiments force, what the last upload decided, what the last evaluation launched
+    FxForce force;
+    FxCaps caps;
+    FxStepPlan plan;
+    std::vector<FxAgentPlan> plan_rows;    // [max_agents], plan.agents
+    FxLaunchPlan launch;
+    int64_t last_live = -1;                // costed candidates of the previous step's agents (max): sizes the one-launch step's obstacle items
+    unsigned long long *d_bar = nullptr;   // the one-launch step's two grid barriers' counter + release-flag blocks, monotonic
     unsigned long long bar_base = 0;       // their value before the next launch
-    int store_force = 0;                   // 0 auto, 1 write-back, 2 write-through plane stores
-    bool wsplit_step = false;
-    int block_step = FX_BLOCK;
-    bool use_grid = false;                 // current step runs fx_eval_grid_kernel
-    size_t lds_step = 0;
-    bool any_bundle = false, any_obst = false, any_extra = false;
     int timing = FX_TIMING_OFF;
-    bool timed_step = false, eval_launched = false;
-    bool fuse_enabled = true, fusable_step = false, fused_step = false;
-    // fused tail (fx_tail.h): the step's last workgroup also counts the collisions in front of the winner / gathers the package
-    bool fuse_any_size = false;       // fx_set_fused_selection(ctx, 2): no candidate bound on the in-kernel collision count
-    bool count_step = false;          // some agent of the upload runs the collision stage inside the evaluation kernel
-    bool wt_step = false;             // the upload's plane stores are write-through
-    uint32_t tail_step = 0;           // FX_TAIL_* of the last evaluation
-    size_t gen_rec_lds = 0;           // generic kernel, >= 4 lanes per candidate: bytes of the staged obstacle records + step masks
+    bool timed_step = false;
     int64_t dev_bytes = 0;
     struct FxRiskState *risk = nullptr;    // trajectory risk (fx_api_risk.hip): obstacle tables and buffers, created on first use
     struct FxSparseState *sparse = nullptr;   // sparse sets of listed candidates (fx_api_materialise.hip), created on first use

@@ -1,0 +1,67 @@
+// policy_table.cpp -- the launch policy (csrc/fx_policy.h) on rows of plan steps read from standard input, without a GPU
+// (tests/test_launch_policy.py builds it with the compiler's host pass and compares its answers with a recording of real contexts).
+//
+// in:  per row  name | max_agents max_cand max_steps max_knots max_obs max_pred | G wpe variant block mapping obst_stage obst_CH fused
+//               store step_kernel step_kernel_CH | package last_live cap3 cap5 cap8 lds_pad obst_wg | n_agents, then per agent
+//               N M K P mode nT nV nD n_rows matrix shard_begin shard_count n_bound have_hull n_cost cost_id...
+// out: per row  name ok <16 numbers of fx_step_info_ex> <one-launch step: CH blocks lds>   or   name err <code> <message>
+#include <iostream>
+#include <string>
+#include <vector>
+
+#include "fx_policy.h"
+
+int main() {
+    std::string name;
+    static const double some_doubles[1] = {0.0};
+    static const int32_t some_ints[1] = {0};
+    while (std::cin >> name) {
+        long long max_cand;
+        int max_agents, max_steps, max_knots, max_obs, max_pred, fused, package, n_agents, cap[3];
+        long long last_live, lds_pad;
+        FxForce f;
+        std::cin >> max_agents >> max_cand >> max_steps >> max_knots >> max_obs >> max_pred;
+        std::cin >> f.G >> f.wpe >> f.variant >> f.block >> f.wsplit >> f.obst_stage >> f.obst_CH >> fused >> f.store >> f.step_kernel >>
+            f.step_kernel_CH;
+        std::cin >> package >> last_live >> cap[0] >> cap[1] >> cap[2] >> lds_pad >> f.obst_wg >> n_agents;
+        f.fuse_enabled = fused != 0;
+        f.fuse_any_size = fused == 2;
+        f.lds_pad = (size_t)lds_pad;
+        std::vector<FxProblem> probs(n_agents);
+        std::vector<std::vector<int32_t>> ids(n_agents);
+        for (int a = 0; a < n_agents; a++) {
+            FxProblem &p = probs[a];
+            p = FxProblem();
+            int matrix, have_hull;
+            long long n_rows, shard_begin, shard_count;
+            std::cin >> p.N >> p.M >> p.K >> p.P >> p.mode >> p.nT >> p.nV >> p.nD >> n_rows >> matrix >> shard_begin >> shard_count >>
+                p.n_bound >> have_hull >> p.n_cost;
+            p.n_rows = n_rows; p.shard_begin = shard_begin; p.shard_count = shard_count;
+            ids[a].resize(p.n_cost);
+            for (int n = 0; n < p.n_cost; n++) std::cin >> ids[a][n];
+            p.cost_id = ids[a].data();
+            if (matrix) p.sampling_matrix = some_doubles;   // (the policy asks only whether the arrays are there)
+            if (have_hull) { p.obs_hull = some_doubles; p.obs_nhull = some_ints; }
+        }
+        if (!std::cin) { std::cerr << "bad row " << name << "\n"; return 2; }
+        std::vector<FxAgentPlan> rows(n_agents);
+        FxStepPlan pl;
+        pl.agents = rows.data();
+        char err[512] = "";
+        const int rc = fx_plan_upload(n_agents, probs.data(), f, fx_caps_of(max_agents, max_cand, max_steps, max_knots, max_obs, max_pred), &pl,
+                                      err, sizeof(err));
+        if (rc) { std::cout << name << " err " << rc << " " << err << "\n"; continue; }
+        FxLaunchPlan L = fx_plan_launches(pl, f, package != 0);
+        FxStepKernelSize sz;
+        if (L.try_step_kernel) {
+            sz = fx_plan_step_kernel(pl, f, last_live, cap);
+            if (sz.CH) fx_take_step_kernel(L, sz);
+        }
+        int64_t v[16];
+        fx_step_info_of(pl, L, 0, v);
+        std::cout << name << " ok";
+        for (int i = 0; i < 16; i++) std::cout << " " << v[i];
+        std::cout << " " << sz.CH << " " << sz.blocks << " " << sz.lds << "\n";
+    }
+    return 0;
+}

@@ -5,7 +5,7 @@ wrapper (oracle/oracle.py) can share the struct definitions.
 """
 import ctypes as C
 
-FX_ABI_VERSION = 13
+FX_ABI_VERSION = 14
 FX_READ_CHUNK_BYTES = 8 << 20   # fx_read_candidates_agent: bytes per chunk (ids + packed records)
 FX_LON_VELOCITY_KEEPING, FX_LON_STOP_POINT = 0, 1
 

@@ -433,6 +433,48 @@ int32_t fx_math_selftest(int32_t n, const double *x, double *atan_out, double *s
     return FX_OK;
 }
 
+// self-test hook: ONE primitive of the kernels' arithmetic over n host elements (synchronous; fx_selftest_kernel.h).  Everything
+// that could keep the kernel running -- the element count, and for wrap_pm_2pi's loop the magnitude of every input -- is checked
+// here, before anything is allocated or launched.
+int32_t fx_device_selftest(int32_t op, int32_t n, const double *const *in, double *const *out) {
+    SelftestShape sh;
+    if (!fx_selftest_shape(op, &sh)) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_device_selftest: unknown op %d", op);
+    if (n < 1 || n > FX_SELFTEST_MAX_N || !in || !out)
+        return set_err(FX_ERR_INVALID_ARGUMENT, "fx_device_selftest: n = %d outside 1 .. %d, or NULL arrays", n, FX_SELFTEST_MAX_N);
+    size_t total = 0;
+    for (int k = 0; k < sh.n_in; k++) {
+        if (!in[k]) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_device_selftest: input %d is NULL", k);
+        total += (size_t)sh.w[k] * n;
+    }
+    for (int k = 0; k < sh.n_out; k++) {
+        if (!out[k]) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_device_selftest: output %d is NULL", k);
+        total += (size_t)n;
+    }
+    if (op == FX_SELFTEST_WRAP_PM_2PI)
+        for (int i = 0; i < n; i++)
+            if (!(std::fabs(in[0][i]) <= FX_SELFTEST_WRAP_MAX))
+                return set_err(FX_ERR_INVALID_ARGUMENT, "fx_device_selftest: wrap_pm_2pi input %d is not finite or beyond %g", i,
+                               FX_SELFTEST_WRAP_MAX);
+    double *d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(double) * total));
+    SelftestArgs a = {};
+    double *p = d;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < sh.n_in && e == hipSuccess; k++) {
+        e = hipMemcpy(p, in[k], sizeof(double) * sh.w[k] * n, hipMemcpyHostToDevice);
+        a.in[k] = p;
+        p += (size_t)sh.w[k] * n;
+    }
+    for (int k = 0; k < sh.n_out; k++, p += n) a.out[k] = p;
+    if (e == hipSuccess) e = fx_launch_selftest(op, n, &a, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (int k = 0; k < sh.n_out && e == hipSuccess; k++) e = hipMemcpy(out[k], a.out[k], sizeof(double) * n, hipMemcpyDeviceToHost);
+    const hipError_t ef = hipFree(d);
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    return FX_OK;
+}
+
 // Road-boundary geometry prep (host only): split segments into pieces, bin them by reference knot.
 int32_t fx_build_boundary_bins(int32_t M, const double *ref_x, const double *ref_y, int32_t n_seg, const double *seg,
                                double max_len, double reach, int32_t piece_cap, double *piece_out, int32_t *n_piece,

@@ -46,6 +46,7 @@ extern "C" hipError_t fx_launch_select(const DevProblem *d_probs, int n_agents, 
                                        unsigned long long seq, double *dev_winner, double *host_pkg, int pkg_stride, int pkg_plane_rows,
                                        hipStream_t stream);
 extern "C" hipError_t fx_launch_math_test(int n, const double *x, double *at, double *sn, double *cs, hipStream_t stream);
+extern "C" hipError_t fx_launch_selftest(int op, int n, const SelftestArgs *args, hipStream_t stream);
 extern "C" hipError_t fx_launch_publish(const double *src, int n, double *host_dst, unsigned long long *host_seq,
                                         unsigned long long seq, hipStream_t stream);
 extern "C" hipError_t fx_launch_stage(const void *src_mapped, void *dst, size_t bytes, hipStream_t stream);

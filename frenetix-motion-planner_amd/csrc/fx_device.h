@@ -299,6 +299,33 @@ struct GatherArgs {
     uint32_t parts;            // FX_GATHER_*
 };
 
+// arguments of the primitives' self-test kernel (fx_selftest_kernel.h; FX_SELFTEST_* op codes: include/fxplan.h)
+struct SelftestArgs {
+    const double *in[4];   // op-specific widths (doubles per element): fx_selftest_shape
+    double *out[6];        // one double per element each
+};
+
+// arrays an op reads and writes: n_in arrays of w[k] doubles per element, n_out arrays of one double per element
+struct SelftestShape {
+    int n_in, w[4], n_out;
+};
+static inline bool fx_selftest_shape(int op, SelftestShape *s) {
+    switch (op) {
+    case FX_SELFTEST_ATAN: case FX_SELFTEST_ATAN_TAB: case FX_SELFTEST_ATAN_SMALL: case FX_SELFTEST_ATAN_SMALL_TAB:
+    case FX_SELFTEST_RCP_NR: case FX_SELFTEST_RCP_PRED: case FX_SELFTEST_NP_ROUND5: case FX_SELFTEST_WRAP_PM_2PI:
+        *s = {1, {1, 0, 0, 0}, 1}; return true;
+    case FX_SELFTEST_SINCOS: case FX_SELFTEST_SINCOS_TAB: case FX_SELFTEST_SQRT_RSQRT:
+        *s = {1, {1, 0, 0, 0}, 2}; return true;
+    case FX_SELFTEST_FDIV: case FX_SELFTEST_DIV_RCP:
+        *s = {2, {1, 1, 0, 0}, 1}; return true;
+    case FX_SELFTEST_OBB_HULL:      // (c0x, c0y, u0x, u0y), (c1x, c1y, u1x, u1y), (hl, hw) -> cx, cy, ex, ey, h1, h2
+        *s = {3, {4, 4, 2, 0}, 6}; return true;
+    case FX_SELFTEST_OBB_OVERLAP:   // two stored boxes (cx, cy, ex, ey, h1, h2) -> 1.0 overlap / 0.0 separated
+        *s = {2, {6, 6, 0, 0}, 1}; return true;
+    default: return false;
+    }
+}
+
 // Pointers stored inside DevProblem are loaded from memory, so the compiler only knows them as generic ("flat")
 // pointers: every access would be a flat_load/flat_store and wave-uniform reads could not become scalar loads.
 // They all point into hipMalloc'ed memory -- say so.

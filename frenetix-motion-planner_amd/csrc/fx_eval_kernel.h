@@ -32,6 +32,13 @@ struct Knot {  // one reference knot as staged in LDS
     double pos, theta, curv, curv_d, x, y, nx, ny;
 };
 
+// A loop of |a| / 2 pi rounds: it ends at once for a NaN (both comparisons fail), never for +-inf (inf - 2 pi = inf) and not in any
+// useful time for a huge finite a.  What keeps the non-finite out: its one caller, make_lon_row, passes
+// div_rcp(dtheta * (s - knot), seg, r_seg) + theta_knot, and div_rcp turns an infinite numerator into NaN -- q = a * r is +-inf and
+// the residual fma(-b, q, a) is inf - inf (b and r have one sign) -- as 0 * inf does for dtheta = 0 and a zero-length segment's
+// 1 / 0 does in rcp_nr.  So a non-finite s, knot position or knot heading reaches the loop as NaN, the row's heading is NaN and the
+// candidate is infeasible (test_non_finite_inputs).  A FINITE s of absurd size is the caller's to refuse, as with the reference's
+// own loop; fx_device_selftest refuses |a| > FX_SELFTEST_WRAP_MAX.  Bit-equal to the same loop in NumPy (tests/test_device_math.py).
 __device__ __forceinline__ double wrap_pm_2pi(double a) {
     // commonroad make_valid_orientation (restated): bring into [-2pi, 2pi]
     while (a > FX_TWO_PI) a -= FX_TWO_PI;
@@ -39,15 +46,18 @@ __device__ __forceinline__ double wrap_pm_2pi(double a) {
     return a;
 }
 
-// a / b given r = RN(1/b): one Newton correction on the quotient (Markstein).  Correctly rounded for the
-// finite, normal operands of this kernel; 3 FP64 ops instead of the ~12-instruction IEEE division sequence.
+// a / b given r = RN(1/b): one Newton correction on the quotient (Markstein); 3 FP64 ops instead of the ~12-instruction IEEE
+// division sequence.  Measured on the MI355X with r = rcp_nr(b) (tests/test_device_math.py): bit-equal to IEEE a / b on all 253 803
+// pairs tried, the kernels' own divisors and the mantissas next to 1.0 and 2.0 included; -0 / b (b > 0) gives +0.
 __device__ __forceinline__ double div_rcp(double a, double b, double r) {
     const double q = a * r;
     const double e = fma(-b, q, a);
     return fma(e, r, q);
 }
 
-// np.round(x, 5) = rint(x * 1e5) / 1e5
+// np.round(x, 5) = rint(x * 1e5) / 1e5.  Measured on the MI355X (tests/test_device_math.py; every decimal tie k * 1e-5 + 5e-6 up to
+// |x| = 2 with both neighbours, 1e-12 .. 1e9): equal to NumPy in value on all 1 400 005 inputs and bit for bit except where NumPy
+// returns -0 -- the device returns +0; the one consumer takes fabs().
 __device__ __forceinline__ double np_round5(double x) { return div_rcp(rint(x * 1e5), 1e5, 1e-5); }
 
 // streaming composite Simpson (scipy.integrate.simpson, equal spacing) over y_0..y_{n-1}
@@ -86,25 +96,47 @@ struct Obb {
 // range on e is therefore [min_j c_j . e - r1, max_j c_j . e + r1], i.e. the hull's centre is the midpoint of the two centres
 // and its half extent |(c1 - c0) . e| / 2 + r1 (likewise on f) -- ~35 operations where forming both boxes' ranges and merging
 // them took ~70 (as many as the twenty prediction visits of the step).  The unit axis comes from v_rsq_f64 + two coupled Newton
-// steps (sqrt_rsqrt in fx_walk.h).  Differs from the oracle's box-by-box form by an ulp or two; decisions are unaffected
+// steps (sqrt_rsqrt in fx_walk.h).  Held to the exact hull (mpmath) at twice the error of the oracle's box-by-box form on the same
+// inputs (tests/test_device_math.py; the figures: DESIGN.md section 2, "The device primitives"); decisions are unaffected
 // (the oracle reports every collision decision closer than 1e-9 to its threshold as fragile, tests/admissible.py).
 __device__ __forceinline__ void sqrt_rsqrt(double x, double &sq, double &rsq);
+#define FX_HULL_NEAR_OPPOSITE 0.0625   // |u0 + u1| below this: box-by-box form (the bisector form is then 4e-15 * hl off, and growing)
 __device__ __forceinline__ Obb obb_hull(double c0x, double c0y, double u0x, double u0y, double c1x, double c1y,
                                         double u1x, double u1y, double hl, double hw) {
     const double mx = u0x + u1x, my = u0y + u1y;
     double mn, r_mn;
     sqrt_rsqrt(fma(mx, mx, my * my), mn, r_mn);
-    const bool flat = !(mn >= 1e-12);   // opposite headings (or a non-finite one): the first box's axis
-    Obb o;
-    o.ex = flat ? u0x : mx * r_mn;
-    o.ey = flat ? u0y : my * r_mn;
-    const double a = flat ? 1.0 : 0.5 * mn;                                    // |u_j . e|
-    const double b = flat ? 0.0 : fabs(fma(u0x, u1y, -(u0y * u1x))) * r_mn;    // |u_j x e|
     const double tx = c1x - c0x, ty = c1y - c0y;
-    o.cx = fma(0.5, tx, c0x);
-    o.cy = fma(0.5, ty, c0y);
-    o.h1 = fma(0.5, fabs(fma(tx, o.ex, ty * o.ey)), fma(hl, a, hw * b));
-    o.h2 = fma(0.5, fabs(fma(ty, o.ex, -(tx * o.ey))), fma(hl, b, hw * a));
+    Obb o;
+    if (mn >= FX_HULL_NEAR_OPPOSITE) {
+        o.ex = mx * r_mn;
+        o.ey = my * r_mn;
+        const double a = 0.5 * mn;                                    // |u_j . e|
+        const double b = fabs(fma(u0x, u1y, -(u0y * u1x))) * r_mn;    // |u_j x e|
+        o.cx = fma(0.5, tx, c0x);
+        o.cy = fma(0.5, ty, c0y);
+        o.h1 = fma(0.5, fabs(fma(tx, o.ex, ty * o.ey)), fma(hl, a, hw * b));
+        o.h2 = fma(0.5, fabs(fma(ty, o.ex, -(tx * o.ey))), fma(hl, b, hw * a));
+    } else {
+        // Headings within FX_HULL_NEAR_OPPOSITE of opposite (never the ego's consecutive steps: a reversal within one time step), or
+        // a non-finite one.  The identities above hold for EXACTLY unit headings; headings that are unit to an ulp miss them by that
+        // ulp over |u0 + u1| -- 5e-10 m at pi - 1e-6 -- and with the first box's axis (|u0 + u1| < 1e-12) the second box is not
+        // aligned with it at all.  Here the two boxes' ranges are formed one by one, relative to c0, and merged, as the definition
+        // says (tests/test_device_math.py).
+        const bool flat = !(mn >= 1e-12);   // opposite headings: the first box's axis
+        o.ex = flat ? u0x : mx * r_mn;
+        o.ey = flat ? u0y : my * r_mn;
+        const double a0 = fabs(fma(u0x, o.ex, u0y * o.ey)), b0 = fabs(fma(u0y, o.ex, -(u0x * o.ey)));
+        const double a1 = fabs(fma(u1x, o.ex, u1y * o.ey)), b1 = fabs(fma(u1y, o.ex, -(u1x * o.ey)));
+        const double r10 = fma(hl, a0, hw * b0), r20 = fma(hl, b0, hw * a0), r11 = fma(hl, a1, hw * b1), r21 = fma(hl, b1, hw * a1);
+        const double s1 = fma(tx, o.ex, ty * o.ey), s2 = fma(ty, o.ex, -(tx * o.ey));   // c1 - c0 on (e, f), f = (-ey, ex)
+        const double lo1 = fmin(-r10, s1 - r11), hi1 = fmax(r10, s1 + r11), lo2 = fmin(-r20, s2 - r21), hi2 = fmax(r20, s2 + r21);
+        const double m1 = 0.5 * (lo1 + hi1), m2 = 0.5 * (lo2 + hi2);
+        o.cx = c0x + fma(m1, o.ex, -(m2 * o.ey));
+        o.cy = c0y + fma(m1, o.ey, m2 * o.ex);
+        o.h1 = 0.5 * (hi1 - lo1);
+        o.h2 = 0.5 * (hi2 - lo2);
+    }
     return o;
 }
 

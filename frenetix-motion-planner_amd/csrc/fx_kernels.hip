@@ -32,6 +32,7 @@
 #include "fx_step_kernel.h"
 #include "fx_risk_kernel.h"
 #include "fx_gather_kernel.h"
+#include "fx_selftest_kernel.h"
 
 using fxk::wave_count;
 
@@ -388,6 +389,13 @@ __global__ void fx_math_test_kernel(int n, const double *__restrict__ x, double 
 
 extern "C" hipError_t fx_launch_math_test(int n, const double *x, double *at, double *sn, double *cs, hipStream_t stream) {
     hipLaunchKernelGGL(fx_math_test_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, x, at, sn, cs);
+    return hipGetLastError();
+}
+
+// one primitive of the kernels' arithmetic, elementwise (fx_selftest_kernel.h; tests/test_device_math.py)
+extern "C" hipError_t fx_launch_selftest(int op, int n, const SelftestArgs *args, hipStream_t stream) {
+    if (n < 1 || n > FX_SELFTEST_MAX_N) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fx_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, op, n, *args);
     return hipGetLastError();
 }
 

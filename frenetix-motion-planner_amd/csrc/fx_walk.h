@@ -58,7 +58,10 @@ static_assert(sizeof(LonRow) == 128, "LonRow must be 128 bytes");
 
 enum : uint32_t { LON_NEG = 1u, LON_ACC = 2u, LON_MOVING = 4u, LON_INDOMAIN = 8u };
 
-// 1/d for normal, finite d: hardware estimate + two Newton steps (full double precision)
+// 1/d for normal, finite d: hardware estimate + two Newton steps.  Measured on the MI355X (tests/test_device_math.py): the
+// correctly rounded 1/d on every operand the kernels form and on 200 000 random ones of either sign; of the 2 000 mantissas
+// next to 2.0 six (0x1.ffffffffffff3 .. dp+0, odd last digits) land on the other neighbour of a near-tie, 0.5000000000000094 ulp
+// from 1/d -- Markstein's exception; never more than that.
 __device__ __forceinline__ double rcp_nr(double d) {
     double r = __builtin_amdgcn_rcp(d);
     double e = fma(-d, r, 1.0);
@@ -112,14 +115,18 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
     return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-// n / d with one residual correction on the quotient (correctly rounded for the operands of this kernel)
+// n / d with one residual correction on the quotient.  Measured on the MI355X (tests/test_device_math.py): bit-equal to IEEE n / d
+// on all 253 803 operand pairs tried -- the kernels' own divisors, 200 000 random pairs, the mantissas next to 1.0 and 2.0 as
+// divisors and as numerators -- with one exception in the sign of zero: -0 / d (d > 0) gives +0.
 __device__ __forceinline__ double fdiv(double n, double d) {
     const double r = rcp_nr(d);
     const double q = n * r;
     return fma(fma(-d, q, n), r, q);
 }
 
-// sqrt(x) and 1/sqrt(x) together: v_rsq_f64 + two coupled (Goldschmidt) Newton steps
+// sqrt(x) and 1/sqrt(x) together: v_rsq_f64 + two coupled (Goldschmidt) Newton steps; positive normal x (0 gives NaN: the callers
+// guard it).  Measured on the MI355X (tests/test_device_math.py, 228 602 operands): sq is the correctly rounded root on every one;
+// rsq carries no residual step and is within 1.83 * 2^-53 relative of 1/sqrt(x) (asserted: 2^-51).
 __device__ __forceinline__ void sqrt_rsqrt(double x, double &sq, double &rsq) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y, h = 0.5 * y;

@@ -193,6 +193,33 @@ def math_selftest(x: np.ndarray):
     return outs
 
 
+# fx_device_selftest: op code, doubles per element of each input array, number of outputs (include/fxplan.h)
+SELFTEST_OPS = {
+    "atan": (0, (1,), 1), "atan_tab": (1, (1,), 1), "atan_small": (2, (1,), 1), "atan_small_tab": (3, (1,), 1),
+    "sincos": (4, (1,), 2), "sincos_tab": (5, (1,), 2), "rcp_nr": (6, (1,), 1), "rcp_pred": (7, (1,), 1), "fdiv": (8, (1, 1), 1),
+    "sqrt_rsqrt": (9, (1,), 2), "div_rcp": (10, (1, 1), 1), "np_round5": (11, (1,), 1), "wrap_pm_2pi": (12, (1,), 1),
+    "obb_hull": (13, (4, 4, 2), 6), "obb_overlap": (14, (6, 6), 1),
+}
+
+
+def device_selftest(op, *arrays):
+    """One arithmetic primitive of the kernels (csrc/fx_math.h, fx_walk.h, fx_eval_kernel.h) on the device, elementwise over the
+    rows of `arrays`: the list of its output arrays.  `op` is a name of SELFTEST_OPS; an input of width w is [n] (w = 1) or [n][w]."""
+    code, widths, n_out = SELFTEST_OPS[op]
+    if len(arrays) != len(widths):
+        raise ValueError(f"{op} takes {len(widths)} arrays")
+    ins = [np.ascontiguousarray(a, dtype=np.float64) for a in arrays]
+    n = ins[0].shape[0] if ins[0].ndim else 0
+    for a, w in zip(ins, widths):
+        if a.shape != ((n,) if w == 1 else (n, w)):
+            raise ValueError(f"{op}: input of shape {a.shape}, expected {(n,) if w == 1 else (n, w)}")
+    outs = [np.zeros(n) for _ in range(n_out)]
+    pd = C.POINTER(C.c_double)
+    check(lib().fx_device_selftest(code, n, (pd * 4)(*[a.ctypes.data_as(pd) for a in ins]),
+                                   (pd * 6)(*[o.ctypes.data_as(pd) for o in outs])))
+    return outs
+
+
 def device_count() -> int:
     n = C.c_int32(0)
     lib().fx_device_count(C.byref(n))

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 13
+#define FX_ABI_VERSION 14
 
 /* ---- status codes (planner.py / reactive_planner_cpp.py raise Python exceptions; the shim maps
  *      <0 -> ValueError, >0 -> RuntimeError, see SURVEY 8b "Error conventions") ---- */
@@ -566,6 +566,26 @@ int32_t fx_set_timing_interval(FxContext *ctx, int32_t every);
 int32_t fx_read_kernel_times(FxContext *ctx, int32_t max_n, double *eval_ms, double *step_ms, int32_t *n_out);
 /* device self-test of the kernel's elementary functions (atan, sin, cos) on n host values */
 int32_t fx_math_selftest(int32_t n, const double *x, double *atan_out, double *sin_out, double *cos_out);
+/* device self-test of ONE arithmetic primitive of the kernels (csrc/fx_math.h, fx_walk.h, fx_eval_kernel.h), elementwise over n
+ * host elements, synchronous: allocates, copies, launches, synchronises, copies back and frees.  in[k] holds n elements of the
+ * op's k-th operand, out[k] receives n doubles of its k-th result (entries beyond what the op uses are not read):
+ *   ATAN, ATAN_TAB, ATAN_SMALL, ATAN_SMALL_TAB, RCP_NR, RCP_PRED, NP_ROUND5, WRAP_PM_2PI   in: x            out: f(x)
+ *   SINCOS, SINCOS_TAB                                                                      in: x            out: sin, cos
+ *   SQRT_RSQRT                                                                              in: x            out: sqrt, 1/sqrt
+ *   FDIV (n / d), DIV_RCP (a / b with the reciprocal of rcp_nr)                             in: n, d         out: quotient
+ *   OBB_HULL     in: [n][4] (c0x, c0y, u0x, u0y), [n][4] (c1x, c1y, u1x, u1y), [n][2] (hl, hw)              out: cx, cy, ex, ey, h1, h2
+ *   OBB_OVERLAP  in: [n][6], [n][6] stored boxes (cx, cy, ex, ey, h1, h2)                                   out: 1.0 overlap, 0.0 separated
+ * 1 <= n <= FX_SELFTEST_MAX_N.  WRAP_PM_2PI is a loop over |x| / 2 pi rounds: an input that is not finite or beyond
+ * FX_SELFTEST_WRAP_MAX is refused (FX_ERR_INVALID_ARGUMENT) before anything is launched. */
+enum {
+    FX_SELFTEST_ATAN = 0, FX_SELFTEST_ATAN_TAB = 1, FX_SELFTEST_ATAN_SMALL = 2, FX_SELFTEST_ATAN_SMALL_TAB = 3,
+    FX_SELFTEST_SINCOS = 4, FX_SELFTEST_SINCOS_TAB = 5, FX_SELFTEST_RCP_NR = 6, FX_SELFTEST_RCP_PRED = 7, FX_SELFTEST_FDIV = 8,
+    FX_SELFTEST_SQRT_RSQRT = 9, FX_SELFTEST_DIV_RCP = 10, FX_SELFTEST_NP_ROUND5 = 11, FX_SELFTEST_WRAP_PM_2PI = 12,
+    FX_SELFTEST_OBB_HULL = 13, FX_SELFTEST_OBB_OVERLAP = 14, FX_SELFTEST_N_OPS = 15
+};
+#define FX_SELFTEST_MAX_N (1 << 22)
+#define FX_SELFTEST_WRAP_MAX 100.0
+int32_t fx_device_selftest(int32_t op, int32_t n, const double *const *in, double *const *out);
 
 /* ---- trajectory risk: collision probability x harm (risk_costs.py:20-118, crash_angle_simplified) -- DESIGN.md section 11 ----
  * Nothing here runs unless called: the plan step, its launches and its buffers are unchanged.  The risk buffers are allocated

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Parse `-Rpass-analysis=kernel-resource-usage` remarks (stdin or file) into one line per kernel: VGPRs, spills, occupancy, LDS."""
+"""Parse `-Rpass-analysis=kernel-resource-usage` remarks (stdin or file) into one line per kernel: VGPRs, SGPRs, spills, occupancy, LDS."""
 import re, sys, subprocess
 txt = open(sys.argv[1]).read() if len(sys.argv) > 1 else sys.stdin.read()
 cur = None
@@ -25,5 +25,5 @@ except Exception:
 for n, d in zip(names, dem):
     r = rows[n]
     short = re.sub(r"\(.*", "", d).replace("void ", "")
-    print(f"{short:60s} VGPR {r.get('VGPRs', -1):4d} spillV {r.get('VGPRs Spill', 0):3d} spillS {r.get('SGPRs Spill', 0):3d} scratch {r.get('ScratchSize [bytes/lane]', 0):4d} "
+    print(f"{short:60s} VGPR {r.get('VGPRs', -1):4d} SGPR {r.get('SGPRs', -1):3d} spillV {r.get('VGPRs Spill', 0):3d} spillS {r.get('SGPRs Spill', 0):3d} scratch {r.get('ScratchSize [bytes/lane]', 0):4d} "
           f"occ {r.get('Occupancy [waves/SIMD]', -1)} lds {r.get('LDS Size [bytes/block]', 0)}")

@@ -158,6 +158,7 @@ int32_t fx_destroy(FxContext *c) {
     for (void *p : dev) if (p) (void)hipFree(p);
     fx_risk_release(c);
     fx_sparse_release(c);
+    fx_sort_release(c);
     if (c->d_bstep) (void)hipFree(c->d_bstep);
     if (c->d_cands) (void)hipFree(c->d_cands);
     if (c->h_cands) (void)hipHostFree(c->h_cands);

@@ -5,6 +5,7 @@
 //   fx_api_host.hip      host geometry of the callers either side of the path, read-back
 //   fx_api_risk.hip      trajectory risk and risk costs beside the plan step
 //   fx_api_materialise.hip  listed candidates of a step re-walked into a sparse set, its read-back and package
+//   fx_api_sort.hip      stable cost order of all candidates beside the step, read back by rank
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -214,10 +215,12 @@ struct FxContext {
     int64_t dev_bytes = 0;
     struct FxRiskState *risk = nullptr;    // trajectory risk (fx_api_risk.hip): obstacle tables and buffers, created on first use
     struct FxSparseState *sparse = nullptr;   // sparse sets of listed candidates (fx_api_materialise.hip), created on first use
+    struct FxSortState *sort = nullptr;       // cost order of all candidates (fx_api_sort.hip), created on first use
 };
 
 void fx_risk_release(FxContext *c);   // (fx_api_risk.hip)
 void fx_sparse_release(FxContext *c);   // (fx_api_materialise.hip)
+void fx_sort_release(FxContext *c);     // (fx_api_sort.hip)
 
 // An agent's sparse set as its consumers see it (fx_api_materialise.hip): the structure-of-arrays rows of
 // the n listed candidates, column = position in the ascending, de-duplicated list `ids`

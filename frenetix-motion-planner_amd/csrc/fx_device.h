@@ -299,6 +299,27 @@ struct GatherArgs {
     uint32_t parts;            // FX_GATHER_*
 };
 
+// arguments of the sort kernels (fx_sort_kernel.h).  One agent's planes and where its segment starts in the
+// sort's own per-candidate arrays; `agents` is indexed by agent0 + blockIdx.y.
+struct FxSortAgent {
+    const double *cost;        // [C] the agent's cost plane (read only)
+    const uint32_t *flags;     // [C] the agent's flag plane (read only)
+    int64_t C;                 // candidates
+    int64_t off;               // start of the agent's segment in key[], idx[], order[]
+};
+struct FxSortArgs {
+    const FxSortAgent *agents;
+    unsigned long long *key[2];   // ping-pong keys of the general decomposition
+    uint32_t *idx[2];             // ... and local indices
+    int64_t *order;               // the result: local indices by rank
+    uint32_t *hist;               // [agent][tiles_max][256] digit counts of a tile, then their exclusive offsets over the tiles in front
+    uint32_t *dbase;              // [agent][256] first rank of a digit
+    uint32_t *tcount;             // [agent][tiles_max][2] pool members / pool NaNs of a tile
+    int64_t *counts;              // [agent][2] n_pool, n_nan
+    uint32_t require, exclude;
+    int32_t agent0, tiles_max;
+};
+
 // arguments of the primitives' self-test kernel (fx_selftest_kernel.h; FX_SELFTEST_* op codes: include/fxplan.h)
 struct SelftestArgs {
     const double *in[4];   // op-specific widths (doubles per element): fx_selftest_shape

@@ -32,6 +32,7 @@
 #include "fx_step_kernel.h"
 #include "fx_risk_kernel.h"
 #include "fx_gather_kernel.h"
+#include "fx_sort_kernel.h"
 #include "fx_selftest_kernel.h"
 
 using fxk::wave_count;
@@ -660,4 +661,48 @@ extern "C" hipError_t fx_launch_eval_list(const DevProblem *d_prob, const int64_
     if (extra) FX_LAUNCH(false, true);
     FX_LAUNCH(false, false);
 #undef FX_LAUNCH
+}
+
+// stable cost order of the candidates of n_agents agents (fx_sort_kernel.h): agents args->agent0 ... are grid.y, the largest of them
+// (max_C candidates) chooses the decomposition.  The events, where given, bracket the whole launch sequence.
+extern "C" hipError_t fx_launch_sort(const FxSortArgs *args, int n_agents, int64_t max_C, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                     hipStream_t stream) {
+    if (n_agents <= 0 || max_C <= 0) return hipSuccess;
+    hipError_t e;
+    if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
+    if (max_C <= FX_SORT_SMALL_MAX) {
+        const size_t lds_bytes = FX_SORT_SMALL_LDS(max_C);
+        static std::atomic<size_t> lds_set_[FX_MAX_DEVICES];   /* per device, see fx_launch_eval */
+        std::atomic<size_t> &hw_ = lds_set_[fx_device_slot()];
+        if (lds_bytes > 48 * 1024 && lds_bytes > hw_.load(std::memory_order_relaxed)) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&fx_sort_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)FX_SORT_SMALL_LDS(FX_SORT_SMALL_MAX));
+            if (e != hipSuccess) return e;
+            hw_.store(FX_SORT_SMALL_LDS(FX_SORT_SMALL_MAX), std::memory_order_relaxed);
+        }
+        hipLaunchKernelGGL(fx_sort_small_kernel, dim3(1, n_agents), dim3(FX_SORT_BLOCK), lds_bytes, stream, *args);
+    } else {
+        const dim3 tiles((unsigned)args->tiles_max, n_agents), one(1, n_agents), block(FX_SORT_BLOCK);
+        hipLaunchKernelGGL(fx_sort_hist_kernel<true>, tiles, block, 0, stream, *args, 0);
+        hipLaunchKernelGGL(fx_sort_scan_kernel<true>, one, block, 0, stream, *args);
+        hipLaunchKernelGGL((fx_sort_scatter_kernel<true, false>), tiles, block, 0, stream, *args, 0);
+        for (int pass = 1; pass < FX_SORT_PASSES; pass++) {
+            hipLaunchKernelGGL(fx_sort_hist_kernel<false>, tiles, block, 0, stream, *args, pass);
+            hipLaunchKernelGGL(fx_sort_scan_kernel<false>, one, block, 0, stream, *args);
+            if (pass == FX_SORT_PASSES - 1) hipLaunchKernelGGL((fx_sort_scatter_kernel<false, true>), tiles, block, 0, stream, *args, pass);
+            else hipLaunchKernelGGL((fx_sort_scatter_kernel<false, false>), tiles, block, 0, stream, *args, pass);
+        }
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
+// cost and flag word of n consecutive ranks of an order (fx_sort_gather_kernel)
+extern "C" hipError_t fx_launch_sort_gather(const int64_t *d_order, int64_t n, const double *cost, const uint32_t *flags, int64_t C,
+                                            unsigned long long *out_cost, uint32_t *out_flags, hipStream_t stream) {
+    if (n > 0)
+        hipLaunchKernelGGL(fx_sort_gather_kernel, dim3((unsigned)((n + FX_SORT_BLOCK - 1) / FX_SORT_BLOCK)), dim3(FX_SORT_BLOCK), 0, stream,
+                           d_order, n, cost, flags, C, out_cost, out_flags);
+    return hipGetLastError();
 }

@@ -234,6 +234,7 @@ class FrenetEngine(StepRegistry):
         self._resident_key = None
         self._resident_keys = None
         self.packaging = False
+        self.sort_serials = {}   # agent -> sorts of that agent so far (PlanStepResult.ranked_ids: is the agent's device order still mine?)
         check(lib().fx_create_batch(C.byref(self._ctx), device, max_agents, int(max_candidates), int(max_steps),
                                     int(max_ref_knots), int(max_obstacles), int(max_pred_steps)))
         self.device = device
@@ -821,6 +822,50 @@ class FrenetEngine(StepRegistry):
     def last_materialise_ms(self) -> float:
         """device time of the last `materialise` call's list kernel"""
         return float(lib().fx_last_materialise_ms(self._ctx))
+
+    # -- stable cost order of all candidates, on the device (DESIGN.md section 15) --
+    def sort_candidates(self, agent: int = 0, require: int = _abi.FX_FLAG_COSTED, exclude: int = 0):
+        """Sort the agent's candidates of the last step by cost on the device (fx_sort_candidates_agent): a stable order, ties and
+        NaNs by index, NaNs last -- np.argsort(kind="stable") over the pool (flags & require) == require and (flags & exclude) == 0.
+        Returns (n_pool, n_nan): the pool's size and how many of its members have a NaN cost (the last n_nan ranks).  The order
+        stays on the device until the next sort of this agent or the next evaluation, upload or state update; `ranked` reads it."""
+        n_pool, n_nan = C.c_int64(0), C.c_int64(0)
+        check(lib().fx_sort_candidates_agent(self._ctx, int(agent), int(require), int(exclude), C.byref(n_pool), C.byref(n_nan)))
+        self.sort_serials[int(agent)] = self.sort_serials.get(int(agent), 0) + 1
+        return int(n_pool.value), int(n_nan.value)
+
+    def sort_candidates_batch(self, require: int = _abi.FX_FLAG_COSTED, exclude: int = 0):
+        """sort_candidates for every agent of the last step in one launch sequence; returns (n_pool [n_agents], n_nan [n_agents])"""
+        n = len(self._inputs)
+        n_pool, n_nan = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        pi64 = C.POINTER(C.c_int64)
+        check(lib().fx_sort_candidates_batch(self._ctx, int(require), int(exclude), n_pool.ctypes.data_as(pi64), n_nan.ctypes.data_as(pi64)))
+        for a in range(n):
+            self.sort_serials[a] = self.sort_serials.get(a, 0) + 1
+        return n_pool, n_nan
+
+    def ranked(self, first: int, n: int, agent: int = 0, with_cost: bool = False):
+        """Ranks [first, first + n) of the agent's last sort: indices within the shard (what candidates(), materialise() and the
+        risk passes take).  with_cost: (ids, cost, flags), the costs and flag words as the step wrote them, bit for bit."""
+        n = int(n)
+        room = min(max(n, 0), self._inputs[agent].n_candidates) if 0 <= agent < len(self._inputs) else 0   # (a longer range is refused)
+        ids = np.empty(room, np.int64)
+        cost = np.empty(room) if with_cost else None
+        flags = np.empty(room, np.uint32) if with_cost else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(lib().fx_read_ranked_agent(self._ctx, int(agent), int(first), n, ptr(ids), ptr(cost), ptr(flags)))
+        return (ids, cost, flags) if with_cost else ids
+
+    def sort_view(self, agent: int = 0):
+        """(device pointer of the agent's order: int64 local indices by rank, n_pool) of a valid order (fx_sort_views)"""
+        p, n_pool = C.c_void_p(), C.c_int64(0)
+        check(lib().fx_sort_views(self._ctx, int(agent), C.byref(p), C.byref(n_pool)))
+        return p.value, int(n_pool.value)
+
+    @property
+    def last_sort_ms(self) -> float:
+        """device time of the last sort's launches"""
+        return float(lib().fx_last_sort_ms(self._ctx))
 
     def plane(self, name_or_index, agent: int = 0) -> np.ndarray:
         """[S, C] one plane of every candidate."""

@@ -224,6 +224,7 @@ class TrajectoryHandler:
         self._low_vel = False
         self._step: Optional[PlanStepResult] = None
         self.draw_traj_set = True      # get_sorted_trajectories() returns feasible and infeasible ones (:353-358)
+        self.device_sort = False       # get_sorted_trajectories(): the order sorted on the device and read by rank
         self.kinematic_debug = True
 
     @property
@@ -374,6 +375,9 @@ class TrajectoryHandler:
         """All evaluated trajectories in stable cost order (feasible and not; the adapter splits them :353-358)."""
         if self._step is None:
             return []
+        if self.device_sort and hasattr(self._step.engine, "ranked"):
+            n_pool, _ = self._step.ranked_count(_abi.FX_FLAG_COSTED)
+            return self._step.samples(self._step.ranked_ids(0, n_pool, _abi.FX_FLAG_COSTED))
         return self._step.sorted_trajectories(_abi.FX_FLAG_COSTED)
 
     @property

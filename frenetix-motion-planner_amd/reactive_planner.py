@@ -97,6 +97,13 @@ class PlannerConfig:
     # the packaging, log_risk and the risk fallbacks then work on that set, every other sample answers as a select-only sample
     # does.  0: the step stores everything, as ever.
     sparse_bundle_k: int = 0
+    # the cost order of all candidates sorted on the device and read by rank where the engine offers it
+    # (`ranked`): all_traj pages through ranks, sparse_bundle_k may exceed 64, and the host road-boundary walk goes on past
+    # `survivors` in pages of SURVIVOR_PAGE until the survivor pool ends, as the reference's does (planner.py:362-390).  Where the
+    # ranks come from is PlanStepResult.ranked_ids' business: from trajectories.DEVICE_SORT_MIN_CANDIDATES (13 000) candidates on
+    # the device sorts and the C costs stay there; below -- every planner-sized step, 630 ... 800 candidates -- the host reads the
+    # costs once and sorts them itself, which is the faster way at that size, and the answers are the same.  False: today's planner.
+    device_sort: bool = False
     # dense grid (n_t, n_v, n_d) in natural order instead of the reference's sampling levels (BASELINE configs 2 - 5): T from
     # t_min in steps of dt, V over the planner's velocity range, D over [d_min, d_max] plus the current d
     dense_grid: Optional[Tuple[int, int, int]] = None
@@ -709,12 +716,18 @@ class ReactivePlannerHip:
         self._infeasible_count_kinematics = hist
         self.infeasible_kinematics_percentage = res["feasible_percentage"]
         self._collision_counter = res["n_collisions"]
+        by_rank = bool(self.config.device_sort) and hasattr(engine, "ranked")
         if self._draw_traj_set or self.save_all_traj:
-            self.all_traj = _LazySortedList(step)
+            self.all_traj = _LazySortedList(step, by_rank)
         if self.config.sparse_bundle_k > 0 and not inputs.write_bundle:
             # the winner and the step's best survivors, re-walked into the agent's sparse set: what the code below reads of them
             keep = [int(res["best_index"])] if res["best_index"] >= 0 else []
-            keep += [int(g) for g in engine.topk(min(int(self.config.sparse_bundle_k), 64))[1][agent] if g >= 0]
+            if by_rank and self.config.sparse_bundle_k > 64:   # (beyond the top-k's bound: the first ranks of the survivor pool)
+                n_pool, n_nan = step.ranked_count(*_SURVIVOR_POOL)
+                keep += [int(g) + inputs.shard_begin
+                         for g in step.ranked_ids(0, min(int(self.config.sparse_bundle_k), n_pool - n_nan), *_SURVIVOR_POOL)]
+            else:
+                keep += [int(g) for g in engine.topk(min(int(self.config.sparse_bundle_k), 64))[1][agent] if g >= 0]
             if keep:
                 step.materialise(np.asarray(keep, np.int64) - inputs.shard_begin)
         if self.occlusion_module is not None:
@@ -726,15 +739,39 @@ class ReactivePlannerHip:
             return best
         # host-side walk over the GPU's survivors for checks that stay on the host (planner.py:362-390)
         _, idx = engine.topk(self.config.survivors)
+        seen = 0
         for g in idx[agent]:
             if g < 0:
                 break
+            seen += 1
             cand = step.sample(int(g) - inputs.shard_begin)
             harm = self.road_boundary_check(cand)
             cand.boundary_harm = harm
             cand._coll_detected = False
             if harm == 0:
                 return cand
+        if by_rank and seen == len(idx[agent]):
+            # the reference walks its sorted list to the end (planner.py:362-390): the ranks behind the top-k, page by page.  The
+            # top-k skips NaN costs; in the order they are the pool's last n_nan ranks and are cut off.
+            n_pool, n_nan = step.ranked_count(*_SURVIVOR_POOL)
+            while seen < n_pool - n_nan:
+                ids = step.ranked_ids(seen, min(SURVIVOR_PAGE, n_pool - n_nan - seen), *_SURVIVOR_POOL)
+                if len(ids) == 0:
+                    break
+                if not (inputs.write_bundle and inputs.write_costmap):
+                    # a select-only step: the page's rows, re-walked beside it.  PlanStepResult.materialise keeps ONE set per step
+                    # and re-walks the union of the pages so far (the device set must hold every listed candidate for the risk
+                    # fallbacks): page p costs 64 p candidates, a walk over n survivors n^2 / 128 -- accepted for the rare walk
+                    # that rejects page after page.
+                    step.materialise(ids)
+                for g in ids:
+                    cand = step.sample(int(g))
+                    harm = self.road_boundary_check(cand)
+                    cand.boundary_harm = harm
+                    cand._coll_detected = False
+                    if harm == 0:
+                        return cand
+                seen += len(ids)
         return self._fallback(step, samp_lvl)
 
     def _occlusion_walk(self, step, samp_lvl):
@@ -888,6 +925,10 @@ class ReactivePlannerHip:
             self._engine = None
 
 
+SURVIVOR_PAGE = 64     # ranks per page of the host walk behind the top-k (PlannerConfig.device_sort): the top-k's own bound
+SORTED_PAGE = 4096     # ranks per page of all_traj read by rank: 32 KiB per read, a handful of reads for a planner-sized step
+_SURVIVOR_POOL = (_abi.FX_FLAG_SELECTABLE, _abi.FX_FLAG_COLLISION | _abi.FX_FLAG_BOUNDARY)   # the top-k's pool (pool_bit, exclude)
+
 _ROWS_XYOV = [0, 1, _abi.PKG_ROW_ORIENTATION, 3]   # x, y, shifted heading, velocity of the package block
 
 
@@ -940,25 +981,55 @@ class _LazySortedList:
     """`all_traj` (reactive_planner.py:245-247): every returned trajectory in stable cost order, created on
     demand instead of as 10^4..10^6 Python objects."""
 
-    def __init__(self, step: PlanStepResult):
+    def __init__(self, step: PlanStepResult, by_rank: bool = False):
         self._step = step
         self._ids = None
+        # by_rank (PlannerConfig.device_sort): the order is read through PlanStepResult.ranked_ids in pages of SORTED_PAGE ranks on
+        # demand and the length is the pool's size.  From trajectories.DEVICE_SORT_MIN_CANDIDATES candidates on the order stays on
+        # the device and the C costs are never read (pages are then read while the step is the engine's last one); below it, at
+        # every planner-sized step, ranked_ids reads the costs once and sorts on the host, as sorted_ids does.
+        self._by_rank = by_rank
+        self._pages = {}
+        self._n = None
 
     def _order(self):
         if self._ids is None:
             self._ids = self._step.sorted_ids(_abi.FX_FLAG_COSTED)
         return self._ids
 
+    def _id_at(self, j: int) -> int:
+        p = j // SORTED_PAGE
+        page = self._pages.get(p)
+        if page is None:
+            page = self._pages[p] = self._step.ranked_ids(p * SORTED_PAGE, SORTED_PAGE, _abi.FX_FLAG_COSTED)
+        return int(page[j - p * SORTED_PAGE])
+
     def __len__(self):
-        return len(self._order())
+        if not self._by_rank:
+            return len(self._order())
+        if self._n is None:
+            self._n = self._step.ranked_count(_abi.FX_FLAG_COSTED)[0]
+        return self._n
 
     def __getitem__(self, j):
+        if self._by_rank:
+            n = len(self)
+            if isinstance(j, slice):
+                return [self._step.sample(self._id_at(i)) for i in range(*j.indices(n))]
+            j = int(j)
+            if j < -n or j >= n:
+                raise IndexError(j)
+            return self._step.sample(self._id_at(j % n))
         ids = self._order()
         if isinstance(j, slice):
             return [self._step.sample(int(g)) for g in ids[j]]
         return self._step.sample(int(ids[j]))
 
     def __iter__(self):
+        if self._by_rank:
+            for i in range(len(self)):
+                yield self._step.sample(self._id_at(i))
+            return
         for g in self._order():
             yield self._step.sample(int(g))
 

@@ -345,6 +345,11 @@ class _RescuedColumn:
         raise RuntimeError(_STALE_MSG)
 
 
+# PlanStepResult.ranked_ids sorts on the device from this many candidates on; below, fx_read_costs plus NumPy's stable argsort is the
+# faster way to the same order (the measured switch: the host wins at 6 400 candidates, the device at 13 000)
+DEVICE_SORT_MIN_CANDIDATES = 13_000
+
+
 class PlanStepResult:
     """Everything one evaluated plan step produced; hands out TrajectorySample views."""
 
@@ -564,6 +569,54 @@ class PlanStepResult:
         """ids of the pool in stable cost order (TrajectoryBundle.sort, trajectories.py:524-561)."""
         ids = np.nonzero(self.mask(pool_bit))[0]
         return ids[np.argsort(self.cost[ids], kind="stable")]
+
+    # ---- the order by rank, sorted on the device (DESIGN.md section 15) ----
+    _rank_pool = None                    # (require, exclude, engine.sort_serials[agent]) of the device order this step last asked for
+    _rank_counts = (0, 0)
+    _host_orders = None                  # (require, exclude) -> ids by rank, where the host arrays answered
+
+    def _device_order(self, require, exclude):
+        """(n_pool, n_nan) with the engine's device order of this step being that of the pool, sorting when it is not; None when
+        the host arrays answer: a stale step, an engine without `ranked`, or an agent below DEVICE_SORT_MIN_CANDIDATES (the
+        measured size under which the host's NumPy sort is the faster one)"""
+        eng = self.engine
+        if self._stale or not hasattr(eng, "ranked") or self.n_candidates < DEVICE_SORT_MIN_CANDIDATES:
+            return None
+        serials = getattr(eng, "sort_serials", None) or {}   # (there is one order per agent on the device: another agent's sort leaves it)
+        if self._rank_pool != (require, exclude, serials.get(self.agent, 0)):
+            self._rank_counts = eng.sort_candidates(self.agent, require, exclude)
+            self._rank_pool = (require, exclude, (getattr(eng, "sort_serials", None) or {}).get(self.agent, 0))
+        return self._rank_counts
+
+    def _host_order(self, require, exclude):
+        if self._host_orders is None:
+            self._host_orders = {}
+        order = self._host_orders.get((require, exclude))
+        if order is None:
+            ids = np.nonzero(((self.flags & require) == require) & ((self.flags & exclude) == 0))[0]
+            order = self._host_orders[(require, exclude)] = ids[np.argsort(self.cost[ids], kind="stable")]
+        return order
+
+    def ranked_count(self, pool_bit=_abi.FX_FLAG_COSTED, exclude=0):
+        """(n_pool, n_nan) of the pool (flags & pool_bit) == pool_bit and (flags & exclude) == 0: its size and how many of its
+        members have a NaN cost -- they are the last n_nan ranks"""
+        counts = self._device_order(int(pool_bit), int(exclude))
+        if counts is None:
+            ids = self._host_order(int(pool_bit), int(exclude))
+            counts = (len(ids), int(np.isnan(self.cost[ids]).sum()))
+        return counts
+
+    def ranked_ids(self, first, n, pool_bit=_abi.FX_FLAG_COSTED, exclude=0) -> np.ndarray:
+        """ids [first, first + n) of the pool in stable cost order, clipped to the pool like a slice: sorted_ids(pool_bit)[first:first + n]
+        -- from DEVICE_SORT_MIN_CANDIDATES candidates on without reading the C costs: the device sorts once per (step, pool), ranges
+        are read by rank; below it the host reads the costs once per step and sorts once per pool.  A stale or rescued step
+        answers from its host arrays, as sorted_ids does."""
+        first, n = max(int(first), 0), max(int(n), 0)
+        counts = self._device_order(int(pool_bit), int(exclude))
+        if counts is None:
+            return self._host_order(int(pool_bit), int(exclude))[first:first + n]
+        n = min(n, max(counts[0] - first, 0))
+        return self.engine.ranked(first, n, self.agent) if n > 0 else np.empty(0, np.int64)
 
     def samples(self, ids) -> List[TrajectorySample]:
         """the samples of `ids` (indices within the shard), in that order"""

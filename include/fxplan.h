@@ -493,6 +493,34 @@ int32_t fx_read_package_materialised(FxContext *ctx, int32_t agent, int64_t inde
 /* device time of the context's last list-kernel launch (events attached to the kernel), ms; -1 before the first.  Waits for it. */
 double fx_last_materialise_ms(FxContext *ctx);
 
+/* ---- stable cost order of ALL candidates of a plan step, sorted beside it and read back by rank -- DESIGN.md section 15 ----
+ *      TrajectoryBundle.sort (trajectories.py:524-561) on the device: a stable radix sort of one agent's candidates by cost, ties
+ *      and NaNs in index order, NaNs last -- np.argsort(kind="stable") of the pool's costs.  The pool is
+ *      (flags & require) == require && (flags & exclude) == 0: require = FX_FLAG_COSTED, exclude = 0 is the reference's sorted
+ *      list; require = FX_FLAG_SELECTABLE, exclude = FX_FLAG_COLLISION | FX_FLAG_BOUNDARY the top-k's survivors without its bound of
+ *      64 (the top-k skips NaN costs: here they are the last n_nan ranks); 0, 0 every candidate.  *n_pool receives the pool's size,
+ *      *n_nan the pool members with a NaN cost.  The calls launch on the context's stream and wait for the counts.  They read the
+ *      cost and flag planes and write a block of their own -- nothing a plan step, the top-k, a sparse set or the risk passes own --
+ *      which is allocated on the first call and only grows: a context that never sorts owns what it always did (fx_device_bytes).
+ *      An order is valid until the next sort of that agent or the next evaluation, upload or state update of the context.
+ *      FX_ERR_NOT_READY before the first evaluated step, when the inputs were rewritten since it, and for the two readers without
+ *      a valid order; FX_ERR_INVALID_ARGUMENT for NULL where a pointer is needed, an agent out of range, first < 0, n < 0 or
+ *      first + n > n_pool -- all checked before anything is launched or written: a refused call leaves the previous order
+ *      readable.  n == 0 is legal. */
+int32_t fx_sort_candidates_agent(FxContext *ctx, int32_t agent, uint32_t require, uint32_t exclude, int64_t *n_pool, int64_t *n_nan);
+/* every agent of the last step in ONE launch sequence (agents are grid.y), each within its own segment */
+int32_t fx_sort_candidates_batch(FxContext *ctx, uint32_t require, uint32_t exclude, int64_t *n_pool /*[n_agents]*/,
+                                 int64_t *n_nan /*[n_agents]*/);
+/* ranks [first, first + n) of the agent's last sort: LOCAL indices in [0, C) -- the convention of fx_read_candidates_agent and
+ * fx_materialise_candidates_agent, which a rank range feeds directly -- and, where asked for, cost[index] and flags[index] gathered
+ * from the agent's planes: the bits as the step wrote them (costs are never rebuilt from sort keys). */
+int32_t fx_read_ranked_agent(FxContext *ctx, int32_t agent, int64_t first, int64_t n, int64_t *index /*[n]*/,
+                             double *cost /*[n] or NULL*/, uint32_t *flags /*[n] or NULL*/);
+/* device pointer of the agent's order, int64 local indices by rank ([0, *n_pool) are the pool), for callers that stay on the GPU */
+int32_t fx_sort_views(FxContext *ctx, int32_t agent, void **d_index, int64_t *n_pool);
+/* device time of the context's last sort (events around its launches), ms; -1 before the first.  Waits for it. */
+double fx_last_sort_ms(FxContext *ctx);
+
 /* ---- road boundary (replaces create_road_boundary_obstacle + trajectories_collision_static_obstacles,
  *      planner.py:362-381,550-565; commonroad-drivability-checker, not in the reference tree) ----
  * fx_build_boundary_bins: host-side geometry, no GPU.  Splits the n_seg boundary segments seg[n_seg][4] =

@@ -151,6 +151,20 @@ class FxRiskCostParams(C.Structure):
                 ("boundary_s", C.c_double), ("boundary_harm", C.c_void_p), ("responsibility", C.c_void_p)]
 
 
+# collision probability as the prediction cost (fxplan.h FxPredProbParams / FxPredProbOutputs)
+FX_PRED_SOURCE_PROBABILITY, FX_PRED_SOURCE_STEP = 0, 1
+PRED_SOURCES = {"probability": FX_PRED_SOURCE_PROBABILITY, "step": FX_PRED_SOURCE_STEP}
+PREDICTION_COSTS = ("inverse_mahalanobis", "collision_probability")   # what the planner and the frenetix route accept
+
+
+class FxPredProbParams(C.Structure):
+    _fields_ = [("ego_length", C.c_double), ("ego_width", C.c_double), ("source", C.c_int32)]
+
+
+class FxPredProbOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("prob", "prob_obs", "total", "best_index", "best_cost")]
+
+
 class FxRiskOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ego_risk", "obst_risk", "obst_harm_occ", "ego_risk_max", "obst_risk_max", "ego_harm_max",
                                           "obst_harm_max", "bayes", "equality", "maximin", "ego", "responsibility", "total",

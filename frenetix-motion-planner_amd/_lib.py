@@ -44,6 +44,7 @@ def exported_symbols():
         "fx_set_reach_sets_agent", "fx_eval_risk_costs_agent",
         "fx_materialise_candidates_agent", "fx_read_materialised_agent", "fx_read_package_materialised", "fx_last_materialise_ms",
         "fx_sort_candidates_agent", "fx_sort_candidates_batch", "fx_read_ranked_agent", "fx_sort_views", "fx_last_sort_ms",
+        "fx_eval_prediction_prob_agent", "fx_last_predprob_ms",
     ]
 
 
@@ -153,6 +154,12 @@ def lib():
         "fx_read_ranked_agent": ([vp, C.c_int32, C.c_int64, C.c_int64, vp, vp, vp], C.c_int32),   # (arrays: plain addresses)
         "fx_sort_views": ([vp, C.c_int32, C.POINTER(vp), pi64], C.c_int32),
         "fx_last_sort_ms": ([vp], C.c_double),
+        "fx_eval_prediction_prob_agent": ([vp, C.c_int32, C.POINTER(_abi.FxPredProbParams), C.c_int64, pi64,
+                                           C.POINTER(_abi.FxPredProbOutputs)], C.c_int32),
+        "fx_last_predprob_ms": ([vp], C.c_double),
+        # (launcher hook of the tests, not part of fxplan.h: steps per chunk of the prediction-probability items, 0 = automatic)
+        "fx_predprob_set_chunk_steps": ([C.c_int32], None),
+        "fx_predprob_chunk_steps": ([C.c_int64, C.c_int32, C.c_int32], C.c_int32),
         "fx_read_plane": ([vp, C.c_int32, pd], C.c_int32),
         "fx_read_plane_agent": ([vp, C.c_int32, C.c_int32, pd], C.c_int32),
         "fx_read_topk": ([vp, C.c_int32, pd, pi64, pi32], C.c_int32),

@@ -2,7 +2,8 @@
 // the risk pass with its arg-min over the materialised bundle of the last plan step (or, for listed candidates of a step that stored
 // none, over the agent's sparse set: fx_api_materialise.hip); the reach sets of an agent and the detail /
 // risk-cost pass.  The two evaluations share one host path (RiskPass) and one device block.  Nothing of
-// this runs in a plan step.
+// this runs in a plan step.  The collision probability as the prediction cost (fx_predprob_kernel.h) is a third
+// entrance on the same host path: the same checks, records, uploads and block.
 #include <cmath>
 #include <vector>
 
@@ -12,6 +13,8 @@
 extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const FxRiskParams *params, double *out_ego, double *out_obst,
                                      double *col, double *out_occ, const RiskCostArgs *cost, long long *out_idx, hipEvent_t ev_start,
                                      hipEvent_t ev_stop, hipStream_t stream);
+extern "C" hipError_t fx_launch_predprob(const PredProbArgs *args, long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                         hipStream_t stream);
 
 namespace {
 // Gauss-Legendre nodes on [-1, 1], positive half: 6, 12 and 20 points (Genz 2004)
@@ -38,6 +41,7 @@ struct FxRiskState {
     size_t cap = 0;          // bytes
     hipEvent_t e0 = nullptr, e1 = nullptr;
     float last_ms = 0.f;
+    float last_pp_ms = -1.f;   // fx_eval_prediction_prob_agent
 };
 
 void fx_risk_release(FxContext *c) {
@@ -184,6 +188,7 @@ struct RiskPass {
     size_t o_rec, o_obs, o_pos, o_yaw, o_v, o_ids, o_ego, o_obst, o_idx;
     size_t o_occ, o_col;                                                 // detail pass only
     size_t o_out, o_bh, o_resp, o_eobs, o_eoff, o_pst, o_voff, o_vert;   // cost pass only
+    size_t o_pstep, o_pprob, o_pobs, o_ptot, o_pbest;                    // prediction-probability pass only
 
     double *D(size_t o) const { return reinterpret_cast<double *>(base + o); }
     int32_t *I(size_t o) const { return reinterpret_cast<int32_t *>(base + o); }
@@ -200,7 +205,7 @@ struct RiskPass {
 // have_out: the entry point's output pointers are there.  detail: the checks of fx_eval_risk_costs_agent -- it reports missing
 // outputs with params, and refuses an obstacle that calc_risk cannot evaluate (the plain pass skips it).
 static int risk_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskParams *params, int64_t n_ids, const int64_t *ids,
-                      bool have_out, bool detail) {
+                      bool have_out, bool detail, bool need_v = true) {
     int rc = check_agent(c, agent);
     if (rc) return rc;
     const FxAgentSlot &s = c->slots[agent];
@@ -236,9 +241,11 @@ static int risk_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskPara
         if (detail && std::min(S - 1, np) <= 0)
             return set_err(FX_ERR_INVALID_ARGUMENT, "obstacle %d: min(S - 1, len(pos_list)) == 0 (calc_risk takes the maximum of an empty "
                            "list upstream)", k);
-        if (a.n_yaw[k] < std::min(S, np) || a.n_v[k] < std::min(S - 1, np))
-            return set_err(FX_ERR_INVALID_ARGUMENT, "obstacle %d: orientation_list (%d) / v_list (%d) shorter than calc_risk indexes "
-                           "(%d / %d)", k, a.n_yaw[k], a.n_v[k], std::min(S, np), std::min(S - 1, np));
+        if (a.n_yaw[k] < std::min(S, np) || (need_v && a.n_v[k] < std::min(S - 1, np)))
+            return need_v ? set_err(FX_ERR_INVALID_ARGUMENT, "obstacle %d: orientation_list (%d) / v_list (%d) shorter than calc_risk indexes "
+                                    "(%d / %d)", k, a.n_yaw[k], a.n_v[k], std::min(S, np), std::min(S - 1, np))
+                          : set_err(FX_ERR_INVALID_ARGUMENT, "obstacle %d: orientation_list (%d) shorter than get_collision_probability_fast "
+                                    "indexes (%d)", k, a.n_yaw[k], std::min(S, np));
     }
     q.c = c, q.agent = agent, q.s = &s, q.r = r, q.a = &a;
     q.S = S, q.K = K, q.P = a.P > 0 ? a.P : 1, q.maha = maha;
@@ -252,7 +259,8 @@ static int risk_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskPara
 
 // The device block of a pass and the uploads every pass makes.  One grow-only allocation, every part 256-byte aligned; the plain
 // pass takes no room for the detail pass's columns, and only a pass with cost parameters for their outputs and tables.
-static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost) {
+// pp_nb > 0: the prediction-probability pass with batches of pp_nb candidates -- room for its per-step scratch and outputs.
+static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, size_t pp_nb = 0) {
     FxContext *c = q.c;
     FxRiskState *r = q.r;
     const FxRiskAgent &a = *q.a;
@@ -272,6 +280,11 @@ static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost) {
         q.o_out = take(sizeof(double) * 7 * n1), q.o_bh = take(sizeof(double) * n1), q.o_resp = take(sizeof(double) * K);
         q.o_eobs = take(sizeof(int32_t) * nE), q.o_eoff = take(sizeof(int32_t) * (nE + 1));
         q.o_pst = take(sizeof(int32_t) * nP), q.o_voff = take(sizeof(int32_t) * (nP + 1)), q.o_vert = take(sizeof(double) * 2 * nV);
+    }
+    if (pp_nb) {
+        q.o_pstep = take(sizeof(double) * K * (size_t)std::max(q.S - 1, 1) * pp_nb);
+        q.o_pprob = take(sizeof(double) * n1), q.o_pobs = take(sizeof(double) * K * n1), q.o_ptot = take(sizeof(double) * n1);
+        q.o_pbest = take(2 * sizeof(long long));
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -443,5 +456,66 @@ extern "C" int32_t fx_eval_risk_costs_agent(FxContext *c, int32_t agent, const F
     }
     return risk_run(q, *params, true, cost ? &ca : nullptr, *out);
 }
+
+// Collision probability as the prediction cost (fxplan.h).  The scratch holds the per-step probabilities of
+// one batch of candidates, [K][S - 1][batch]: the batch bounds it to FX_PREDPROB_SCRATCH_BYTES where one candidate's share allows.
+#define FX_PREDPROB_SCRATCH_BYTES ((size_t)64 << 20)
+extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, const FxPredProbParams *params, int64_t n_ids,
+                                                 const int64_t *ids, const FxPredProbOutputs *out) {
+    int rc = check_agent(c, agent);
+    if (rc) return rc;
+    // (the planes and the cost map are the last EVALUATED step's: inputs rewritten since belong to a step that has not run -- the
+    // condition of the sort and of the sparse set, fx_api_sort.hip / fx_api_materialise.hip)
+    if (c->probs_dirty || c->dirty_hi > c->dirty_lo)
+        return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
+    if (!(c->slots[agent].mode & FX_MODE_WRITE_COSTMAP)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_COSTMAP");
+    FxRiskParams rp{};   // what risk_check and step_probability read of it: the MVN mode and the ego's footprint
+    rp.prob_mode = FX_RISK_PROB_MVN;
+    rp.prot_model = rp.unprot_ego_model = FX_RISK_HARM_LOGISTIC;
+    rp.ego_mass = 1.0;
+    if (params) { rp.ego_length = params->ego_length; rp.ego_width = params->ego_width; }
+    RiskPass q;
+    if ((rc = risk_check(q, c, agent, params ? &rp : nullptr, n_ids, ids, out != nullptr, false, false))) return rc;
+    if (params->source != FX_PRED_SOURCE_PROBABILITY && params->source != FX_PRED_SOURCE_STEP)
+        return set_err(FX_ERR_INVALID_ARGUMENT, "source %d", params->source);
+    const DevProblem &hp = c->h_probs[agent];
+    int n_pred = -1;
+    for (int m = 0; m < hp.n_cost; m++)
+        if (hp.cost_id[m] == FX_COST_PREDICTION) n_pred = m;
+    if (n_pred < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "the cost list has no FX_COST_PREDICTION");
+    const size_t per_cand = sizeof(double) * (size_t)std::max(q.K, 1) * (size_t)std::max(q.S - 1, 1);
+    const size_t n1 = (size_t)std::max<int64_t>(q.n, 1);
+    size_t nb = std::max<size_t>(FX_PREDPROB_SCRATCH_BYTES / per_cand / 64, 1) * 64;   // whole tiles
+    nb = std::min(nb, (n1 + 63) / 64 * 64);
+    if ((rc = risk_stage(q, false, nullptr, nb))) return rc;
+    FxRiskState *r = q.r;
+    PredProbArgs a{};
+    a.planes = q.planes, a.ld = q.ld, a.S = q.S, a.K = q.K, a.n = q.n, a.ids = q.d_ids(), a.flags = q.flags, a.rec = q.D(q.o_rec);
+    a.ego_length = params->ego_length, a.ego_width = params->ego_width, a.source = params->source;
+    a.costmap = q.sparse ? q.set.costmap : c->d_costmap + (size_t)FX_NUM_COSTS * q.s->cand_off;
+    a.n_cost = hp.n_cost, a.n_pred = n_pred;
+    // (a sparse set's rows were closed by the list kernel, which never defers)
+    a.deferred = (!q.sparse && (hp.mode & FX_MODE_INT_DEFER_OBST)) ? 1 : 0;
+    for (int m = 0; m < hp.n_cost; m++) a.cost_w[m] = hp.cost_w[m];
+    a.step = q.D(q.o_pstep), a.nb = (int64_t)nb;
+    a.prob = q.D(q.o_pprob), a.prob_obs = out->prob_obs ? q.D(q.o_pobs) : nullptr, a.total = q.D(q.o_ptot);
+    long long *d_best = reinterpret_cast<long long *>(q.base + q.o_pbest);
+    HIP_TRY(fx_launch_predprob(&a, d_best, r->e0, r->e1, c->stream));
+    const size_t nn = (size_t)q.n;
+    HIP_TRY(q.down(out->prob, q.o_pprob, nn));
+    HIP_TRY(q.down(out->prob_obs, q.o_pobs, (size_t)q.K * nn));
+    HIP_TRY(q.down(out->total, q.o_ptot, nn));
+    long long best[2] = {-1, 0};
+    HIP_TRY(hipMemcpyAsync(best, d_best, sizeof(best), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&r->last_pp_ms, r->e0, r->e1));
+    // (sparse set: the arg-min ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
+    if (q.sparse && best[0] >= 0) best[0] = (long long)q.set.ids[best[0]];
+    if (out->best_index) *out->best_index = (int64_t)best[0];
+    if (out->best_cost) memcpy(out->best_cost, &best[1], sizeof(double));
+    return FX_OK;
+}
+
+extern "C" double fx_last_predprob_ms(FxContext *c) { return (c && c->risk) ? (double)c->risk->last_pp_ms : -1.0; }
 
 extern "C" double fx_last_risk_ms(FxContext *c) { return (c && c->risk) ? (double)c->risk->last_ms : -1.0; }

@@ -31,6 +31,7 @@
 #include "fx_obstacle_kernel.h"
 #include "fx_step_kernel.h"
 #include "fx_risk_kernel.h"
+#include "fx_predprob_kernel.h"
 #include "fx_gather_kernel.h"
 #include "fx_sort_kernel.h"
 #include "fx_selftest_kernel.h"
@@ -627,6 +628,41 @@ extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const FxRiskParam
     }
     if (ev_stop) { hipError_t e = hipEventRecord(ev_stop, stream); if (e != hipSuccess) return e; }
     return hipGetLastError();
+}
+
+// collision probability as the prediction cost (fx_predprob_kernel.h) over the a.n listed candidates, in
+// batches of a.nb: per batch the (tile, chunk, obstacle) items and the finish kernel, then the arg-min of the total into out_idx.
+// Steps per chunk: as many as keep the call at FX_PREDPROB_WAVES items or more, at least one -- or what fx_predprob_set_chunk_steps
+// forces (tests: the results do not depend on it).  ev_start / ev_stop bracket all launches.
+#define FX_PREDPROB_WAVES 4096
+static std::atomic<int> fx_predprob_chunk_forced{0};
+extern "C" void fx_predprob_set_chunk_steps(int32_t steps) { fx_predprob_chunk_forced.store(steps > 0 ? steps : 0, std::memory_order_relaxed); }
+extern "C" int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K) {
+    const int forced = fx_predprob_chunk_forced.load(std::memory_order_relaxed);
+    const int steps = S - 1 > 0 ? S - 1 : 1;
+    if (forced > 0) return std::min(forced, steps);
+    const int64_t per_step = ((n + 63) / 64) * std::max(K, 1);   // items of a call with one step per chunk
+    int cs = 1;
+    while (cs < steps && per_step * ((steps + 2 * cs - 1) / (2 * cs)) >= FX_PREDPROB_WAVES) cs *= 2;
+    return std::min(cs, steps);
+}
+extern "C" hipError_t fx_launch_predprob(const PredProbArgs *args, long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                         hipStream_t stream) {
+    const PredProbArgs &a = *args;
+    hipError_t e;
+    if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
+    const int cs = fx_predprob_chunk_steps(a.n, a.S, a.K);
+    const unsigned chunks = (unsigned)((std::max(a.S - 1, 1) + cs - 1) / cs);
+    for (int64_t j0 = 0; j0 < a.n; j0 += a.nb) {
+        const int64_t m = std::min<int64_t>(a.nb, a.n - j0);
+        if (a.source == FX_PRED_SOURCE_PROBABILITY && a.K > 0 && a.S > 1)
+            hipLaunchKernelGGL(fxpp::fx_predprob_item_kernel, dim3((unsigned)((m + 63) / 64), chunks, (unsigned)a.K), dim3(64), 0, stream, a, j0, cs);
+        hipLaunchKernelGGL(fxpp::fx_predprob_finish_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, a, j0);
+    }
+    hipLaunchKernelGGL(fxpp::fx_predprob_argmin_kernel, dim3(1), dim3(1024), 0, stream, a.total, a.n, a.ids, a.flags, out_idx);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
+    return hipSuccess;
 }
 
 // batched candidate read-back (fx_gather_kernel.h): one workgroup per listed candidate

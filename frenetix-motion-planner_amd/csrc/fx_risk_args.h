@@ -1,6 +1,6 @@
 // fx_risk_args.h -- what the host code of the trajectory risk (fx_api_risk.hip), its launcher (fx_kernels.hip) and its kernels
 // (fx_risk_kernel.h) share: the layout of the records the host builds and the kernels read, the arguments of the candidate walk
-// and the argument block of the risk-cost kernel.  DESIGN.md sections 11 and 13.
+// and the argument blocks of the risk-cost kernel and of the prediction-probability pass.  DESIGN.md sections 11, 13 and 16.
 #pragma once
 
 #include <stdint.h>
@@ -66,4 +66,26 @@ struct RiskCostArgs {
     const double *verts;       // [n_verts][2]
     double w[5], eps, scale;
     double *out;               // [7][n]: bayes | equality | maximin | ego | responsibility | total | boundary_harm
+};
+
+// arguments of the prediction-probability pass (fx_predprob_kernel.h), device pointers
+struct PredProbArgs {
+    const double *planes;      // [FX_NUM_PLANES][S][ld] of the agent (or of its sparse set)
+    int64_t ld;
+    int32_t S, K;
+    int64_t n;                 // listed candidates (or C)
+    const int64_t *ids;        // [n] or null: every candidate, NaN rows for the ones without FX_FLAG_COSTED
+    const uint32_t *flags;     // [ld]
+    const double *rec;         // [K][S][FXR_STRIDE], MVN mode
+    double ego_length, ego_width;
+    int32_t source;            // FX_PRED_SOURCE_*
+    // the re-sum
+    const double *costmap;     // [n_cost][ld] raw cost rows of the step
+    int32_t n_cost, n_pred;    // n_pred: position of FX_COST_PREDICTION in the cost list
+    int32_t deferred;          // the step closed its sum in the obstacle kernel (FX_MODE_INT_DEFER_OBST)
+    double cost_w[FX_NUM_COSTS];
+    // scratch and outputs
+    double *step;              // [K][S - 1][nb] probabilities of one batch of nb candidates
+    int64_t nb;
+    double *prob, *prob_obs, *total;   // [n], [K][n], [n]
 };

@@ -966,6 +966,41 @@ class FrenetEngine(StepRegistry):
         """device time of the last `risk` / `risk_detail` / `risk_costs` call (its kernels)"""
         return float(lib().fx_last_risk_ms(self._ctx))
 
+    # -- collision probability as the prediction cost (DESIGN.md section 16) --
+    def prediction_probability(self, ego_length: float, ego_width: float, ids=None, agent: int = 0, per_obstacle: bool = False,
+                               source: str = "probability") -> dict:
+        """The `prediction` cost of the reference's C++ route (cf.CalculateCollisionProbabilityFast) for candidates of the last plan
+        step, on the device (fx_eval_prediction_prob_agent): prob [n], the sum over the obstacles of `set_risk_obstacles` -- in
+        their order -- of the summed get_collision_probability_fast; total [n], the step's weighted cost re-summed from its raw cost
+        rows with prob in the prediction entry; best_index / best_cost, the (total, index) minimum over the selectable
+        collision-free candidates (-1 / NaN when there is none); per_obstacle: prob_obs [n, K].  ids None: every candidate, NaN
+        rows for the ones without a cost.  source "step" re-sums with the step's own prediction entry instead (no probability is
+        evaluated): its total is the step's cost bit for bit.  Needs write_costmap and a cost list with a prediction term, and the
+        bundle or ids inside the agent's sparse set (`materialise`).  Nothing the step wrote is touched."""
+        if source not in _abi.PRED_SOURCES:
+            raise ValueError(f"source {source!r}: one of {sorted(_abi.PRED_SOURCES)}")
+        K = getattr(self, "_risk_K", {}).get(agent, 0)
+        n, n_ids, idp, ids = self._risk_ids(ids, agent)
+        params = _abi.FxPredProbParams(float(ego_length), float(ego_width), _abi.PRED_SOURCES[source])
+        res = dict(prob=np.zeros(max(n, 1)), total=np.zeros(max(n, 1)))
+        if per_obstacle:
+            res["prob_obs"] = np.zeros((K, max(n, 1)))
+        best_index, best_cost = np.full(1, -1, np.int64), np.full(1, np.nan)
+        out = _abi.FxPredProbOutputs()
+        for k, a in res.items():
+            setattr(out, k, a.ctypes.data)
+        out.best_index, out.best_cost = best_index.ctypes.data, best_cost.ctypes.data
+        if n > 0 or ids is None:   # (an empty id list: nothing to evaluate, no arg-min)
+            check(lib().fx_eval_prediction_prob_agent(self._ctx, int(agent), C.byref(params), n_ids, idp, C.byref(out)))
+        res = {k: (a[:, :n].T if k == "prob_obs" else a[:n]) for k, a in res.items()}
+        res["best_index"], res["best_cost"] = int(best_index[0]), float(best_cost[0])
+        return res
+
+    @property
+    def last_predprob_ms(self) -> float:
+        """device time of the last `prediction_probability` call (its kernels); -1 before the first"""
+        return float(lib().fx_last_predprob_ms(self._ctx))
+
     def topk(self, k: int):
         n = len(self._inputs)
         cost = np.zeros((n, k))

@@ -149,6 +149,11 @@ class CalculateLaneCenterOffsetCost(_Cost):
 
 
 class CalculateCollisionProbabilityFast(_Cost):
+    """reactive_planner_cpp.py:151-155.  What it evaluates is TrajectoryHandler.prediction_cost: the inverse Mahalanobis sum of
+    the Python back-end (the default), or the collision probability, get_collision_probability_fast summed as prediction_costs
+    does, with this functor's length and width as the ego's footprint.  wb_rear_axle is stored and not
+    used by either: get_collision_probability_fast takes traj.cartesian.x / y unshifted, and the C++ functor's source is not in
+    the reference tree (UNPINNED)."""
     cost_name = "prediction"
 
     def __init__(self, name, weight, predictions: Dict[int, PredictedObject], length, width, wb_rear_axle):
@@ -211,6 +216,14 @@ class TrajectoryHandler:
     # optimal_trajectory and all_traj across plan steps, reactive_planner_cpp.py:330, 430, 437).  False: nothing is read, such
     # reads raise -- for callers that hold the whole list and never look at it again.
     retain_samples = True
+    # what the `prediction` functor evaluates: "inverse_mahalanobis" (partial_cost_functions.py:349, the Python back-end's) or
+    # "collision_probability" (collision_probability.py:141-261 summed per trajectory): a pass over every costed candidate beside
+    # the plan step whose totals replace the step's costs in everything this handler hands out (PlanStepResult.set_cost_override).
+    # Two things stay the step's own: the dict the evaluate calls return and `last_result` (best_index, counters: the step's
+    # selection -- the override's winner is `_step.best`), and costs() / topk() of the engine.  The pass needs obstacle tables on
+    # the engine and REPLACES the ones of an earlier set_risk_obstacles with placeholders for what it does not read (every type
+    # "car", speeds 0): a caller that also runs risk() / risk_costs() on this engine sets its own tables again before it does.
+    prediction_cost = "inverse_mahalanobis"
 
     def __init__(self, dt: float, engine=None, device: int = 0):
         self.dt = float(dt)
@@ -324,6 +337,8 @@ class TrajectoryHandler:
             raise RuntimeError("generate_trajectories() must be called before evaluation")
         if self._fill is None:
             raise RuntimeError("FillCoordinates must be registered (add_function) before evaluation")
+        if self.prediction_cost not in _abi.PREDICTION_COSTS:   # (before anything is evaluated or replaced)
+            raise ValueError(f"prediction_cost {self.prediction_cost!r}: one of {_abi.PREDICTION_COSTS}")
         from .engine import build_obstacle_hulls
         weights = {n: f.weight for n, f in self._costs.items() if f.weight != 0}
         vo = self._costs.get("velocity_offset")
@@ -363,6 +378,14 @@ class TrajectoryHandler:
             res = self.engine.plan_step(inputs)
         self._step = PlanStepResult(self.engine, inputs, res)
         self._step.retain = bool(self.retain_samples)
+        pc = self._costs.get("prediction")
+        if self.prediction_cost == "collision_probability" and pc is not None and pc.weight != 0:
+            from . import risk
+            # (of the tables only pos, cov, yaw, their lengths and the obstacle's length are read: no speeds, no obstacle types)
+            tabs = risk.obstacle_tables({k: dict(p, v_list=np.zeros(len(p["pos_list"]))) for k, p in (preds or {}).items()},
+                                        {k: "car" for k in (preds or {})})
+            self.engine.set_risk_obstacles(tabs)
+            self._step.apply_prediction_probability(pc.length, pc.width)
         return res
 
     def evaluate_all_current_functions(self, calculate_all_costs: bool = True):

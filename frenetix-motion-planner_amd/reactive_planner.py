@@ -107,6 +107,12 @@ class PlannerConfig:
     # dense grid (n_t, n_v, n_d) in natural order instead of the reference's sampling levels (BASELINE configs 2 - 5): T from
     # t_min in steps of dt, V over the planner's velocity range, D over [d_min, d_max] plus the current d
     dense_grid: Optional[Tuple[int, int, int]] = None
+    # what the `prediction` cost term is: "inverse_mahalanobis", the Python back-end's and the plan step's own
+    # (partial_cost_functions.py:349), or "collision_probability", the C++ route's functor (reactive_planner_cpp.py:151-155;
+    # DESIGN.md section 16): per sampling level a pass beside the plan step sums get_collision_probability_fast for every costed
+    # candidate, re-sums the cost with it, and the planner walks that order.  It reads the step's bundle and cost map:
+    # sparse_bundle_k > 0 (a select-only step) is refused.
+    prediction_cost: str = "inverse_mahalanobis"
 
 
 class ReactivePlannerHip:
@@ -249,6 +255,31 @@ class ReactivePlannerHip:
     def set_cost_function(self, cost_weights):
         self.cost_weights = dict(cost_weights)
         self._weights_nz = None
+        self._check_prediction_cost()
+
+    def _check_prediction_cost(self):
+        """PlannerConfig.prediction_cost against the rest of the configuration; True when the pass runs"""
+        pc = self.config.prediction_cost
+        if pc not in _abi.PREDICTION_COSTS:
+            raise ValueError(f"PlannerConfig.prediction_cost {pc!r}: one of {_abi.PREDICTION_COSTS}")
+        if pc != "collision_probability" or not self.cost_weights.get("prediction"):
+            return False
+        if self.config.sparse_bundle_k > 0:
+            raise ValueError("prediction_cost='collision_probability' reads the plan step's bundle and cost map: it needs bundle mode "
+                             "(PlannerConfig.sparse_bundle_k = 0), not a select-only step")
+        return True
+
+    def _apply_prediction_cost(self, step):
+        """the collision-probability pass over the step's costed candidates, installed as the step's cost override.  The tables it
+        sets on the engine carry placeholders for what the pass does not read; the planner's own risk paths (_eval_risk,
+        _risk_costs_on) set theirs through _set_risk_obstacles before every evaluation, a caller that uses engine.risk() directly
+        sets its own again.  step.result keeps the step's own best_index; the override's winner is step.best."""
+        from . import risk
+        preds = (self.predictions if self.use_prediction else None) or {}
+        # (of the tables only pos, cov, yaw, their lengths and the obstacle's length are read: no speeds, no obstacle types)
+        tabs = risk.obstacle_tables({k: dict(p, v_list=np.zeros(len(p["pos_list"]))) for k, p in preds.items()}, {k: "car" for k in preds})
+        step.engine.set_risk_obstacles(tabs, step.agent)
+        step.apply_prediction_probability(self.vehicle_params.length, self.vehicle_params.width)
 
     def set_fallback_selector(self, selector: Optional[Callable]):
         """What happens at the LAST sampling level when no feasible candidate is collision-free.  The reference's Python
@@ -552,6 +583,7 @@ class ReactivePlannerHip:
             raise RuntimeError("x_cl should have been set prior to plan()")  # reactive_planner_cpp.py:308-309
         if self.desired_velocity is None:
             raise RuntimeError("desired velocity not set (update_externals(desired_velocity=...))")
+        self._check_prediction_cost()   # (a select-only configuration with the collision-probability cost: refused before any launch)
         if stop_point_s is not None and stop_point_s < self.x_cl[0][0]:
             self.msg_logger.info("stop point behind current longitudinal position, falling back to regular planning")
             stop_point_s = None  # reactive_planner_cpp.py:263-264,336-341
@@ -570,6 +602,7 @@ class ReactivePlannerHip:
             raise RuntimeError("x_cl should have been set prior to plan()")
         if self.desired_velocity is None:
             raise RuntimeError("desired velocity not set (update_externals(desired_velocity=...))")
+        self._check_prediction_cost()   # (a select-only configuration with the collision-probability cost: refused before any launch)
         if stop_point_s is not None and stop_point_s < self.x_cl[0][0]:
             stop_point_s = None
         self._stop_point_s = stop_point_s
@@ -716,6 +749,10 @@ class ReactivePlannerHip:
         self._infeasible_count_kinematics = hist
         self.infeasible_kinematics_percentage = res["feasible_percentage"]
         self._collision_counter = res["n_collisions"]
+        if self._check_prediction_cost():
+            if not (inputs.write_bundle and inputs.write_costmap):
+                raise ValueError("prediction_cost='collision_probability' needs a plan step that stored the bundle and the cost map")
+            self._apply_prediction_cost(step)
         by_rank = bool(self.config.device_sort) and hasattr(engine, "ranked")
         if self._draw_traj_set or self.save_all_traj:
             self.all_traj = _LazySortedList(step, by_rank)
@@ -737,6 +774,18 @@ class ReactivePlannerHip:
             return self._fallback(step, samp_lvl)
         if self.road_boundary_check is None:
             return best
+        if step._override is not None:
+            # the top-k reads the step's own costs: with a cost override the survivors are walked in the override's order
+            for g in step.ranked_ids(0, step.n_candidates, *_SURVIVOR_POOL):
+                if np.isnan(step.cost[g]):
+                    break   # (NaN costs are the pool's last ranks; the selection skips them)
+                cand = step.sample(int(g))
+                harm = self.road_boundary_check(cand)
+                cand.boundary_harm = harm
+                cand._coll_detected = False
+                if harm == 0:
+                    return cand
+            return self._fallback(step, samp_lvl)
         # host-side walk over the GPU's survivors for checks that stay on the host (planner.py:362-390)
         _, idx = engine.topk(self.config.survivors)
         seen = 0

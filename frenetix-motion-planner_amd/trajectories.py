@@ -153,6 +153,8 @@ class TrajectorySample:
             if rec["raw_costs"] is not None:
                 names, w = step.inputs.cost_names, step.inputs.cost_weights
                 d["_costmap"] = {n: (float(rec["raw_costs"][k]), float(w[n] * rec["raw_costs"][k])) for k, n in enumerate(names)}
+        if step._override is not None:   # (a cost override is installed with the step's arrays loaded: only the winner gets here)
+            d["_cost"] = float(step.cost[index])
         d["_flags"] = flags
         d["feasible"] = bool(flags & _abi.FX_FLAG_FEASIBLE)
         d["valid"] = bool(flags & _abi.FX_FLAG_VALID)
@@ -246,12 +248,12 @@ class TrajectorySample:
             raw = self._pkg.raw_cost_list()
             if raw is not None:
                 names, w = self._step.inputs.cost_names, self._step.inputs.cost_weights
-                self._costmap = {n: (raw[k], float(w[n] * raw[k])) for k, n in enumerate(names)}
+                self._costmap = self._step._override_costmap(self.uniqueId, {n: (raw[k], float(w[n] * raw[k])) for k, n in enumerate(names)})
         if self._costmap is None:
             raw = self._step.fetch_costmap_row(self.uniqueId)
             names = self._step.inputs.cost_names
             w = self._step.inputs.cost_weights
-            self._costmap = {n: (float(raw[k]), float(w[n] * raw[k])) for k, n in enumerate(names)}
+            self._costmap = self._step._override_costmap(self.uniqueId, {n: (float(raw[k]), float(w[n] * raw[k])) for k, n in enumerate(names)})
         return self._costmap
 
     def _need_coeffs(self):
@@ -358,6 +360,7 @@ class PlanStepResult:
     _snap = _snap_ids = None             # rescue(): engine.candidates() of the rescued indices (ascending) and those indices
     _written = None                      # index -> {attribute: value}: what was assigned to samples from outside (TrajectorySample.__setattr__)
     _mat = _mat_ids = None               # materialise(): engine.materialise() of the listed indices (ascending) and those indices
+    _override = None                     # set_cost_override(): (cost [C], raw prediction cost [C], best index within the shard or -1)
 
     def __init__(self, engine, inputs, result: dict, agent: int = 0):
         self.engine, self.inputs, self.result, self.agent = engine, inputs, result, agent
@@ -388,7 +391,38 @@ class PlanStepResult:
     @property
     def cost(self) -> np.ndarray:
         self._load_arrays()
-        return self._cost
+        return self._cost if self._override is None else self._override[0]
+
+    # ---- a cost computed beside the step in place of the step's own ----
+    def set_cost_override(self, total, prediction, best_index):
+        """Answer `cost`, TrajectorySample.cost and costMap["prediction"] from a pass that ran beside the step: total [C] the
+        re-summed cost, prediction [C] the raw prediction cost it was summed with (NaN rows: candidates without a cost, which keep
+        the step's values), best_index the pass's winner within the shard (-1: none).  sorted_ids, ranked_ids,
+        sorted_trajectories and `best` then order by `total` with the host's stable argsort over the same pools; the device sort
+        reads the step's own cost plane and is not used.  Install it before samples are handed out: a sample built earlier keeps
+        the cost it was built with.  None (the default) changes nothing."""
+        self._load_arrays()
+        total, prediction = np.asarray(total, np.float64), np.asarray(prediction, np.float64)
+        if total.shape != self._cost.shape or prediction.shape != self._cost.shape:
+            raise ValueError(f"cost override of {total.shape} / {prediction.shape} entries for {self._cost.shape} candidates")
+        costed = (self._flags & _abi.FX_FLAG_COSTED) != 0
+        self._override = (np.where(costed, total, self._cost), np.where(costed, prediction, np.nan), int(best_index))
+        self._host_orders = None
+
+    def apply_prediction_probability(self, ego_length: float, ego_width: float):
+        """Run engine.prediction_probability over every candidate of this step -- the obstacles are the ones of the engine's last
+        set_risk_obstacles -- and install its result as the cost override.  Returns the pass's dict."""
+        self._check()
+        r = self.engine.prediction_probability(ego_length, ego_width, agent=self.agent)
+        self.set_cost_override(r["total"], r["prob"], r["best_index"])
+        return r
+
+    def _override_costmap(self, index, costmap: dict) -> dict:
+        ov = self._override
+        if ov is not None and "prediction" in costmap and not np.isnan(ov[1][index]):
+            p = float(ov[1][index])
+            costmap["prediction"] = (p, float(self.inputs.cost_weights["prediction"] * p))
+        return costmap
 
     @property
     def flags(self) -> np.ndarray:
@@ -580,8 +614,8 @@ class PlanStepResult:
         the host arrays answer: a stale step, an engine without `ranked`, or an agent below DEVICE_SORT_MIN_CANDIDATES (the
         measured size under which the host's NumPy sort is the faster one)"""
         eng = self.engine
-        if self._stale or not hasattr(eng, "ranked") or self.n_candidates < DEVICE_SORT_MIN_CANDIDATES:
-            return None
+        if self._stale or not hasattr(eng, "ranked") or self.n_candidates < DEVICE_SORT_MIN_CANDIDATES or self._override is not None:
+            return None   # (an override: the device sort reads the step's own cost plane)
         serials = getattr(eng, "sort_serials", None) or {}   # (there is one order per agent on the device: another agent's sort leaves it)
         if self._rank_pool != (require, exclude, serials.get(self.agent, 0)):
             self._rank_counts = eng.sort_candidates(self.agent, require, exclude)
@@ -643,5 +677,8 @@ class PlanStepResult:
 
     @property
     def best(self) -> Optional[TrajectorySample]:
+        if self._override is not None:
+            g = self._override[2]
+            return self.sample(g) if g >= 0 else None
         g = self.result["best_index"] - self.inputs.shard_begin
         return self.sample(int(g)) if self.result["best_index"] >= 0 else None

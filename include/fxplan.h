@@ -706,6 +706,41 @@ int32_t fx_set_reach_sets_agent(FxContext *ctx, int32_t agent, int32_t n_entries
 int32_t fx_eval_risk_costs_agent(FxContext *ctx, int32_t agent, const FxRiskParams *params, const FxRiskCostParams *cost /* NULL: detail only */,
                                  int64_t n_ids, const int64_t *ids, const FxRiskOutputs *out);
 
+/* ---- Collision probability as the prediction cost (additive within ABI 14) ----
+ * The `prediction` cost of the reference's C++ route, cf.CalculateCollisionProbabilityFast (reactive_planner_cpp.py:151-155):
+ * Sum over the predictions, in their order, of Sum_i get_collision_probability_fast(...)[i] (collision_probability.py:141-261;
+ * partial_cost_functions.py:344-356, the commented-out branch) for candidates of the last plan step, and the step's weighted cost
+ * re-summed with that entry in place of the step's own.  A pass of its own beside the step: nothing a plan step, the top-k, a
+ * sparse set, a sort or the risk passes own is written.  Obstacles: the tables of fx_set_risk_obstacles_agent, of which pos, cov,
+ * yaw, n_pos, n_yaw and length are read.  wb_rear_axle of the functor is not used (UNPINNED: DESIGN.md section 16). */
+enum { FX_PRED_SOURCE_PROBABILITY = 0,   /* the collision probability */
+       FX_PRED_SOURCE_STEP = 1 };        /* the step's own raw prediction entry: no probability kernel runs and `total` is the
+                                            step's cost bit for bit -- the self-check of summation order and weights */
+typedef struct FxPredProbParams {
+    double ego_length, ego_width;
+    int32_t source;                      /* FX_PRED_SOURCE_* */
+} FxPredProbParams;
+typedef struct FxPredProbOutputs {       /* rows in the order of ids, or [C] with ids == NULL: NaN for candidates without
+                                            FX_FLAG_COSTED, which the arg-min skips.  Any pointer may be NULL */
+    double *prob;                        /* [n] raw cost Sum_k Sum_i p (FX_PRED_SOURCE_STEP: the step's raw prediction entry) */
+    double *prob_obs;                    /* [K][n] per prediction, obstacle-major (FX_PRED_SOURCE_STEP: NaN) */
+    double *total;                       /* [n] the weighted cost sum of the step's raw cost rows with the prediction entry replaced
+                                            by prob, in the step's own order of operations */
+    int64_t *best_index;                 /* lexicographic (total, index) minimum over the candidates with FX_FLAG_SELECTABLE and
+                                            neither FX_FLAG_COLLISION nor FX_FLAG_BOUNDARY, NaN totals skipped; -1: none */
+    double *best_cost;                   /* its total (NaN with -1) */
+} FxPredProbOutputs;
+/* ids as in fx_eval_risk_agent (n_ids == 0 with ids == NULL: every candidate).  Checked before anything is launched or written:
+ * FX_ERR_NOT_READY before the first evaluated step or when inputs were rewritten since it, for a step without
+ * FX_MODE_WRITE_COSTMAP, and without FX_MODE_WRITE_BUNDLE unless every listed id lies in the agent's sparse set;
+ * FX_ERR_INVALID_ARGUMENT for a cost list without FX_COST_PREDICTION, NULL params or out, lengths that are not positive, an unknown
+ * source, ids out of range, or an obstacle whose yaw is shorter than min(S, n_pos).  K = 0 is legal: prob = 0, total = the re-sum.
+ * Synchronous; its part of the risk passes' device block is allocated on first use, only grows and is counted in fx_device_bytes. */
+int32_t fx_eval_prediction_prob_agent(FxContext *ctx, int32_t agent, const FxPredProbParams *params, int64_t n_ids, const int64_t *ids,
+                                      const FxPredProbOutputs *out);
+/* device time of the last fx_eval_prediction_prob_agent (all its kernels), ms; -1 before the first */
+double fx_last_predprob_ms(FxContext *ctx);
+
 #ifdef __cplusplus
 }
 #endif

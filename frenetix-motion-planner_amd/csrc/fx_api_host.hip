@@ -1,6 +1,6 @@
 // fx_api_host.hip -- host geometry of the callers either side of the path (no GPU involved) and the read-back of a step's
 // per-candidate outputs (header: include/fxplan.h; context: fx_context.h).
-#include "fx_context.h"
+#include "fx_pass.h"
 
 extern "C" {
 
@@ -133,10 +133,9 @@ int32_t fx_build_obstacle_hulls_batch(int32_t K, int32_t P, const int32_t *n_use
 // ---- read-back ----
 
 int32_t fx_read_costs_agent(FxContext *c, int32_t agent, double *cost, uint32_t *flags) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     const FxAgentSlot &s = c->slots[agent];
-    { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+    FX_TRY(fx_drain(c));
     if (cost) HIP_TRY(hipMemcpy(cost, c->d_cost + s.cand_off, sizeof(double) * s.C, hipMemcpyDeviceToHost));
     if (flags) HIP_TRY(hipMemcpy(flags, c->d_flags + s.cand_off, sizeof(uint32_t) * s.C, hipMemcpyDeviceToHost));
     return FX_OK;
@@ -144,11 +143,10 @@ int32_t fx_read_costs_agent(FxContext *c, int32_t agent, double *cost, uint32_t 
 int32_t fx_read_costs(FxContext *c, double *cost, uint32_t *flags) { return fx_read_costs_agent(c, 0, cost, flags); }
 
 int32_t fx_read_costmap_agent(FxContext *c, int32_t agent, double *raw) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     const FxAgentSlot &s = c->slots[agent];
     if (!(s.mode & FX_MODE_WRITE_COSTMAP)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_COSTMAP");
-    { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+    FX_TRY(fx_drain(c));
     HIP_TRY(hipMemcpy2D(raw, sizeof(double) * s.C, c->d_costmap + (size_t)FX_NUM_COSTS * s.cand_off, sizeof(double) * s.ld,
                         sizeof(double) * s.C, s.n_cost, hipMemcpyDeviceToHost));
     return FX_OK;
@@ -156,13 +154,12 @@ int32_t fx_read_costmap_agent(FxContext *c, int32_t agent, double *raw) {
 int32_t fx_read_costmap(FxContext *c, double *raw) { return fx_read_costmap_agent(c, 0, raw); }
 
 static int32_t read_coeff_rows(FxContext *c, int32_t agent, int64_t index, double *lon6, double *lat6, double *tau_lat, int32_t *traj_len) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     const FxAgentSlot &s = c->slots[agent];
     if (!(s.mode & FX_MODE_WRITE_BUNDLE)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_BUNDLE");
     if (index < 0 || index >= s.C) return set_err(FX_ERR_INVALID_ARGUMENT, "candidate %lld out of range", (long long)index);
     double tmp[FX_COEFF_ROWS];
-    { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+    FX_TRY(fx_drain(c));
     HIP_TRY(hipMemcpy2D(tmp, sizeof(double), c->d_coeffs + (size_t)FX_COEFF_ROWS * s.cand_off + index, sizeof(double) * s.ld,
                         sizeof(double), FX_COEFF_ROWS, hipMemcpyDeviceToHost));
     if (lon6) memcpy(lon6, tmp, 6 * sizeof(double));
@@ -179,13 +176,12 @@ int32_t fx_read_lat_tau_agent(FxContext *c, int32_t agent, int64_t index, double
     return read_coeff_rows(c, agent, index, nullptr, nullptr, tau_lat, nullptr);
 }
 int32_t fx_read_boundary_steps_agent(FxContext *c, int32_t agent, int32_t *steps) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     if (!steps) return set_err(FX_ERR_INVALID_ARGUMENT, "steps is NULL");
     const FxAgentSlot &s = c->slots[agent];
     if (!(s.mode & FX_MODE_ROAD_BOUNDARY)) return set_err(FX_ERR_NOT_READY, "the step ran without FX_MODE_ROAD_BOUNDARY");
     HIP_TRY(hipMemcpyAsync(steps, c->d_bstep + s.cand_off, sizeof(int32_t) * s.C, hipMemcpyDeviceToHost, c->stream));
-    { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+    FX_TRY(fx_drain(c));
     return FX_OK;
 }
 int32_t fx_read_boundary_steps(FxContext *c, int32_t *steps) { return fx_read_boundary_steps_agent(c, 0, steps); }
@@ -195,12 +191,11 @@ int32_t fx_read_coeffs(FxContext *c, int64_t index, double *lon6, double *lat6, 
 }
 
 int32_t fx_read_sample_agent(FxContext *c, int32_t agent, int64_t index, double *planes) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     const FxAgentSlot &s = c->slots[agent];
     if (!(s.mode & FX_MODE_WRITE_BUNDLE)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_BUNDLE");
     if (index < 0 || index >= s.C) return set_err(FX_ERR_INVALID_ARGUMENT, "candidate %lld out of range", (long long)index);
-    { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+    FX_TRY(fx_drain(c));
     // one strided gather: 14*S elements, pitch = ld doubles
     HIP_TRY(hipMemcpy2D(planes, sizeof(double), c->h_probs[agent].planes + index, sizeof(double) * s.ld, sizeof(double),
                         (size_t)FX_NUM_PLANES * s.S, hipMemcpyDeviceToHost));
@@ -210,8 +205,7 @@ int32_t fx_read_sample(FxContext *c, int64_t index, double *planes) { return fx_
 
 int32_t fx_read_candidate_agent(FxContext *c, int32_t agent, int64_t index, double *planes, double *coeffs13, int32_t *traj_len,
                                 double *raw_costs, double *cost, uint32_t *flags) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     const FxAgentSlot &s = c->slots[agent];
     if (index < 0 || index >= s.C) return set_err(FX_ERR_INVALID_ARGUMENT, "candidate %lld out of range", (long long)index);
     const bool bundle = (s.mode & FX_MODE_WRITE_BUNDLE) != 0, cmap = (s.mode & FX_MODE_WRITE_COSTMAP) != 0;
@@ -236,7 +230,7 @@ int32_t fx_read_candidate_agent(FxContext *c, int32_t agent, int64_t index, doub
                                  sizeof(double), s.n_cost, hipMemcpyDeviceToHost, c->stream));
     if (cost) HIP_TRY(hipMemcpyAsync(h_c, c->d_cost + s.cand_off + index, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (flags) HIP_TRY(hipMemcpyAsync(h_fl, c->d_flags + s.cand_off + index, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+    FX_TRY(fx_drain(c));
     if (planes) memcpy(planes, hp, sizeof(double) * n_pl);
     if (coeffs13) memcpy(coeffs13, h_co, sizeof(double) * FX_COEFF_ROWS);
     if (traj_len) *traj_len = *h_tl;
@@ -277,7 +271,7 @@ int fx_gather_rows(FxContext *c, const GatherArgs &ga, int64_t n, const int64_t 
         HIP_TRY(fx_launch_gather_candidates(&ga, d_ids, m, d_rec, c->stream));
         HIP_TRY(hipMemcpyAsync(c->h_cands + sizeof(int64_t) * m_max, d_rec, sizeof(unsigned long long) * W * m, hipMemcpyDeviceToHost,
                                c->stream));
-        { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+        FX_TRY(fx_drain(c));
         for (int64_t j = 0; j < m; j++) {
             const unsigned long long *r = h_rec + (size_t)j * W;
             const unsigned long long *t = r + n_pl + FX_COEFF_ROWS + n_cost;   // cost | traj_len | flags | boundary_step
@@ -302,12 +296,9 @@ extern "C" {
 // on the first call: a context that never comes here owns what it always did.
 int32_t fx_read_candidates_agent(FxContext *c, int32_t agent, int64_t n, const int64_t *ids, double *planes, double *coeffs13,
                                  int32_t *traj_len, double *raw_costs, double *cost, uint32_t *flags, int32_t *boundary_step) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     const FxAgentSlot &s = c->slots[agent];
-    if (n < 0 || (n > 0 && !ids)) return set_err(FX_ERR_INVALID_ARGUMENT, "ids inconsistent (n=%lld)", (long long)n);
-    for (int64_t j = 0; j < n; j++)
-        if (ids[j] < 0 || ids[j] >= s.C) return set_err(FX_ERR_INVALID_ARGUMENT, "candidate %lld out of range", (long long)ids[j]);
+    FX_TRY(fx_check_ids(n, ids, s.C, "n"));
     const bool bundle = (s.mode & FX_MODE_WRITE_BUNDLE) != 0, cmap = (s.mode & FX_MODE_WRITE_COSTMAP) != 0;
     const bool bound = (s.mode & FX_MODE_ROAD_BOUNDARY) != 0;
     if ((planes || coeffs13 || traj_len) && !bundle) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_BUNDLE");
@@ -330,12 +321,11 @@ int32_t fx_read_candidates_agent(FxContext *c, int32_t agent, int64_t n, const i
 }
 
 int32_t fx_read_plane_agent(FxContext *c, int32_t agent, int32_t plane, double *out) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     const FxAgentSlot &s = c->slots[agent];
     if (!(s.mode & FX_MODE_WRITE_BUNDLE)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_BUNDLE");
     if (plane < 0 || plane >= FX_NUM_PLANES) return set_err(FX_ERR_INVALID_ARGUMENT, "plane %d out of range", plane);
-    { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+    FX_TRY(fx_drain(c));
     HIP_TRY(hipMemcpy2D(out, sizeof(double) * s.C, c->h_probs[agent].planes + (size_t)plane * s.S * s.ld, sizeof(double) * s.ld,
                         sizeof(double) * s.C, s.S, hipMemcpyDeviceToHost));
     return FX_OK;
@@ -359,7 +349,7 @@ int32_t fx_read_topk_batch(FxContext *c, int32_t k, double *cost, int64_t *index
     const size_t n = (size_t)k * c->n_agents;
     HIP_TRY(hipMemcpyAsync(c->h_topk_cost, c->d_topk_cost, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(c->h_topk_idx, c->d_topk_idx, sizeof(long long) * n, hipMemcpyDeviceToHost, c->stream));
-    { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+    FX_TRY(fx_drain(c));
     memcpy(cost, c->h_topk_cost, sizeof(double) * n);
     for (size_t i = 0; i < n; i++) index[i] = (int64_t)c->h_topk_idx[i];
     return FX_OK;

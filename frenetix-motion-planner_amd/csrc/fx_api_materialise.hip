@@ -3,15 +3,14 @@
 // (fx_eval_list_kernel.h) into a compact structure-of-arrays block per agent, the "sparse set"; fx_read_materialised_agent and
 // fx_read_package_materialised read it back (the gather kernel of the batched read-back, pointed at the block), the risk passes
 // evaluate on it (fx_api_risk.hip).  Nothing here runs in a plan step, and nothing a plan step wrote or published is touched.
-#include "fx_context.h"
+#include "fx_pass.h"
 
 // One agent's set.  `ids` is kept ascending and de-duplicated: positions are monotone in the candidate index, so an arg-min over
 // positions with ties to the lower position is the arg-min over candidates with ties to the lower index.
 struct FxSparseSet {
     std::vector<int64_t> ids;
     long long step = -1;      // FxContext.n_steps when the set was made: the next evaluation ends it
-    char *d_buf = nullptr;    // grow-only block, every part 256-byte aligned
-    size_t cap = 0;
+    FxDeviceBlock block;      // every part 256-byte aligned (FxBlockLayout)
     int64_t ld = 0;
     size_t o_planes = 0, o_coeffs = 0, o_trajlen = 0, o_costmap = 0, o_cost = 0, o_flags = 0, o_bstep = 0;
     DevProblem clone;         // host copy of the problem the list kernel was launched with
@@ -19,37 +18,31 @@ struct FxSparseSet {
 
 struct FxSparseState {
     std::vector<FxSparseSet> agents;
-    hipEvent_t e0 = nullptr, e1 = nullptr;   // attached to the last list-kernel launch (fx_last_materialise_ms)
-    bool timed = false;
+    FxEventPair ev;   // attached to the last list-kernel launch (fx_last_materialise_ms)
 };
 
 void fx_sparse_release(FxContext *c) {
     if (!c || !c->sparse) return;
-    for (FxSparseSet &s : c->sparse->agents)
-        if (s.d_buf) { (void)hipFree(s.d_buf); c->dev_bytes -= (int64_t)s.cap; }
-    if (c->sparse->e0) (void)hipEventDestroy(c->sparse->e0);
-    if (c->sparse->e1) (void)hipEventDestroy(c->sparse->e1);
+    for (FxSparseSet &s : c->sparse->agents) s.block.release(c);
+    c->sparse->ev.release();
     delete c->sparse;
     c->sparse = nullptr;
 }
 
-// the resident inputs are the ones the last evaluation read: no upload (clears `evaluated`) and no state update since
-static bool inputs_current(const FxContext *c) { return c->evaluated && !c->probs_dirty && !(c->dirty_hi > c->dirty_lo); }
-
 bool fx_sparse_view(FxContext *c, int32_t agent, FxSparseView *v) {
     if (!c || !c->sparse || agent < 0 || agent >= (int)c->sparse->agents.size()) return false;
     const FxSparseSet &s = c->sparse->agents[agent];
-    if (s.ids.empty() || s.step != c->n_steps || !inputs_current(c)) return false;
+    if (s.ids.empty() || s.step != c->n_steps || !fx_inputs_current(c)) return false;
     v->ids = s.ids.data();
     v->n = (int64_t)s.ids.size();
     v->ld = s.ld;
-    v->planes = reinterpret_cast<const double *>(s.d_buf + s.o_planes);
-    v->coeffs = reinterpret_cast<const double *>(s.d_buf + s.o_coeffs);
-    v->costmap = reinterpret_cast<const double *>(s.d_buf + s.o_costmap);
-    v->cost = reinterpret_cast<const double *>(s.d_buf + s.o_cost);
-    v->flags = reinterpret_cast<const uint32_t *>(s.d_buf + s.o_flags);
-    v->traj_len = reinterpret_cast<const int32_t *>(s.d_buf + s.o_trajlen);
-    v->bound_step = reinterpret_cast<const int32_t *>(s.d_buf + s.o_bstep);
+    v->planes = reinterpret_cast<const double *>(s.block.p + s.o_planes);
+    v->coeffs = reinterpret_cast<const double *>(s.block.p + s.o_coeffs);
+    v->costmap = reinterpret_cast<const double *>(s.block.p + s.o_costmap);
+    v->cost = reinterpret_cast<const double *>(s.block.p + s.o_cost);
+    v->flags = reinterpret_cast<const uint32_t *>(s.block.p + s.o_flags);
+    v->traj_len = reinterpret_cast<const int32_t *>(s.block.p + s.o_trajlen);
+    v->bound_step = reinterpret_cast<const int32_t *>(s.block.p + s.o_bstep);
     return true;
 }
 
@@ -66,13 +59,10 @@ bool fx_sparse_positions(const FxSparseView &v, int64_t n, const int64_t *ids, s
 extern "C" {
 
 int32_t fx_materialise_candidates_agent(FxContext *c, int32_t agent, int64_t n, const int64_t *ids) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     const FxAgentSlot &sl = c->slots[agent];
-    if (n < 0 || (n > 0 && !ids)) return set_err(FX_ERR_INVALID_ARGUMENT, "ids inconsistent (n=%lld)", (long long)n);
-    for (int64_t j = 0; j < n; j++)
-        if (ids[j] < 0 || ids[j] >= sl.C) return set_err(FX_ERR_INVALID_ARGUMENT, "candidate %lld out of range", (long long)ids[j]);
-    if (!inputs_current(c))
+    FX_TRY(fx_check_ids(n, ids, sl.C, "n"));
+    if (!fx_inputs_current(c))
         return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): the re-walk would use another state");
     if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
     if (!c->sparse) c->sparse = new FxSparseState();
@@ -82,8 +72,8 @@ int32_t fx_materialise_candidates_agent(FxContext *c, int32_t agent, int64_t n, 
 
     const DevProblem &src = c->h_probs[agent];
     const int S = sl.S, M = sl.M;
-    const size_t lds = sizeof(double) * ((size_t)M * FX_REF_FIELDS + FX_TP * (size_t)S + (((size_t)M + 1) & ~(size_t)1));
-    if (((size_t)M * (FX_REF_FIELDS + 1) + 2 + FX_TP * (size_t)S) * sizeof(double) > 160 * 1024 - 1024)
+    const size_t lds = fx_generic_lds(M, S, 0);
+    if (fx_generic_base_lds(M, S) > 160 * 1024 - 1024)
         return set_err(FX_ERR_CAPACITY, "reference with %d knots does not fit the 160 KiB LDS of the list kernel", M);
     std::vector<int64_t> sorted(ids, ids + n);
     std::sort(sorted.begin(), sorted.end());
@@ -95,24 +85,18 @@ int32_t fx_materialise_candidates_agent(FxContext *c, int32_t agent, int64_t n, 
     const size_t n_rows = (size_t)std::max(sl.n_cost, 1);
 
     // ---- the block: the set's arrays, the kernel's own selection scratch, the list, the clone ----
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 8), 256); return o; };
-    const size_t o_planes = take(sizeof(double) * FX_NUM_PLANES * (size_t)S * ld), o_coeffs = take(sizeof(double) * FX_COEFF_ROWS * ld);
-    const size_t o_trajlen = take(sizeof(int32_t) * ld), o_costmap = take(sizeof(double) * n_rows * ld), o_cost = take(sizeof(double) * ld);
-    const size_t o_flags = take(sizeof(uint32_t) * ld), o_bstep = take(sizeof(int32_t) * ld);
-    const size_t o_cnt = take(sizeof(unsigned long long) * FX_CNT_COUNT), o_pc = take(sizeof(double) * n_blocks);
-    const size_t o_pi = take(sizeof(int64_t) * n_blocks), o_ids = take(sizeof(int64_t) * ld), o_prob = take(sizeof(DevProblem));
+    FxBlockLayout lay;
+    const size_t o_planes = lay.take(sizeof(double) * FX_NUM_PLANES * (size_t)S * ld), o_coeffs = lay.take(sizeof(double) * FX_COEFF_ROWS * ld);
+    const size_t o_trajlen = lay.take(sizeof(int32_t) * ld), o_costmap = lay.take(sizeof(double) * n_rows * ld), o_cost = lay.take(sizeof(double) * ld);
+    const size_t o_flags = lay.take(sizeof(uint32_t) * ld), o_bstep = lay.take(sizeof(int32_t) * ld);
+    const size_t o_cnt = lay.take(sizeof(unsigned long long) * FX_CNT_COUNT), o_pc = lay.take(sizeof(double) * n_blocks);
+    const size_t o_pi = lay.take(sizeof(int64_t) * n_blocks), o_ids = lay.take(sizeof(int64_t) * ld), o_prob = lay.take(sizeof(DevProblem));
     HIP_TRY(hipSetDevice(c->device));
     // (the previous call's uploads came from this set's host members: they have landed before those are rewritten)
-    { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+    FX_TRY(fx_drain(c));
     s.ids.clear();   // from here on the previous set is gone
-    if (off > s.cap) {
-        if (s.d_buf) { HIP_TRY(hipFree(s.d_buf)); c->dev_bytes -= (int64_t)s.cap; s.d_buf = nullptr; s.cap = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_buf), off));
-        s.cap = off;
-        c->dev_bytes += (int64_t)off;
-    }
-    char *base = s.d_buf;
+    FX_TRY(s.block.ensure(c, lay.size()));
+    char *base = s.block.p;
     s.o_planes = o_planes, s.o_coeffs = o_coeffs, s.o_trajlen = o_trajlen, s.o_costmap = o_costmap, s.o_cost = o_cost;
     s.o_flags = o_flags, s.o_bstep = o_bstep, s.ld = ld;
 
@@ -133,11 +117,7 @@ int32_t fx_materialise_candidates_agent(FxContext *c, int32_t agent, int64_t n, 
     d.cost_tail = nullptr; d.obs_part = nullptr; d.obs_colm = nullptr; d.obs_ticket = nullptr; d.obs_list = nullptr;
     d.pkg_out = nullptr; d.pkg_seq = nullptr; d.pkg_plane_rows = 0;
     bool extra = false;
-    for (int q = 0; q < d.n_cost; q++) {
-        const int id = d.cost_id[q];
-        extra |= id == FX_COST_ACCELERATION || id == FX_COST_JERK || id == FX_COST_ORIENTATION_OFFSET || id == FX_COST_PATH_LENGTH ||
-                 id == FX_COST_DISTANCE_TO_OBSTACLES || id == FX_COST_LANE_CENTER_OFFSET;
-    }
+    for (int q = 0; q < d.n_cost; q++) extra |= fx_is_windowed_cost(d.cost_id[q]);
     const bool obst = d.K > 0 || (d.mode & FX_MODE_ROAD_BOUNDARY) != 0;
 
     int64_t *d_ids = reinterpret_cast<int64_t *>(base + o_ids);
@@ -148,10 +128,10 @@ int32_t fx_materialise_candidates_agent(FxContext *c, int32_t agent, int64_t n, 
     HIP_TRY(hipMemcpyAsync(d_ids, s.ids.data(), sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(base + o_prob, &d, sizeof(DevProblem), hipMemcpyHostToDevice, c->stream));
     FxSparseState *st = c->sparse;
-    if (!st->e0) { HIP_TRY(hipEventCreate(&st->e0)); HIP_TRY(hipEventCreate(&st->e1)); }
-    st->timed = false;
-    HIP_TRY(fx_launch_eval_list(d_prob, d_ids, m, lds, obst, extra, st->e0, st->e1, c->stream));
-    st->timed = true;
+    FX_TRY(st->ev.ensure());
+    st->ev.timed = false;
+    HIP_TRY(fx_launch_eval_list(d_prob, d_ids, m, lds, obst, extra, st->ev.e0, st->ev.e1, c->stream));
+    st->ev.timed = true;
     // the kernel reads the input arena: a state update or an upload behind it waits for the stream first
     c->in_flight = true; c->tail_work = true;
     s.step = c->n_steps;
@@ -160,12 +140,9 @@ int32_t fx_materialise_candidates_agent(FxContext *c, int32_t agent, int64_t n, 
 
 int32_t fx_read_materialised_agent(FxContext *c, int32_t agent, int64_t n, const int64_t *ids, double *planes, double *coeffs13,
                                    int32_t *traj_len, double *raw_costs, double *cost, uint32_t *flags, int32_t *boundary_step) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     const FxAgentSlot &sl = c->slots[agent];
-    if (n < 0 || (n > 0 && !ids)) return set_err(FX_ERR_INVALID_ARGUMENT, "ids inconsistent (n=%lld)", (long long)n);
-    for (int64_t j = 0; j < n; j++)
-        if (ids[j] < 0 || ids[j] >= sl.C) return set_err(FX_ERR_INVALID_ARGUMENT, "candidate %lld out of range", (long long)ids[j]);
+    FX_TRY(fx_check_ids(n, ids, sl.C, "n"));
     if (boundary_step && !(sl.mode & FX_MODE_ROAD_BOUNDARY)) return set_err(FX_ERR_NOT_READY, "the step ran without FX_MODE_ROAD_BOUNDARY");
     if (n == 0) return FX_OK;
     FxSparseView v;
@@ -182,8 +159,7 @@ int32_t fx_read_materialised_agent(FxContext *c, int32_t agent, int64_t n, const
 }
 
 int32_t fx_read_package_materialised(FxContext *c, int32_t agent, int64_t index, double yaw_rate0, FxPackage *pkg, double *block) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     if (!pkg) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_read_package_materialised: NULL argument");
     const FxAgentSlot &sl = c->slots[agent];
     const DevProblem &d = c->h_probs[agent];
@@ -192,7 +168,7 @@ int32_t fx_read_package_materialised(FxContext *c, int32_t agent, int64_t index,
     uint32_t fl = 0;
     std::vector<double> own;   // (planes are read either way: one record, one copy)
     if (!block) { own.resize((size_t)FX_NUM_PLANES * sl.S); }
-    if ((rc = fx_read_materialised_agent(c, agent, 1, &index, block ? block : own.data(), co, &tl, raw, &cost, &fl, nullptr))) return rc;
+    FX_TRY(fx_read_materialised_agent(c, agent, 1, &index, block ? block : own.data(), co, &tl, raw, &cost, &fl, nullptr));
     memset(pkg, 0, sizeof(*pkg));
     pkg->found = 1;
     pkg->S = sl.S;
@@ -210,14 +186,6 @@ int32_t fx_read_package_materialised(FxContext *c, int32_t agent, int64_t index,
 }
 
 // device time of the last list-kernel launch of this context (events attached to the kernel itself), ms; -1 before the first
-double fx_last_materialise_ms(FxContext *c) {
-    if (!c || !c->sparse || !c->sparse->timed) return -1.0;
-    float ms = -1.f;
-    if (hipEventSynchronize(c->sparse->e1) != hipSuccess || hipEventElapsedTime(&ms, c->sparse->e0, c->sparse->e1) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0;
-    }
-    return (double)ms;
-}
+double fx_last_materialise_ms(FxContext *c) { return (c && c->sparse) ? c->sparse->ev.elapsed_ms() : -1.0; }
 
 }  // extern "C"

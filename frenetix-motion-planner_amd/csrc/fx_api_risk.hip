@@ -7,7 +7,7 @@
 #include <cmath>
 #include <vector>
 
-#include "fx_context.h"
+#include "fx_pass.h"
 #include "fx_risk_args.h"
 
 extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const FxRiskParams *params, double *out_ego, double *out_obst,
@@ -37,9 +37,8 @@ struct FxRiskAgent {
 
 struct FxRiskState {
     std::vector<FxRiskAgent> agents;
-    char *d_buf = nullptr;   // the block of a risk pass (RiskPass): grows to the largest call, never shrinks
-    size_t cap = 0;          // bytes
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    FxDeviceBlock block;     // the block of a risk pass (RiskPass): grows to the largest call, never shrinks
+    FxEventPair ev;          // around a pass's launches; read at once into the two times below
     float last_ms = 0.f;
     float last_pp_ms = -1.f;   // fx_eval_prediction_prob_agent
 };
@@ -47,9 +46,8 @@ struct FxRiskState {
 void fx_risk_release(FxContext *c) {
     if (!c || !c->risk) return;
     FxRiskState *r = c->risk;
-    if (r->d_buf) { (void)hipFree(r->d_buf); c->dev_bytes -= (int64_t)r->cap; }
-    if (r->e0) (void)hipEventDestroy(r->e0);
-    if (r->e1) (void)hipEventDestroy(r->e1);
+    r->block.release(c);
+    r->ev.release();
     delete r;
     c->risk = nullptr;
 }
@@ -206,8 +204,7 @@ struct RiskPass {
 // outputs with params, and refuses an obstacle that calc_risk cannot evaluate (the plain pass skips it).
 static int risk_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskParams *params, int64_t n_ids, const int64_t *ids,
                       bool have_out, bool detail, bool need_v = true) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     const FxAgentSlot &s = c->slots[agent];
     q.sparse = !(s.mode & FX_MODE_WRITE_BUNDLE);
     if (q.sparse) {   // every listed candidate has been materialised since the step, or the pass has nothing to read
@@ -227,10 +224,9 @@ static int risk_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskPara
         return set_err(FX_ERR_INVALID_ARGUMENT, "n_edges %d", p.n_edges);
     if (!(p.ego_mass > 0.0) || !(p.ego_length > 0.0) || !(p.ego_width > 0.0))
         return set_err(FX_ERR_INVALID_ARGUMENT, "ego length / width / mass must be positive");
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return set_err(FX_ERR_INVALID_ARGUMENT, "ids inconsistent (n_ids=%lld)", (long long)n_ids);
+    FX_TRY(fx_check_id_list(n_ids, ids, "n_ids"));
     if (!have_out) return set_err(FX_ERR_INVALID_ARGUMENT, "an output pointer is NULL");
-    for (int64_t j = 0; ids && j < n_ids; j++)
-        if (ids[j] < 0 || ids[j] >= s.C) return set_err(FX_ERR_INVALID_ARGUMENT, "candidate %lld out of range", (long long)ids[j]);
+    FX_TRY(fx_check_id_range(n_ids, ids, s.C));
     FxRiskState *r = risk_state(c);
     const FxRiskAgent &a = r->agents[agent];
     const int S = s.S, K = a.K;
@@ -266,37 +262,30 @@ static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, si
     const FxRiskAgent &a = *q.a;
     build_records(a, q.S, q.maha, q.rec);
     const size_t n1 = (size_t)std::max<int64_t>(q.n, 1), K = (size_t)q.K, KP = K * q.P;
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 8), 256); return o; };
-    q.o_rec = take(sizeof(double) * q.rec.size()), q.o_obs = take(sizeof(double) * a.obs.size());
-    q.o_pos = take(sizeof(double) * 2 * KP), q.o_yaw = take(sizeof(double) * KP), q.o_v = take(sizeof(double) * KP);
-    q.o_ids = take(sizeof(int64_t) * n1), q.o_ego = take(sizeof(double) * n1), q.o_obst = take(sizeof(double) * n1);
-    q.o_idx = take(2 * sizeof(long long));
-    if (detail) q.o_occ = take(sizeof(double) * n1), q.o_col = take(sizeof(double) * 4 * K * n1);
+    FxBlockLayout lay;
+    q.o_rec = lay.take(sizeof(double) * q.rec.size()), q.o_obs = lay.take(sizeof(double) * a.obs.size());
+    q.o_pos = lay.take(sizeof(double) * 2 * KP), q.o_yaw = lay.take(sizeof(double) * KP), q.o_v = lay.take(sizeof(double) * KP);
+    q.o_ids = lay.take(sizeof(int64_t) * n1), q.o_ego = lay.take(sizeof(double) * n1), q.o_obst = lay.take(sizeof(double) * n1);
+    q.o_idx = lay.take(2 * sizeof(long long));
+    if (detail) q.o_occ = lay.take(sizeof(double) * n1), q.o_col = lay.take(sizeof(double) * 4 * K * n1);
     if (cost) {
         const bool reach = cost->responsibility_mode == FX_RISK_RESP_REACH_SET;
         const size_t nE = q.nE = reach ? a.rs_obs.size() : 0, nP = q.nP = reach ? a.rs_step.size() : 0;
         const size_t nV = q.nV = reach ? a.rs_verts.size() / 2 : 0;
-        q.o_out = take(sizeof(double) * 7 * n1), q.o_bh = take(sizeof(double) * n1), q.o_resp = take(sizeof(double) * K);
-        q.o_eobs = take(sizeof(int32_t) * nE), q.o_eoff = take(sizeof(int32_t) * (nE + 1));
-        q.o_pst = take(sizeof(int32_t) * nP), q.o_voff = take(sizeof(int32_t) * (nP + 1)), q.o_vert = take(sizeof(double) * 2 * nV);
+        q.o_out = lay.take(sizeof(double) * 7 * n1), q.o_bh = lay.take(sizeof(double) * n1), q.o_resp = lay.take(sizeof(double) * K);
+        q.o_eobs = lay.take(sizeof(int32_t) * nE), q.o_eoff = lay.take(sizeof(int32_t) * (nE + 1));
+        q.o_pst = lay.take(sizeof(int32_t) * nP), q.o_voff = lay.take(sizeof(int32_t) * (nP + 1)), q.o_vert = lay.take(sizeof(double) * 2 * nV);
     }
     if (pp_nb) {
-        q.o_pstep = take(sizeof(double) * K * (size_t)std::max(q.S - 1, 1) * pp_nb);
-        q.o_pprob = take(sizeof(double) * n1), q.o_pobs = take(sizeof(double) * K * n1), q.o_ptot = take(sizeof(double) * n1);
-        q.o_pbest = take(2 * sizeof(long long));
+        q.o_pstep = lay.take(sizeof(double) * K * (size_t)std::max(q.S - 1, 1) * pp_nb);
+        q.o_pprob = lay.take(sizeof(double) * n1), q.o_pobs = lay.take(sizeof(double) * K * n1), q.o_ptot = lay.take(sizeof(double) * n1);
+        q.o_pbest = lay.take(2 * sizeof(long long));
     }
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->tail_work = c->user_stream;
-    if (off > r->cap) {
-        if (r->d_buf) { HIP_TRY(hipFree(r->d_buf)); c->dev_bytes -= (int64_t)r->cap; r->d_buf = nullptr; r->cap = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&r->d_buf), off));
-        r->cap = off;
-        c->dev_bytes += (int64_t)off;
-    }
-    if (!r->e0) { HIP_TRY(hipEventCreate(&r->e0)); HIP_TRY(hipEventCreate(&r->e1)); }
-    q.base = r->d_buf;
+    FX_TRY(fx_drain(c));
+    FX_TRY(r->block.ensure(c, lay.size()));
+    FX_TRY(r->ev.ensure());
+    q.base = r->block.p;
     if (q.K > 0) {
         HIP_TRY(q.up(q.o_rec, q.rec.data(), sizeof(double) * q.rec.size()));
         HIP_TRY(q.up(q.o_obs, a.obs.data(), sizeof(double) * a.obs.size()));
@@ -316,7 +305,7 @@ static int risk_run(RiskPass &q, const FxRiskParams &p, bool detail, const RiskC
                          q.D(q.o_pos), q.D(q.o_yaw), q.D(q.o_v), q.K, q.P};
     long long *d_idx = reinterpret_cast<long long *>(q.base + q.o_idx);
     HIP_TRY(fx_launch_risk(&w, &p, q.D(q.o_ego), q.D(q.o_obst), detail ? q.D(q.o_col) : nullptr, detail ? q.D(q.o_occ) : nullptr, ca, d_idx,
-                           r->e0, r->e1, c->stream));
+                           r->ev.e0, r->ev.e1, c->stream));
     const size_t nn = (size_t)q.n, Kn = (size_t)q.K * nn;
     HIP_TRY(q.down(out.ego_risk, q.o_ego, nn));
     HIP_TRY(q.down(out.obst_risk, q.o_obst, nn));
@@ -332,7 +321,7 @@ static int risk_run(RiskPass &q, const FxRiskParams &p, bool detail, const RiskC
     long long idx[2] = {-1, -1};   // (the second one: the cost pass's arg-min)
     HIP_TRY(hipMemcpyAsync(idx, d_idx, sizeof(long long) * (ca ? 2 : 1), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&r->last_ms, r->e0, r->e1));
+    HIP_TRY(hipEventElapsedTime(&r->last_ms, r->ev.e0, r->ev.e1));
     // (sparse set: the arg-min ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
     for (long long &i : idx)
         if (q.sparse && i >= 0) i = (long long)q.set.ids[i];
@@ -462,11 +451,10 @@ extern "C" int32_t fx_eval_risk_costs_agent(FxContext *c, int32_t agent, const F
 #define FX_PREDPROB_SCRATCH_BYTES ((size_t)64 << 20)
 extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, const FxPredProbParams *params, int64_t n_ids,
                                                  const int64_t *ids, const FxPredProbOutputs *out) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     // (the planes and the cost map are the last EVALUATED step's: inputs rewritten since belong to a step that has not run -- the
     // condition of the sort and of the sparse set, fx_api_sort.hip / fx_api_materialise.hip)
-    if (c->probs_dirty || c->dirty_hi > c->dirty_lo)
+    if (!fx_inputs_current(c))   // (check_agent has established `evaluated`)
         return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
     if (!(c->slots[agent].mode & FX_MODE_WRITE_COSTMAP)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_COSTMAP");
     FxRiskParams rp{};   // what risk_check and step_probability read of it: the MVN mode and the ego's footprint
@@ -475,7 +463,7 @@ extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, co
     rp.ego_mass = 1.0;
     if (params) { rp.ego_length = params->ego_length; rp.ego_width = params->ego_width; }
     RiskPass q;
-    if ((rc = risk_check(q, c, agent, params ? &rp : nullptr, n_ids, ids, out != nullptr, false, false))) return rc;
+    FX_TRY(risk_check(q, c, agent, params ? &rp : nullptr, n_ids, ids, out != nullptr, false, false));
     if (params->source != FX_PRED_SOURCE_PROBABILITY && params->source != FX_PRED_SOURCE_STEP)
         return set_err(FX_ERR_INVALID_ARGUMENT, "source %d", params->source);
     const DevProblem &hp = c->h_probs[agent];
@@ -487,7 +475,7 @@ extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, co
     const size_t n1 = (size_t)std::max<int64_t>(q.n, 1);
     size_t nb = std::max<size_t>(FX_PREDPROB_SCRATCH_BYTES / per_cand / 64, 1) * 64;   // whole tiles
     nb = std::min(nb, (n1 + 63) / 64 * 64);
-    if ((rc = risk_stage(q, false, nullptr, nb))) return rc;
+    FX_TRY(risk_stage(q, false, nullptr, nb));
     FxRiskState *r = q.r;
     PredProbArgs a{};
     a.planes = q.planes, a.ld = q.ld, a.S = q.S, a.K = q.K, a.n = q.n, a.ids = q.d_ids(), a.flags = q.flags, a.rec = q.D(q.o_rec);
@@ -500,7 +488,7 @@ extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, co
     a.step = q.D(q.o_pstep), a.nb = (int64_t)nb;
     a.prob = q.D(q.o_pprob), a.prob_obs = out->prob_obs ? q.D(q.o_pobs) : nullptr, a.total = q.D(q.o_ptot);
     long long *d_best = reinterpret_cast<long long *>(q.base + q.o_pbest);
-    HIP_TRY(fx_launch_predprob(&a, d_best, r->e0, r->e1, c->stream));
+    HIP_TRY(fx_launch_predprob(&a, d_best, r->ev.e0, r->ev.e1, c->stream));
     const size_t nn = (size_t)q.n;
     HIP_TRY(q.down(out->prob, q.o_pprob, nn));
     HIP_TRY(q.down(out->prob_obs, q.o_pobs, (size_t)q.K * nn));
@@ -508,7 +496,7 @@ extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, co
     long long best[2] = {-1, 0};
     HIP_TRY(hipMemcpyAsync(best, d_best, sizeof(best), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&r->last_pp_ms, r->e0, r->e1));
+    HIP_TRY(hipEventElapsedTime(&r->last_pp_ms, r->ev.e0, r->ev.e1));
     // (sparse set: the arg-min ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
     if (q.sparse && best[0] >= 0) best[0] = (long long)q.set.ids[best[0]];
     if (out->best_index) *out->best_index = (int64_t)best[0];

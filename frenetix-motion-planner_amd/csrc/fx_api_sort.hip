@@ -2,7 +2,7 @@
 // rank (header: include/fxplan.h; kernels: fx_sort_kernel.h).  Nothing here runs in a plan step, and nothing a
 // plan step, the top-k, a sparse set or the risk passes wrote or published is touched: the pass reads the cost and flag planes and
 // writes its own block.
-#include "fx_context.h"
+#include "fx_pass.h"
 
 extern "C" hipError_t fx_launch_sort(const FxSortArgs *args, int n_agents, int64_t max_C, hipEvent_t ev_start, hipEvent_t ev_stop,
                                      hipStream_t stream);
@@ -18,40 +18,38 @@ struct FxSortOrder {
 };
 
 struct FxSortState {
-    char *d_buf = nullptr;      // grow-only block, every part 256-byte aligned
-    size_t cap = 0;
+    FxDeviceBlock block;        // every part 256-byte aligned (FxBlockLayout)
     int64_t total = 0;          // candidates (sum of the agents' leading dimensions) and tiles the layout below was made for
     int32_t tiles_max = 0, n_agents = 0;
-    FxSortArgs args;            // device pointers into d_buf
+    FxSortArgs args;            // device pointers into the block
     std::vector<FxSortAgent> agents;   // host copy of args.agents (uploaded when it changes: it must outlive the copy)
     bool agents_resident = false;      // the device holds `agents` as they are
     int64_t *h_counts = nullptr;       // pinned + mapped [max_agents][2]: the kernels write n_pool, n_nan straight to the host
     std::vector<FxSortOrder> orders;   // [max_agents]
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool timed = false;
+    FxEventPair ev;
 };
 
 void fx_sort_release(FxContext *c) {
     if (!c || !c->sort) return;
-    if (c->sort->d_buf) { (void)hipFree(c->sort->d_buf); c->dev_bytes -= (int64_t)c->sort->cap; }
+    c->sort->block.release(c);
     if (c->sort->h_counts) (void)hipHostFree(c->sort->h_counts);
-    if (c->sort->e0) (void)hipEventDestroy(c->sort->e0);
-    if (c->sort->e1) (void)hipEventDestroy(c->sort->e1);
+    c->sort->ev.release();
     delete c->sort;
     c->sort = nullptr;
 }
 
-// the planes are the ones the last evaluation wrote: no upload (clears `evaluated`) and no state update since
-static bool sort_inputs_current(const FxContext *c) { return c->evaluated && !c->probs_dirty && !(c->dirty_hi > c->dirty_lo); }
-
 static const FxSortOrder *valid_order(const FxContext *c, int agent) {
     if (!c->sort || agent < 0 || agent >= (int)c->sort->orders.size()) return nullptr;
     const FxSortOrder &o = c->sort->orders[agent];
-    return (o.step == c->n_steps && sort_inputs_current(c)) ? &o : nullptr;
+    return (o.step == c->n_steps && fx_inputs_current(c)) ? &o : nullptr;
 }
 
-// sort agents [agent0, agent0 + n) of the last step; everything is checked by the callers before this launches or writes
+// sort agents [agent0, agent0 + n) of the last step; the callers have checked their arguments, everything else is checked here
+// before this launches or writes
 static int sort_agents(FxContext *c, int agent0, int n, uint32_t require, uint32_t exclude, int64_t *n_pool, int64_t *n_nan) {
+    if (!fx_inputs_current(c))
+        return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
+    if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
     if (!c->sort) {
         c->sort = new FxSortState();
         c->sort->orders.resize((size_t)c->max_agents);
@@ -71,24 +69,19 @@ static int sort_agents(FxContext *c, int agent0, int n, uint32_t require, uint32
         HIP_TRY(hipHostGetDevicePointer(&dp, st->h_counts, 0));
         st->args.counts = reinterpret_cast<int64_t *>(dp);
     }
-    if (total != st->total || tiles_max != st->tiles_max || A != st->n_agents || !st->d_buf) {
+    if (total != st->total || tiles_max != st->tiles_max || A != st->n_agents || !st->block.p) {
         // another upload: a new layout, and no order of the old one is left
-        size_t off = 0;
-        auto take = [&off](size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 8), 256); return o; };
-        const size_t o_order = take(sizeof(int64_t) * total), o_k0 = take(sizeof(uint64_t) * total), o_k1 = take(sizeof(uint64_t) * total);
-        const size_t o_i0 = take(sizeof(uint32_t) * total), o_i1 = take(sizeof(uint32_t) * total);
-        const size_t o_hist = take(sizeof(uint32_t) * 256 * (size_t)tiles_max * A), o_dbase = take(sizeof(uint32_t) * 256 * A);
-        const size_t o_tc = take(sizeof(uint32_t) * 2 * (size_t)tiles_max * A);
-        const size_t o_ag = take(sizeof(FxSortAgent) * A);
+        FxBlockLayout lay;
+        const size_t o_order = lay.take(sizeof(int64_t) * total), o_k0 = lay.take(sizeof(uint64_t) * total), o_k1 = lay.take(sizeof(uint64_t) * total);
+        const size_t o_i0 = lay.take(sizeof(uint32_t) * total), o_i1 = lay.take(sizeof(uint32_t) * total);
+        const size_t o_hist = lay.take(sizeof(uint32_t) * 256 * (size_t)tiles_max * A), o_dbase = lay.take(sizeof(uint32_t) * 256 * A);
+        const size_t o_tc = lay.take(sizeof(uint32_t) * 2 * (size_t)tiles_max * A);
+        const size_t o_ag = lay.take(sizeof(FxSortAgent) * A);
         for (FxSortOrder &o : st->orders) o.step = -1;
-        if (off > st->cap) {
-            if (st->d_buf) HIP_TRY(hipStreamSynchronize(c->stream));
-            if (st->d_buf) { HIP_TRY(hipFree(st->d_buf)); c->dev_bytes -= (int64_t)st->cap; st->d_buf = nullptr; st->cap = 0; }
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&st->d_buf), off));
-            st->cap = off;
-            c->dev_bytes += (int64_t)off;
-        }
-        char *b = st->d_buf;
+        // (a block that grows is freed: what was queued on it runs out first; tail_work stays as it is)
+        if (lay.size() > st->block.cap && st->block.p) HIP_TRY(hipStreamSynchronize(c->stream));
+        FX_TRY(st->block.ensure(c, lay.size()));
+        char *b = st->block.p;
         FxSortArgs &g = st->args;
         g.order = reinterpret_cast<int64_t *>(b + o_order);
         g.key[0] = reinterpret_cast<unsigned long long *>(b + o_k0); g.key[1] = reinterpret_cast<unsigned long long *>(b + o_k1);
@@ -108,7 +101,7 @@ static int sort_agents(FxContext *c, int agent0, int n, uint32_t require, uint32
     }
     if (!same) {
         // (an earlier upload came from this host vector: it has landed before the vector is rewritten)
-        { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+        FX_TRY(fx_drain(c));
         for (int a = 0; a < A; a++) {
             const FxAgentSlot &sl = c->slots[a];
             st->agents[a] = FxSortAgent{c->d_cost + sl.cand_off, c->d_flags + sl.cand_off, sl.C, sl.cand_off};
@@ -118,17 +111,17 @@ static int sort_agents(FxContext *c, int agent0, int n, uint32_t require, uint32
     FxSortArgs g = st->args;
     g.require = require; g.exclude = exclude; g.agent0 = agent0; g.tiles_max = tiles_max;
     for (int a = agent0; a < agent0 + n; a++) st->orders[a].step = -1;   // from here on the previous orders of these agents are gone
-    if (!st->e0) { HIP_TRY(hipEventCreate(&st->e0)); HIP_TRY(hipEventCreate(&st->e1)); }
-    st->timed = false;
+    FX_TRY(st->ev.ensure());
+    st->ev.timed = false;
     if (!st->agents_resident) {
         HIP_TRY(hipMemcpyAsync(const_cast<FxSortAgent *>(g.agents), st->agents.data(), sizeof(FxSortAgent) * A, hipMemcpyHostToDevice, c->stream));
         st->agents_resident = true;
     }
     for (int a = agent0; a < agent0 + n; a++) st->h_counts[2 * a] = st->h_counts[2 * a + 1] = -1;   // (the stream is idle or behind a kernel boundary)
-    HIP_TRY(fx_launch_sort(&g, n, max_C, st->e0, st->e1, c->stream));
-    st->timed = true;
+    HIP_TRY(fx_launch_sort(&g, n, max_C, st->ev.e0, st->ev.e1, c->stream));
+    st->ev.timed = true;
     c->in_flight = true; c->tail_work = true;
-    { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+    FX_TRY(fx_drain(c));
     for (int a = agent0; a < agent0 + n; a++) {
         FxSortOrder &o = st->orders[a];
         o.n_pool = st->h_counts[2 * a]; o.n_nan = st->h_counts[2 * a + 1];
@@ -145,28 +138,19 @@ static int sort_agents(FxContext *c, int agent0, int n, uint32_t require, uint32
 extern "C" {
 
 int32_t fx_sort_candidates_agent(FxContext *c, int32_t agent, uint32_t require, uint32_t exclude, int64_t *n_pool, int64_t *n_nan) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     if (!n_pool || !n_nan) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_sort_candidates_agent: NULL argument");
-    if (!sort_inputs_current(c))
-        return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
-    if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
     return sort_agents(c, agent, 1, require, exclude, n_pool, n_nan);
 }
 
 int32_t fx_sort_candidates_batch(FxContext *c, uint32_t require, uint32_t exclude, int64_t *n_pool, int64_t *n_nan) {
-    int rc = check_agent(c, 0);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, 0));
     if (!n_pool || !n_nan) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_sort_candidates_batch: NULL argument");
-    if (!sort_inputs_current(c))
-        return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
-    if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
     return sort_agents(c, 0, c->n_agents, require, exclude, n_pool, n_nan);
 }
 
 int32_t fx_read_ranked_agent(FxContext *c, int32_t agent, int64_t first, int64_t n, int64_t *index, double *cost, uint32_t *flags) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     const FxSortOrder *o = valid_order(c, agent);
     if (!o) return set_err(FX_ERR_NOT_READY, "agent %d has no valid order (fx_sort_candidates_agent since the last evaluation)", agent);
     if (first < 0 || n < 0 || first > o->n_pool || n > o->n_pool - first)
@@ -186,19 +170,18 @@ int32_t fx_read_ranked_agent(FxContext *c, int32_t agent, int64_t first, int64_t
         HIP_TRY(fx_launch_sort_gather(d_order, n, c->d_cost + sl.cand_off, c->d_flags + sl.cand_off, sl.C, cost ? g_cost : nullptr,
                                       flags ? g_flags : nullptr, c->stream));
         c->in_flight = true; c->tail_work = true;
-        { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+        FX_TRY(fx_drain(c));
         if (cost) HIP_TRY(hipMemcpy(cost, g_cost, sizeof(double) * n, hipMemcpyDeviceToHost));
         if (flags) HIP_TRY(hipMemcpy(flags, g_flags, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
     } else {
-        { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+        FX_TRY(fx_drain(c));
     }
     HIP_TRY(hipMemcpy(index, d_order, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
     return FX_OK;
 }
 
 int32_t fx_sort_views(FxContext *c, int32_t agent, void **d_index, int64_t *n_pool) {
-    int rc = check_agent(c, agent);
-    if (rc) return rc;
+    FX_TRY(check_agent(c, agent));
     if (!d_index) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_sort_views: d_index is NULL");
     const FxSortOrder *o = valid_order(c, agent);
     if (!o) return set_err(FX_ERR_NOT_READY, "agent %d has no valid order (fx_sort_candidates_agent since the last evaluation)", agent);
@@ -208,14 +191,6 @@ int32_t fx_sort_views(FxContext *c, int32_t agent, void **d_index, int64_t *n_po
 }
 
 // device time of the context's last sort (events around its launch sequence), ms; -1 before the first
-double fx_last_sort_ms(FxContext *c) {
-    if (!c || !c->sort || !c->sort->timed) return -1.0;
-    float ms = -1.f;
-    if (hipEventSynchronize(c->sort->e1) != hipSuccess || hipEventElapsedTime(&ms, c->sort->e0, c->sort->e1) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0;
-    }
-    return (double)ms;
-}
+double fx_last_sort_ms(FxContext *c) { return (c && c->sort) ? c->sort->ev.elapsed_ms() : -1.0; }
 
 }  // extern "C"

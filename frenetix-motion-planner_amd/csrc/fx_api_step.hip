@@ -1,6 +1,6 @@
 // fx_api_step.hip -- the plan step through the C-ABI: upload, fx_evaluate (launch policy: fx_policy.h), results, state
 // updates, the winner package and the batched plan calls (header: include/fxplan.h; context: fx_context.h).
-#include "fx_context.h"
+#include "fx_pass.h"
 
 // the derived columns of planner.py:394-447 (_compute_trajectory_pair) behind the FX_NUM_PLANES planes of a package block: yaw rate by
 // backward differences of the heading, steering angle of the kinematic single-track model, heading shifted into
@@ -49,7 +49,7 @@ int32_t fx_upload_batch(FxContext *c, int32_t n_agents, const FxProblem *probs) 
     if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out (its stream may never drain): destroy it");
     HIP_TRY(hipSetDevice(c->device));
     if (c->in_flight) {  // the pinned staging block is about to be rewritten: earlier copies must have landed
-        { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+        FX_TRY(fx_drain(c));
         c->in_flight = false;
     }
     c->uploaded = c->evaluated = false;
@@ -92,7 +92,7 @@ int32_t fx_upload_batch(FxContext *c, int32_t n_agents, const FxProblem *probs) 
     if (pl.planes_bytes && (rc = ensure_planes(c, pl.planes_bytes))) return rc;
     if (pl.obs_part_n) {   // scratch of the obstacle kernel: tickets start (and are left) zeroed
         if (pl.obs_part_n > c->obs_part_cap || pl.obs_colm_n > c->obs_colm_cap) {
-            { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+            FX_TRY(fx_drain(c));
             if (c->d_obs_part) { (void)hipFree(c->d_obs_part); c->dev_bytes -= (int64_t)(sizeof(double) * c->obs_part_cap); }
             if (c->d_obs_colm) { (void)hipFree(c->d_obs_colm); c->dev_bytes -= (int64_t)(sizeof(unsigned long long) * c->obs_colm_cap); }
             c->d_obs_part = nullptr; c->d_obs_colm = nullptr;
@@ -321,10 +321,8 @@ int32_t fx_evaluate(FxContext *c) {
             HIP_TRY(fx_launch_eval_grid(c->d_probs, c->n_agents, pl.max_blocks, pl.block, pl.lds, pl.G, pl.any_bundle, pl.any_obst, pl.wpe,
                                         pl.wsplit, k0, k1, fuse, c->stream));
         else
-            HIP_TRY(fx_launch_eval(c->d_probs, c->n_agents, pl.max_blocks,
-                                   sizeof(double) * ((size_t)pl.M_max * FX_REF_FIELDS + FX_TP * (size_t)pl.S_max +
-                                                     (((size_t)pl.M_max + 1) & ~(size_t)1)) + pl.gen_rec_lds,
-                                   pl.G, pl.any_bundle, pl.any_obst, pl.any_extra, pl.wpe, k0, k1, fuse, c->stream));
+            HIP_TRY(fx_launch_eval(c->d_probs, c->n_agents, pl.max_blocks, fx_generic_lds(pl.M_max, pl.S_max, pl.gen_rec_lds), pl.G,
+                                   pl.any_bundle, pl.any_obst, pl.any_extra, pl.wpe, k0, k1, fuse, c->stream));
     }
     if (timed && !attached) HIP_TRY(hipEventRecord(ts->e_eval, c->stream));
     if (L.obstacle) {
@@ -407,7 +405,7 @@ int32_t fx_update_state(FxContext *c, int32_t agent, const FxStateUpdate *u) {
     if (agent < 0 || agent >= c->n_agents) return set_err(FX_ERR_INVALID_ARGUMENT, "agent %d out of range", agent);
     if (c->in_flight) {  // a copy out of the staging block may still be running: let it land before rewriting its source
         HIP_TRY(hipSetDevice(c->device));
-        { HIP_TRY(hipStreamSynchronize(c->stream)); c->tail_work = c->user_stream; }
+        FX_TRY(fx_drain(c));
         c->in_flight = false;
     }
     FxAgentSlot &sl = c->slots[agent];

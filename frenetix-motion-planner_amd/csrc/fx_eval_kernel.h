@@ -1,5 +1,28 @@
 // fx_eval_kernel.h -- the fused evaluation kernel (included by fx_kernels.hip).
 //
+// The fused Frenet sampling-and-evaluation pipeline for gfx950 (MI355X).
+// One lane evaluates one candidate trajectory end to end, streaming over the horizon:
+//   sampling index -> (T, v1, d1)                       reactive_planner.py:149-158 / sampling_matrix.py:85-121
+//   quartic / quintic coefficients (closed form)        polynomial_trajectory.py:293-343, :452-488
+//   s, s', s'', d, d', d'' on the reference time grid   reactive_planner.py:295-346
+//   Frenet -> Cartesian kinematics                      reactive_planner.py:389-478
+//   five kinematic constraints -> reason bits           reactive_planner.py:480-533
+//   (s, d) -> (x, y) along the reference polyline       utils_coordinate_system.py:263-270 (CCosy)
+//   partial costs, weighted sum                         partial_cost_functions.py, cost_function.py:78-91
+//   OBB-sum hull + SAT vs predicted obstacle hulls      planner.py:342-357, collision_check.py:110-200
+//   (cost, index) arg-min over the workgroup            trajectories.py:560 + planner.py:336-390
+//
+// Why lane-per-candidate: every quantity of step i depends on step i-1 of the same candidate (theta/kappa
+// finite differences, horizon extension, standstill carry), and nothing depends on another candidate.  A lane
+// that walks its own horizon needs no cross-lane traffic, all 64 lanes of a wave are busy for any horizon
+// length, and every SoA plane store is a 512-byte contiguous row segment (plane[p][step][candidate]).
+// Reference knots (64 B per knot, AoS) are staged once per workgroup in LDS -- the only divergent reads.
+// Everything indexed by (step) or (obstacle, step) is wave-uniform and comes in through scalar loads.
+//
+// FP64 throughout, compiled with -ffp-contract=off: the expression trees mirror the NumPy expressions of the
+// reference term by term (the CPU oracle does the same), so GPU and oracle differ only in libm (OCML vs glibc)
+// and in the order of the long cost sums (the device accumulates in step order, NumPy pairwise).
+//
 // Work decomposition.  A candidate's horizon of S samples is cut into G contiguous chunks ("parts") that are
 // walked by G adjacent lanes; G = 1 ... 32 is chosen on the host from the candidate count:
 //   * G = 1 -- one lane per candidate.  Zero redundancy; right once there are enough candidates to fill the

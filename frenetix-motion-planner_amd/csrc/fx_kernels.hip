@@ -1,26 +1,6 @@
-// fx_kernels.hip -- the fused Frenet sampling-and-evaluation pipeline for gfx950 (MI355X).
-//
-// One lane evaluates one candidate trajectory end to end, streaming over the horizon:
-//   sampling index -> (T, v1, d1)                       reactive_planner.py:149-158 / sampling_matrix.py:85-121
-//   quartic / quintic coefficients (closed form)        polynomial_trajectory.py:293-343, :452-488
-//   s, s', s'', d, d', d'' on the reference time grid   reactive_planner.py:295-346
-//   Frenet -> Cartesian kinematics                      reactive_planner.py:389-478
-//   five kinematic constraints -> reason bits           reactive_planner.py:480-533
-//   (s, d) -> (x, y) along the reference polyline       utils_coordinate_system.py:263-270 (CCosy)
-//   partial costs, weighted sum                         partial_cost_functions.py, cost_function.py:78-91
-//   OBB-sum hull + SAT vs predicted obstacle hulls      planner.py:342-357, collision_check.py:110-200
-//   (cost, index) arg-min over the workgroup            trajectories.py:560 + planner.py:336-390
-//
-// Why lane-per-candidate: every quantity of step i depends on step i-1 of the same candidate (theta/kappa
-// finite differences, horizon extension, standstill carry), and nothing depends on another candidate.  A lane
-// that walks its own horizon needs no cross-lane traffic, all 64 lanes of a wave are busy for any horizon
-// length, and every SoA plane store is a 512-byte contiguous row segment (plane[p][step][candidate]).
-// Reference knots (64 B per knot, AoS) are staged once per workgroup in LDS -- the only divergent reads.
-// Everything indexed by (step) or (obstacle, step) is wave-uniform and comes in through scalar loads.
-//
-// FP64 throughout, compiled with -ffp-contract=off: the expression trees mirror the NumPy expressions of the
-// reference term by term (the CPU oracle does the same), so GPU and oracle differ only in libm (OCML vs glibc)
-// and in the order of the long cost sums (the device accumulates in step order, NumPy pairwise).
+// fx_kernels.hip -- the one translation unit of libfxplan.so with device code: it includes every kernel family (fx_*_kernel.h,
+// fx_select.h) and holds their launchers (declared in fx_context.h, called by fx_api*.hip) and a few kernels too small for a header
+// of their own.  What runs when is decided by the callers (fx_policy.h); the evaluation pipeline is described in fx_eval_kernel.h.
 #include <hip/hip_ext.h>
 
 #include <atomic>
@@ -49,6 +29,23 @@ static inline int fx_device_slot() {
     int d = 0;
     if (hipGetDevice(&d) != hipSuccess || d < 0) d = 0;
     return d % FX_MAX_DEVICES;
+}
+
+// Let `Kernel` be launched with lds_bytes of dynamic LDS: above 48 KiB the limit has to be raised, PER DEVICE (the attribute is per
+// device; the call costs microseconds: once per size, not per launch).  The table holds the largest size each device has been
+// enabled for -- one table per kernel specialisation; relaxed atomics: two threads at worst both set the attribute.  set_to: the
+// size to enable instead of lds_bytes (a kernel whose largest size is known).
+template <auto Kernel>
+static hipError_t fx_allow_dynamic_lds(size_t lds_bytes, size_t set_to = 0) {
+    static std::atomic<size_t> lds_set_[FX_MAX_DEVICES];
+    std::atomic<size_t> &hw_ = lds_set_[fx_device_slot()];
+    if (lds_bytes > 48 * 1024 && lds_bytes > hw_.load(std::memory_order_relaxed)) {
+        const size_t bytes = set_to ? set_to : lds_bytes;
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+        hw_.store(bytes, std::memory_order_relaxed);
+    }
+    return hipSuccess;
 }
 
 #ifdef FX_CULL_STATS
@@ -93,251 +90,10 @@ extern "C" hipError_t fx_launch_package(const DevProblem *d_probs, int n_agents,
 
 #include "fx_select.h"   // fx_select_kernel
 
-// ---------------------------------------------------------------------------------------------------
-// Top-k: the k best selectable collision-free candidates in (cost, index) order (k <= 64).
-// Two small launches: FX_TOPK_SLICES workgroups per agent each extract the k best of a contiguous slice
-// (k rounds of arg-min with a strict lower bound, over 1/64 of the candidates), then one workgroup per agent
-// merges the 64 x k survivors.  Only the multi-GPU exchange and the host-side road-boundary walk need it.
-// ---------------------------------------------------------------------------------------------------
+// top-k: slices per agent, entries per lane of the one-wave kernels -- the sizes at which fx_launch_topk changes kernels
 #define FX_TOPK_SLICES 64
-
-__device__ __forceinline__ void block_argmin(double &bc, long long &bi, double *sc, long long *si) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double oc = __shfl_xor(bc, off);
-        const long long oi = __shfl_xor(bi, off);
-        if (oc < bc || (oc == bc && oi < bi)) { bc = oc; bi = oi; }
-    }
-    __syncthreads();
-    if (lane == 0) { sc[wave] = bc; si[wave] = bi; }
-    __syncthreads();
-    bc = sc[0]; bi = si[0];
-    for (int w = 1; w < nw; w++)
-        if (sc[w] < bc || (sc[w] == bc && si[w] < bi)) { bc = sc[w]; bi = si[w]; }
-}
-
-__global__ __launch_bounds__(256) void fx_topk_slice_kernel(const DevProblem *__restrict__ probs, int k, double *scr_cost,
-                                                            long long *scr_idx) {
-    __shared__ double sc[4];
-    __shared__ long long si[4];
-    const DevProblem &P = probs[blockIdx.y];
-    const int tid = threadIdx.x;
-    const int64_t per = (P.C + FX_TOPK_SLICES - 1) / FX_TOPK_SLICES;
-    const int64_t lo = (int64_t)blockIdx.x * per, hi = min(P.C, lo + per);
-    const FX_GLOBAL uint32_t *__restrict__ flags = as_global(P.flags);
-    const FX_GLOBAL double *__restrict__ cost = as_global(P.cost);
-    const long long NONE = 0x7fffffffffffffffLL;
-    double lb_c = -INFINITY;
-    long long lb_i = -1;
-    const size_t out = ((size_t)blockIdx.y * FX_TOPK_SLICES + blockIdx.x) * k;
-    for (int r = 0; r < k; r++) {
-        double bc = INFINITY;
-        long long bi = NONE;
-        for (int64_t g = lo + tid; g < hi; g += 256) {
-            const uint32_t f = flags[g];
-            if ((f & FX_FLAG_SELECTABLE) && !(f & (FX_FLAG_COLLISION | FX_FLAG_BOUNDARY))) {
-                const double c = cost[g];
-                const long long gg = (long long)(g + P.g_base);
-                const bool after = c > lb_c || (c == lb_c && gg > lb_i);
-                if (after && (c < bc || (c == bc && gg < bi))) { bc = c; bi = gg; }
-            }
-        }
-        block_argmin(bc, bi, sc, si);
-        const bool none = bi == NONE;
-        if (tid == 0) { scr_cost[out + r] = none ? INFINITY : bc; scr_idx[out + r] = none ? -1 : bi; }
-        if (none) { lb_c = INFINITY; lb_i = NONE; } else { lb_c = bc; lb_i = bi; }
-    }
-}
-
-__global__ __launch_bounds__(256) void fx_topk_merge_kernel(int k, const double *__restrict__ scr_cost,
-                                                            const long long *__restrict__ scr_idx, double *out_cost,
-                                                            long long *out_idx) {
-    __shared__ double sc[4];
-    __shared__ long long si[4];
-    const int tid = threadIdx.x;
-    const int n = FX_TOPK_SLICES * k;
-    const size_t base = (size_t)blockIdx.x * n;
-    const long long NONE = 0x7fffffffffffffffLL;
-    double lb_c = -INFINITY;
-    long long lb_i = -1;
-    for (int r = 0; r < k; r++) {
-        double bc = INFINITY;
-        long long bi = NONE;
-        for (int e = tid; e < n; e += 256) {
-            const long long gg = scr_idx[base + e];
-            if (gg >= 0) {
-                const double c = scr_cost[base + e];
-                const bool after = c > lb_c || (c == lb_c && gg > lb_i);
-                if (after && (c < bc || (c == bc && gg < bi))) { bc = c; bi = gg; }
-            }
-        }
-        block_argmin(bc, bi, sc, si);
-        const bool none = bi == NONE;
-        if (tid == 0) { out_cost[(size_t)blockIdx.x * k + r] = none ? INFINITY : bc; out_idx[(size_t)blockIdx.x * k + r] = none ? -1 : bi; }
-        if (none) { lb_c = INFINITY; lb_i = NONE; } else { lb_c = bc; lb_i = bi; }
-    }
-}
-
-// One-wave variants (slices / survivor sets of at most 64 x FX_TOPK_R entries: grids up to 131 072 candidates per agent, k <= 32):
-// ONE pass over memory into registers, then k rounds of a wave-level arg-min -- no workgroup barrier anywhere; every lane keeps
-// the minimum of its own entries and only the owner of a round's winner retires it and looks again.  The k block-wide
-// reductions of the general kernels above (two barriers each, eight workgroups per CU contending) cost 135 + 112 us per step for
-// config 5's 32 agents x k = 32; the (cost, index) order is the same.
-#define FX_TOPK_R 32   // entries per lane
-// order-preserving key of a (non-NaN, no negative zero) double
-__device__ __forceinline__ unsigned long long f64_key(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
-}
-
-// min over the wave of a 64-bit key, wave-uniform result: row shifts and row broadcasts of the vector unit's data-parallel
-// primitives on the two halves (no LDS crossbar: a __shfl_xor chain on 64-bit values costs ~3 000 cycles per reduction)
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-    unsigned hi = (unsigned)(v >> 32), lo = (unsigned)v;
-#define FX_DPP_MIN64(ctrl, rows)                                                                              \
-    {                                                                                                          \
-        const unsigned oh = (unsigned)__builtin_amdgcn_update_dpp((int)hi, (int)hi, ctrl, rows, 0xf, false);   \
-        const unsigned ol = (unsigned)__builtin_amdgcn_update_dpp((int)lo, (int)lo, ctrl, rows, 0xf, false);   \
-        const bool lt = oh < hi || (oh == hi && ol < lo);                                                      \
-        hi = lt ? oh : hi; lo = lt ? ol : lo;                                                                  \
-    }
-    FX_DPP_MIN64(0x111, 0xf);  // row_shr:1
-    FX_DPP_MIN64(0x112, 0xf);  // row_shr:2
-    FX_DPP_MIN64(0x114, 0xf);  // row_shr:4
-    FX_DPP_MIN64(0x118, 0xf);  // row_shr:8   -> lane 15 of every row holds the row's minimum
-    FX_DPP_MIN64(0x142, 0xa);  // row_bcast:15 into rows 1 and 3
-    FX_DPP_MIN64(0x143, 0xc);  // row_bcast:31 into rows 2 and 3
-#undef FX_DPP_MIN64
-    return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)hi, 63) << 32) | (unsigned)__builtin_amdgcn_readlane((int)lo, 63);
-}
-
-__device__ __forceinline__ long long readlane_i64(long long v, int lane) {
-    return (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)((unsigned long long)v >> 32), lane) << 32) |
-                       (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane));
-}
-
-// One round's winner over the wave: minimum cost over the lanes' own minima, the lowest `id` among the lanes that hold it.
-// Returns the owner lane (wave-uniform), -1 when no lane has anything left.
-__device__ __forceinline__ int wave_round_owner(const double mc, const bool have, const long long id) {
-    const unsigned long long key = have ? f64_key(mc) : ~0ULL;
-    const unsigned long long kmin = wave_min_u64(key);
-    unsigned long long tie = __builtin_amdgcn_ballot_w64(have && key == kmin);
-    if (tie == 0ULL) return -1;
-    int owner = __builtin_ctzll(tie);
-    tie &= tie - 1;
-    if (tie) {   // equal costs on several lanes (rare): the lowest index
-        long long bi = readlane_i64(id, owner);
-        while (tie) {
-            const int l = __builtin_ctzll(tie);
-            tie &= tie - 1;
-            const long long oi = readlane_i64(id, l);
-            if (oi < bi) { bi = oi; owner = l; }
-        }
-    }
-    return owner;
-}
-
-__global__ __launch_bounds__(64) void fx_topk_slice_wave_kernel(const DevProblem *__restrict__ probs, int k, double *scr_cost,
-                                                                long long *scr_idx) {
-    const DevProblem &P = probs[blockIdx.y];
-    const int lane = threadIdx.x;
-    const int64_t per = (P.C + FX_TOPK_SLICES - 1) / FX_TOPK_SLICES;
-    const int64_t lo = (int64_t)blockIdx.x * per, hi = min(P.C, lo + per);
-    const FX_GLOBAL uint32_t *__restrict__ flags = as_global(P.flags);
-    const FX_GLOBAL double *__restrict__ cost = as_global(P.cost);
-    // slot u of lane l holds candidate lo + l + 64 u: its cost, or NaN when it is not eligible (a NaN cost is never selected:
-    // the comparisons of the general kernel drop it the same way)
-    double c[FX_TOPK_R];
-#pragma unroll
-    for (int u = 0; u < FX_TOPK_R; u++) {
-        const int64_t g = lo + lane + (int64_t)u * 64;
-        c[u] = __builtin_nan("");
-        if (g < hi) {
-            const uint32_t f = flags[g];
-            const double cg = cost[g];
-            if ((f & FX_FLAG_SELECTABLE) && !(f & (FX_FLAG_COLLISION | FX_FLAG_BOUNDARY))) c[u] = cg + 0.0;   // (+ 0.0: no negative zero in the keys)
-        }
-    }
-    const size_t out = ((size_t)blockIdx.y * FX_TOPK_SLICES + blockIdx.x) * k;
-    // the lane's minimum is kept per group of eight slots: retiring an entry re-scans its group only (the rounds are bound by
-    // the instructions of that re-scan: 2 048 waves x k rounds)
-    double gm[FX_TOPK_R / 8];
-    int gu[FX_TOPK_R / 8];
-    auto scan_group = [&](auto Q) {
-        constexpr int q = decltype(Q)::value;
-        double m = INFINITY;
-        int mu_ = -1;
-#pragma unroll
-        for (int u = 8 * q; u < 8 * q + 8; u++)
-            if (c[u] < m || (mu_ < 0 && c[u] == c[u])) { m = c[u]; mu_ = u; }   // (an infinite cost is still a candidate)
-        gm[q] = m; gu[q] = mu_;
-    };
-    auto retire_in_group = [&](auto Q, int slot) {
-        constexpr int q = decltype(Q)::value;
-#pragma unroll
-        for (int u = 8 * q; u < 8 * q + 8; u++)
-            if (u == slot) c[u] = __builtin_nan("");
-        scan_group(Q);
-    };
-    static_assert(FX_TOPK_R == 32, "four groups of eight slots below");
-    scan_group(std::integral_constant<int, 0>{}); scan_group(std::integral_constant<int, 1>{});
-    scan_group(std::integral_constant<int, 2>{}); scan_group(std::integral_constant<int, 3>{});
-    for (int r = 0; r < k; r++) {
-        // first group that holds the smallest cost: slots grow with the group, so this is the lane's (cost, index) minimum
-        double mc = gm[0];
-        int mu = gu[0];
-#pragma unroll
-        for (int q = 1; q < FX_TOPK_R / 8; q++)
-            if (gu[q] >= 0 && (mu < 0 || gm[q] < mc)) { mc = gm[q]; mu = gu[q]; }
-        const long long id = (long long)(lo + lane + (int64_t)mu * 64 + P.g_base);
-        const int owner = wave_round_owner(mc, mu >= 0, id);
-        if (owner < 0) {
-            if (lane == 0) { scr_cost[out + r] = INFINITY; scr_idx[out + r] = -1; }
-            continue;
-        }
-        if (lane == owner) {   // publish, retire the entry, look again in its group (only this lane does anything here)
-            scr_cost[out + r] = mc; scr_idx[out + r] = id;
-            switch (mu >> 3) {
-            case 0: retire_in_group(std::integral_constant<int, 0>{}, mu); break;
-            case 1: retire_in_group(std::integral_constant<int, 1>{}, mu); break;
-            case 2: retire_in_group(std::integral_constant<int, 2>{}, mu); break;
-            default: retire_in_group(std::integral_constant<int, 3>{}, mu); break;
-            }
-        }
-    }
-}
-
-// Merge of the 64 slices' sorted lists: lane l walks slice l's list through a head pointer (the lists sit in LDS), one round per
-// output -- no rescans at all.
-__global__ __launch_bounds__(64) void fx_topk_merge_wave_kernel(int k, const double *__restrict__ scr_cost, const long long *__restrict__ scr_idx,
-                                                                double *out_cost, long long *out_idx) {
-    __shared__ double l_cost[FX_TOPK_SLICES * FX_TOPK_R];
-    __shared__ long long l_idx[FX_TOPK_SLICES * FX_TOPK_R];
-    const int lane = threadIdx.x;
-    const int n = FX_TOPK_SLICES * k;   // host: k <= FX_TOPK_R
-    const size_t base = (size_t)blockIdx.x * n;
-    for (int e = lane; e < n; e += 64) { l_cost[e] = scr_cost[base + e] + 0.0; l_idx[e] = scr_idx[base + e]; }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    int head = 0;
-    double mc = l_cost[lane * k];
-    long long mi = l_idx[lane * k];   // -1: the slice's list has ended
-    for (int r = 0; r < k; r++) {
-        const int owner = wave_round_owner(mc, mi >= 0, mi);
-        if (owner < 0) {
-            if (lane == 0) { out_cost[(size_t)blockIdx.x * k + r] = INFINITY; out_idx[(size_t)blockIdx.x * k + r] = -1; }
-            continue;
-        }
-        if (lane == owner) {
-            out_cost[(size_t)blockIdx.x * k + r] = mc; out_idx[(size_t)blockIdx.x * k + r] = mi;
-            head++;
-            mi = head < k ? l_idx[lane * k + head] : -1;
-            mc = head < k ? l_cost[lane * k + head] : INFINITY;
-        }
-    }
-}
+#define FX_TOPK_R 32
+#include "fx_topk_kernel.h"   // fx_topk_*_kernel
 
 // Copy a small device buffer (the all-gathered survivors) into pinned host memory and publish a sequence word:
 // the host polls instead of paying for a D2H copy + stream synchronisation.
@@ -409,16 +165,7 @@ extern "C" hipError_t fx_launch_eval(const DevProblem *d_probs, int n_agents, in
     dim3 grid(max_blocks, n_agents), block(FX_BLOCK);
 #define FX_LAUNCH(Gv, B, O, E, W)                                                                                \
     do {                                                                                                        \
-        /* largest dynamic LDS size this specialisation has been enabled for, PER DEVICE (the attribute is per device; the call */ \
-        /* costs microseconds: once per size, not per launch); relaxed atomics: two threads at worst both set the attribute */  \
-        static std::atomic<size_t> lds_set_[FX_MAX_DEVICES];                                                    \
-        std::atomic<size_t> &hw_ = lds_set_[fx_device_slot()];                                                  \
-        if (lds_bytes > 48 * 1024 && lds_bytes > hw_.load(std::memory_order_relaxed)) {                         \
-            hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&fx_eval_kernel<Gv, B, O, E, W>), \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);    \
-            if (e_ != hipSuccess) return e_;                                                                    \
-            hw_.store(lds_bytes, std::memory_order_relaxed);                                                    \
-        }                                                                                                       \
+        if (const hipError_t e_ = fx_allow_dynamic_lds<&fx_eval_kernel<Gv, B, O, E, W>>(lds_bytes); e_ != hipSuccess) return e_; \
         hipExtLaunchKernelGGL((fx_eval_kernel<Gv, B, O, E, W>), grid, block, lds_bytes, stream, ev_start, ev_stop, 0, d_probs, fuse); \
         return hipGetLastError();                                                                               \
     } while (0)
@@ -465,14 +212,7 @@ extern "C" hipError_t fx_launch_eval_grid(const DevProblem *d_probs, int n_agent
     dim3 grid(max_blocks, n_agents), block(block_size);
 #define FX_LAUNCH(Gv, B, O, W, WS)                                                                                 \
     do {                                                                                                          \
-        static std::atomic<size_t> lds_set_[FX_MAX_DEVICES];   /* per device, see fx_launch_eval */                 \
-        std::atomic<size_t> &hw_ = lds_set_[fx_device_slot()];                                                    \
-        if (lds_bytes > 48 * 1024 && lds_bytes > hw_.load(std::memory_order_relaxed)) {                           \
-            hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&fx_eval_grid_kernel<Gv, B, O, W, WS>), \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);      \
-            if (e_ != hipSuccess) return e_;                                                                      \
-            hw_.store(lds_bytes, std::memory_order_relaxed);                                                      \
-        }                                                                                                         \
+        if (const hipError_t e_ = fx_allow_dynamic_lds<&fx_eval_grid_kernel<Gv, B, O, W, WS>>(lds_bytes); e_ != hipSuccess) return e_; \
         hipExtLaunchKernelGGL((fx_eval_grid_kernel<Gv, B, O, W, WS>), grid, block, lds_bytes, stream, ev_start, ev_stop, 0, d_probs, fuse); \
         return hipGetLastError();                                                                                 \
     } while (0)
@@ -516,14 +256,7 @@ extern "C" hipError_t fx_launch_obstacle(const DevProblem *d_probs, int n_agents
 #define FX_LAUNCH(CHv)                                                                                                                \
     do {                                                                                                                            \
         if (wg_waves > 0) {                                                                                                         \
-            static std::atomic<size_t> lds_set_[FX_MAX_DEVICES];                                                                    \
-            std::atomic<size_t> &hw_ = lds_set_[fx_device_slot()];                                                                  \
-            if (lds_bytes > 48 * 1024 && lds_bytes > hw_.load(std::memory_order_relaxed)) {                                         \
-                hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&fxk::fx_obstacle_kernel<CHv, 4, true>),          \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                    \
-                if (e_ != hipSuccess) return e_;                                                                                    \
-                hw_.store(lds_bytes, std::memory_order_relaxed);                                                                    \
-            }                                                                                                                       \
+            if (const hipError_t e_ = fx_allow_dynamic_lds<&fxk::fx_obstacle_kernel<CHv, 4, true>>(lds_bytes); e_ != hipSuccess) return e_; \
             hipExtLaunchKernelGGL((fxk::fx_obstacle_kernel<CHv, 4, true>), dim3(max_tiles, n_agents), dim3(64 * wg_waves), lds_bytes, stream, \
                                   ev_start, ev_stop, 0, d_probs);                                                                   \
         } else {                                                                                                                    \
@@ -681,14 +414,7 @@ extern "C" hipError_t fx_launch_eval_list(const DevProblem *d_prob, const int64_
     const dim3 grid((unsigned)((n + FX_BLOCK - 1) / FX_BLOCK)), block(FX_BLOCK);
 #define FX_LAUNCH(O, E)                                                                                         \
     do {                                                                                                        \
-        static std::atomic<size_t> lds_set_[FX_MAX_DEVICES];   /* per device, see fx_launch_eval */               \
-        std::atomic<size_t> &hw_ = lds_set_[fx_device_slot()];                                                  \
-        if (lds_bytes > 48 * 1024 && lds_bytes > hw_.load(std::memory_order_relaxed)) {                         \
-            hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&fx_eval_list_kernel<O, E>),     \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);    \
-            if (e_ != hipSuccess) return e_;                                                                    \
-            hw_.store(lds_bytes, std::memory_order_relaxed);                                                    \
-        }                                                                                                       \
+        if (const hipError_t e_ = fx_allow_dynamic_lds<&fx_eval_list_kernel<O, E>>(lds_bytes); e_ != hipSuccess) return e_; \
         hipExtLaunchKernelGGL((fx_eval_list_kernel<O, E>), grid, block, lds_bytes, stream, ev_start, ev_stop, 0, d_prob, d_ids); \
         return hipGetLastError();                                                                               \
     } while (0)
@@ -708,14 +434,7 @@ extern "C" hipError_t fx_launch_sort(const FxSortArgs *args, int n_agents, int64
     if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
     if (max_C <= FX_SORT_SMALL_MAX) {
         const size_t lds_bytes = FX_SORT_SMALL_LDS(max_C);
-        static std::atomic<size_t> lds_set_[FX_MAX_DEVICES];   /* per device, see fx_launch_eval */
-        std::atomic<size_t> &hw_ = lds_set_[fx_device_slot()];
-        if (lds_bytes > 48 * 1024 && lds_bytes > hw_.load(std::memory_order_relaxed)) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&fx_sort_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)FX_SORT_SMALL_LDS(FX_SORT_SMALL_MAX));
-            if (e != hipSuccess) return e;
-            hw_.store(FX_SORT_SMALL_LDS(FX_SORT_SMALL_MAX), std::memory_order_relaxed);
-        }
+        if ((e = fx_allow_dynamic_lds<&fx_sort_small_kernel>(lds_bytes, FX_SORT_SMALL_LDS(FX_SORT_SMALL_MAX))) != hipSuccess) return e;
         hipLaunchKernelGGL(fx_sort_small_kernel, dim3(1, n_agents), dim3(FX_SORT_BLOCK), lds_bytes, stream, *args);
     } else {
         const dim3 tiles((unsigned)args->tiles_max, n_agents), one(1, n_agents), block(FX_SORT_BLOCK);

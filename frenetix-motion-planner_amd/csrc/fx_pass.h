@@ -1,0 +1,78 @@
+// fx_pass.h -- the host scaffold of the passes that run beside the plan step (fx_api_risk.hip, fx_api_sort.hip,
+// fx_api_materialise.hip, the read-back of fx_api_host.hip), each piece written once.  Nothing here launches a kernel.
+#pragma once
+
+#include "fx_context.h"
+
+#define FX_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+// The parts of one device block, every part 256-byte aligned and at least 8 bytes.  Pure: no HIP call (tests/policy_table.cpp).
+struct FxBlockLayout {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += align_up(std::max<size_t>(bytes, 8), 256); return o; }
+    size_t size() const { return off; }
+};
+
+// A grow-only device block: it grows to the largest call and never shrinks.  Whether the stream is drained before a block that
+// may still be read is freed is the caller's decision.
+struct FxDeviceBlock {
+    char *p = nullptr;
+    size_t cap = 0;   // bytes
+    int ensure(FxContext *c, size_t bytes) {
+        if (bytes <= cap) return FX_OK;
+        if (p) { HIP_TRY(hipFree(p)); c->dev_bytes -= (int64_t)cap; p = nullptr; cap = 0; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), bytes));
+        cap = bytes;
+        c->dev_bytes += (int64_t)bytes;
+        return FX_OK;
+    }
+    void release(FxContext *c) {
+        if (p) { (void)hipFree(p); c->dev_bytes -= (int64_t)cap; p = nullptr; cap = 0; }
+    }
+};
+
+// The events around a pass's launches, created on first use.  `timed`: they bracket a launch sequence that was enqueued whole.
+struct FxEventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool timed = false;
+    int ensure() {
+        if (!e0) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); }
+        return FX_OK;
+    }
+    // device time between the two, ms (waits for the second one); -1 before the first timed launch and on any failure
+    double elapsed_ms() const {
+        float ms = -1.f;
+        if (timed && (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) { (void)hipGetLastError(); ms = -1.f; }
+        return (double)ms;
+    }
+    void release() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        e0 = e1 = nullptr; timed = false;
+    }
+};
+
+// wait for everything on the context's stream; what stays unknown is what a caller's own stream may hold (FxContext.tail_work)
+inline int fx_drain(FxContext *c) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->tail_work = c->user_stream;
+    return FX_OK;
+}
+
+// the resident inputs and outputs are the last evaluation's: no upload (clears `evaluated`) and no state update since
+inline bool fx_inputs_current(const FxContext *c) { return c->evaluated && !c->probs_dirty && !(c->dirty_hi > c->dirty_lo); }
+
+// a caller's list of n candidates of an agent with C of them: the list is there (fx_check_id_list), every entry is a candidate
+// (fx_check_id_range); fx_check_ids is both, for the callers that have nothing to check in between
+inline int fx_check_id_list(int64_t n, const int64_t *ids, const char *count_name) {
+    return (n < 0 || (n > 0 && !ids)) ? set_err(FX_ERR_INVALID_ARGUMENT, "ids inconsistent (%s=%lld)", count_name, (long long)n) : FX_OK;
+}
+inline int fx_check_id_range(int64_t n, const int64_t *ids, int64_t C) {
+    for (int64_t j = 0; ids && j < n; j++)
+        if (ids[j] < 0 || ids[j] >= C) return set_err(FX_ERR_INVALID_ARGUMENT, "candidate %lld out of range", (long long)ids[j]);
+    return FX_OK;
+}
+inline int fx_check_ids(int64_t n, const int64_t *ids, int64_t C, const char *count_name) {
+    const int rc = fx_check_id_list(n, ids, count_name);
+    return rc ? rc : fx_check_id_range(n, ids, C);
+}

@@ -136,9 +136,13 @@ inline size_t fx_rec_lds_bytes(bool lane_split_with_stage, int S, int K) {
     const size_t rec_bytes = sizeof(double) * (size_t)S_rec_doubles(S, std::max(K, 0));
     return (lane_split_with_stage && K > 0 && K <= 64 && rec_bytes <= FX_REC_LDS_MAX) ? rec_bytes + 16 * (size_t)S : 0;
 }
-// what the generic kernel stages of an agent in LDS: the whole knot records (64 B each), the knots' arc lengths, the time table
-inline size_t fx_generic_base_lds(const FxProblem *p) {
-    return sizeof(double) * ((size_t)p->M * (FX_REF_FIELDS + 1) + 2 + FX_TP * ((size_t)p->N + 1));
+// what the generic kernel stages of an agent (M knots, S samples) in LDS: the whole knot records (64 B each), the knots' arc
+// lengths, the time table -- what must fit ...
+inline size_t fx_generic_base_lds(int M, int S) { return sizeof(double) * ((size_t)M * (FX_REF_FIELDS + 1) + 2 + FX_TP * (size_t)S); }
+inline size_t fx_generic_base_lds(const FxProblem *p) { return fx_generic_base_lds(p->M, p->N + 1); }
+// ... and what a launch of it (or of its list form) asks for: an even count of arc lengths, FxStepPlan.gen_rec_lds behind them
+inline size_t fx_generic_lds(int M, int S, size_t rec_lds) {
+    return sizeof(double) * ((size_t)M * FX_REF_FIELDS + FX_TP * (size_t)S + (((size_t)M + 1) & ~(size_t)1)) + rec_lds;
 }
 
 // dynamic LDS of a grid-kernel workgroup of blk lanes

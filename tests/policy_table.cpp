@@ -4,11 +4,16 @@
 // in:  per row  name | max_agents max_cand max_steps max_knots max_obs max_pred | G wpe variant block mapping obst_stage obst_CH fused
 //               store step_kernel step_kernel_CH | package last_live cap3 cap5 cap8 lds_pad obst_wg | n_agents, then per agent
 //               N M K P mode nT nV nD n_rows matrix shard_begin shard_count n_bound have_hull n_cost cost_id...
-// out: per row  name ok <16 numbers of fx_step_info_ex> <one-launch step: CH blocks lds>   or   name err <code> <message>
+// out: per row  name lds <per agent: M S rec base generic generic_rec>   the generic kernel's LDS: what must fit (fx_generic_base_lds),
+//                        what a launch asks for without and with rec bytes of staged records (fx_generic_lds), rec = fx_rec_lds_bytes
+//      then      name ok <16 numbers of fx_step_info_ex> <one-launch step: CH blocks lds>   or   name err <code> <message>
+//      then      name launch <M_max S_max gen_rec_lds> <fx_generic_lds of them>   for a row the generic kernel runs
+//      at the end, per part list:  #layout <n> <bytes...> <offsets...> <size>   an FxBlockLayout walk (csrc/fx_pass.h)
 #include <iostream>
 #include <string>
 #include <vector>
 
+#include "fx_pass.h"
 #include "fx_policy.h"
 
 int main() {
@@ -44,6 +49,14 @@ int main() {
             if (have_hull) { p.obs_hull = some_doubles; p.obs_nhull = some_ints; }
         }
         if (!std::cin) { std::cerr << "bad row " << name << "\n"; return 2; }
+        std::cout << name << " lds";
+        for (const FxProblem &p : probs) {
+            const int S = p.N + 1;
+            const size_t rec = fx_rec_lds_bytes(true, S, p.K);
+            std::cout << " " << p.M << " " << S << " " << rec << " " << fx_generic_base_lds(&p) << " " << fx_generic_lds(p.M, S, 0) << " "
+                      << fx_generic_lds(p.M, S, rec);
+        }
+        std::cout << "\n";
         std::vector<FxAgentPlan> rows(n_agents);
         FxStepPlan pl;
         pl.agents = rows.data();
@@ -62,6 +75,21 @@ int main() {
         std::cout << name << " ok";
         for (int i = 0; i < 16; i++) std::cout << " " << v[i];
         std::cout << " " << sz.CH << " " << sz.blocks << " " << sz.lds << "\n";
+        if (!pl.use_grid)
+            std::cout << name << " launch " << pl.M_max << " " << pl.S_max << " " << pl.gen_rec_lds << " "
+                      << fx_generic_lds(pl.M_max, pl.S_max, pl.gen_rec_lds) << "\n";
+    }
+    // the layout of a device block: the sizes either side of the 8-byte floor and of the 256-byte alignment, a large part, none
+    const std::vector<std::vector<size_t>> part_lists = {
+        {0, 1, 255, 256, 257}, {257, 256, 255, 1, 0}, {8, 7, 9, 511, 512, 513, 0, 0}, {1}, {(size_t)5 << 30, 3, 1000000007}, {}};
+    for (const std::vector<size_t> &parts : part_lists) {
+        FxBlockLayout lay;
+        std::vector<size_t> offs;
+        for (size_t b : parts) offs.push_back(lay.take(b));
+        std::cout << "#layout " << parts.size();
+        for (size_t b : parts) std::cout << " " << b;
+        for (size_t o : offs) std::cout << " " << o;
+        std::cout << " " << lay.size() << "\n";
     }
     return 0;
 }

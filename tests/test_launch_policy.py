@@ -4,7 +4,11 @@ MI355X at the commit named inside: sizes either side of every threshold, every f
 what real contexts answered: the 16 numbers of fx_step_info_ex, or the refusal's error code and message.
 
 The rows of the one-launch step depend on the device's occupancy answer in [11] - [13] and bit 16 of [15]; the recording keeps the
-three answers next to the row, and the second test holds the pure sizing function to the recorded (steps per item, workgroups, LDS)."""
+three answers next to the row, and the second test holds the pure sizing function to the recorded (steps per item, workgroups, LDS).
+
+The same program prints, for the rows' agents, the generic kernel's LDS sizes (fx_generic_base_lds, fx_generic_lds) -- held here to the
+closed forms the launch sites spelled out before the rules were written once -- and walks of the passes' block layout (csrc/fx_pass.h,
+FxBlockLayout), held to its rule: every part at a multiple of 256 bytes, at least 8 bytes long, none overlapping."""
 import importlib.util
 import json
 import os
@@ -51,16 +55,26 @@ def answers(tmp_path_factory):
     rows = recorded_rows()
     text = [row_text(r) for r in rows] + [row_text(r, second=True) for r in rows if "info_second" in r]
     out = subprocess.run([exe], input="\n".join(text) + "\n", capture_output=True, text=True, check=True).stdout
-    got = {}
+    got, lds, launch, layouts = {}, {}, {}, []
     for line in out.splitlines():
-        name, kind, rest = line.split(" ", 2)
-        if kind == "ok":
+        name, kind, rest = (line.split(" ", 2) + [""])[:3]
+        if name == "#layout":
+            v = [int(x) for x in line.split()[1:]]
+            assert len(v) == 2 * v[0] + 2
+            layouts.append((v[1:1 + v[0]], v[1 + v[0]:1 + 2 * v[0]], v[-1]))
+        elif kind == "lds":
+            v = [int(x) for x in rest.split()]
+            lds[name] = [tuple(v[i:i + 6]) for i in range(0, len(v), 6)]
+        elif kind == "launch":
+            launch[name] = tuple(int(x) for x in rest.split())
+        elif kind == "ok":
             v = [int(x) for x in rest.split()]
             got[name] = ("ok", v[:16], tuple(v[16:]))
         else:
             code, msg = rest.split(" ", 1)
             got[name] = ("err", int(code), msg)
-    assert len(got) == len(text)
+    assert len(got) == len(text) and len(lds) == len(text)
+    got["#lds"], got["#launch"], got["#layouts"] = lds, launch, layouts
     return got
 
 
@@ -103,3 +117,52 @@ def test_one_launch_step_sizing_as_recorded(answers):
             if name.endswith("#second") and (answers[name][0] != "ok" or answers[name][1] != info):   # (with the occupancy: all 16)
                 wrong.append((name, info, answers[name][1]))
     assert not wrong, wrong
+
+
+FX_REF_FIELDS, FX_TP = 8, 14   # csrc/fx_device.h: doubles per reference knot / per step of the time table in LDS
+
+
+def generic_launch_lds(M, S, rec):
+    """what fx_evaluate and fx_materialise_candidates_agent asked of the generic kernel's launch before fx_generic_lds"""
+    return 8 * (M * FX_REF_FIELDS + FX_TP * S + ((M + 1) & ~1)) + rec
+
+
+def generic_base_lds(M, S):
+    """what the upload and the list pass held against the 160 KiB of a CU (minus 1 KiB) before they shared fx_generic_base_lds"""
+    return (M * (FX_REF_FIELDS + 1) + 2 + FX_TP * S) * 8
+
+
+def test_generic_lds_closed_forms(answers):
+    rows = recorded_rows()
+    agents = 0
+    for r in rows:
+        per_agent = answers["#lds"][r["name"]]
+        assert len(per_agent) == len(r["agents"])
+        for a, (M, S, rec, base, generic, generic_rec) in zip(r["agents"], per_agent):
+            assert (M, S) == (a["M"], a["N"] + 1)
+            assert base == generic_base_lds(M, S), (r["name"], M, S)
+            assert generic == generic_launch_lds(M, S, 0) and generic_rec == generic_launch_lds(M, S, rec), (r["name"], M, S, rec)
+            agents += 1
+    launches = answers["#launch"]
+    for name, (M, S, rec, lds) in launches.items():
+        assert lds == generic_launch_lds(M, S, rec), name
+    # the table reaches what the forms depend on: odd and even knot counts, several horizons, launches with staged records
+    assert agents >= 150 and len(launches) >= 10 and any(v[2] > 0 for v in launches.values())
+    assert {M & 1 for per in answers["#lds"].values() for (M, *_r) in per} == {0, 1}
+    assert len({S for per in answers["#lds"].values() for (_m, S, *_r) in per}) >= 2
+    assert any(rec > 0 for per in answers["#lds"].values() for (_m, _s, rec, *_r) in per)
+
+
+def test_block_layout_rule(answers):
+    layouts = answers["#layouts"]
+    assert any(sorted(parts) == [0, 1, 255, 256, 257] for parts, _o, _t in layouts) and any(not parts for parts, _o, _t in layouts)
+    for parts, offs, total in layouts:
+        at = 0
+        for b, o in zip(parts, offs):
+            assert o % 256 == 0 and o == at, (parts, offs)      # aligned, and the first free byte: no overlap, no hole beyond the padding
+            room = -(-max(b, 8) // 256) * 256                    # at least 8 bytes, whole 256-byte units
+            assert room >= max(b, 8) and room - max(b, 8) < 256
+            at = o + room
+        assert total == at and total % 256 == 0, (parts, offs, total)
+        spans = sorted((o, o + max(b, 8)) for b, o in zip(parts, offs))
+        assert all(e0 <= s1 for (_s0, e0), (s1, _e1) in zip(spans, spans[1:])), (parts, offs)

@@ -1,4 +1,4 @@
-"""The four top-k kernels (csrc/fx_kernels.hip) on planes written by the test, at the sizes where fx_launch_topk changes kernels.
+"""The four top-k kernels (csrc/fx_topk_kernel.h; launcher: csrc/fx_kernels.hip) on planes written by the test, at the sizes where fx_launch_topk changes kernels.
 
 Slice stage: fx_topk_slice_wave_kernel while ceil(C / 64) <= 64 x 32, i.e. up to 131 072 candidates (every register slot of
 every lane full there), fx_topk_slice_kernel from 131 073 on.  Merge stage: fx_topk_merge_wave_kernel up to k = 32,

@@ -216,10 +216,8 @@ __device__ __forceinline__ void fx_eval_grid_body(const DevProblem *__restrict__
         }
         double cl3, cl4, cl5;
         lon_coeffs(P.lon_mode, s0, ss0, sss0, T, v1, 0.0, cl3, cl4, cl5);
-        int traj_len = (int)ceil((T + dt) / dt);
-        traj_len = traj_len > S ? S : (traj_len < 1 ? 1 : traj_len);
         rows[item] = make_lon_row(
-            i, S, M, dt, a_max, s0, ss0, .5 * sss0, cl3, cl4, cl5, traj_len, tp, rp_first, rp_last, guess_scale, want_trig,
+            i, S, M, dt, a_max, s0, ss0, .5 * sss0, cl3, cl4, cl5, traj_len_of(T, dt, S), tp, rp_first, rp_last, guess_scale, want_trig,
             [&](int k) {
                 const FX_GLOBAL double *q = kn + (int64_t)k * FX_REF_FIELDS;
                 Knot kt;
@@ -237,24 +235,10 @@ __device__ __forceinline__ void fx_eval_grid_body(const DevProblem *__restrict__
     double cl3, cl4, cl5;
     lon_coeffs(P.lon_mode, s0, ss0, sss0, T, v1, 0.0, cl3, cl4, cl5);
     double tau = T;
-    if (low_vel) {
-        const double cl0 = s0, cl1 = ss0, cl2 = .5 * sss0;
-        double t2 = T * T, t3 = t2 * T, t4 = t2 * t2, t5 = t3 * t2;  // evaluate_state_at_tau, polynomial_trajectory.py:213-216
-        double s_lon_goal = (cl0 + cl1 * T + cl2 * t2 + cl3 * t3 + cl4 * t4 + cl5 * t5) - s0;
-        if (s_lon_goal <= 0) s_lon_goal = T;
-        tau = s_lon_goal;
-    }
+    if (low_vel) tau = lon_goal_span(T, s0, s0, ss0, .5 * sss0, cl3, cl4, cl5);
     LatPoly L;
-    {
-        double T2 = tau * tau, T3 = T2 * tau, T4 = T3 * tau, T5 = T4 * tau;
-        double b0 = d1 - d0 - dd0 * tau - .5 * ddd0 * T2;
-        double b1 = 0.0 - dd0 - ddd0 * tau;
-        double b2 = 0.0 - ddd0;
-        L.set(d0, dd0, .5 * ddd0, fdiv(10.0 * b0 - 4.0 * b1 * tau + .5 * b2 * T2, T3),
-              fdiv(-15.0 * b0 + 7.0 * b1 * tau - b2 * T2, T4), fdiv(6.0 * b0 - 3.0 * b1 * tau + .5 * b2 * T2, T5));
-    }
-    int traj_len = (int)ceil((T + dt) / dt);
-    traj_len = traj_len > S ? S : (traj_len < 1 ? 1 : traj_len);
+    lat_quintic(L, tau, d0, dd0, ddd0, d1, 0.0, 0.0);
+    const int traj_len = traj_len_of(T, dt, S);
 
     if (bundle && active && part == 0) {
         FX_GLOBAL double *__restrict__ co = as_global(P.coeffs) + g;
@@ -267,12 +251,7 @@ __device__ __forceinline__ void fx_eval_grid_body(const DevProblem *__restrict__
         st_out(as_global(P.traj_len) + g, (int32_t)traj_len, wt);
     }
 
-    auto lat_eval = [&](int i, double u_lowvel, double &d, double &dv, double &da) {
-        LatU U;
-        if (low_vel) U.from_parameter(u_lowvel);
-        else U.from_table(tp + i * FX_TP);
-        L.eval(U, d, dv, da);
-    };
+    auto lat_eval = [&](int i, double u_lowvel, double &d, double &dv, double &da) { lat_at(L, low_vel, tp, i, u_lowvel, d, dv, da); };
     // lateral value the extension holds: d[traj_len-1] (reactive_planner.py:344)
     double d_ext, dv_u, da_u;
     lat_eval(traj_len - 1, my[traj_len - 1].u1, d_ext, dv_u, da_u);
@@ -289,7 +268,7 @@ __device__ __forceinline__ void fx_eval_grid_body(const DevProblem *__restrict__
     // The walk's wave-uniform doubles live in VGPRs (KV): the loop keeps ~50 lane masks and pointers in scalar registers and
     // the allocator otherwise parks these constants in VGPR lanes and reads them back (v_readlane) every step.
     auto KV = [](double x) { return WPE <= 3 ? fxk::uniform_to_vgpr(x) : x; };  // 256 VGPRs to spend only at two waves per SIMD
-    StepConst K;
+    StepConst K;   // (mirrors fill_step_const, fx_walk.h: called with KV as a wrapper it moved these kernels' code)
     K.dt = KV(dt); K.r_dt = KV(1.0 / dt); K.kappa_max = KV(P.veh.kappa_max); K.a_max = KV(a_max); K.v_switch = KV(P.veh.v_switch);
     K.av_switch = KV(a_max * P.veh.v_switch); K.v_des = KV(P.v_des); K.wb = KV(P.veh.wb_rear_axle); K.half_len = KV(P.veh.length / 2);
     K.half_wid = KV(P.veh.width / 2); K.S = S; K.half = S / 2; K.K = P.K; K.low_vel = low_vel; K.dbg = dbg;
@@ -304,7 +283,7 @@ __device__ __forceinline__ void fx_eval_grid_body(const DevProblem *__restrict__
     const FX_GLOBAL unsigned long long *__restrict__ obs_hmask = as_global(P.obs_hmask);
 
     StepCarry Cy;
-    Cy.th_prev = P.x0_orientation; Cy.kap_prev = 0.0; Cy.bx_prev = Cy.by_prev = Cy.ux_prev = Cy.uy_prev = 0.0;
+    Cy.reset(P.x0_orientation);
     // one step per lane: the 32 lanes of a candidate hold its steps in order, so ONE ballot of "my step moves" tells every lane
     // the last moving step in front of its own (a lane-by-lane scan back through the LDS rows cost the workgroups whose pair ends
     // in the extension at the slowest sampled velocity -- every step behind T stands still there -- 2 us: they were the last to take
@@ -345,9 +324,7 @@ __device__ __forceinline__ void fx_eval_grid_body(const DevProblem *__restrict__
         }
     }
     StepAcc A;
-    A.neg = A.acc_viol = A.collided = false;
-    A.step_reasons = 0; A.first_key = 0xffffffffu; A.fail_step = 0x7fffffff; A.bound_step = 0x7fffffff;
-    A.sum_abs_d = A.sum_voff = A.pred = A.d_end = A.v_end = 0.0;
+    A.reset();
     StepOut O;
     FX_GLOBAL double *__restrict__ planes = as_global(P.planes);
     const int64_t ps = (int64_t)S * ld;
@@ -417,7 +394,7 @@ __device__ __forceinline__ void fx_eval_grid_body(const DevProblem *__restrict__
     W.neg = A.neg; W.acc_viol = A.acc_viol; W.collided = A.collided;
     W.step_reasons = A.step_reasons; W.first_key = A.first_key; W.fail_step = A.fail_step; W.bound_step = A.bound_step;
     W.sum_abs_d = A.sum_abs_d; W.sum_voff = A.sum_voff; W.pred = A.pred; W.dto = 0.0; W.lane_off = 0.0; W.d_end = A.d_end; W.v_end = A.v_end;
-    W.cl3 = cl3; W.cl4 = cl4; W.cl5 = cl5; W.ct3 = L.c3; W.ct4 = L.c4; W.ct5 = L.c5;
+    W.set_poly(cl3, cl4, cl5, L);
     // wave split: the exchange block sits behind the rows in dynamic LDS
     double *xch = reinterpret_cast<double *>(rows + (size_t)n_pairs_max * S);
     finish_candidate<G, BUNDLE, OBST, false, WSPLIT, MEGA>(P, Pg, W, g, active, part, i_begin, i_end, bundle, do_collision, dbg, D,

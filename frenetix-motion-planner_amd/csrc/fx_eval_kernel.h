@@ -268,6 +268,9 @@ struct WalkResult {
     double sum_abs_d, sum_voff, pred, dto, lane_off, d_end, v_end;
     double cl3, cl4, cl5, ct3, ct4, ct5;
     Simpson sim_acc, sim_jerk, sim_orient, sim_path;
+    __device__ __forceinline__ void set_poly(double l3, double l4, double l5, const LatPoly &L) {   // the jerk costs' coefficients
+        cl3 = l3; cl4 = l4; cl5 = l5; ct3 = L.c3; ct4 = L.c4; ct5 = L.c5;
+    }
 };
 
 // Combine the G lanes of a candidate, assemble the flag word exactly as check_feasibility does, form the weighted
@@ -812,24 +815,10 @@ __global__ __launch_bounds__(FX_BLOCK, WPE) void fx_eval_kernel(const DevProblem
     lon_coeffs(P.has_matrix ? FX_LON_VELOCITY_KEEPING : P.lon_mode, s0, ss0, sss0, T, v1, a1, cl3, cl4, cl5);
     // ---- lateral quintic over time (high speed) or arclength (LOW_VEL_MODE), reactive_planner.py:161-171 ----
     double tau = T;
-    if (low_vel) {
-        double t2 = T * T, t3 = t2 * T, t4 = t2 * t2, t5 = t3 * t2;
-        double s_lon_goal = (cl0 + cl1 * T + cl2 * t2 + cl3 * t3 + cl4 * t4 + cl5 * t5) - s0;
-        if (s_lon_goal <= 0) s_lon_goal = T;
-        tau = s_lon_goal;
-    }
+    if (low_vel) tau = lon_goal_span(T, s0, cl0, cl1, cl2, cl3, cl4, cl5);
     LatPoly L;
-    {
-        double T2 = tau * tau, T3 = T2 * tau, T4 = T3 * tau, T5 = T4 * tau;
-        double b0 = d1 - d0 - dd0 * tau - .5 * ddd0 * T2;
-        double b1 = dd1 - dd0 - ddd0 * tau;
-        double b2 = ddd1 - ddd0;
-        L.set(d0, dd0, .5 * ddd0, fdiv(10.0 * b0 - 4.0 * b1 * tau + .5 * b2 * T2, T3),
-              fdiv(-15.0 * b0 + 7.0 * b1 * tau - b2 * T2, T4), fdiv(6.0 * b0 - 3.0 * b1 * tau + .5 * b2 * T2, T5));
-    }
-    // len(np.arange(0, T+dt, dt)) (reactive_planner.py:296,303), clamped to the horizon
-    int traj_len = (int)ceil((T + dt) / dt);
-    traj_len = traj_len > S ? S : (traj_len < 1 ? 1 : traj_len);
+    lat_quintic(L, tau, d0, dd0, ddd0, d1, dd1, ddd1);
+    const int traj_len = traj_len_of(T, dt, S);
 
     if (bundle && active && part == 0) {
         FX_GLOBAL double *__restrict__ co = as_global(P.coeffs) + g;
@@ -851,12 +840,7 @@ __global__ __launch_bounds__(FX_BLOCK, WPE) void fx_eval_kernel(const DevProblem
                             want_trig, [&](int k) { return knots[k]; }, [&](int k) { return rpos[k]; },
                             (P.mode & FX_MODE_PROJ_PSEUDO_NORMAL) != 0);
     };
-    auto lat_eval = [&](int i, double u_lowvel, double &d, double &dv, double &da) {
-        LatU U;
-        if (low_vel) U.from_parameter(u_lowvel);
-        else U.from_table(tp + i * FX_TP);
-        L.eval(U, d, dv, da);
-    };
+    auto lat_eval = [&](int i, double u_lowvel, double &d, double &dv, double &da) { lat_at(L, low_vel, tp, i, u_lowvel, d, dv, da); };
     // lateral value the extension holds: d[traj_len-1] (reactive_planner.py:344)
     double d_ext, dv_u, da_u;
     {
@@ -874,13 +858,8 @@ __global__ __launch_bounds__(FX_BLOCK, WPE) void fx_eval_kernel(const DevProblem
     const int i_first = (G > 1 && part > 0 && !neigh) ? i_begin - 1 : i_begin;
 
     StepConst K;
-    K.dt = dt; K.r_dt = 1.0 / dt; K.kappa_max = P.veh.kappa_max; K.a_max = a_max; K.v_switch = P.veh.v_switch;
-    K.av_switch = a_max * P.veh.v_switch; K.v_des = P.v_des; K.wb = P.veh.wb_rear_axle; K.half_len = P.veh.length / 2;
-    K.half_wid = P.veh.width / 2; K.S = S; K.half = S / 2; K.K = P.K; K.low_vel = low_vel; K.dbg = dbg;
-    K.do_collision = do_collision; K.store_wt = (P.mode & FX_MODE_INT_STORE_WT) != 0;
-    K.n_bound = (OBST && (P.mode & FX_MODE_ROAD_BOUNDARY)) ? P.n_bound : 0; K.bound_d_reach = P.bound_d_reach;
-    K.ox = P.hot_origin[0]; K.oy = P.hot_origin[1]; K.gap_margin = P.hot_gap_margin;
-    K.cull_r0 = (float)(1.41423 * sqrt(P.veh.length * P.veh.length + P.veh.width * P.veh.width) * 0.5);
+    fill_step_const<OBST>(K, P);
+    K.low_vel = low_vel; K.dbg = dbg; K.do_collision = do_collision; K.store_wt = (P.mode & FX_MODE_INT_STORE_WT) != 0;
     K.atan_k = nullptr;
     const BoundView Bv{as_global(P.bound_piece), as_global(P.bound_bin), as_global(P.bound_item)};
     const FX_GLOBAL double *__restrict__ obs_rec = as_global(P.obs_rec);
@@ -888,7 +867,7 @@ __global__ __launch_bounds__(FX_BLOCK, WPE) void fx_eval_kernel(const DevProblem
     const FX_GLOBAL unsigned long long *__restrict__ obs_hmask = as_global(P.obs_hmask);
 
     StepCarry Cy;
-    Cy.th_prev = P.x0_orientation; Cy.kap_prev = 0.0; Cy.bx_prev = Cy.by_prev = Cy.ux_prev = Cy.uy_prev = 0.0;
+    Cy.reset(P.x0_orientation);
     // one step per lane (32 lanes per candidate): the lanes ARE the candidate's steps, so one ballot of "my step moves" answers
     // every lane's "last moving step in front of mine" (fx_eval_grid_kernel.h has the same; a lane-by-lane scan made the
     // workgroups of rows that end in the extension at the slowest sampled velocity the last to take their ticket)
@@ -932,9 +911,7 @@ __global__ __launch_bounds__(FX_BLOCK, WPE) void fx_eval_kernel(const DevProblem
         }
     }
     StepAcc A;
-    A.neg = A.acc_viol = A.collided = false;
-    A.step_reasons = 0; A.first_key = 0xffffffffu; A.fail_step = 0x7fffffff; A.bound_step = 0x7fffffff;
-    A.sum_abs_d = A.sum_voff = A.pred = A.d_end = A.v_end = 0.0;
+    A.reset();
     StepOut O;
     Simpson sim_acc, sim_jerk, sim_orient, sim_path;
     double a_prev = 0.0, thcl_prev = 0.0, dto = 0.0;
@@ -984,7 +961,7 @@ __global__ __launch_bounds__(FX_BLOCK, WPE) void fx_eval_kernel(const DevProblem
     W.neg = A.neg; W.acc_viol = A.acc_viol; W.collided = A.collided;
     W.step_reasons = A.step_reasons; W.first_key = A.first_key; W.fail_step = A.fail_step; W.bound_step = A.bound_step;
     W.sum_abs_d = A.sum_abs_d; W.sum_voff = A.sum_voff; W.pred = A.pred; W.dto = dto; W.lane_off = lane_off; W.d_end = A.d_end; W.v_end = A.v_end;
-    W.cl3 = cl3; W.cl4 = cl4; W.cl5 = cl5; W.ct3 = L.c3; W.ct4 = L.c4; W.ct5 = L.c5;
+    W.set_poly(cl3, cl4, cl5, L);
     if (EXTRA) { W.sim_acc = sim_acc; W.sim_jerk = sim_jerk; W.sim_orient = sim_orient; W.sim_path = sim_path; }
     finish_candidate<G, BUNDLE, OBST, EXTRA>(P, Pg, W, g, active, part, i_begin, i_end, bundle, do_collision, dbg, D, red_cost,
                                              red_idx, red_cnt, fuse);

@@ -7,8 +7,11 @@
 // to column pos of the problem's arrays.  The problem is a CLONE of the agent's DevProblem whose outputs (planes, coeffs,
 // traj_len, costmap, cost, flags, bound_step) and selection scratch (counters, part_cost, part_idx) address the sparse block,
 // with C = n, ld = n rounded up to 64, the bundle and the cost map on, FX_MODE_INT_DEFER_OBST off: nothing of the step is
-// written.  The arithmetic is the step's own -- row_at / lat_eval / walk_step / finish_candidate of the generic kernel, the
-// obstacle stage fused into the walk -- so a row equals the row the generic kernel stores for that candidate bit for bit.
+// written.  The arithmetic is the step's own -- lon_coeffs, lon_goal_span, lat_quintic, traj_len_of, make_lon_row, lat_at,
+// fill_step_const, walk_step with the obstacle stage fused in and finish_candidate are the functions the generic kernel calls
+// (fx_walk.h, fx_eval_kernel.h) -- so a row equals the row the generic kernel stores for that candidate bit for bit.  Table
+// staging, candidate parameters, coefficient store, windowed terms and the accumulators' hand-over are still written out here
+// as in fx_eval_kernel.h: made a shared function, each of them changed the generic kernels' instruction text.
 //
 // The launch passes no fused selection (FuseArgs.host_result == nullptr): finish_candidate stores the outputs, adds to the
 // clone's own counters, writes the workgroup's arg-min partial into the clone's scratch and returns.  No tail, no ticket, no
@@ -69,7 +72,7 @@ __global__ __launch_bounds__(FX_BLOCK, 2) void fx_eval_list_kernel(const DevProb
     const double a_max = P.veh.a_max;
     const int64_t ld = P.ld;
 
-    // ---- candidate parameters, polynomials, horizon length: fx_eval_kernel.h, the same expressions ----
+    // ---- candidate parameters: fx_eval_kernel.h, the same expressions ----
     double T, s0, ss0, sss0, v1, a1, d0, dd0, ddd0, d1, dd1, ddd1;
     if (P.has_matrix) {
         const FX_GLOBAL double *__restrict__ r = as_global(P.matrix) + 13 * gg;
@@ -92,23 +95,10 @@ __global__ __launch_bounds__(FX_BLOCK, 2) void fx_eval_list_kernel(const DevProb
     double cl0 = s0, cl1 = ss0, cl2 = .5 * sss0, cl3, cl4, cl5;
     lon_coeffs(P.has_matrix ? FX_LON_VELOCITY_KEEPING : P.lon_mode, s0, ss0, sss0, T, v1, a1, cl3, cl4, cl5);
     double tau = T;
-    if (low_vel) {
-        double t2 = T * T, t3 = t2 * T, t4 = t2 * t2, t5 = t3 * t2;
-        double s_lon_goal = (cl0 + cl1 * T + cl2 * t2 + cl3 * t3 + cl4 * t4 + cl5 * t5) - s0;
-        if (s_lon_goal <= 0) s_lon_goal = T;
-        tau = s_lon_goal;
-    }
+    if (low_vel) tau = lon_goal_span(T, s0, cl0, cl1, cl2, cl3, cl4, cl5);
     LatPoly L;
-    {
-        double T2 = tau * tau, T3 = T2 * tau, T4 = T3 * tau, T5 = T4 * tau;
-        double b0 = d1 - d0 - dd0 * tau - .5 * ddd0 * T2;
-        double b1 = dd1 - dd0 - ddd0 * tau;
-        double b2 = ddd1 - ddd0;
-        L.set(d0, dd0, .5 * ddd0, fdiv(10.0 * b0 - 4.0 * b1 * tau + .5 * b2 * T2, T3),
-              fdiv(-15.0 * b0 + 7.0 * b1 * tau - b2 * T2, T4), fdiv(6.0 * b0 - 3.0 * b1 * tau + .5 * b2 * T2, T5));
-    }
-    int traj_len = (int)ceil((T + dt) / dt);
-    traj_len = traj_len > S ? S : (traj_len < 1 ? 1 : traj_len);
+    lat_quintic(L, tau, d0, dd0, ddd0, d1, dd1, ddd1);
+    const int traj_len = traj_len_of(T, dt, S);
 
     if (bundle && active) {
         FX_GLOBAL double *__restrict__ co = as_global(P.coeffs) + g;
@@ -126,12 +116,7 @@ __global__ __launch_bounds__(FX_BLOCK, 2) void fx_eval_list_kernel(const DevProb
                             want_trig, [&](int k) { return knots[k]; }, [&](int k) { return rpos[k]; },
                             (P.mode & FX_MODE_PROJ_PSEUDO_NORMAL) != 0);
     };
-    auto lat_eval = [&](int i, double u_lowvel, double &d, double &dv, double &da) {
-        LatU U;
-        if (low_vel) U.from_parameter(u_lowvel);
-        else U.from_table(tp + i * FX_TP);
-        L.eval(U, d, dv, da);
-    };
+    auto lat_eval = [&](int i, double u_lowvel, double &d, double &dv, double &da) { lat_at(L, low_vel, tp, i, u_lowvel, d, dv, da); };
     double d_ext, dv_u, da_u;
     {
         const LonRow rl = row_at(traj_len - 1);
@@ -139,13 +124,8 @@ __global__ __launch_bounds__(FX_BLOCK, 2) void fx_eval_list_kernel(const DevProb
     }
 
     StepConst K;
-    K.dt = dt; K.r_dt = 1.0 / dt; K.kappa_max = P.veh.kappa_max; K.a_max = a_max; K.v_switch = P.veh.v_switch;
-    K.av_switch = a_max * P.veh.v_switch; K.v_des = P.v_des; K.wb = P.veh.wb_rear_axle; K.half_len = P.veh.length / 2;
-    K.half_wid = P.veh.width / 2; K.S = S; K.half = S / 2; K.K = P.K; K.low_vel = low_vel; K.dbg = dbg;
-    K.do_collision = do_collision; K.store_wt = (P.mode & FX_MODE_INT_STORE_WT) != 0;
-    K.n_bound = (OBST && (P.mode & FX_MODE_ROAD_BOUNDARY)) ? P.n_bound : 0; K.bound_d_reach = P.bound_d_reach;
-    K.ox = P.hot_origin[0]; K.oy = P.hot_origin[1]; K.gap_margin = P.hot_gap_margin;
-    K.cull_r0 = (float)(1.41423 * sqrt(P.veh.length * P.veh.length + P.veh.width * P.veh.width) * 0.5);
+    fill_step_const<OBST>(K, P);
+    K.low_vel = low_vel; K.dbg = dbg; K.do_collision = do_collision; K.store_wt = (P.mode & FX_MODE_INT_STORE_WT) != 0;
     K.atan_k = nullptr;
     const BoundView Bv{as_global(P.bound_piece), as_global(P.bound_bin), as_global(P.bound_item)};
     const FX_GLOBAL double *__restrict__ obs_rec = as_global(P.obs_rec);
@@ -153,11 +133,9 @@ __global__ __launch_bounds__(FX_BLOCK, 2) void fx_eval_list_kernel(const DevProb
     const FX_GLOBAL unsigned long long *__restrict__ obs_hmask = as_global(P.obs_hmask);
 
     StepCarry Cy;
-    Cy.th_prev = P.x0_orientation; Cy.kap_prev = 0.0; Cy.bx_prev = Cy.by_prev = Cy.ux_prev = Cy.uy_prev = 0.0;
+    Cy.reset(P.x0_orientation);
     StepAcc A;
-    A.neg = A.acc_viol = A.collided = false;
-    A.step_reasons = 0; A.first_key = 0xffffffffu; A.fail_step = 0x7fffffff; A.bound_step = 0x7fffffff;
-    A.sum_abs_d = A.sum_voff = A.pred = A.d_end = A.v_end = 0.0;
+    A.reset();
     StepOut O;
     Simpson sim_acc, sim_jerk, sim_orient, sim_path;
     double a_prev = 0.0, thcl_prev = 0.0, dto = 0.0;
@@ -200,7 +178,7 @@ __global__ __launch_bounds__(FX_BLOCK, 2) void fx_eval_list_kernel(const DevProb
     W.neg = A.neg; W.acc_viol = A.acc_viol; W.collided = A.collided;
     W.step_reasons = A.step_reasons; W.first_key = A.first_key; W.fail_step = A.fail_step; W.bound_step = A.bound_step;
     W.sum_abs_d = A.sum_abs_d; W.sum_voff = A.sum_voff; W.pred = A.pred; W.dto = dto; W.lane_off = lane_off; W.d_end = A.d_end; W.v_end = A.v_end;
-    W.cl3 = cl3; W.cl4 = cl4; W.cl5 = cl5; W.ct3 = L.c3; W.ct4 = L.c4; W.ct5 = L.c5;
+    W.set_poly(cl3, cl4, cl5, L);
     if (EXTRA) { W.sim_acc = sim_acc; W.sim_jerk = sim_jerk; W.sim_orient = sim_orient; W.sim_path = sim_path; }
     const FuseArgs no_fuse{nullptr, 0ULL, nullptr, 0};   // no fused selection, no tail: the outputs and the clone's own scratch only
     finish_candidate<1, true, OBST, EXTRA>(P, Pg, W, g, active, 0, 0, S, bundle, do_collision, dbg, D, red_cost, red_idx, red_cnt, no_fuse);

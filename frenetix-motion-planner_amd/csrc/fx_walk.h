@@ -284,6 +284,46 @@ struct LatPoly {
     }
 };
 
+// ---- a candidate's polynomials and horizon: written once and called by the generic, the grid and the list kernel, which is why a
+// ---- candidate's coefficients are the same bits whichever of them walks it.  (The helpers are the ones that leave every kernel's
+// ---- instruction text as it was with the block written out: tools/isa/compare_isa.py, profiles/eval_helpers/.)
+
+// len(np.arange(0, T+dt, dt)) (reactive_planner.py:296,303), clamped to the horizon
+__device__ __forceinline__ int traj_len_of(double T, double dt, int S) {
+    const int traj_len = (int)ceil((T + dt) / dt);
+    return traj_len > S ? S : (traj_len < 1 ? 1 : traj_len);
+}
+
+// LOW_VEL_MODE span of the lateral quintic (reactive_planner.py:161-171): the arc length the longitudinal polynomial covers in T
+// (evaluate_state_at_tau, polynomial_trajectory.py:213-216), T where that is not positive.  At high speed the span is T itself: the
+// caller branches on the mode (the branch inside the helper moved the kernels' code).
+__device__ __forceinline__ double lon_goal_span(double T, double s0, double cl0, double cl1, double cl2, double cl3, double cl4, double cl5) {
+    double t2 = T * T, t3 = t2 * T, t4 = t2 * t2, t5 = t3 * t2;
+    double s_lon_goal = (cl0 + cl1 * T + cl2 * t2 + cl3 * t3 + cl4 * t4 + cl5 * t5) - s0;
+    if (s_lon_goal <= 0) s_lon_goal = T;
+    return s_lon_goal;
+}
+
+// lateral quintic from (d0, dd0, ddd0) to (d1, dd1, ddd1) over tau (reactive_planner.py:158-171; closed form of the reference's
+// solve, polynomial_trajectory.py:293-343).  On the sampling grid the end state is (d1, 0, 0).
+__device__ __forceinline__ void lat_quintic(LatPoly &L, double tau, double d0, double dd0, double ddd0, double d1, double dd1, double ddd1) {
+    double T2 = tau * tau, T3 = T2 * tau, T4 = T3 * tau, T5 = T4 * tau;
+    double b0 = d1 - d0 - dd0 * tau - .5 * ddd0 * T2;
+    double b1 = dd1 - dd0 - ddd0 * tau;
+    double b2 = ddd1 - ddd0;
+    L.set(d0, dd0, .5 * ddd0, fdiv(10.0 * b0 - 4.0 * b1 * tau + .5 * b2 * T2, T3),
+          fdiv(-15.0 * b0 + 7.0 * b1 * tau - b2 * T2, T4), fdiv(6.0 * b0 - 3.0 * b1 * tau + .5 * b2 * T2, T5));
+}
+
+// lateral position, velocity, acceleration at step i: over the step's time (the table row) or, LOW_VEL_MODE, over u = s - s0
+__device__ __forceinline__ void lat_at(const LatPoly &L, bool low_vel, const double *tp, int i, double u_lowvel, double &d, double &dv,
+                                       double &da) {
+    LatU U;
+    if (low_vel) U.from_parameter(u_lowvel);
+    else U.from_table(tp + i * FX_TP);
+    L.eval(U, d, dv, da);
+}
+
 // a 64-bit value known to be wave-uniform, moved to scalar registers
 __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {
     return (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v & 0xffffffffu)) |
@@ -306,6 +346,9 @@ struct StepConst {  // wave-uniform constants of the walk
 struct StepCarry {  // per-lane state carried from step to step
     double th_prev, kap_prev;
     double bx_prev, by_prev, ux_prev, uy_prev;
+    __device__ __forceinline__ void reset(double theta0) {   // in front of step 0: the ego's heading
+        th_prev = theta0; kap_prev = 0.0; bx_prev = by_prev = ux_prev = uy_prev = 0.0;
+    }
 };
 
 struct StepAcc {  // per-lane accumulators over the emitted steps
@@ -314,7 +357,26 @@ struct StepAcc {  // per-lane accumulators over the emitted steps
     int fail_step;
     int bound_step;  // first emitted step whose footprint meets the road boundary, INT_MAX if none
     double sum_abs_d, sum_voff, pred, d_end, v_end;
+    __device__ __forceinline__ void reset() {
+        neg = acc_viol = collided = false;
+        step_reasons = 0; first_key = 0xffffffffu; fail_step = 0x7fffffff; bound_step = 0x7fffffff;
+        sum_abs_d = sum_voff = pred = d_end = v_end = 0.0;
+    }
 };
+
+// The walk's numeric constants from the agent's problem (the generic and the list kernel).  The flags -- low_vel, dbg, do_collision,
+// store_wt -- and atan_k are the caller's to set: with the flags inside, the helper moved the generic kernels' code.
+template <bool OBST>
+__device__ __forceinline__ void fill_step_const(StepConst &K, const ProblemRegs &P) {
+    const double dt = P.dt, a_max = P.veh.a_max;
+    const int S = P.S;
+    K.dt = dt; K.r_dt = 1.0 / dt; K.kappa_max = P.veh.kappa_max; K.a_max = a_max; K.v_switch = P.veh.v_switch;
+    K.av_switch = a_max * P.veh.v_switch; K.v_des = P.v_des; K.wb = P.veh.wb_rear_axle; K.half_len = P.veh.length / 2;
+    K.half_wid = P.veh.width / 2; K.S = S; K.half = S / 2; K.K = P.K;
+    K.n_bound = (OBST && (P.mode & FX_MODE_ROAD_BOUNDARY)) ? P.n_bound : 0; K.bound_d_reach = P.bound_d_reach;
+    K.ox = P.hot_origin[0]; K.oy = P.hot_origin[1]; K.gap_margin = P.hot_gap_margin;
+    K.cull_r0 = (float)(1.41423 * sqrt(P.veh.length * P.veh.length + P.veh.width * P.veh.width) * 0.5);
+}
 
 struct StepOut {  // per-step values the windowed (EXTRA) costs of the generic kernel need
     double a, v, th_cl, x, y;

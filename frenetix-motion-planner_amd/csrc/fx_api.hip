@@ -4,7 +4,7 @@
 // step is ONE H2D copy, (b) the per-candidate outputs (cost, flags, cost map, SoA bundle), (c) a pinned
 // read-back block for the counters/winner, so a plan step is ONE small D2H copy.  All work is enqueued on the
 // context's HIP stream; nothing synchronises until fx_finish().
-#include "fx_context.h"
+#include "fx_pass.h"
 
 thread_local char g_err[512] = "";
 
@@ -42,6 +42,7 @@ int32_t fx_device_count(int32_t *count) {
 
 int32_t fx_create_batch(FxContext **out, int32_t device, int32_t max_agents, int64_t max_candidates_total,
                         int32_t max_steps, int32_t max_ref_knots, int32_t max_obstacles, int32_t max_pred_steps) {
+    if (out) *out = nullptr;   // and it stays NULL unless everything below succeeds: the owners give back what a failed create had built
     if (!out || max_candidates_total < 1 || max_steps < 1 || max_steps + 1 > FX_MAX_SAMPLES || max_ref_knots < 2 ||
         max_agents < 1 || max_obstacles < 0 || max_pred_steps < 0)
         return set_err(FX_ERR_INVALID_ARGUMENT, "fx_create: bad capacity arguments");
@@ -52,91 +53,77 @@ int32_t fx_create_batch(FxContext **out, int32_t device, int32_t max_agents, int
     }
     if (device < 0 || device >= ndev) return set_err(FX_ERR_INVALID_ARGUMENT, "device %d out of range (%d devices)", device, ndev);
     HIP_TRY(hipSetDevice(device));
-    FxContext *c = new (std::nothrow) FxContext();
+    std::unique_ptr<FxContext> ctx(new (std::nothrow) FxContext());
+    FxContext *c = ctx.get();
     if (!c) return set_err(FX_ERR_HIP, "out of host memory");
     c->device = device;
     c->caps = fx_caps_of(max_agents, max_candidates_total, max_steps, max_ref_knots, max_obstacles, max_pred_steps);
     c->max_agents = max_agents;
-    *out = c;
     {   // FX_STREAM_PRIORITY=low|high: experiments with two contexts sharing the device (tools/ns_two_streams.py)
         const char *pr = getenv("FX_STREAM_PRIORITY");
         int least = 0, greatest = 0;
-        if (pr && *pr && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-            HIP_TRY(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, pr[0] == 'l' ? least : greatest));
-        else
-            HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+        const bool with_priority = pr && *pr && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest;
+        const int priority = pr && pr[0] == 'l' ? least : greatest;
+        FX_TRY(c->stream.create(with_priority ? &priority : nullptr));
     }
-    c->own_stream = true;
-    for (auto &t : c->ring) {
-        HIP_TRY(hipEventCreate(&t.e0));
-        HIP_TRY(hipEventCreate(&t.e_eval));
-        HIP_TRY(hipEventCreate(&t.e_end));
-        HIP_TRY(hipEventCreate(&t.e_obs0));
-        HIP_TRY(hipEventCreate(&t.e_obs1));
-    }
+    for (auto &t : c->ring)
+        for (FxEvent *e : {&t.e0, &t.e_eval, &t.e_end, &t.e_obs0, &t.e_obs1}) FX_TRY(e->create());
     const int S = max_steps + 1;
-    const int64_t total_ld = c->caps.total_ld;
-    c->in_bytes = (size_t)max_agents * input_bytes_for(0, S, max_ref_knots, max_obstacles, c->caps.max_pred, false) +
+    const size_t total_ld = (size_t)c->caps.total_ld, A = (size_t)max_agents;
+    const unsigned mapped = hipHostMallocMapped | hipHostMallocCoherent;
+    c->in_bytes = A * input_bytes_for(0, S, max_ref_knots, max_obstacles, c->caps.max_pred, false) +
                   align_up(sizeof(double) * 13 * (size_t)max_candidates_total, 256) + 4096;
-    c->probs_bytes = align_up(sizeof(DevProblem) * (size_t)max_agents, 256);
+    c->probs_bytes = align_up(sizeof(DevProblem) * A, 256);
     c->in_bytes += c->probs_bytes;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_in), c->in_bytes, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_in_dev), c->h_in, 0));
+    FX_TRY(c->h_in.alloc(c->in_bytes, hipHostMallocMapped));
     if (const char *sm = getenv("FX_STAGE")) c->stage_mode = !strcmp(sm, "dma") ? 1 : (!strcmp(sm, "kernel") ? 2 : (!strcmp(sm, "bar") ? 3 : 0));
     if (const char *of = getenv("FX_OBST_STAGE")) c->force.obst_stage = std::max(0, std::min(2, atoi(of)));   // experiments: fx_set_obstacle_stage's first argument
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_in), c->in_bytes));
-    c->dev_bytes += (int64_t)c->in_bytes;
+    FX_TRY(c->d_in.alloc(c->in_bytes));
     if (c->stage_mode == 3) {   // opt-in (see probe_host_writes)
         c->bar_ok = probe_host_writes(c, device, c->d_in, c->in_bytes);
         if (!c->bar_ok)
             return set_err(FX_ERR_HIP, "FX_STAGE=bar: the device memory of GPU %d is not host-writable from this process, has no HDP flush "
                            "register, or a kernel did not see a rewritten line", device);
     }
-    c->h_probs = reinterpret_cast<DevProblem *>(c->h_in);
-    c->d_probs = reinterpret_cast<DevProblem *>(c->d_in);
-    int rc;
-    if ((rc = dev_alloc(c, &c->d_cost, total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_cost_tail, total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_flags, total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_costmap, (size_t)FX_NUM_COSTS * total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_coeffs, (size_t)FX_COEFF_ROWS * total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_trajlen, total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_bstep, total_ld))) return rc;
-    if ((rc = dev_alloc(c, &c->d_part_cost, c->caps.max_blocks_total))) return rc;
-    if ((rc = dev_alloc(c, &c->d_part_idx, c->caps.max_blocks_total))) return rc;
-    if ((rc = dev_alloc(c, &c->d_counters, (size_t)max_agents * FX_CNT_COUNT))) return rc;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_counters), sizeof(unsigned long long) * max_agents * (FX_CNT_COUNT + 1),
-                          hipHostMallocMapped | hipHostMallocCoherent));
-    memset(c->h_counters, 0, sizeof(unsigned long long) * max_agents * (FX_CNT_COUNT + 1));
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_counters_dev), c->h_counters, 0));
+    c->h_probs = reinterpret_cast<DevProblem *>(c->h_in.get());
+    c->d_probs = reinterpret_cast<DevProblem *>(c->d_in.get());
+    FX_TRY(c->d_cost.alloc(total_ld));
+    FX_TRY(c->d_cost_tail.alloc(total_ld));
+    FX_TRY(c->d_flags.alloc(total_ld));
+    FX_TRY(c->d_costmap.alloc((size_t)FX_NUM_COSTS * total_ld));
+    FX_TRY(c->d_coeffs.alloc((size_t)FX_COEFF_ROWS * total_ld));
+    FX_TRY(c->d_trajlen.alloc(total_ld));
+    FX_TRY(c->d_bstep.alloc(total_ld));
+    FX_TRY(c->d_part_cost.alloc(c->caps.max_blocks_total));
+    FX_TRY(c->d_part_idx.alloc(c->caps.max_blocks_total));
+    FX_TRY(c->d_counters.alloc(A * FX_CNT_COUNT));
+    FX_TRY(c->h_counters.alloc(A * (FX_CNT_COUNT + 1), mapped));
+    memset(c->h_counters, 0, sizeof(unsigned long long) * A * (FX_CNT_COUNT + 1));
     // ON THE CONTEXT'S STREAM: hipMemset on device memory runs on the null stream and may return before it has executed, and
     // a non-blocking stream does not wait for the null stream -- on a busy GPU (a second process) the zeroing landed behind the
     // first step's counter atomics and the step published zeros (tests/test_soak_parity.py, once in a few hundred contexts)
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(unsigned long long) * max_agents * FX_CNT_COUNT, c->stream));
-    if ((rc = dev_alloc(c, &c->d_bar, 2 * 16 * 65))) return rc;   // (two barrier blocks: fx_step_kernel.h, FX_BAR_WORDS)
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(unsigned long long) * A * FX_CNT_COUNT, c->stream));
+    FX_TRY(c->d_bar.alloc(2 * 16 * 65));   // (two barrier blocks: fx_step_kernel.h, FX_BAR_WORDS)
     HIP_TRY(hipMemsetAsync(c->d_bar, 0, sizeof(unsigned long long) * 2 * 16 * 65, c->stream));
     if (const char *e = getenv("FX_STEP_KERNEL")) c->force.step_kernel = atoi(e) ? 2 : 1;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_pub), sizeof(double) * (FX_PUB_MAX + 1), hipHostMallocMapped | hipHostMallocCoherent));
+    FX_TRY(c->h_pub.alloc(FX_PUB_MAX + 1, mapped));
     memset(c->h_pub, 0, sizeof(double) * (FX_PUB_MAX + 1));
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_pub_dev), c->h_pub, 0));
-    if ((rc = dev_alloc(c, &c->d_topk_cost, (size_t)max_agents * 64))) return rc;
-    if ((rc = dev_alloc(c, &c->d_topk_idx, (size_t)max_agents * 64))) return rc;
-    if ((rc = dev_alloc(c, &c->d_topk_scr_cost, (size_t)max_agents * 64 * 64))) return rc;
-    if ((rc = dev_alloc(c, &c->d_topk_scr_idx, (size_t)max_agents * 64 * 64))) return rc;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_topk_cost), sizeof(double) * max_agents * 64, hipHostMallocDefault));
+    FX_TRY(c->d_topk_cost.alloc(A * 64));
+    FX_TRY(c->d_topk_idx.alloc(A * 64));
+    FX_TRY(c->d_topk_scr_cost.alloc(A * 64 * 64));
+    FX_TRY(c->d_topk_scr_idx.alloc(A * 64 * 64));
+    FX_TRY(c->h_topk_cost.alloc(A * 64, hipHostMallocDefault));
     c->pkg_plane_rows = FX_NUM_PLANES * (max_steps + 1);
     c->pkg_stride = (c->pkg_plane_rows + FX_PKG_TAIL + 1 + 7) & ~7;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_pkg), sizeof(double) * (size_t)max_agents * c->pkg_stride,
-                          hipHostMallocMapped | hipHostMallocCoherent));
-    memset(c->h_pkg, 0, sizeof(double) * (size_t)max_agents * c->pkg_stride);
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&c->h_pkg_dev), c->h_pkg, 0));
-    if ((rc = dev_alloc(c, &c->d_winner_own, (size_t)max_agents * 2))) return rc;
-    c->h_cand_doubles = (size_t)FX_NUM_PLANES * (max_steps + 1) + FX_COEFF_ROWS + FX_NUM_COSTS + 4;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_cand), sizeof(double) * c->h_cand_doubles, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_topk_idx), sizeof(long long) * max_agents * 64, hipHostMallocDefault));
+    FX_TRY(c->h_pkg.alloc(A * c->pkg_stride, mapped));
+    memset(c->h_pkg, 0, sizeof(double) * A * c->pkg_stride);
+    FX_TRY(c->d_winner_own.alloc(A * 2));
+    FX_TRY(c->h_cand.alloc((size_t)FX_NUM_PLANES * (max_steps + 1) + FX_COEFF_ROWS + FX_NUM_COSTS + 4, hipHostMallocDefault));
+    FX_TRY(c->h_topk_idx.alloc(A * 64, hipHostMallocDefault));
     c->slots.resize(max_agents);
     c->plan_rows.resize(max_agents);
     c->plan.agents = c->plan_rows.data();
+    *out = ctx.release();
     return FX_OK;
 }
 
@@ -152,37 +139,8 @@ int32_t fx_destroy(FxContext *c) {
     if (c->timed_out) return FX_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void *dev[] = {c->d_in, c->d_cost, c->d_cost_tail, c->d_flags, c->d_costmap, c->d_coeffs, c->d_trajlen, c->d_planes,
-                   c->d_part_cost, c->d_part_idx, c->d_counters, c->d_topk_cost, c->d_topk_idx, c->d_topk_scr_cost,
-                   c->d_topk_scr_idx};
-    for (void *p : dev) if (p) (void)hipFree(p);
-    fx_risk_release(c);
-    fx_sparse_release(c);
-    fx_sort_release(c);
-    if (c->d_bstep) (void)hipFree(c->d_bstep);
-    if (c->d_cands) (void)hipFree(c->d_cands);
-    if (c->h_cands) (void)hipHostFree(c->h_cands);
-    if (c->d_obs_part) (void)hipFree(c->d_obs_part);
-    if (c->d_obs_colm) (void)hipFree(c->d_obs_colm);
-    if (c->d_obs_ticket) (void)hipFree(c->d_obs_ticket);
-    if (c->d_obs_list) (void)hipFree(c->d_obs_list);
-    if (c->d_bar) (void)hipFree(c->d_bar);
-    if (c->d_bound) (void)hipFree(c->d_bound);
-    if (c->h_bound) (void)hipHostFree(c->h_bound);
     if (c->comm) (void)fx_comm_destroy(c);
-    if (c->d_winner_own) (void)hipFree(c->d_winner_own);
-    if (c->d_xsend) (void)hipFree(c->d_xsend);
-    void *host[] = {c->h_in, c->h_counters, c->h_topk_cost, c->h_topk_idx, c->h_pub, c->h_cand, c->h_pkg};
-    for (void *p : host) if (p) (void)hipHostFree(p);
-    for (auto &t : c->ring) {
-        if (t.e0) (void)hipEventDestroy(t.e0);
-        if (t.e_eval) (void)hipEventDestroy(t.e_eval);
-        if (t.e_end) (void)hipEventDestroy(t.e_end);
-        if (t.e_obs0) (void)hipEventDestroy(t.e_obs0);
-        if (t.e_obs1) (void)hipEventDestroy(t.e_obs1);
-    }
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // every member gives back what it holds (fx_owner.h), the stream last
     return FX_OK;
 }
 
@@ -194,8 +152,8 @@ int32_t fx_publish(FxContext *c, const void *d_src, int32_t n) {
     HIP_TRY(hipSetDevice(c->device));
     c->pub_seq++;
     c->pub_n = n;
-    HIP_TRY(fx_launch_publish(reinterpret_cast<const double *>(d_src), n, c->h_pub_dev,
-                              reinterpret_cast<unsigned long long *>(c->h_pub_dev + FX_PUB_MAX), c->pub_seq, c->stream));
+    HIP_TRY(fx_launch_publish(reinterpret_cast<const double *>(d_src), n, c->h_pub.dev,
+                              reinterpret_cast<unsigned long long *>(c->h_pub.dev + FX_PUB_MAX), c->pub_seq, c->stream));
     c->in_flight = true; c->tail_work = true;
     return FX_OK;
 }
@@ -261,9 +219,7 @@ int32_t fx_set_tuning(FxContext *c, int32_t lanes_per_candidate, int32_t waves_p
 
 int32_t fx_set_stream(FxContext *c, void *hip_stream) {
     if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
-    if (c->own_stream && c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    c->stream = reinterpret_cast<hipStream_t>(hip_stream);
-    c->own_stream = false;
+    c->stream.borrow(reinterpret_cast<hipStream_t>(hip_stream));
     c->user_stream = c->tail_work = true;   // (whatever else the caller queues on it may read the arena: no host writes, ever)
     return FX_OK;
 }

@@ -1,6 +1,6 @@
 // fx_api_exchange.hip -- the survivor exchange inside the library: RCCL bound at run time, one all-gather per step (header:
 // include/fxplan.h; context: fx_context.h).
-#include "fx_context.h"
+#include "fx_pass.h"
 
 extern "C" {
 
@@ -75,17 +75,9 @@ int32_t fx_comm_init(FxContext *c, const uint8_t *id128, int32_t rank, int32_t w
     HIP_TRY(hipSetDevice(c->device));
     // everything that can fail locally comes BEFORE the collective call
     const size_t need = (size_t)world * c->max_agents * 2;
-    if (c->d_gather && c->gather_cap < need) {   // (left by an earlier communicator of this context)
-        (void)hipFree(c->d_gather);
-        c->dev_bytes -= (int64_t)(sizeof(double) * c->gather_cap);
-        c->d_gather = nullptr; c->gather_cap = 0;
-    }
-    if (!c->d_gather) {
-        if ((rc = dev_alloc(c, &c->d_gather, need))) return rc;
-        c->gather_cap = need;
-    }
-    if (!c->d_winner_own && (rc = dev_alloc(c, &c->d_winner_own, (size_t)c->max_agents * 2))) return rc;
-    if (!c->d_xsend && (rc = dev_alloc(c, &c->d_xsend, (size_t)c->max_agents * 2 * 64))) return rc;
+    FX_TRY(c->d_gather.ensure(need));   // (an earlier communicator of this context may have left a smaller one)
+    if (!c->d_winner_own) FX_TRY(c->d_winner_own.alloc((size_t)c->max_agents * 2));
+    if (!c->d_xsend) FX_TRY(c->d_xsend.alloc((size_t)c->max_agents * 2 * 64));
     // ncclCommInitRank is a blocking collective without a time bound of its own: a peer that never arrives (or a fabric that
     // never answers) would hold this thread forever.  It runs on a helper thread; this one waits for it with the context's time
     // bound and, past it, gives the communicator up (the helper is left behind, detached, with its state) -- the caller falls
@@ -155,7 +147,7 @@ int32_t fx_comm_destroy(FxContext *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)rccl()->CommDestroy(c->comm);
     c->comm = nullptr;
-    if (c->d_gather) { (void)hipFree(c->d_gather); c->d_gather = nullptr; c->gather_cap = 0; }
+    c->d_gather.release();
     return FX_OK;
 }
 
@@ -188,12 +180,12 @@ int32_t fx_set_exchange_mode(FxContext *c, int32_t mode) {
     c->exchange_mode = mode;
     return FX_OK;
 }
-static double *exchange_recv(FxContext *c) { return c->exchange_mode == 1 ? c->h_pub_dev : c->d_gather; }
+static double *exchange_recv(FxContext *c) { return c->exchange_mode == 1 ? c->h_pub.dev : c->d_gather; }
 static int exchange_signal(FxContext *c, int32_t total) {
     if (c->exchange_mode != 1) return fx_publish(c, c->d_gather, total);
     c->pub_seq++;
     c->pub_n = total;
-    HIP_TRY(hipStreamWriteValue64(c->stream, c->h_pub_dev + FX_PUB_MAX, c->pub_seq, 0));
+    HIP_TRY(hipStreamWriteValue64(c->stream, c->h_pub.dev + FX_PUB_MAX, c->pub_seq, 0));
     c->in_flight = true; c->tail_work = true;
     return FX_OK;
 }
@@ -266,12 +258,8 @@ int32_t fx_step_exchange_topk(FxContext *c, int32_t k, FxResult *res, double *co
     auto keep = [&](int rc) { if (rc && !rc_local) { rc_local = rc; memcpy(err_local, g_err, sizeof(err_local)); } };
     auto keep_hip = [&](hipError_t e, const char *what) { if (e != hipSuccess) keep(set_err(FX_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e))); };
     keep_hip(hipSetDevice(c->device), "hipSetDevice");
-    if (total > c->gather_cap) {   // (a function of (communicator, k) as well; a failed allocation leaves the old buffer in place)
-        double *bigger = nullptr;
-        if (hipStreamSynchronize(c->stream) == hipSuccess && hipMalloc(reinterpret_cast<void **>(&bigger), sizeof(double) * (size_t)FX_PUB_MAX) == hipSuccess) {
-            if (c->d_gather) { (void)hipFree(c->d_gather); c->dev_bytes -= (int64_t)(sizeof(double) * c->gather_cap); }
-            c->d_gather = bigger; c->gather_cap = FX_PUB_MAX; c->dev_bytes += (int64_t)(sizeof(double) * (size_t)FX_PUB_MAX);
-        } else {
+    if (total > c->d_gather.size()) {   // (a function of (communicator, k) as well)
+        if (hipStreamSynchronize(c->stream) != hipSuccess || c->d_gather.ensure(FX_PUB_MAX)) {
             (void)hipGetLastError();
             // without a receive buffer of the agreed size this rank cannot take part: the one failure that cannot be carried
             // through the collective (its peers run into their time bound)

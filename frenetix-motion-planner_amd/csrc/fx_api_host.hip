@@ -217,7 +217,7 @@ int32_t fx_read_candidate_agent(FxContext *c, int32_t agent, int64_t index, doub
     double *h_co = hp + n_pl, *h_rc = h_co + FX_COEFF_ROWS, *h_c = h_rc + FX_NUM_COSTS;
     int32_t *h_tl = reinterpret_cast<int32_t *>(h_c + 1);
     uint32_t *h_fl = reinterpret_cast<uint32_t *>(h_c + 2);
-    if (n_pl + FX_COEFF_ROWS + FX_NUM_COSTS + 4 > c->h_cand_doubles) return set_err(FX_ERR_CAPACITY, "candidate staging block too small");
+    if (n_pl + FX_COEFF_ROWS + FX_NUM_COSTS + 4 > c->h_cand.size()) return set_err(FX_ERR_CAPACITY, "candidate staging block too small");
     if (planes)
         HIP_TRY(hipMemcpy2DAsync(hp, sizeof(double), c->h_probs[agent].planes + index, sizeof(double) * s.ld, sizeof(double), n_pl,
                                  hipMemcpyDeviceToHost, c->stream));
@@ -247,13 +247,10 @@ int32_t fx_read_candidate_agent(FxContext *c, int32_t agent, int64_t index, doub
 // the list and set ga.parts.
 int fx_gather_rows(FxContext *c, const GatherArgs &ga, int64_t n, const int64_t *ids, double *planes, double *coeffs13, int32_t *traj_len,
                    double *raw_costs, double *cost, uint32_t *flags, int32_t *boundary_step) {
-    int rc;
     if (n == 0) return FX_OK;
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->d_cands) {
-        if (!c->h_cands) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_cands), FX_READ_CHUNK_BYTES, hipHostMallocDefault));
-        if ((rc = dev_alloc(c, &c->d_cands, (size_t)FX_READ_CHUNK_BYTES))) return rc;
-    }
+    FX_TRY(c->h_cands.ensure(FX_READ_CHUNK_BYTES, hipHostMallocDefault));
+    FX_TRY(c->d_cands.ensure(FX_READ_CHUNK_BYTES));
     const int S = ga.S, n_cost = ga.n_cost;
     const size_t n_pl = (size_t)FX_NUM_PLANES * S;
     const size_t W = (size_t)FX_GATHER_WORDS(S, n_cost);
@@ -262,10 +259,10 @@ int fx_gather_rows(FxContext *c, const GatherArgs &ga, int64_t n, const int64_t 
     if (m_max < 1) return set_err(FX_ERR_CAPACITY, "candidate record larger than the read-back chunk");
     for (int64_t at = 0; at < n; at += m_max) {
         const int64_t m = std::min(m_max, n - at);
-        int64_t *h_ids = reinterpret_cast<int64_t *>(c->h_cands);
-        int64_t *d_ids = reinterpret_cast<int64_t *>(c->d_cands);
-        const unsigned long long *h_rec = reinterpret_cast<const unsigned long long *>(c->h_cands) + m_max;
-        unsigned long long *d_rec = reinterpret_cast<unsigned long long *>(c->d_cands) + m_max;
+        int64_t *h_ids = reinterpret_cast<int64_t *>(c->h_cands.get());
+        int64_t *d_ids = reinterpret_cast<int64_t *>(c->d_cands.get());
+        const unsigned long long *h_rec = reinterpret_cast<const unsigned long long *>(c->h_cands.get()) + m_max;
+        unsigned long long *d_rec = reinterpret_cast<unsigned long long *>(c->d_cands.get()) + m_max;
         memcpy(h_ids, ids + at, sizeof(int64_t) * m);
         HIP_TRY(hipMemcpyAsync(d_ids, h_ids, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(fx_launch_gather_candidates(&ga, d_ids, m, d_rec, c->stream));
@@ -411,15 +408,14 @@ int32_t fx_build_obstacle_hulls(int32_t n_pred, const double *pos, const double 
 // self-test hook: atan / sin / cos of the device math kernels for n host values (synchronous)
 int32_t fx_math_selftest(int32_t n, const double *x, double *atan_out, double *sin_out, double *cos_out) {
     if (n < 1 || !x || !atan_out || !sin_out || !cos_out) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_math_selftest: bad argument");
-    double *d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(double) * 4 * n));
+    FxDeviceArray<double> d;   // (no account: a temporary of this call)
+    FX_TRY(d.alloc((size_t)4 * n));
     HIP_TRY(hipMemcpy(d, x, sizeof(double) * n, hipMemcpyHostToDevice));
     HIP_TRY(fx_launch_math_test(n, d, d + n, d + 2 * n, d + 3 * n, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(atan_out, d + n, sizeof(double) * n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(sin_out, d + 2 * n, sizeof(double) * n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(cos_out, d + 3 * n, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d));
     return FX_OK;
 }
 
@@ -445,8 +441,8 @@ int32_t fx_device_selftest(int32_t op, int32_t n, const double *const *in, doubl
             if (!(std::fabs(in[0][i]) <= FX_SELFTEST_WRAP_MAX))
                 return set_err(FX_ERR_INVALID_ARGUMENT, "fx_device_selftest: wrap_pm_2pi input %d is not finite or beyond %g", i,
                                FX_SELFTEST_WRAP_MAX);
-    double *d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(double) * total));
+    FxDeviceArray<double> d;   // (no account: a temporary of this call)
+    FX_TRY(d.alloc(total));
     SelftestArgs a = {};
     double *p = d;
     hipError_t e = hipSuccess;
@@ -459,9 +455,7 @@ int32_t fx_device_selftest(int32_t op, int32_t n, const double *const *in, doubl
     if (e == hipSuccess) e = fx_launch_selftest(op, n, &a, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     for (int k = 0; k < sh.n_out && e == hipSuccess; k++) e = hipMemcpy(out[k], a.out[k], sizeof(double) * n, hipMemcpyDeviceToHost);
-    const hipError_t ef = hipFree(d);
     HIP_TRY(e);
-    HIP_TRY(ef);
     return FX_OK;
 }
 

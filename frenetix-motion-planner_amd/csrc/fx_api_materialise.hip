@@ -8,6 +8,7 @@
 // One agent's set.  `ids` is kept ascending and de-duplicated: positions are monotone in the candidate index, so an arg-min over
 // positions with ties to the lower position is the arg-min over candidates with ties to the lower index.
 struct FxSparseSet {
+    explicit FxSparseSet(FxContext *c) : block(&c->dev_bytes) {}
     std::vector<int64_t> ids;
     long long step = -1;      // FxContext.n_steps when the set was made: the next evaluation ends it
     FxDeviceBlock block;      // every part 256-byte aligned (FxBlockLayout)
@@ -21,13 +22,7 @@ struct FxSparseState {
     FxEventPair ev;   // attached to the last list-kernel launch (fx_last_materialise_ms)
 };
 
-void fx_sparse_release(FxContext *c) {
-    if (!c || !c->sparse) return;
-    for (FxSparseSet &s : c->sparse->agents) s.block.release(c);
-    c->sparse->ev.release();
-    delete c->sparse;
-    c->sparse = nullptr;
-}
+void fx_sparse_release(FxSparseState *s) { delete s; }
 
 bool fx_sparse_view(FxContext *c, int32_t agent, FxSparseView *v) {
     if (!c || !c->sparse || agent < 0 || agent >= (int)c->sparse->agents.size()) return false;
@@ -36,13 +31,13 @@ bool fx_sparse_view(FxContext *c, int32_t agent, FxSparseView *v) {
     v->ids = s.ids.data();
     v->n = (int64_t)s.ids.size();
     v->ld = s.ld;
-    v->planes = reinterpret_cast<const double *>(s.block.p + s.o_planes);
-    v->coeffs = reinterpret_cast<const double *>(s.block.p + s.o_coeffs);
-    v->costmap = reinterpret_cast<const double *>(s.block.p + s.o_costmap);
-    v->cost = reinterpret_cast<const double *>(s.block.p + s.o_cost);
-    v->flags = reinterpret_cast<const uint32_t *>(s.block.p + s.o_flags);
-    v->traj_len = reinterpret_cast<const int32_t *>(s.block.p + s.o_trajlen);
-    v->bound_step = reinterpret_cast<const int32_t *>(s.block.p + s.o_bstep);
+    v->planes = reinterpret_cast<const double *>(s.block + s.o_planes);
+    v->coeffs = reinterpret_cast<const double *>(s.block + s.o_coeffs);
+    v->costmap = reinterpret_cast<const double *>(s.block + s.o_costmap);
+    v->cost = reinterpret_cast<const double *>(s.block + s.o_cost);
+    v->flags = reinterpret_cast<const uint32_t *>(s.block + s.o_flags);
+    v->traj_len = reinterpret_cast<const int32_t *>(s.block + s.o_trajlen);
+    v->bound_step = reinterpret_cast<const int32_t *>(s.block + s.o_bstep);
     return true;
 }
 
@@ -65,8 +60,8 @@ int32_t fx_materialise_candidates_agent(FxContext *c, int32_t agent, int64_t n, 
     if (!fx_inputs_current(c))
         return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): the re-walk would use another state");
     if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
-    if (!c->sparse) c->sparse = new FxSparseState();
-    if ((int)c->sparse->agents.size() < c->max_agents) c->sparse->agents.resize(c->max_agents);
+    if (!c->sparse) c->sparse.reset(new FxSparseState());
+    while ((int)c->sparse->agents.size() < c->max_agents) c->sparse->agents.emplace_back(c);
     FxSparseSet &s = c->sparse->agents[agent];
     if (n == 0) { s.ids.clear(); return FX_OK; }
 
@@ -95,8 +90,8 @@ int32_t fx_materialise_candidates_agent(FxContext *c, int32_t agent, int64_t n, 
     // (the previous call's uploads came from this set's host members: they have landed before those are rewritten)
     FX_TRY(fx_drain(c));
     s.ids.clear();   // from here on the previous set is gone
-    FX_TRY(s.block.ensure(c, lay.size()));
-    char *base = s.block.p;
+    FX_TRY(s.block.ensure(lay.size()));
+    char *base = s.block;
     s.o_planes = o_planes, s.o_coeffs = o_coeffs, s.o_trajlen = o_trajlen, s.o_costmap = o_costmap, s.o_cost = o_cost;
     s.o_flags = o_flags, s.o_bstep = o_bstep, s.ld = ld;
 
@@ -127,7 +122,7 @@ int32_t fx_materialise_candidates_agent(FxContext *c, int32_t agent, int64_t n, 
     HIP_TRY(hipMemsetAsync(base + o_cnt, 0, sizeof(unsigned long long) * FX_CNT_COUNT, c->stream));
     HIP_TRY(hipMemcpyAsync(d_ids, s.ids.data(), sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(base + o_prob, &d, sizeof(DevProblem), hipMemcpyHostToDevice, c->stream));
-    FxSparseState *st = c->sparse;
+    FxSparseState *st = c->sparse.get();
     FX_TRY(st->ev.ensure());
     st->ev.timed = false;
     HIP_TRY(fx_launch_eval_list(d_prob, d_ids, m, lds, obst, extra, st->ev.e0, st->ev.e1, c->stream));

@@ -36,6 +36,7 @@ struct FxRiskAgent {
 };
 
 struct FxRiskState {
+    explicit FxRiskState(FxContext *c) : block(&c->dev_bytes) {}
     std::vector<FxRiskAgent> agents;
     FxDeviceBlock block;     // the block of a risk pass (RiskPass): grows to the largest call, never shrinks
     FxEventPair ev;          // around a pass's launches; read at once into the two times below
@@ -43,19 +44,12 @@ struct FxRiskState {
     float last_pp_ms = -1.f;   // fx_eval_prediction_prob_agent
 };
 
-void fx_risk_release(FxContext *c) {
-    if (!c || !c->risk) return;
-    FxRiskState *r = c->risk;
-    r->block.release(c);
-    r->ev.release();
-    delete r;
-    c->risk = nullptr;
-}
+void fx_risk_release(FxRiskState *r) { delete r; }
 
 static FxRiskState *risk_state(FxContext *c) {
-    if (!c->risk) c->risk = new FxRiskState();
+    if (!c->risk) c->risk.reset(new FxRiskState(c));
     if ((int)c->risk->agents.size() < c->max_agents) c->risk->agents.resize(c->max_agents);
-    return c->risk;
+    return c->risk.get();
 }
 
 extern "C" int32_t fx_set_risk_obstacles_agent(FxContext *c, int32_t agent, int32_t K, int32_t P, const double *pos, const double *cov,
@@ -283,9 +277,9 @@ static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, si
     }
     HIP_TRY(hipSetDevice(c->device));
     FX_TRY(fx_drain(c));
-    FX_TRY(r->block.ensure(c, lay.size()));
+    FX_TRY(r->block.ensure(lay.size()));
     FX_TRY(r->ev.ensure());
-    q.base = r->block.p;
+    q.base = r->block;
     if (q.K > 0) {
         HIP_TRY(q.up(q.o_rec, q.rec.data(), sizeof(double) * q.rec.size()));
         HIP_TRY(q.up(q.o_obs, a.obs.data(), sizeof(double) * a.obs.size()));

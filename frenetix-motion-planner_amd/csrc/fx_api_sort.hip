@@ -18,25 +18,19 @@ struct FxSortOrder {
 };
 
 struct FxSortState {
+    explicit FxSortState(FxContext *c) : block(&c->dev_bytes) {}
     FxDeviceBlock block;        // every part 256-byte aligned (FxBlockLayout)
     int64_t total = 0;          // candidates (sum of the agents' leading dimensions) and tiles the layout below was made for
     int32_t tiles_max = 0, n_agents = 0;
     FxSortArgs args;            // device pointers into the block
     std::vector<FxSortAgent> agents;   // host copy of args.agents (uploaded when it changes: it must outlive the copy)
     bool agents_resident = false;      // the device holds `agents` as they are
-    int64_t *h_counts = nullptr;       // pinned + mapped [max_agents][2]: the kernels write n_pool, n_nan straight to the host
+    FxPinned<int64_t> h_counts;        // pinned + mapped [max_agents][2]: the kernels write n_pool, n_nan straight to the host
     std::vector<FxSortOrder> orders;   // [max_agents]
     FxEventPair ev;
 };
 
-void fx_sort_release(FxContext *c) {
-    if (!c || !c->sort) return;
-    c->sort->block.release(c);
-    if (c->sort->h_counts) (void)hipHostFree(c->sort->h_counts);
-    c->sort->ev.release();
-    delete c->sort;
-    c->sort = nullptr;
-}
+void fx_sort_release(FxSortState *s) { delete s; }
 
 static const FxSortOrder *valid_order(const FxContext *c, int agent) {
     if (!c->sort || agent < 0 || agent >= (int)c->sort->orders.size()) return nullptr;
@@ -51,10 +45,10 @@ static int sort_agents(FxContext *c, int agent0, int n, uint32_t require, uint32
         return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
     if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
     if (!c->sort) {
-        c->sort = new FxSortState();
+        c->sort.reset(new FxSortState(c));
         c->sort->orders.resize((size_t)c->max_agents);
     }
-    FxSortState *st = c->sort;
+    FxSortState *st = c->sort.get();
     const int A = c->n_agents;
     int64_t total = 0, max_all = 0, max_C = 0;
     for (int a = 0; a < A; a++) { total = std::max(total, c->slots[a].cand_off + c->slots[a].ld); max_all = std::max(max_all, c->slots[a].C); }
@@ -64,12 +58,10 @@ static int sort_agents(FxContext *c, int agent0, int n, uint32_t require, uint32
 
     HIP_TRY(hipSetDevice(c->device));
     if (!st->h_counts) {
-        void *dp = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&st->h_counts), sizeof(int64_t) * 2 * (size_t)c->max_agents, hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer(&dp, st->h_counts, 0));
-        st->args.counts = reinterpret_cast<int64_t *>(dp);
+        FX_TRY(st->h_counts.alloc(2 * (size_t)c->max_agents, hipHostMallocMapped));
+        st->args.counts = st->h_counts.dev;
     }
-    if (total != st->total || tiles_max != st->tiles_max || A != st->n_agents || !st->block.p) {
+    if (total != st->total || tiles_max != st->tiles_max || A != st->n_agents || !st->block) {
         // another upload: a new layout, and no order of the old one is left
         FxBlockLayout lay;
         const size_t o_order = lay.take(sizeof(int64_t) * total), o_k0 = lay.take(sizeof(uint64_t) * total), o_k1 = lay.take(sizeof(uint64_t) * total);
@@ -79,9 +71,9 @@ static int sort_agents(FxContext *c, int agent0, int n, uint32_t require, uint32
         const size_t o_ag = lay.take(sizeof(FxSortAgent) * A);
         for (FxSortOrder &o : st->orders) o.step = -1;
         // (a block that grows is freed: what was queued on it runs out first; tail_work stays as it is)
-        if (lay.size() > st->block.cap && st->block.p) HIP_TRY(hipStreamSynchronize(c->stream));
-        FX_TRY(st->block.ensure(c, lay.size()));
-        char *b = st->block.p;
+        if (lay.size() > st->block.size() && st->block) HIP_TRY(hipStreamSynchronize(c->stream));
+        FX_TRY(st->block.ensure(lay.size()));
+        char *b = st->block;
         FxSortArgs &g = st->args;
         g.order = reinterpret_cast<int64_t *>(b + o_order);
         g.key[0] = reinterpret_cast<unsigned long long *>(b + o_k0); g.key[1] = reinterpret_cast<unsigned long long *>(b + o_k1);
@@ -159,7 +151,7 @@ int32_t fx_read_ranked_agent(FxContext *c, int32_t agent, int64_t first, int64_t
     if (n > 0 && !index) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_read_ranked_agent: index is NULL");
     if (n == 0) return FX_OK;
     if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
-    const FxSortState *st = c->sort;
+    const FxSortState *st = c->sort.get();
     const FxAgentSlot &sl = c->slots[agent];
     const int64_t *d_order = st->args.order + sl.cand_off + first;
     HIP_TRY(hipSetDevice(c->device));

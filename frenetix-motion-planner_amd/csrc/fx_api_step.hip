@@ -33,7 +33,7 @@ static int stage_range(FxContext *c, size_t lo, size_t hi) {
     if (hi16 <= c->in_bytes && host_stage_allowed(c, hi16 - lo16))
         host_stage(c, lo16, hi16);
     else if (c->stage_mode == 2 || (c->stage_mode != 1 && hi16 - lo16 <= FX_STAGE_KERNEL_MAX && hi16 <= c->in_bytes)) {
-        HIP_TRY(fx_launch_stage(c->h_in_dev + lo16, c->d_in + lo16, hi16 - lo16, c->stream));
+        HIP_TRY(fx_launch_stage(c->h_in.dev + lo16, c->d_in + lo16, hi16 - lo16, c->stream));
         c->stage_path = 2;
     } else {
         HIP_TRY(hipMemcpyAsync(c->d_in + lo, c->h_in + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
@@ -78,39 +78,29 @@ int32_t fx_upload_batch(FxContext *c, int32_t n_agents, const FxProblem *probs) 
                           align_up(sizeof(double) * 2 * (size_t)p->lane_poly_off[p->n_lane], 256) +
                           align_up(sizeof(double) * 2 * (size_t)p->lane_ctr_off[p->n_lane], 256);
     }
-    if (bound_need > c->bound_cap) {
-        if (c->h_bound) (void)hipHostFree(c->h_bound);
-        if (c->d_bound) { (void)hipFree(c->d_bound); c->dev_bytes -= (int64_t)c->bound_cap; }
-        c->h_bound = c->d_bound = nullptr;
-        c->bound_cap = 0;
+    if (bound_need > std::min(c->h_bound.size(), c->d_bound.size())) {
         const size_t cap = std::max<size_t>(2 * bound_need, 64 * 1024);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_bound), cap, hipHostMallocDefault));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_bound), cap));
-        c->bound_cap = cap;
-        c->dev_bytes += (int64_t)cap;
+        FX_TRY(c->h_bound.ensure(cap, hipHostMallocDefault));
+        FX_TRY(c->d_bound.ensure(cap));
     }
-    if (pl.planes_bytes && (rc = ensure_planes(c, pl.planes_bytes))) return rc;
+    FX_TRY(c->d_planes.ensure(pl.planes_bytes / sizeof(double)));
     if (pl.obs_part_n) {   // scratch of the obstacle kernel: tickets start (and are left) zeroed
-        if (pl.obs_part_n > c->obs_part_cap || pl.obs_colm_n > c->obs_colm_cap) {
+        if (pl.obs_part_n > c->d_obs_part.size() || pl.obs_colm_n > c->d_obs_colm.size()) {   // both anew, at this step's sizes
             FX_TRY(fx_drain(c));
-            if (c->d_obs_part) { (void)hipFree(c->d_obs_part); c->dev_bytes -= (int64_t)(sizeof(double) * c->obs_part_cap); }
-            if (c->d_obs_colm) { (void)hipFree(c->d_obs_colm); c->dev_bytes -= (int64_t)(sizeof(unsigned long long) * c->obs_colm_cap); }
-            c->d_obs_part = nullptr; c->d_obs_colm = nullptr;
-            c->obs_part_cap = c->obs_colm_cap = 0;
-            if ((rc = dev_alloc(c, &c->d_obs_part, pl.obs_part_n))) return rc;
-            if ((rc = dev_alloc(c, &c->d_obs_colm, pl.obs_colm_n))) return rc;
-            c->obs_part_cap = pl.obs_part_n; c->obs_colm_cap = pl.obs_colm_n;
+            c->d_obs_part.release(); c->d_obs_colm.release();
+            FX_TRY(c->d_obs_part.alloc(pl.obs_part_n));
+            FX_TRY(c->d_obs_colm.alloc(pl.obs_colm_n));
         }
         if (!c->d_obs_ticket) {
             const size_t n_tick = (size_t)(c->caps.total_ld / 64) + (size_t)c->max_agents;
-            if ((rc = dev_alloc(c, &c->d_obs_ticket, n_tick))) return rc;
+            FX_TRY(c->d_obs_ticket.alloc(n_tick));
             HIP_TRY(hipMemsetAsync(c->d_obs_ticket, 0, sizeof(unsigned int) * n_tick, c->stream));   // (in order with the step's kernels)
         }
-        if (!c->d_obs_list && (rc = dev_alloc(c, &c->d_obs_list, (size_t)c->caps.total_ld))) return rc;
+        if (!c->d_obs_list) FX_TRY(c->d_obs_list.alloc((size_t)c->caps.total_ld));
     }
     // the bytes, and every agent's DevProblem from its row of the plan
     Arena ar{c->h_in, c->d_in, c->probs_bytes, c->in_bytes};
-    Arena br{c->h_bound, c->d_bound, 0, c->bound_cap};
+    Arena br{c->h_bound, c->d_bound, 0, c->d_bound.size()};
     for (int a = 0; a < n_agents; a++) {
         const FxProblem *p = &probs[a];
         const FxAgentPlan &r = pl.agents[a];
@@ -223,10 +213,10 @@ int32_t fx_upload_batch(FxContext *c, int32_t n_agents, const FxProblem *probs) 
         d.part_cost = c->d_part_cost + r.block_off;
         d.part_idx = c->d_part_idx + r.block_off;
         d.counters = c->d_counters + (size_t)a * FX_CNT_COUNT;
-        d.pkg_out = c->h_pkg_dev + (size_t)a * c->pkg_stride;
+        d.pkg_out = c->h_pkg.dev + (size_t)a * c->pkg_stride;
         d.pkg_seq = reinterpret_cast<unsigned long long *>(d.pkg_out + c->pkg_stride - 1);
         d.pkg_plane_rows = c->pkg_plane_rows;
-        if (r.mode & FX_MODE_WRITE_BUNDLE) d.planes = reinterpret_cast<double *>(reinterpret_cast<char *>(c->d_planes) + r.planes_off);
+        if (r.mode & FX_MODE_WRITE_BUNDLE) d.planes = c->d_planes + r.planes_off / sizeof(double);
         sl.C = r.C; sl.ld = r.ld; sl.cand_off = r.cand_off; sl.S = S; sl.n_cost = p->n_cost; sl.n_blocks = r.n_blocks; sl.mode = r.mode;
     }
     c->last_live = -1;
@@ -296,8 +286,8 @@ int32_t fx_evaluate(FxContext *c) {
     if (timed && !attached) HIP_TRY(hipEventRecord(ts->e0, c->stream));
     c->seq++;
     double *winner = c->dev_winner ? c->dev_winner : (L.pkg ? c->d_winner_own : nullptr);
-    double *host_pkg = L.pkg ? c->h_pkg_dev : nullptr;
-    FuseArgs fuse{L.fused ? c->h_counters_dev : nullptr, c->seq, winner, (int32_t)((uint32_t)pl.K_max | (L.tail << 16))};
+    double *host_pkg = L.pkg ? c->h_pkg.dev : nullptr;
+    FuseArgs fuse{L.fused ? c->h_counters.dev : nullptr, c->seq, winner, (int32_t)((uint32_t)pl.K_max | (L.tail << 16))};
     // ---- the whole step in ONE launch (fx_step_kernel.h) where the upload qualifies and the device holds the launch at once ----
     if (L.try_step_kernel) {
         int cap[3] = {0, 0, 0};
@@ -308,7 +298,7 @@ int32_t fx_evaluate(FxContext *c) {
         if (sz.CH) {
             StepArgs sa{};
             sa.bar = c->d_bar; sa.bar_base = c->bar_base;
-            sa.host_result = c->h_counters_dev; sa.seq = c->seq; sa.dev_winner = winner;
+            sa.host_result = c->h_counters.dev; sa.seq = c->seq; sa.dev_winner = winner;
             sa.host_pkg = host_pkg; sa.pkg_stride = c->pkg_stride; sa.pkg_plane_rows = c->pkg_plane_rows;
             sa.walk_blocks = pl.max_blocks;
             HIP_TRY(fx_launch_step(c->d_probs, c->n_agents, sz.blocks, sz.lds, sz.CH, k0, k1, fuse, sa, c->stream));
@@ -332,10 +322,10 @@ int32_t fx_evaluate(FxContext *c) {
         if (timed) ts->obst_timed = t_obs;
     }
     if (L.select)
-        HIP_TRY(fx_launch_select(c->d_probs, c->n_agents, pl.C_max, c->h_counters_dev, c->seq, winner, host_pkg, c->pkg_stride,
+        HIP_TRY(fx_launch_select(c->d_probs, c->n_agents, pl.C_max, c->h_counters.dev, c->seq, winner, host_pkg, c->pkg_stride,
                                  c->pkg_plane_rows, c->stream));
     if (L.package)
-        HIP_TRY(fx_launch_package(c->d_probs, c->n_agents, winner, c->h_pkg_dev, c->pkg_stride, c->pkg_plane_rows, c->seq, c->stream));
+        HIP_TRY(fx_launch_package(c->d_probs, c->n_agents, winner, c->h_pkg.dev, c->pkg_stride, c->pkg_plane_rows, c->seq, c->stream));
     if (timed && !L.one_launch) HIP_TRY(hipEventRecord(ts->e_end, c->stream));
     if (timed) { ts->fused = L.one_launch; c->n_timed++; }
     c->timed_step = timed;

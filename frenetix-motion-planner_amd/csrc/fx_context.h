@@ -8,13 +8,9 @@
 //   fx_api_sort.hip      stable cost order of all candidates beside the step, read back by rank
 #pragma once
 
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
@@ -30,7 +26,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 
-#include "fx_policy.h"
+#include "fx_owner.h"
 
 extern "C" hipError_t fx_launch_eval(const DevProblem *d_probs, int n_agents, int max_blocks, size_t lds_bytes, int G,
                                      bool bundle, bool obst, bool extra, int wpe, hipEvent_t ev_start, hipEvent_t ev_stop,
@@ -62,23 +58,6 @@ extern "C" hipError_t fx_launch_gather_candidates(const GatherArgs *args, const 
 extern "C" hipError_t fx_launch_eval_list(const DevProblem *d_prob, const int64_t *d_ids, int64_t n, size_t lds_bytes, bool obst, bool extra,
                                           hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream);
 
-extern thread_local char g_err[512];   // (defined in fx_api.hip)
-
-inline int set_err(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return set_err(FX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                             __FILE__, __LINE__);                                           \
-    } while (0)
-
 // state updates up to this many bytes are staged by a copy kernel reading the mapped pinned block, larger ones by the DMA engine
 #define FX_STAGE_KERNEL_MAX ((size_t)1 << 20)
 #define FX_STAGE_HOST_MAX ((size_t)4 << 20)     // host writes into the device arena (large BAR): ~50 GB/s of posted writes
@@ -99,14 +78,18 @@ struct FxAgentSlot {
     bool have_hull = false, want_collision = false;
 };
 
+void fx_risk_release(struct FxRiskState *r);       // (fx_api_risk.hip)
+void fx_sparse_release(struct FxSparseState *s);   // (fx_api_materialise.hip)
+void fx_sort_release(struct FxSortState *s);       // (fx_api_sort.hip)
+
 struct FxContext {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    FxStream stream;             // the first owner: everything below is given back before the stream is destroyed
+    int64_t dev_bytes = 0;       // device memory held (fx_device_bytes): kept by the device arrays below and by the passes' blocks
     // timing ring: per timed step (start, evaluation end, step end) events; elapsed times are read lazily, so a
     // timed step never waits for its own events
     struct TimeSlot {
-        hipEvent_t e0 = nullptr, e_eval = nullptr, e_end = nullptr, e_obs0 = nullptr, e_obs1 = nullptr;
+        FxEvent e0, e_eval, e_end, e_obs0, e_obs1;
         bool eval_launched = false, fused = false, fetched = false, obst_timed = false;
         float step_ms = 0.f, eval_ms = 0.f, obst_ms = 0.f;
     };
@@ -119,8 +102,7 @@ struct FxContext {
     int32_t max_agents = 1;                // (the others: caps)
     // input arena
     size_t in_bytes = 0;
-    char *h_in = nullptr;   // pinned + mapped
-    char *h_in_dev = nullptr;  // device address of the same block (the staging kernel reads it)
+    FxPinned<char> h_in;       // pinned + mapped (the staging kernel reads it through h_in.dev)
     int stage_mode = 0;        // 0 auto: kernel copy up to FX_STAGE_KERNEL_MAX bytes, DMA above; 1 DMA; 2 kernel; 3 host writes into
                                // device memory -- OPT-IN, or fail (FX_STAGE=dma|kernel|bar)
     bool user_stream = false;  // fx_set_stream handed in a caller's stream: what else is queued on it is unknown
@@ -128,34 +110,31 @@ struct FxContext {
                                // and a kernel that had the lines cached sees a second write (probed at fx_create)
     volatile uint32_t *hdp_flush = nullptr;   // the device's HDP flush register (hipDeviceAttributeHdpMemFlushCntl), written behind host stores
     int stage_path = 0;        // how the latest inputs reached the device: 1 DMA copy, 2 staging kernel, 3 host writes
-    char *d_in = nullptr;
+    FxDeviceArray<char> d_in{&dev_bytes};
     // problems
     DevProblem *h_probs = nullptr;  // [max_agents], the front of the pinned staging block h_in ...
     DevProblem *d_probs = nullptr;  // ... and of its device twin d_in: problems and inputs travel in ONE copy
     size_t probs_bytes = 0;
     // outputs
-    double *d_cost = nullptr;
-    double *d_cost_tail = nullptr;     // [total_ld] cost terms behind the prediction term (obstacle stage as its own kernel)
+    FxDeviceArray<double> d_cost{&dev_bytes};
+    FxDeviceArray<double> d_cost_tail{&dev_bytes};     // [total_ld] cost terms behind the prediction term (obstacle stage as its own kernel)
     // obstacle kernel scratch (allocated on first use): partial sums [chunks][ld], collision ballots [chunks][tiles], tile tickets
-    double *d_obs_part = nullptr;
-    unsigned long long *d_obs_colm = nullptr;
-    unsigned int *d_obs_ticket = nullptr;
-    int32_t *d_obs_list = nullptr;     // [total_ld] the walk's list of costed candidates per agent (obstacle stage as its own kernel)
-    size_t obs_part_cap = 0, obs_colm_cap = 0;
-    uint32_t *d_flags = nullptr;
-    double *d_costmap = nullptr;
-    double *d_coeffs = nullptr;
-    int32_t *d_trajlen = nullptr;
-    int32_t *d_bstep = nullptr;       // [total_ld] first road-boundary step per candidate
-    char *h_bound = nullptr, *d_bound = nullptr;  // road-boundary pieces / bins / items (grown on demand)
-    size_t bound_cap = 0;
-    double *d_planes = nullptr;
-    size_t planes_bytes = 0;
-    double *d_part_cost = nullptr;
-    int64_t *d_part_idx = nullptr;
-    unsigned long long *d_counters = nullptr;  // [max_agents][FX_CNT_COUNT]
-    unsigned long long *h_counters = nullptr;  // pinned + mapped: [max_agents][FX_CNT_COUNT + 1], last word = sequence
-    unsigned long long *h_counters_dev = nullptr;  // device address of the same block
+    FxDeviceArray<double> d_obs_part{&dev_bytes};
+    FxDeviceArray<unsigned long long> d_obs_colm{&dev_bytes};
+    FxDeviceArray<unsigned int> d_obs_ticket{&dev_bytes};
+    FxDeviceArray<int32_t> d_obs_list{&dev_bytes};     // [total_ld] the walk's list of costed candidates per agent (obstacle stage as its own kernel)
+    FxDeviceArray<uint32_t> d_flags{&dev_bytes};
+    FxDeviceArray<double> d_costmap{&dev_bytes};
+    FxDeviceArray<double> d_coeffs{&dev_bytes};
+    FxDeviceArray<int32_t> d_trajlen{&dev_bytes};
+    FxDeviceArray<int32_t> d_bstep{&dev_bytes};       // [total_ld] first road-boundary step per candidate
+    FxPinned<char> h_bound;                // road-boundary pieces / bins / items (grown on demand) ...
+    FxDeviceArray<char> d_bound{&dev_bytes};   // ... and their device twin, of the same size
+    FxDeviceArray<double> d_planes{&dev_bytes};   // the bundle (grown on demand)
+    FxDeviceArray<double> d_part_cost{&dev_bytes};
+    FxDeviceArray<int64_t> d_part_idx{&dev_bytes};
+    FxDeviceArray<unsigned long long> d_counters{&dev_bytes};  // [max_agents][FX_CNT_COUNT]
+    FxPinned<unsigned long long> h_counters;   // pinned + mapped: [max_agents][FX_CNT_COUNT + 1], last word = sequence
     unsigned long long seq = 0;
     // survivor exchange inside the library (fx_comm_init): an RCCL communicator of this context's own, the gathered winners
     void *comm = nullptr;                  // ncclComm_t
@@ -165,12 +144,11 @@ struct FxContext {
     int comm_k_clean = 0;                  // ... for this k (0: the winner buffer)
     bool comm_init_failed = false;         // an fx_comm_init on this context timed out: never retried
     int exchange_mode = 0;                 // fx_set_exchange_mode: 0 receive in device memory + publication kernel, 1 receive straight in the pinned block
-    double *d_gather = nullptr;            // [world][max_agents][2] (grown to [world][max_agents][2 k] by the top-k exchange)
-    size_t gather_cap = 0;                 // doubles
-    double *d_xsend = nullptr;             // [max_agents][2][64]: a rank's survivors, [cost n k | index n k], the all-gather's send buffer
+    FxDeviceArray<double> d_gather{&dev_bytes};   // [world][max_agents][2] (grown to [world][max_agents][2 k] by the top-k exchange)
+    FxDeviceArray<double> d_xsend{&dev_bytes};    // [max_agents][2][64]: a rank's survivors, [cost n k | index n k], the all-gather's send buffer
     int timeout_ms = 20000;                // bound of every host wait on device work (fx_set_timeout_ms)
     bool timed_out = false;                // a wait ran out: the stream may never drain, the context refuses further steps
-    double *h_pub = nullptr, *h_pub_dev = nullptr;   // pinned + mapped [FX_PUB_MAX + 1]: published buffer, last word = sequence
+    FxPinned<double> h_pub;                // pinned + mapped [FX_PUB_MAX + 1]: published buffer, last word = sequence
     unsigned long long pub_seq = 0;
     int pub_n = 0;
     double *dev_winner = nullptr;          // caller-owned device buffer [n_agents][2] the selection kernel also fills
@@ -178,22 +156,22 @@ struct FxContext {
     bool tail_work = false;                // work queued behind the evaluation whose completion NO sequence word reports (top-k, publication,
                                            // exchange) or a caller's own stream (fx_set_stream): cleared only by a stream synchronise --
                                            // fx_finish_batch clears in_flight when the evaluation's words arrive, which says nothing about these
-    double *d_topk_cost = nullptr;
-    long long *d_topk_idx = nullptr;
-    double *d_topk_scr_cost = nullptr;     // [max_agents][64 slices][64]
-    long long *d_topk_scr_idx = nullptr;
-    double *h_topk_cost = nullptr;
+    FxDeviceArray<double> d_topk_cost{&dev_bytes};
+    FxDeviceArray<long long> d_topk_idx{&dev_bytes};
+    FxDeviceArray<double> d_topk_scr_cost{&dev_bytes};     // [max_agents][64 slices][64]
+    FxDeviceArray<long long> d_topk_scr_idx{&dev_bytes};
+    FxPinned<double> h_topk_cost;
     // winner package (fx_set_package): pinned + mapped [max_agents][pkg_stride] doubles the package kernel fills behind the selection
-    double *h_pkg = nullptr, *h_pkg_dev = nullptr;
+    FxPinned<double> h_pkg;
     int pkg_stride = 0, pkg_plane_rows = 0;
-    double *d_winner_own = nullptr;        // [max_agents][2]: the winner stays device-resident for the package kernel
+    FxDeviceArray<double> d_winner_own{&dev_bytes};   // [max_agents][2]: the winner stays device-resident for the package kernel
     bool package_enabled = false;
-    double *h_cand = nullptr;  // pinned staging of fx_read_candidate_agent: planes | coeffs | raw costs | cost | traj_len | flags
-    size_t h_cand_doubles = 0;
+    FxPinned<double> h_cand;   // pinned staging of fx_read_candidate_agent: planes | coeffs | raw costs | cost | traj_len | flags
     // chunk of fx_read_candidates_agent (FX_READ_CHUNK_BYTES each, allocated on its first call): ids | packed records, on the device
     // and pinned
-    char *d_cands = nullptr, *h_cands = nullptr;
-    long long *h_topk_idx = nullptr;
+    FxDeviceArray<char> d_cands{&dev_bytes};
+    FxPinned<char> h_cands;
+    FxPinned<long long> h_topk_idx;
     // current step
     int n_agents = 0;
     std::vector<FxAgentSlot> slots;
@@ -208,19 +186,15 @@ struct FxContext {
     std::vector<FxAgentPlan> plan_rows;    // [max_agents], plan.agents
     FxLaunchPlan launch;
     int64_t last_live = -1;                // costed candidates of the previous step's agents (max): sizes the one-launch step's obstacle items
-    unsigned long long *d_bar = nullptr;   // the one-launch step's two grid barriers' counter + release-flag blocks, monotonic
+    FxDeviceArray<unsigned long long> d_bar{&dev_bytes};   // the one-launch step's two grid barriers' counter + release-flag blocks, monotonic
     unsigned long long bar_base = 0;       // their value before the next launch
     int timing = FX_TIMING_OFF;
     bool timed_step = false;
-    int64_t dev_bytes = 0;
-    struct FxRiskState *risk = nullptr;    // trajectory risk (fx_api_risk.hip): obstacle tables and buffers, created on first use
-    struct FxSparseState *sparse = nullptr;   // sparse sets of listed candidates (fx_api_materialise.hip), created on first use
-    struct FxSortState *sort = nullptr;       // cost order of all candidates (fx_api_sort.hip), created on first use
+    // the states of the passes beside the step, created on first use; each is deleted where its type is complete
+    std::unique_ptr<FxRiskState, void (*)(FxRiskState *)> risk{nullptr, fx_risk_release};         // trajectory risk: obstacle tables and buffers
+    std::unique_ptr<FxSparseState, void (*)(FxSparseState *)> sparse{nullptr, fx_sparse_release};   // sparse sets of listed candidates
+    std::unique_ptr<FxSortState, void (*)(FxSortState *)> sort{nullptr, fx_sort_release};           // cost order of all candidates
 };
-
-void fx_risk_release(FxContext *c);   // (fx_api_risk.hip)
-void fx_sparse_release(FxContext *c);   // (fx_api_materialise.hip)
-void fx_sort_release(FxContext *c);     // (fx_api_sort.hip)
 
 // An agent's sparse set as its consumers see it (fx_api_materialise.hip): the structure-of-arrays rows of
 // the n listed candidates, column = position in the ascending, de-duplicated list `ids`
@@ -249,13 +223,6 @@ inline int wait_seq(FxContext *c, const volatile unsigned long long *word, unsig
     const int rc = fx_wait_word(word, expected, c->timeout_ms);
     if (rc == FX_ERR_TIMEOUT) c->timed_out = true;
     return rc;
-}
-
-template <typename T>
-inline int dev_alloc(FxContext *c, T **p, size_t n) {
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(n, 1) * sizeof(T)));
-    c->dev_bytes += (int64_t)(std::max<size_t>(n, 1) * sizeof(T));
-    return FX_OK;
 }
 
 // per-step obstacle masks: one 64-bit word per 64 obstacles, word-major ([word][step]) so that the first word is the whole
@@ -312,20 +279,6 @@ inline int fetch_slot(FxContext *c, FxContext::TimeSlot &t) {
     t.obst_ms = 0.f;
     if (t.obst_timed) HIP_TRY(hipEventElapsedTime(&t.obst_ms, t.e_obs0, t.e_obs1));
     t.fetched = true;
-    return FX_OK;
-}
-
-inline int ensure_planes(FxContext *c, size_t bytes) {
-    if (bytes <= c->planes_bytes) return FX_OK;
-    if (c->d_planes) {
-        HIP_TRY(hipFree(c->d_planes));
-        c->dev_bytes -= (int64_t)c->planes_bytes;
-        c->d_planes = nullptr;
-        c->planes_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_planes), bytes));
-    c->planes_bytes = bytes;
-    c->dev_bytes += (int64_t)bytes;
     return FX_OK;
 }
 
@@ -475,8 +428,8 @@ inline bool probe_host_writes(FxContext *c, int device, char *d_in, size_t bytes
     // a kernel reads what the host wrote: 64 workgroups (all XCDs) copy the probed line into a scratch buffer, which a plain copy
     // brings back; three rounds with different patterns over the SAME lines
     constexpr int kProbeBlocks = 64;
-    char *scratch = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&scratch), 64 * kProbeBlocks) != hipSuccess) { (void)hipGetLastError(); return false; }
+    FxDeviceBlock scratch;
+    if (scratch.alloc(64 * kProbeBlocks)) { (void)hipGetLastError(); return false; }
     bool ok = true;
     unsigned long long pat[8], back[8];
     std::vector<unsigned long long> seen(8 * kProbeBlocks);
@@ -487,12 +440,11 @@ inline bool probe_host_writes(FxContext *c, int device, char *d_in, size_t bytes
             memcpy(at, pat, sizeof(pat));
             __builtin_ia32_sfence();
             *c->hdp_flush = 1u; (void)*c->hdp_flush;
-            ok = ok && fx_launch_probe_read(at, scratch, kProbeBlocks, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess &&
+            ok = ok && fx_launch_probe_read(at, scratch.get(), kProbeBlocks, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess &&
                  hipMemcpy(seen.data(), scratch, 64 * kProbeBlocks, hipMemcpyDeviceToHost) == hipSuccess &&
                  hipMemcpy(back, at, sizeof(back), hipMemcpyDeviceToHost) == hipSuccess && !memcmp(pat, back, sizeof(pat));
             for (int b = 0; b < kProbeBlocks && ok; b++) ok = !memcmp(pat, seen.data() + 8 * b, sizeof(pat));
         }
-    (void)hipFree(scratch);
     if (!ok) { (void)hipGetLastError(); c->hdp_flush = nullptr; }
     return ok;
 }

@@ -1,5 +1,6 @@
 // fx_pass.h -- the host scaffold of the passes that run beside the plan step (fx_api_risk.hip, fx_api_sort.hip,
-// fx_api_materialise.hip, the read-back of fx_api_host.hip), each piece written once.  Nothing here launches a kernel.
+// fx_api_materialise.hip, the read-back of fx_api_host.hip), each piece written once.  Nothing here launches a kernel.  The block of
+// a pass is an FxDeviceBlock (fx_owner.h): grow-only, laid out by FxBlockLayout.
 #pragma once
 
 #include "fx_context.h"
@@ -13,42 +14,19 @@ struct FxBlockLayout {
     size_t size() const { return off; }
 };
 
-// A grow-only device block: it grows to the largest call and never shrinks.  Whether the stream is drained before a block that
-// may still be read is freed is the caller's decision.
-struct FxDeviceBlock {
-    char *p = nullptr;
-    size_t cap = 0;   // bytes
-    int ensure(FxContext *c, size_t bytes) {
-        if (bytes <= cap) return FX_OK;
-        if (p) { HIP_TRY(hipFree(p)); c->dev_bytes -= (int64_t)cap; p = nullptr; cap = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), bytes));
-        cap = bytes;
-        c->dev_bytes += (int64_t)bytes;
-        return FX_OK;
-    }
-    void release(FxContext *c) {
-        if (p) { (void)hipFree(p); c->dev_bytes -= (int64_t)cap; p = nullptr; cap = 0; }
-    }
-};
-
 // The events around a pass's launches, created on first use.  `timed`: they bracket a launch sequence that was enqueued whole.
 struct FxEventPair {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    FxEvent e0, e1;
     bool timed = false;
     int ensure() {
-        if (!e0) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); }
-        return FX_OK;
+        FX_TRY(e0.create());
+        return e1.create();
     }
     // device time between the two, ms (waits for the second one); -1 before the first timed launch and on any failure
     double elapsed_ms() const {
         float ms = -1.f;
         if (timed && (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) { (void)hipGetLastError(); ms = -1.f; }
         return (double)ms;
-    }
-    void release() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        e0 = e1 = nullptr; timed = false;
     }
 };
 

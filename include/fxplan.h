@@ -221,7 +221,8 @@ int32_t fx_device_count(int32_t *count);  /* no context needed */
 
 /* ---- context: owns device buffers sized for up to max_candidates x (max_steps+1); one per
  *      planner instance (frenetix.TrajectoryHandler(dt=) at reactive_planner_cpp.py:49).
- *      stream: a hipStream_t as void* (0 -> the context creates its own). ---- */
+ *      stream: a hipStream_t as void* (0 -> the context creates its own).
+ *      A create that fails stores NULL in *out and has given back everything it had built: there is nothing to destroy. ---- */
 int32_t fx_create(FxContext **out, int32_t device, int64_t max_candidates, int32_t max_steps,
                   int32_t max_ref_knots, int32_t max_obstacles, int32_t max_pred_steps);
 int32_t fx_destroy(FxContext *ctx);

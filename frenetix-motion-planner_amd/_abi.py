@@ -165,6 +165,20 @@ class FxPredProbOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("prob", "prob_obs", "total", "best_index", "best_cost")]
 
 
+# the risk walk's decomposition and the responsibility cost as a weighted term (fxplan.h)
+BESIDE_STEP_COSTS = ("responsibility",)   # cost names the planner evaluates by a pass beside the plan step (PlanInputs refuses them)
+FX_RISK_DECOMP_WALK, FX_RISK_DECOMP_ITEMS = 0, 1
+RISK_DECOMPOSITIONS = {"walk": FX_RISK_DECOMP_WALK, "items": FX_RISK_DECOMP_ITEMS}
+
+
+class FxRespCostParams(C.Structure):
+    _fields_ = [("weight", C.c_double), ("responsibility_mode", C.c_int32), ("responsibility", C.c_void_p), ("prediction", C.c_void_p)]
+
+
+class FxRespCostOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("resp", "total", "ego_risk", "obst_risk", "best_index", "best_cost")]
+
+
 class FxRiskOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ego_risk", "obst_risk", "obst_harm_occ", "ego_risk_max", "obst_risk_max", "ego_harm_max",
                                           "obst_harm_max", "bayes", "equality", "maximin", "ego", "responsibility", "total",

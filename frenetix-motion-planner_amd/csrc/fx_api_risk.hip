@@ -4,6 +4,7 @@
 // risk-cost pass.  The two evaluations share one host path (RiskPass) and one device block.  Nothing of
 // this runs in a plan step.  The collision probability as the prediction cost (fx_predprob_kernel.h) is a third
 // entrance on the same host path: the same checks, records, uploads and block.
+#include <atomic>
 #include <cmath>
 #include <vector>
 
@@ -12,7 +13,8 @@
 
 extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const FxRiskParams *params, double *out_ego, double *out_obst,
                                      double *col, double *out_occ, const RiskCostArgs *cost, long long *out_idx, hipEvent_t ev_start,
-                                     hipEvent_t ev_stop, hipStream_t stream);
+                                     hipEvent_t ev_stop, hipStream_t stream, const RiskItemArgs *items, const RespSumArgs *resp,
+                                     long long *resp_idx);
 extern "C" hipError_t fx_launch_predprob(const PredProbArgs *args, long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
                                          hipStream_t stream);
 
@@ -42,6 +44,7 @@ struct FxRiskState {
     FxEventPair ev;          // around a pass's launches; read at once into the two times below
     float last_ms = 0.f;
     float last_pp_ms = -1.f;   // fx_eval_prediction_prob_agent
+    int decomposition = FX_RISK_DECOMP_WALK;   // fx_set_risk_decomposition
 };
 
 void fx_risk_release(FxRiskState *r) { delete r; }
@@ -181,6 +184,11 @@ struct RiskPass {
     size_t o_occ, o_col;                                                 // detail pass only
     size_t o_out, o_bh, o_resp, o_eobs, o_eoff, o_pst, o_voff, o_vert;   // cost pass only
     size_t o_pstep, o_pprob, o_pobs, o_ptot, o_pbest;                    // prediction-probability pass only
+    bool items = false;      // the walk in the item decomposition (fx_risk_items_kernel.h): `it`, its partials at o_part
+    RiskItemArgs it{};
+    size_t o_part, o_prm;
+    const FxRiskParams *prm;   // the call's parameters (risk_check)
+    size_t o_rresp, o_rtot, o_rpred, o_rbest;                            // responsibility pass only
 
     double *D(size_t o) const { return reinterpret_cast<double *>(base + o); }
     int32_t *I(size_t o) const { return reinterpret_cast<int32_t *>(base + o); }
@@ -237,7 +245,7 @@ static int risk_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskPara
                           : set_err(FX_ERR_INVALID_ARGUMENT, "obstacle %d: orientation_list (%d) shorter than get_collision_probability_fast "
                                     "indexes (%d)", k, a.n_yaw[k], std::min(S, np));
     }
-    q.c = c, q.agent = agent, q.s = &s, q.r = r, q.a = &a;
+    q.c = c, q.agent = agent, q.s = &s, q.r = r, q.a = &a, q.prm = params;
     q.S = S, q.K = K, q.P = a.P > 0 ? a.P : 1, q.maha = maha;
     q.n = ids ? n_ids : s.C, q.ids = ids;
     q.planes = q.sparse ? q.set.planes : c->h_probs[agent].planes;
@@ -247,10 +255,25 @@ static int risk_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskPara
     return FX_OK;
 }
 
+// The scratch of the passes that work in items -- the per-step probabilities of fx_eval_prediction_prob_agent, the partials of the
+// risk items -- holds one batch of candidates: the batch bounds it to FX_PREDPROB_SCRATCH_BYTES where one candidate's share allows.
+#define FX_PREDPROB_SCRATCH_BYTES ((size_t)64 << 20)
+// Steps per chunk of the risk items (fx_item_chunk_steps, fx_pass.h), or what fx_risk_items_set_chunk_steps forces (tests: the
+// results do not depend on it)
+static std::atomic<int> fx_risk_items_chunk_forced{0};
+extern "C" void fx_risk_items_set_chunk_steps(int32_t steps) { fx_risk_items_chunk_forced.store(steps > 0 ? steps : 0, std::memory_order_relaxed); }
+extern "C" int32_t fx_risk_items_chunk_steps(int64_t n, int32_t S, int32_t K) {
+    return fx_item_chunk_steps(n, S, K, fx_risk_items_chunk_forced.load(std::memory_order_relaxed));
+}
+
 // The device block of a pass and the uploads every pass makes.  One grow-only allocation, every part 256-byte aligned; the plain
 // pass takes no room for the detail pass's columns, and only a pass with cost parameters for their outputs and tables.
 // pp_nb > 0: the prediction-probability pass with batches of pp_nb candidates -- room for its per-step scratch and outputs.
-static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, size_t pp_nb = 0) {
+// items: the walk runs in the item decomposition -- room for the partials of one batch, the batch sized so that they stay within
+// FX_PREDPROB_SCRATCH_BYTES where one candidate's share allows; need: the flags a candidate needs when no ids are given.
+// resp: the responsibility pass -- room for its outputs.
+static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, size_t pp_nb = 0, bool items = false,
+                      uint32_t need = FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED, bool resp = false) {
     FxContext *c = q.c;
     FxRiskState *r = q.r;
     const FxRiskAgent &a = *q.a;
@@ -275,11 +298,32 @@ static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, si
         q.o_pprob = lay.take(sizeof(double) * n1), q.o_pobs = lay.take(sizeof(double) * K * n1), q.o_ptot = lay.take(sizeof(double) * n1);
         q.o_pbest = lay.take(2 * sizeof(long long));
     }
+    q.items = items;
+    if (items) {
+        const size_t steps = (size_t)std::max(q.S - 1, 1), nv = detail ? 7 : 2;
+        q.it.cs = fx_risk_items_chunk_steps(q.n, q.S, q.K);
+        q.it.chunks = (int32_t)((steps + q.it.cs - 1) / q.it.cs);
+        const size_t per_cand = sizeof(double) * nv * std::max<size_t>(K, 1) * (size_t)q.it.chunks;
+        size_t nb = std::max<size_t>(FX_PREDPROB_SCRATCH_BYTES / per_cand / 64, 1) * 64;   // whole tiles
+        nb = std::min(nb, (n1 + 63) / 64 * 64);
+        q.it.nb = (int64_t)nb;
+        q.it.need = need;
+        q.o_part = lay.take(per_cand * nb), q.o_prm = lay.take(sizeof(FxRiskParams));
+    }
+    if (resp) {
+        q.o_rresp = lay.take(sizeof(double) * n1), q.o_rtot = lay.take(sizeof(double) * n1), q.o_rpred = lay.take(sizeof(double) * n1);
+        q.o_rbest = lay.take(2 * sizeof(long long));
+    }
     HIP_TRY(hipSetDevice(c->device));
     FX_TRY(fx_drain(c));
     FX_TRY(r->block.ensure(lay.size()));
     FX_TRY(r->ev.ensure());
     q.base = r->block;
+    if (items) {
+        q.it.part = q.D(q.o_part);
+        q.it.params = reinterpret_cast<const FxRiskParams *>(q.base + q.o_prm);
+        HIP_TRY(q.up(q.o_prm, q.prm, sizeof(FxRiskParams)));
+    }
     if (q.K > 0) {
         HIP_TRY(q.up(q.o_rec, q.rec.data(), sizeof(double) * q.rec.size()));
         HIP_TRY(q.up(q.o_obs, a.obs.data(), sizeof(double) * a.obs.size()));
@@ -292,14 +336,16 @@ static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, si
 }
 
 // The launches of a pass (fx_launch_risk), the read-back of what the caller asked for, and the device time
-static int risk_run(RiskPass &q, const FxRiskParams &p, bool detail, const RiskCostArgs *ca, const FxRiskOutputs &out) {
+static int risk_run(RiskPass &q, const FxRiskParams &p, bool detail, const RiskCostArgs *ca, const FxRiskOutputs &out,
+                    const RespSumArgs *rs = nullptr) {
     FxContext *c = q.c;
     FxRiskState *r = q.r;
     const RiskWalkArgs w{q.planes, q.ld, q.S, q.n, q.d_ids(), q.flags, q.D(q.o_rec), q.D(q.o_obs),
                          q.D(q.o_pos), q.D(q.o_yaw), q.D(q.o_v), q.K, q.P};
     long long *d_idx = reinterpret_cast<long long *>(q.base + q.o_idx);
     HIP_TRY(fx_launch_risk(&w, &p, q.D(q.o_ego), q.D(q.o_obst), detail ? q.D(q.o_col) : nullptr, detail ? q.D(q.o_occ) : nullptr, ca, d_idx,
-                           r->ev.e0, r->ev.e1, c->stream));
+                           r->ev.e0, r->ev.e1, c->stream, q.items ? &q.it : nullptr, rs,
+                           rs ? reinterpret_cast<long long *>(q.base + q.o_rbest) : nullptr));
     const size_t nn = (size_t)q.n, Kn = (size_t)q.K * nn;
     HIP_TRY(q.down(out.ego_risk, q.o_ego, nn));
     HIP_TRY(q.down(out.obst_risk, q.o_obst, nn));
@@ -310,7 +356,14 @@ static int risk_run(RiskPass &q, const FxRiskParams &p, bool detail, const RiskC
     }
     if (ca) {
         double *const pr[7] = {out.bayes, out.equality, out.maximin, out.ego, out.responsibility, out.total, out.boundary_harm};
-        for (int k = 0; k < 7; k++) HIP_TRY(q.down(pr[k], q.o_out + sizeof(double) * k * nn, nn));
+        for (int k = 0; k < 7; k++) {
+            if (rs && (k == 4 || k == 5)) continue;   // (the responsibility pass answers these two from its own sum, below)
+            HIP_TRY(q.down(pr[k], q.o_out + sizeof(double) * k * nn, nn));
+        }
+    }
+    if (rs) {
+        HIP_TRY(q.down(out.responsibility, q.o_rresp, nn));
+        HIP_TRY(q.down(out.total, q.o_rtot, nn));
     }
     long long idx[2] = {-1, -1};   // (the second one: the cost pass's arg-min)
     HIP_TRY(hipMemcpyAsync(idx, d_idx, sizeof(long long) * (ca ? 2 : 1), hipMemcpyDeviceToHost, c->stream));
@@ -328,7 +381,7 @@ extern "C" int32_t fx_eval_risk_agent(FxContext *c, int32_t agent, const FxRiskP
                                       double *ego_risk, double *obst_risk, int64_t *min_risk_index) {
     RiskPass q;
     int rc = risk_check(q, c, agent, params, n_ids, ids, ego_risk && obst_risk && min_risk_index, false);
-    if (rc || (rc = risk_stage(q, false, nullptr))) return rc;
+    if (rc || (rc = risk_stage(q, false, nullptr, 0, q.r->decomposition == FX_RISK_DECOMP_ITEMS))) return rc;
     FxRiskOutputs out{};
     out.ego_risk = ego_risk, out.obst_risk = obst_risk, out.min_risk_index = min_risk_index;
     return risk_run(q, *params, false, nullptr, out);
@@ -370,79 +423,160 @@ extern "C" int32_t fx_set_reach_sets_agent(FxContext *c, int32_t agent, int32_t 
     return FX_OK;
 }
 
+// the checks of a cost pass's parameters against the agent's obstacles, reach sets and horizon
+static int risk_cost_check(const RiskPass &q, const FxRiskCostParams *cost) {
+    const FxRiskAgent &a = *q.a;
+    const int S = q.S, K = q.K;
+    if (cost->boundary_mode < FX_RISK_BOUNDARY_ZERO || cost->boundary_mode > FX_RISK_BOUNDARY_STEP ||
+        (cost->boundary_mode == FX_RISK_BOUNDARY_ARRAY && !cost->boundary_harm))
+        return set_err(FX_ERR_INVALID_ARGUMENT, "boundary_mode %d", cost->boundary_mode);
+    if (cost->responsibility_mode < FX_RISK_RESP_NONE || cost->responsibility_mode > FX_RISK_RESP_REACH_SET ||
+        (cost->responsibility_mode == FX_RISK_RESP_ACTION_SPACE && K > 0 && !cost->responsibility))
+        return set_err(FX_ERR_INVALID_ARGUMENT, "responsibility_mode %d", cost->responsibility_mode);
+    if (cost->responsibility_mode == FX_RISK_RESP_REACH_SET) {
+        for (size_t e = 0; e < a.rs_obs.size(); e++)
+            if (a.rs_obs[e] >= K)
+                return set_err(FX_ERR_INVALID_ARGUMENT, "reach-set entry %d: obstacle index %d is not among the %d predictions", (int)e,
+                               a.rs_obs[e], K);
+        for (size_t t = 0; t < a.rs_step.size(); t++)
+            if (a.rs_step[t] >= S)
+                return set_err(FX_ERR_INVALID_ARGUMENT, "reach-set part %d: step index %d outside the horizon (S=%d)", (int)t, a.rs_step[t], S);
+    }
+    return FX_OK;
+}
+
+// the uploads of a staged cost pass and the argument block of its kernel
+static int risk_cost_args(const RiskPass &q, const FxRiskCostParams *cost, RiskCostArgs &ca) {
+    const FxAgentSlot &s = *q.s;
+    const FxRiskAgent &a = *q.a;
+    const int S = q.S, K = q.K;
+    const int64_t n = q.n;
+    const size_t nE = q.nE, nP = q.nP, nV = q.nV;
+    if (cost->boundary_mode == FX_RISK_BOUNDARY_ARRAY && n > 0) HIP_TRY(q.up(q.o_bh, cost->boundary_harm, sizeof(double) * n));
+    if (cost->responsibility_mode == FX_RISK_RESP_ACTION_SPACE && K > 0) HIP_TRY(q.up(q.o_resp, cost->responsibility, sizeof(double) * K));
+    if (nE > 0) {
+        HIP_TRY(q.up(q.o_eobs, a.rs_obs.data(), sizeof(int32_t) * nE));
+        HIP_TRY(q.up(q.o_eoff, a.rs_off.data(), sizeof(int32_t) * (nE + 1)));
+        if (nP > 0) {
+            HIP_TRY(q.up(q.o_pst, a.rs_step.data(), sizeof(int32_t) * nP));
+            HIP_TRY(q.up(q.o_voff, a.rs_voff.data(), sizeof(int32_t) * (nP + 1)));
+            HIP_TRY(q.up(q.o_vert, a.rs_verts.data(), sizeof(double) * 2 * nV));
+        }
+    }
+    ca.col = q.D(q.o_col);
+    ca.n = n;
+    ca.ids = q.d_ids();
+    ca.flags = q.flags;
+    ca.planes = q.planes;
+    ca.ld = q.ld;
+    ca.S = S;
+    ca.K = K;
+    ca.bh_in = cost->boundary_mode == FX_RISK_BOUNDARY_ARRAY ? q.D(q.o_bh) : nullptr;
+    ca.bstep = (cost->boundary_mode == FX_RISK_BOUNDARY_STEP && (s.mode & FX_MODE_ROAD_BOUNDARY)) ? q.bstep : nullptr;
+    ca.bh_c = cost->boundary_c;
+    ca.bh_s = cost->boundary_s;
+    ca.resp_mode = cost->responsibility_mode;
+    ca.n_entries = (int32_t)nE;
+    ca.resp = q.D(q.o_resp);
+    ca.entry_obs = q.I(q.o_eobs);
+    ca.entry_off = q.I(q.o_eoff);
+    ca.part_step = q.I(q.o_pst);
+    ca.vert_off = q.I(q.o_voff);
+    ca.verts = q.D(q.o_vert);
+    for (int k = 0; k < 5; k++) ca.w[k] = cost->weights[k];
+    ca.eps = cost->maximin_eps;
+    ca.scale = cost->maximin_scale;
+    ca.out = q.D(q.o_out);
+    return FX_OK;
+}
+
 extern "C" int32_t fx_eval_risk_costs_agent(FxContext *c, int32_t agent, const FxRiskParams *params, const FxRiskCostParams *cost,
                                             int64_t n_ids, const int64_t *ids, const FxRiskOutputs *out) {
     RiskPass q;
     int rc = risk_check(q, c, agent, params, n_ids, ids, out != nullptr, true);
     if (rc) return rc;
-    const FxAgentSlot &s = *q.s;
-    const FxRiskAgent &a = *q.a;
-    const int S = q.S, K = q.K;
-    const int64_t n = q.n;
-    const bool reach = cost && cost->responsibility_mode == FX_RISK_RESP_REACH_SET;
-    if (cost) {
-        if (cost->boundary_mode < FX_RISK_BOUNDARY_ZERO || cost->boundary_mode > FX_RISK_BOUNDARY_STEP ||
-            (cost->boundary_mode == FX_RISK_BOUNDARY_ARRAY && !cost->boundary_harm))
-            return set_err(FX_ERR_INVALID_ARGUMENT, "boundary_mode %d", cost->boundary_mode);
-        if (cost->responsibility_mode < FX_RISK_RESP_NONE || cost->responsibility_mode > FX_RISK_RESP_REACH_SET ||
-            (cost->responsibility_mode == FX_RISK_RESP_ACTION_SPACE && K > 0 && !cost->responsibility))
-            return set_err(FX_ERR_INVALID_ARGUMENT, "responsibility_mode %d", cost->responsibility_mode);
-        if (reach) {
-            for (size_t e = 0; e < a.rs_obs.size(); e++)
-                if (a.rs_obs[e] >= K)
-                    return set_err(FX_ERR_INVALID_ARGUMENT, "reach-set entry %d: obstacle index %d is not among the %d predictions", (int)e,
-                                   a.rs_obs[e], K);
-            for (size_t t = 0; t < a.rs_step.size(); t++)
-                if (a.rs_step[t] >= S)
-                    return set_err(FX_ERR_INVALID_ARGUMENT, "reach-set part %d: step index %d outside the horizon (S=%d)", (int)t, a.rs_step[t], S);
-        }
-    }
-    if ((rc = risk_stage(q, true, cost))) return rc;
+    if (cost) FX_TRY(risk_cost_check(q, cost));
+    if ((rc = risk_stage(q, true, cost, 0, q.r->decomposition == FX_RISK_DECOMP_ITEMS))) return rc;
     RiskCostArgs ca{};
-    if (cost) {
-        const size_t nE = q.nE, nP = q.nP, nV = q.nV;
-        if (cost->boundary_mode == FX_RISK_BOUNDARY_ARRAY && n > 0) HIP_TRY(q.up(q.o_bh, cost->boundary_harm, sizeof(double) * n));
-        if (cost->responsibility_mode == FX_RISK_RESP_ACTION_SPACE && K > 0) HIP_TRY(q.up(q.o_resp, cost->responsibility, sizeof(double) * K));
-        if (nE > 0) {
-            HIP_TRY(q.up(q.o_eobs, a.rs_obs.data(), sizeof(int32_t) * nE));
-            HIP_TRY(q.up(q.o_eoff, a.rs_off.data(), sizeof(int32_t) * (nE + 1)));
-            if (nP > 0) {
-                HIP_TRY(q.up(q.o_pst, a.rs_step.data(), sizeof(int32_t) * nP));
-                HIP_TRY(q.up(q.o_voff, a.rs_voff.data(), sizeof(int32_t) * (nP + 1)));
-                HIP_TRY(q.up(q.o_vert, a.rs_verts.data(), sizeof(double) * 2 * nV));
-            }
-        }
-        ca.col = q.D(q.o_col);
-        ca.n = n;
-        ca.ids = q.d_ids();
-        ca.flags = q.flags;
-        ca.planes = q.planes;
-        ca.ld = q.ld;
-        ca.S = S;
-        ca.K = K;
-        ca.bh_in = cost->boundary_mode == FX_RISK_BOUNDARY_ARRAY ? q.D(q.o_bh) : nullptr;
-        ca.bstep = (cost->boundary_mode == FX_RISK_BOUNDARY_STEP && (s.mode & FX_MODE_ROAD_BOUNDARY)) ? q.bstep : nullptr;
-        ca.bh_c = cost->boundary_c;
-        ca.bh_s = cost->boundary_s;
-        ca.resp_mode = cost->responsibility_mode;
-        ca.n_entries = (int32_t)nE;
-        ca.resp = q.D(q.o_resp);
-        ca.entry_obs = q.I(q.o_eobs);
-        ca.entry_off = q.I(q.o_eoff);
-        ca.part_step = q.I(q.o_pst);
-        ca.vert_off = q.I(q.o_voff);
-        ca.verts = q.D(q.o_vert);
-        for (int k = 0; k < 5; k++) ca.w[k] = cost->weights[k];
-        ca.eps = cost->maximin_eps;
-        ca.scale = cost->maximin_scale;
-        ca.out = q.D(q.o_out);
-    }
+    if (cost) FX_TRY(risk_cost_args(q, cost, ca));
     return risk_run(q, *params, true, cost ? &ca : nullptr, *out);
+}
+
+extern "C" int32_t fx_set_risk_decomposition(FxContext *c, int32_t mode) {
+    if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
+    if (mode != FX_RISK_DECOMP_WALK && mode != FX_RISK_DECOMP_ITEMS) return set_err(FX_ERR_INVALID_ARGUMENT, "risk decomposition %d", mode);
+    risk_state(c)->decomposition = mode;
+    return FX_OK;
+}
+
+// The responsibility cost as a weighted term of the step's cost (fxplan.h): the detail pass in the item
+// decomposition, the responsibility part of the cost pass over its columns, and the re-sum with its arg-min.
+extern "C" int32_t fx_eval_responsibility_cost_agent(FxContext *c, int32_t agent, const FxRiskParams *params, const FxRespCostParams *resp,
+                                                     int64_t n_ids, const int64_t *ids, const FxRespCostOutputs *out) {
+    FX_TRY(check_agent(c, agent));
+    if (!fx_inputs_current(c))   // (the condition of fx_eval_prediction_prob_agent: the planes and cost rows are the last evaluated step's)
+        return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
+    if (!(c->slots[agent].mode & FX_MODE_WRITE_COSTMAP)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_COSTMAP");
+    RiskPass q;
+    FX_TRY(risk_check(q, c, agent, (params && resp) ? params : nullptr, n_ids, ids,
+                      out && out->resp && out->total && out->ego_risk && out->obst_risk && out->best_index && out->best_cost, true));
+    if (!(resp->weight != 0.0) || resp->weight != resp->weight) return set_err(FX_ERR_INVALID_ARGUMENT, "responsibility weight %g", resp->weight);
+    if (resp->responsibility_mode != FX_RISK_RESP_ACTION_SPACE && resp->responsibility_mode != FX_RISK_RESP_REACH_SET)
+        return set_err(FX_ERR_INVALID_ARGUMENT, "responsibility_mode %d", resp->responsibility_mode);
+    FxRiskCostParams cost{};   // the cost pass with the responsibility alone: no boundary harm, total = the responsibility cost
+    cost.weights[4] = 1.0;
+    cost.maximin_scale = 1.0;
+    cost.boundary_mode = FX_RISK_BOUNDARY_ZERO;
+    cost.responsibility_mode = resp->responsibility_mode;
+    cost.responsibility = resp->responsibility;
+    FX_TRY(risk_cost_check(q, &cost));
+    const DevProblem &hp = c->h_probs[agent];
+    RespSumArgs rs{};
+    rs.n_pred = -1;
+    rs.at = hp.n_cost;   // in front of the first name behind "responsibility" in the sorted list
+    for (int m = hp.n_cost - 1; m >= 0; m--) {
+        if (hp.cost_id[m] == FX_COST_PREDICTION) rs.n_pred = m;
+        if (hp.cost_id[m] > FX_COST_PREDICTION) rs.at = m;
+    }
+    const uint32_t need = FX_FLAG_COSTED;
+    FX_TRY(risk_stage(q, true, &cost, 0, true, need, true));
+    RiskCostArgs ca{};
+    FX_TRY(risk_cost_args(q, &cost, ca));
+    if (!q.ids && q.n > 0) {
+        // every candidate: the cost kernel's own rule for that (VALID, FEASIBLE and RETURNED) is not this pass's (COSTED), so it gets
+        // the identity list and evaluates every row; the rows of candidates without a cost are NaN columns in, NaN out, never read
+        std::vector<int64_t> all((size_t)q.n);
+        for (int64_t j = 0; j < q.n; j++) all[(size_t)j] = j;
+        HIP_TRY(q.up(q.o_ids, all.data(), sizeof(int64_t) * all.size()));
+        HIP_TRY(hipStreamSynchronize(c->stream));   // (the list is a local)
+        ca.ids = reinterpret_cast<const int64_t *>(q.base + q.o_ids);
+    }
+    if (resp->prediction && q.n > 0) HIP_TRY(q.up(q.o_rpred, resp->prediction, sizeof(double) * q.n));
+    rs.n = q.n, rs.ids = q.d_ids(), rs.flags = q.flags, rs.need = need;
+    rs.resp = q.D(q.o_out) + 4 * (size_t)q.n;
+    rs.pred = (resp->prediction && rs.n_pred >= 0) ? q.D(q.o_rpred) : nullptr;
+    rs.costmap = q.sparse ? q.set.costmap : c->d_costmap + (size_t)FX_NUM_COSTS * q.s->cand_off;
+    rs.ld = q.ld;
+    rs.n_cost = hp.n_cost;
+    // (a sparse set's rows were closed by the list kernel, which never defers)
+    rs.deferred = (!q.sparse && (hp.mode & FX_MODE_INT_DEFER_OBST)) ? 1 : 0;
+    for (int m = 0; m < hp.n_cost; m++) rs.cost_w[m] = hp.cost_w[m];
+    rs.w_resp = resp->weight;
+    rs.resp_out = q.D(q.o_rresp), rs.total = q.D(q.o_rtot);
+    FxRiskOutputs ro{};
+    ro.ego_risk = out->ego_risk, ro.obst_risk = out->obst_risk, ro.responsibility = out->resp, ro.total = out->total;
+    FX_TRY(risk_run(q, *params, true, &ca, ro, &rs));
+    long long best[2] = {-1, 0};
+    HIP_TRY(hipMemcpy(best, q.base + q.o_rbest, sizeof(best), hipMemcpyDeviceToHost));
+    // (sparse set: the arg-min ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
+    if (q.sparse && best[0] >= 0) best[0] = (long long)q.set.ids[best[0]];
+    *out->best_index = (int64_t)best[0];
+    memcpy(out->best_cost, &best[1], sizeof(double));
+    return FX_OK;
 }
 
 // Collision probability as the prediction cost (fxplan.h).  The scratch holds the per-step probabilities of
 // one batch of candidates, [K][S - 1][batch]: the batch bounds it to FX_PREDPROB_SCRATCH_BYTES where one candidate's share allows.
-#define FX_PREDPROB_SCRATCH_BYTES ((size_t)64 << 20)
 extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, const FxPredProbParams *params, int64_t n_ids,
                                                  const int64_t *ids, const FxPredProbOutputs *out) {
     FX_TRY(check_agent(c, agent));

@@ -12,9 +12,11 @@
 #include "fx_step_kernel.h"
 #include "fx_risk_kernel.h"
 #include "fx_predprob_kernel.h"
+#include "fx_risk_items_kernel.h"
 #include "fx_gather_kernel.h"
 #include "fx_sort_kernel.h"
 #include "fx_selftest_kernel.h"
+#include "fx_pass.h"
 
 using fxk::wave_count;
 
@@ -340,14 +342,31 @@ extern "C" hipError_t fx_launch_topk(const DevProblem *d_probs, int n_agents, in
 
 // trajectory risk (fx_risk_kernel.h; DESIGN.md sections 11 and 13) over the w.n listed candidates: the walk -- the plain one, or
 // with col / out_occ the detail one -- and the arg-min of ego + obst into out_idx[0]; then, cost != null, the cost pass over the
-// columns and the arg-min of its total into out_idx[1].  ev_start / ev_stop (may be null) bracket all of them
+// columns and the arg-min of its total into out_idx[1].  ev_start / ev_stop (may be null) bracket all of them.
+// items != null: the walk in the item decomposition (fx_risk_items_kernel.h), in batches of items->nb
+// candidates -- per batch the (tile, chunk, obstacle) items and the finish kernel -- into the same outputs.  resp != null: behind
+// the cost pass the re-sum of the step's cost with the responsibility term and its arg-min into resp_idx[0 .. 1].
 extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const FxRiskParams *params, double *out_ego, double *out_obst,
                                      double *col, double *out_occ, const RiskCostArgs *cost, long long *out_idx, hipEvent_t ev_start,
-                                     hipEvent_t ev_stop, hipStream_t stream) {
+                                     hipEvent_t ev_stop, hipStream_t stream, const RiskItemArgs *items, const RespSumArgs *resp,
+                                     long long *resp_idx) {
     const RiskWalkArgs &w = *walk;
     if (ev_start) { hipError_t e = hipEventRecord(ev_start, stream); if (e != hipSuccess) return e; }
     const dim3 grid((unsigned)((w.n + 255) / 256));
-    if (w.n > 0 && col)
+    if (items) {
+        const RiskItemArgs &it = *items;
+        for (int64_t j0 = 0; j0 < w.n; j0 += it.nb) {
+            const int64_t m = std::min<int64_t>(it.nb, w.n - j0);
+            const dim3 igrid((unsigned)((m + 63) / 64), (unsigned)it.chunks, (unsigned)w.K), fgrid((unsigned)((m + 255) / 256));
+            if (col) {
+                if (w.K > 0 && w.S > 1) hipLaunchKernelGGL(fxri::fx_risk_item_kernel<true>, igrid, dim3(64), 0, stream, w, it, j0);
+                hipLaunchKernelGGL(fxri::fx_risk_items_finish_kernel<true>, fgrid, dim3(256), 0, stream, w, it, j0, out_ego, out_obst, col, out_occ);
+            } else {
+                if (w.K > 0 && w.S > 1) hipLaunchKernelGGL(fxri::fx_risk_item_kernel<false>, igrid, dim3(64), 0, stream, w, it, j0);
+                hipLaunchKernelGGL(fxri::fx_risk_items_finish_kernel<false>, fgrid, dim3(256), 0, stream, w, it, j0, out_ego, out_obst, col, out_occ);
+            }
+        }
+    } else if (w.n > 0 && col)
         hipLaunchKernelGGL(fxrisk::fx_risk_detail_kernel, grid, dim3(256), 0, stream, w.planes, w.ld, w.S, w.n, w.ids, w.flags, w.rec,
                            w.obs, w.pos, w.yaw, w.vo, w.K, w.P, *params, out_ego, out_obst, col, out_occ);
     else if (w.n > 0)
@@ -359,25 +378,22 @@ extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const FxRiskParam
         hipLaunchKernelGGL(fxrisk::fx_risk_cost_argmin_kernel, dim3(1), dim3(1024), 0, stream, cost->out + 5 * (size_t)w.n, w.n, w.ids,
                            out_idx + 1);
     }
+    if (resp) {
+        if (w.n > 0) hipLaunchKernelGGL(fxri::fx_resp_finish_kernel, grid, dim3(256), 0, stream, *resp);
+        hipLaunchKernelGGL(fxpp::fx_predprob_argmin_kernel, dim3(1), dim3(1024), 0, stream, resp->total, w.n, w.ids, w.flags, resp_idx);
+    }
     if (ev_stop) { hipError_t e = hipEventRecord(ev_stop, stream); if (e != hipSuccess) return e; }
     return hipGetLastError();
 }
 
 // collision probability as the prediction cost (fx_predprob_kernel.h) over the a.n listed candidates, in
 // batches of a.nb: per batch the (tile, chunk, obstacle) items and the finish kernel, then the arg-min of the total into out_idx.
-// Steps per chunk: as many as keep the call at FX_PREDPROB_WAVES items or more, at least one -- or what fx_predprob_set_chunk_steps
-// forces (tests: the results do not depend on it).  ev_start / ev_stop bracket all launches.
-#define FX_PREDPROB_WAVES 4096
+// Steps per chunk: fx_item_chunk_steps (fx_pass.h) -- or what fx_predprob_set_chunk_steps forces (tests: the results do not depend
+// on it).  ev_start / ev_stop bracket all launches.
 static std::atomic<int> fx_predprob_chunk_forced{0};
 extern "C" void fx_predprob_set_chunk_steps(int32_t steps) { fx_predprob_chunk_forced.store(steps > 0 ? steps : 0, std::memory_order_relaxed); }
 extern "C" int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K) {
-    const int forced = fx_predprob_chunk_forced.load(std::memory_order_relaxed);
-    const int steps = S - 1 > 0 ? S - 1 : 1;
-    if (forced > 0) return std::min(forced, steps);
-    const int64_t per_step = ((n + 63) / 64) * std::max(K, 1);   // items of a call with one step per chunk
-    int cs = 1;
-    while (cs < steps && per_step * ((steps + 2 * cs - 1) / (2 * cs)) >= FX_PREDPROB_WAVES) cs *= 2;
-    return std::min(cs, steps);
+    return fx_item_chunk_steps(n, S, K, fx_predprob_chunk_forced.load(std::memory_order_relaxed));
 }
 extern "C" hipError_t fx_launch_predprob(const PredProbArgs *args, long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
                                          hipStream_t stream) {

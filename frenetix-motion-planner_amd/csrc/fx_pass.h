@@ -30,6 +30,19 @@ struct FxEventPair {
     }
 };
 
+// Steps per chunk of an item decomposition -- one wave per (tile of 64 candidates, chunk of steps, obstacle) -- over n candidates,
+// S - 1 steps and K obstacles: as many as keep the call at FX_ITEM_WAVES items or more, at least one -- or `forced` > 0, a test's
+// choice.  The one rule of the prediction-probability launcher (fx_kernels.hip) and the risk items (fx_api_risk.hip).  Pure: no HIP call.
+#define FX_ITEM_WAVES 4096
+inline int fx_item_chunk_steps(int64_t n, int S, int K, int forced) {
+    const int steps = S - 1 > 0 ? S - 1 : 1;
+    if (forced > 0) return std::min(forced, steps);
+    const int64_t per_step = ((n + 63) / 64) * std::max(K, 1);   // items of a call with one step per chunk
+    int cs = 1;
+    while (cs < steps && per_step * ((steps + 2 * cs - 1) / (2 * cs)) >= FX_ITEM_WAVES) cs *= 2;
+    return std::min(cs, steps);
+}
+
 // wait for everything on the context's stream; what stays unknown is what a caller's own stream may hold (FxContext.tail_work)
 inline int fx_drain(FxContext *c) {
     HIP_TRY(hipStreamSynchronize(c->stream));

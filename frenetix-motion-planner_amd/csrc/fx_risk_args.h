@@ -45,6 +45,32 @@ struct RiskWalkArgs {
     int32_t K, P;
 };
 
+// the item decomposition of the candidate walk (fx_risk_items_kernel.h), device pointers
+struct RiskItemArgs {
+    const FxRiskParams *params;// the call's parameters, in device memory
+    double *part;              // [K][chunks][NV][nb] partials of one batch of nb candidates (NV = 2, detail 7)
+    int64_t nb;                // candidates per batch: whole tiles of 64
+    int32_t cs, chunks;        // steps per chunk, chunks = ceil(max(S - 1, 1) / cs)
+    uint32_t need;             // ids == null: the flags a candidate needs; the others get NaN rows
+};
+
+// arguments of the responsibility term's re-sum (fx_resp_finish_kernel), device pointers
+struct RespSumArgs {
+    int64_t n;
+    const int64_t *ids;        // [n] or null: every candidate, NaN rows for the ones that lack a flag of `need`
+    const uint32_t *flags;     // [ld]
+    uint32_t need;
+    const double *resp;        // [n] responsibility cost (row 4 of the cost pass's output)
+    const double *pred;        // [n] prediction entry to use instead of the step's own, or null
+    const double *costmap;     // [n_cost][ld] raw cost rows of the step
+    int64_t ld;
+    int32_t n_cost, n_pred;    // n_pred: position of FX_COST_PREDICTION in the cost list, -1 without one
+    int32_t at;                // the term is added in front of entry `at` of the cost list (n_cost: behind all)
+    int32_t deferred;          // the step closed its sum in the obstacle kernel (FX_MODE_INT_DEFER_OBST)
+    double cost_w[FX_NUM_COSTS], w_resp;
+    double *resp_out, *total;  // [n]
+};
+
 struct RiskCostArgs {
     const double *col;         // [4][K][n]: ego_risk_max | obst_risk_max | ego_harm_max | obst_harm_max of the detail pass
     int64_t n;

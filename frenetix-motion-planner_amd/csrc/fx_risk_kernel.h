@@ -130,6 +130,30 @@ __device__ __forceinline__ double step_probability(const FxRiskParams &p, const 
     return prob / 3.0;
 }
 
+// harm of ego point (x, y, th, v) against a prediction (px, py, yo, vob) of an obstacle (harm_estimation.py:282-300): the ego's
+// and the obstacle's.  Shared by the candidate walk below and the item kernel of fx_risk_items_kernel.h.
+__device__ __forceinline__ void step_harm(const FxRiskParams &p, bool prot, double f_ego, double f_obs, double x, double y, double th,
+                                          double v, double yo, double vob, double px, double py, double &he, double &ho) {
+    const double pdof = (yo - th) + 3.141592653589793;
+    const double rel = atan2(py - y, px - x);
+    const double dv = sqrt((v * v + vob * vob) + ((2.0 * v) * vob) * cos(pdof));
+    const double dve = f_ego * dv, dvo = f_obs * dv;
+    if (prot) {
+        if (p.prot_model == FX_RISK_HARM_LOGISTIC) {
+            const double ae = angle_coef(p, rel - th), ao = angle_coef(p, (3.141592653589793 + rel) - yo);
+            he = 1.0 / (1.0 + exp(((-p.prot_c) - p.prot_s * dve) - ae));
+            ho = 1.0 / (1.0 + exp(((-p.prot_c) - p.prot_s * dvo) - ao));
+        } else {
+            he = ref_speed(dve, p.prot_ref, p.prot_exp);
+            ho = ref_speed(dvo, p.prot_ref, p.prot_exp);
+        }
+    } else {
+        he = p.unprot_ego_model == FX_RISK_HARM_LOGISTIC ? 1.0 / (1.0 + exp((-p.uego_c) - p.uego_s * dve))
+                                                         : ref_speed(dve, p.uego_ref, p.uego_exp);
+        ho = 1.0 / (1.0 + exp(p.ped_c - p.ped_s * dvo));
+    }
+}
+
 // The candidate walk of lane j.  DETAIL = false: ego / obstacle risk (max over obstacles of max over steps of harm x probability),
 // harm evaluated only where the probability is not zero.  DETAIL = true adds what calc_risk returns per
 // obstacle -- col [4][K][n] = ego_risk_max | obst_risk_max | ego_harm_max | obst_harm_max, obstacle-major, so that the 64 lanes of a
@@ -185,25 +209,8 @@ __device__ __forceinline__ void risk_walk(const double *__restrict__ planes, int
                 const double x = X[(size_t)t * ld], y = Y[(size_t)t * ld], th = TH[(size_t)t * ld], v = V[(size_t)t * ld];
                 const size_t kt = (size_t)k * P + t;
                 const double yo = yaw[kt], vob = vo[kt], px = pos[2 * kt], py = pos[2 * kt + 1];
-                const double pdof = (yo - th) + 3.141592653589793;
-                const double rel = atan2(py - y, px - x);
-                const double dv = sqrt((v * v + vob * vob) + ((2.0 * v) * vob) * cos(pdof));
-                const double dve = f_ego * dv, dvo = f_obs * dv;
                 double he, ho;
-                if (prot) {
-                    if (p.prot_model == FX_RISK_HARM_LOGISTIC) {
-                        const double ae = angle_coef(p, rel - th), ao = angle_coef(p, (3.141592653589793 + rel) - yo);
-                        he = 1.0 / (1.0 + exp(((-p.prot_c) - p.prot_s * dve) - ae));
-                        ho = 1.0 / (1.0 + exp(((-p.prot_c) - p.prot_s * dvo) - ao));
-                    } else {
-                        he = ref_speed(dve, p.prot_ref, p.prot_exp);
-                        ho = ref_speed(dvo, p.prot_ref, p.prot_exp);
-                    }
-                } else {
-                    he = p.unprot_ego_model == FX_RISK_HARM_LOGISTIC ? 1.0 / (1.0 + exp((-p.uego_c) - p.uego_s * dve))
-                                                                     : ref_speed(dve, p.uego_ref, p.uego_exp);
-                    ho = 1.0 / (1.0 + exp(p.ped_c - p.ped_s * dvo));
-                }
+                step_harm(p, prot, f_ego, f_obs, x, y, th, v, yo, vob, px, py, he, ho);
                 re = prob != 0.0 ? he * prob : 0.0;
                 ro = prob != 0.0 ? ho * prob : 0.0;
                 if (DETAIL) {

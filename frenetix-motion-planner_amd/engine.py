@@ -963,8 +963,57 @@ class FrenetEngine(StepRegistry):
 
     @property
     def last_risk_ms(self) -> float:
-        """device time of the last `risk` / `risk_detail` / `risk_costs` call (its kernels)"""
+        """device time of the last `risk` / `risk_detail` / `risk_costs` / `responsibility_cost` call (its kernels)"""
         return float(lib().fx_last_risk_ms(self._ctx))
+
+    # -- the walk in the item decomposition, the responsibility cost as a weighted term (DESIGN.md section 17) --
+    def set_risk_decomposition(self, mode: str = "walk"):
+        """How `risk`, `risk_detail` and `risk_costs` evaluate the (obstacle, step) pairs: "walk" (the default), one lane per
+        candidate over all of them, or "items", one wave per (tile of 64 candidates, chunk of steps, obstacle).  Every output is
+        the same bit for bit in both (fx_set_risk_decomposition)."""
+        if mode not in _abi.RISK_DECOMPOSITIONS:
+            raise ValueError(f"risk decomposition {mode!r}: one of {sorted(_abi.RISK_DECOMPOSITIONS)}")
+        check(lib().fx_set_risk_decomposition(self._ctx, _abi.RISK_DECOMPOSITIONS[mode]))
+
+    def responsibility_cost(self, params, cost_params, weight: float, ids=None, agent: int = 0, prediction: str = "step") -> dict:
+        """The `responsibility` cost term (partial_cost_functions.py:359-387) for candidates of the last plan step, on the device
+        (fx_eval_responsibility_cost_agent): resp [n], get_responsibility_cost over calc_risk's obst_risk_max in the mode of
+        cost_params (risk.risk_cost_params with responsibility= the [K] vector or "reach_set"; nothing else of it is read);
+        total [n], the step's weighted cost re-summed from its raw cost rows with weight * resp at its place in the name-sorted
+        list; ego_risk, obst_risk [n] as `risk` returns them; best_index / best_cost as `prediction_probability`; prediction, the
+        [n] entry summed instead of the step's own (None with "step").  ids None: every
+        candidate, NaN rows for the ones without a cost.  prediction "probability": the prediction entry of the re-sum is the
+        prob of `prediction_probability` (ego length and width of params) over the same candidates instead of the step's own.
+        Needs write_costmap, and the bundle or ids inside the agent's sparse set.  Nothing the step wrote is touched."""
+        if prediction not in ("step", "probability"):
+            raise ValueError(f"prediction {prediction!r}: 'step' or 'probability'")
+        K = getattr(self, "_risk_K", {}).get(agent, 0)
+        lens = getattr(cost_params, "_lengths", {})
+        if lens.get("responsibility", K) != K:
+            raise ValueError(f"responsibility has {lens['responsibility']} entries for {K} obstacles")
+        # (the library refuses these two as well: here they are refused before the probability pass below is launched)
+        if not float(weight) or np.isnan(float(weight)):
+            raise ValueError(f"responsibility weight {weight!r}: a non-zero number")
+        if cost_params.responsibility_mode not in (_abi.FX_RISK_RESP_ACTION_SPACE, _abi.FX_RISK_RESP_REACH_SET):
+            raise ValueError(f"responsibility_mode {cost_params.responsibility_mode}: the action-space factors or 'reach_set'")
+        pred = None
+        if prediction == "probability":
+            pred = np.ascontiguousarray(self.prediction_probability(params.ego_length, params.ego_width, ids=ids, agent=agent)["prob"])
+        n, n_ids, idp, ids = self._risk_ids(ids, agent)
+        rp = _abi.FxRespCostParams(float(weight), int(cost_params.responsibility_mode), cost_params.responsibility,
+                                   pred.ctypes.data if pred is not None and len(pred) else None)
+        res = {k: np.zeros(max(n, 1)) for k in ("resp", "total", "ego_risk", "obst_risk")}
+        best_index, best_cost = np.full(1, -1, np.int64), np.full(1, np.nan)
+        out = _abi.FxRespCostOutputs()
+        for k, a in res.items():
+            setattr(out, k, a.ctypes.data)
+        out.best_index, out.best_cost = best_index.ctypes.data, best_cost.ctypes.data
+        if n > 0 or ids is None:   # (an empty id list: nothing to evaluate, no arg-min)
+            check(lib().fx_eval_responsibility_cost_agent(self._ctx, int(agent), C.byref(params), C.byref(rp), n_ids, idp, C.byref(out)))
+        res = {k: a[:n] for k, a in res.items()}
+        res["best_index"], res["best_cost"] = int(best_index[0]), float(best_cost[0])
+        res["prediction"] = pred   # (the prediction entry that was summed instead of the step's own, or None)
+        return res
 
     # -- collision probability as the prediction cost (DESIGN.md section 16) --
     def prediction_probability(self, ego_length: float, ego_width: float, ids=None, agent: int = 0, per_obstacle: bool = False,

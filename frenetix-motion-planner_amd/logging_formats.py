@@ -74,10 +74,8 @@ class _BulkStep:
         self.cost = step.cost[ids]
         self.flags = step.flags[ids]
         inp = step.inputs
-        self.names = list(inp.cost_names)
-        cm = eng.costmap(agent)[ids] if self.names else np.zeros((len(ids), 0))
-        self.raw = cm
-        self.weights = np.array([inp.cost_weights[n] for n in self.names])
+        # the terms as costMap reports them: a pass beside the step may have replaced `prediction` and added `responsibility`
+        self.names, self.raw, self.weights = step.cost_columns(ids)
         self.params = np.array([inp.candidate_params(int(g) + inp.shard_begin) for g in ids]).reshape(len(ids), 13)
         self.dt = inp.dt
         self.samples = [step.sample(int(g)) for g in ids]  # cheap views; risk / harm fields live there

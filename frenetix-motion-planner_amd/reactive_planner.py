@@ -113,6 +113,10 @@ class PlannerConfig:
     # candidate, re-sums the cost with it, and the planner walks that order.  It reads the step's bundle and cost map:
     # sparse_bundle_k > 0 (a select-only step) is refused.
     prediction_cost: str = "inverse_mahalanobis"
+    # How cost_weights["responsibility"] != 0 computes get_responsibility_cost (partial_cost_functions.py:359-387; DESIGN.md section
+    # 17): "reach_set" (upstream's default: calc_responsibility_reach_set on set_reach_set's sets) or "action_space".  The term is
+    # evaluated by a pass beside the plan step, per sampling level; it needs set_risk_model and bundle mode (sparse_bundle_k = 0).
+    responsibility_mode: str = "reach_set"
 
 
 class ReactivePlannerHip:
@@ -256,6 +260,7 @@ class ReactivePlannerHip:
         self.cost_weights = dict(cost_weights)
         self._weights_nz = None
         self._check_prediction_cost()
+        self._check_responsibility_cost()
 
     def _check_prediction_cost(self):
         """PlannerConfig.prediction_cost against the rest of the configuration; True when the pass runs"""
@@ -268,6 +273,44 @@ class ReactivePlannerHip:
             raise ValueError("prediction_cost='collision_probability' reads the plan step's bundle and cost map: it needs bundle mode "
                              "(PlannerConfig.sparse_bundle_k = 0), not a select-only step")
         return True
+
+    def _check_responsibility_cost(self):
+        """cost_weights["responsibility"] against the rest of the configuration; True when the term is weighted"""
+        w = self.cost_weights.get("responsibility") if self.cost_weights else None
+        if not w:
+            return False
+        if self.config.responsibility_mode not in ("reach_set", "action_space"):
+            raise ValueError(f"PlannerConfig.responsibility_mode {self.config.responsibility_mode!r}: 'reach_set' or 'action_space'")
+        if getattr(self, "_risk_model", None) is None:
+            raise ValueError("cost_weights['responsibility'] needs the risk model: call set_risk_model before set_cost_function")
+        if self.config.sparse_bundle_k > 0:
+            raise ValueError("cost_weights['responsibility'] reads the plan step's bundle and cost map: it needs bundle mode "
+                             "(PlannerConfig.sparse_bundle_k = 0), not a select-only step")
+        return True
+
+    def _apply_responsibility_cost(self, step, probability: bool):
+        """the responsibility pass over the step's candidates, installed as the step's cost override together with -- probability
+        -- the collision probability as the prediction entry: ONE override.  Upstream's condition (partial_cost_functions.py:371):
+        without predictions, or in reach-set mode without a reach set, the term is 0.0 for every candidate and no pass runs:
+        costMap["responsibility"] is (0.0, 0.0) and the step's costs and orders stay its own."""
+        from . import risk
+        preds = self.predictions if self.use_prediction else None
+        mode = self.config.responsibility_mode
+        if preds is None or (mode == "reach_set" and self.reach_set is None):
+            if probability:
+                self._apply_prediction_cost(step)
+            step.set_cost_extras({"responsibility": (np.zeros(step.inputs.n_candidates), float(self.cost_weights["responsibility"]))})
+            return
+        tabs = self._set_risk_obstacles(step)
+        if mode == "action_space":
+            resp = risk.action_space_responsibility(preds, self.x_0.position, self.x_0.orientation)
+        else:
+            sets = self.reach_set.reach_sets[self.x_0.time_step]
+            step.engine.set_reach_sets(risk.reach_set_tables(sets, tabs["keys"], self.dT, step.inputs.n_samples), step.agent)
+            resp = "reach_set"
+        cp = risk.risk_cost_params([0.0, 0.0, 0.0, 0.0, 1.0], responsibility=resp)
+        step.apply_responsibility_cost(self._risk_model["params"], cp, float(self.cost_weights["responsibility"]),
+                                       prediction="probability" if probability else "step")
 
     def _apply_prediction_cost(self, step):
         """the collision-probability pass over the step's costed candidates, installed as the step's cost override.  The tables it
@@ -334,8 +377,10 @@ class ReactivePlannerHip:
         """Weights of the risk-cost total (bayes, equality, maximin, ego, responsibility: a dict by name or a sequence) and how
         the responsibility cost is computed: None (0), "action_space" (assign_responsibility_by_action_space on the ego state of the
         step) or "reach_set" (calc_responsibility_reach_set on set_reach_set's sets).  Upstream's `responsibility_costs` unpacks
-        six of calc_risk's seven values and reads `planner.reachset`, so it raises there; here the cost is a post-step evaluation
-        (risk_costs, the "min_risk_cost" fallback), not a weighted plan-step term.  DESIGN.md section 13."""
+        six of calc_risk's seven values and reads `planner.reachset`, so it raises there; here these weights serve the post-step
+        evaluation (risk_costs, the "min_risk_cost" fallback).  The responsibility cost as a weighted term of
+        the plan step's cost is cost_weights["responsibility"] with PlannerConfig.responsibility_mode,
+        independent of these weights."""
         from . import risk
         if responsibility_mode not in (None, "action_space", "reach_set"):
             raise ValueError(f"responsibility_mode {responsibility_mode!r}: None, 'action_space' or 'reach_set'")
@@ -539,7 +584,8 @@ class ReactivePlannerHip:
         weights, cw = self._weights_nz, self.cost_weights
         sig = tuple(cw.items())   # exact: an in-place swap of two weights keeps length and sum
         if weights is None or self._weights_src is not cw or self._weights_sig != sig:   # replaced, or edited in place
-            weights = self._weights_nz = {k: w for k, w in cw.items() if w != 0}
+            # (_abi.BESIDE_STEP_COSTS: evaluated by a pass beside the step, never among the weights the plan step is given)
+            weights = self._weights_nz = {k: w for k, w in cw.items() if w != 0 and k not in _abi.BESIDE_STEP_COSTS}
             self._weights_src, self._weights_sig = cw, sig
         prev = self._prev_inputs
         if (prev is not None and prev.cost_weights is weights and prev.coordinate_system is self.coordinate_system
@@ -584,6 +630,7 @@ class ReactivePlannerHip:
         if self.desired_velocity is None:
             raise RuntimeError("desired velocity not set (update_externals(desired_velocity=...))")
         self._check_prediction_cost()   # (a select-only configuration with the collision-probability cost: refused before any launch)
+        self._check_responsibility_cost()
         if stop_point_s is not None and stop_point_s < self.x_cl[0][0]:
             self.msg_logger.info("stop point behind current longitudinal position, falling back to regular planning")
             stop_point_s = None  # reactive_planner_cpp.py:263-264,336-341
@@ -603,6 +650,7 @@ class ReactivePlannerHip:
         if self.desired_velocity is None:
             raise RuntimeError("desired velocity not set (update_externals(desired_velocity=...))")
         self._check_prediction_cost()   # (a select-only configuration with the collision-probability cost: refused before any launch)
+        self._check_responsibility_cost()
         if stop_point_s is not None and stop_point_s < self.x_cl[0][0]:
             stop_point_s = None
         self._stop_point_s = stop_point_s
@@ -749,9 +797,13 @@ class ReactivePlannerHip:
         self._infeasible_count_kinematics = hist
         self.infeasible_kinematics_percentage = res["feasible_percentage"]
         self._collision_counter = res["n_collisions"]
-        if self._check_prediction_cost():
-            if not (inputs.write_bundle and inputs.write_costmap):
-                raise ValueError("prediction_cost='collision_probability' needs a plan step that stored the bundle and the cost map")
+        probability, responsibility = self._check_prediction_cost(), self._check_responsibility_cost()
+        if (probability or responsibility) and not (inputs.write_bundle and inputs.write_costmap):
+            raise ValueError("prediction_cost='collision_probability' and cost_weights['responsibility'] need a plan step that stored "
+                             "the bundle and the cost map")
+        if responsibility:
+            self._apply_responsibility_cost(step, probability)
+        elif probability:
             self._apply_prediction_cost(step)
         by_rank = bool(self.config.device_sort) and hasattr(engine, "ranked")
         if self._draw_traj_set or self.save_all_traj:

@@ -361,6 +361,8 @@ class PlanStepResult:
     _written = None                      # index -> {attribute: value}: what was assigned to samples from outside (TrajectorySample.__setattr__)
     _mat = _mat_ids = None               # materialise(): engine.materialise() of the listed indices (ascending) and those indices
     _override = None                     # set_cost_override(): (cost [C], raw prediction cost [C], best index within the shard or -1)
+    _extras = {}                         # set_cost_extras(): name -> (raw [C], weight) of the terms evaluated beside the step
+    _risk = None                         # apply_responsibility_cost(): (ego_risk [C], obst_risk [C]) of the pass
 
     def __init__(self, engine, inputs, result: dict, agent: int = 0):
         self.engine, self.inputs, self.result, self.agent = engine, inputs, result, agent
@@ -394,10 +396,12 @@ class PlanStepResult:
         return self._cost if self._override is None else self._override[0]
 
     # ---- a cost computed beside the step in place of the step's own ----
-    def set_cost_override(self, total, prediction, best_index):
+    def set_cost_override(self, total, prediction, best_index, extras=None):
         """Answer `cost`, TrajectorySample.cost and costMap["prediction"] from a pass that ran beside the step: total [C] the
         re-summed cost, prediction [C] the raw prediction cost it was summed with (NaN rows: candidates without a cost, which keep
-        the step's values), best_index the pass's winner within the shard (-1: none).  sorted_ids, ranked_ids,
+        the step's values), best_index the pass's winner within the shard (-1: none).  extras (optional): name -> (raw [C],
+        weight) of further terms the pass summed in, which the step does not know -- costMap[name] = (raw, weight * raw) for the
+        candidates whose raw value is not NaN.  sorted_ids, ranked_ids,
         sorted_trajectories and `best` then order by `total` with the host's stable argsort over the same pools; the device sort
         reads the step's own cost plane and is not used.  Install it before samples are handed out: a sample built earlier keeps
         the cost it was built with.  None (the default) changes nothing."""
@@ -406,8 +410,55 @@ class PlanStepResult:
         if total.shape != self._cost.shape or prediction.shape != self._cost.shape:
             raise ValueError(f"cost override of {total.shape} / {prediction.shape} entries for {self._cost.shape} candidates")
         costed = (self._flags & _abi.FX_FLAG_COSTED) != 0
+        self.set_cost_extras({name: (np.where(costed, np.asarray(raw, np.float64), np.nan), weight)
+                              for name, (raw, weight) in (extras or {}).items()})
         self._override = (np.where(costed, total, self._cost), np.where(costed, prediction, np.nan), int(best_index))
         self._host_orders = None
+
+    def set_cost_extras(self, extras):
+        """name -> (raw [C], weight): terms evaluated beside the step, which the step does not know.  costMap[name] = (raw,
+        weight * raw) for the candidates whose raw value is not NaN, and the bulk logs get a column per name.  Without
+        set_cost_override the step's costs and orders stay its own: that is for a term that is 0.0 for every candidate."""
+        ex = {}
+        for name, (raw, weight) in extras.items():
+            raw = np.asarray(raw, np.float64)
+            if raw.shape != (self.inputs.n_candidates,):
+                raise ValueError(f"extra term {name!r} of {raw.shape} entries for {self.inputs.n_candidates} candidates")
+            ex[name] = (raw, float(weight))
+        self._extras = ex
+
+    def cost_columns(self, ids):
+        """(names, raw [len(ids), n], weights [n]) of the cost terms of the candidates `ids` as costMap reports them: the step's
+        cost map with the override's prediction entry, then the extra terms (0.0 where a candidate has none)."""
+        names = list(self.inputs.cost_names)
+        raw = np.array(self.engine.costmap(self.agent)[ids], np.float64) if names else np.zeros((len(ids), 0))
+        weights = [self.inputs.cost_weights[n] for n in names]
+        if self._override is not None and "prediction" in names:
+            p, k = self._override[1][ids], names.index("prediction")
+            raw[:, k] = np.where(np.isnan(p), raw[:, k], p)
+        for name, (r, w) in self._extras.items():
+            names.append(name)
+            raw = np.column_stack([raw, np.nan_to_num(r[ids], nan=0.0)])
+            weights.append(w)
+        return names, raw, np.array(weights, np.float64)
+
+    def apply_responsibility_cost(self, params, cost_params, weight: float, prediction: str = "step"):
+        """Run engine.responsibility_cost over every candidate of this step -- the obstacles and reach sets are the engine's last
+        ones -- and install its result: total and best as the cost override, costMap["responsibility"], and _ego_risk /
+        _obst_risk of every sample of the step (partial_cost_functions.py:373-374).  prediction "probability": the collision
+        probability replaces the step's prediction entry in the same override.  Returns the pass's dict."""
+        self._check()
+        r = self.engine.responsibility_cost(params, cost_params, weight, agent=self.agent, prediction=prediction)
+        pred = r["prediction"] if r["prediction"] is not None else np.full(len(r["total"]), np.nan)
+        self.set_cost_override(r["total"], pred, r["best_index"], extras={"responsibility": (r["resp"], weight)})
+        self._risk = (r["ego_risk"], r["obst_risk"])
+        return r
+
+    def _risk_fields(self, t):
+        """_ego_risk / _obst_risk of a new sample from the responsibility pass (what was written to the candidate since wins)"""
+        rk = self._risk
+        if rk is not None and not np.isnan(rk[0][t.uniqueId]):
+            t.__dict__["_ego_risk"], t.__dict__["_obst_risk"] = float(rk[0][t.uniqueId]), float(rk[1][t.uniqueId])
 
     def apply_prediction_probability(self, ego_length: float, ego_width: float):
         """Run engine.prediction_probability over every candidate of this step -- the obstacles are the ones of the engine's last
@@ -422,6 +473,9 @@ class PlanStepResult:
         if ov is not None and "prediction" in costmap and not np.isnan(ov[1][index]):
             p = float(ov[1][index])
             costmap["prediction"] = (p, float(self.inputs.cost_weights["prediction"] * p))
+        for name, (raw, weight) in self._extras.items():
+            if not np.isnan(raw[index]):
+                costmap[name] = (float(raw[index]), float(weight * raw[index]))
         return costmap
 
     @property
@@ -586,6 +640,7 @@ class PlanStepResult:
             self._samples[index] = weakref.ref(t)
             if t._pkg is None and not self._open:
                 self._opened()
+            self._risk_fields(t)
             w = self._written
             if w is not None and index in w:   # an earlier object of this candidate was written to and dropped
                 t.__dict__.update(w[index])
@@ -665,6 +720,7 @@ class PlanStepResult:
             for t in TrajectorySample.bulk(self, todo):
                 known[t.uniqueId] = weakref.ref(t)
                 made[t.uniqueId] = t
+                self._risk_fields(t)
                 if w is not None and t.uniqueId in w:
                     t.__dict__.update(w[t.uniqueId])
         return [made.get(g) or self.sample(g) for g in ids]

@@ -315,15 +315,18 @@ int32_t fx_evaluate(FxContext *c) {
                                    pl.any_bundle, pl.any_obst, pl.any_extra, pl.wpe, k0, k1, fuse, c->stream));
     }
     if (timed && !attached) HIP_TRY(hipEventRecord(ts->e_eval, c->stream));
+    // one agent: the kernels of the split step take what their first loads need from their leading arguments (the host's copy of
+    // the problem is the staged one: fx_update_state rewrites it and the staging above has copied it)
+    const DevProblem *head = c->n_agents == 1 ? &c->h_probs[0] : nullptr;
     if (L.obstacle) {
         const bool t_obs = timed && c->timing == FX_TIMING_KERNEL;
         HIP_TRY(fx_launch_obstacle(c->d_probs, c->n_agents, pl.obs_blocks, L.obs_lds, pl.split_CH, t_obs ? ts->e_obs0 : nullptr,
-                                   t_obs ? ts->e_obs1 : nullptr, c->stream, L.obs_wg, pl.obs_tiles));
+                                   t_obs ? ts->e_obs1 : nullptr, c->stream, L.obs_wg, pl.obs_tiles, head));
         if (timed) ts->obst_timed = t_obs;
     }
     if (L.select)
         HIP_TRY(fx_launch_select(c->d_probs, c->n_agents, pl.C_max, c->h_counters.dev, c->seq, winner, host_pkg, c->pkg_stride,
-                                 c->pkg_plane_rows, c->stream));
+                                 c->pkg_plane_rows, c->stream, head));
     if (L.package)
         HIP_TRY(fx_launch_package(c->d_probs, c->n_agents, winner, c->h_pkg.dev, c->pkg_stride, c->pkg_plane_rows, c->seq, c->stream));
     if (timed && !L.one_launch) HIP_TRY(hipEventRecord(ts->e_end, c->stream));

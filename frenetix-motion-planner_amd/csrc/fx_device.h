@@ -14,6 +14,11 @@
 // walk (fx_obstacle_kernel.h): the walk leaves the cost sum up to the prediction term in cost[], the terms behind it in
 // cost_tail[], and no arg-min partial; the obstacle kernel completes cost / flags / cost map and writes the partials
 #define FX_MODE_INT_DEFER_OBST (1u << 29)
+// the walk of a split step whose bundle is stored write-through stores its per-candidate outputs (cost sums, flag words, list
+// entries, coefficients, cost map) write-through as well: nothing dirty is left for the kernel boundary in front of the obstacle kernel
+__host__ __device__ inline bool fx_split_wt(uint32_t mode) {
+    return (mode & (FX_MODE_INT_DEFER_OBST | FX_MODE_INT_STORE_WT)) == (FX_MODE_INT_DEFER_OBST | FX_MODE_INT_STORE_WT);
+}
 // internal DevProblem.mode bit: the agent's obstacle record table rec[S][K][12] and its two step masks are staged in the dynamic
 // LDS of the lane-split evaluation kernels (the host has sized the launch's LDS for them: fx_api.hip)
 #define FX_MODE_INT_REC_LDS (1u << 28)

@@ -243,7 +243,9 @@ __device__ __forceinline__ void fx_eval_grid_body(const DevProblem *__restrict__
     if (bundle && active && part == 0) {
         FX_GLOBAL double *__restrict__ co = as_global(P.coeffs) + g;
         // (write-through where the step's last workgroup gathers the winner package itself, fx_tail.h)
-        const bool wt = MEGA || (FX_TAIL_IN_KERNEL(G, false) && fuse.host_result != nullptr && (fuse.tail() & FX_TAIL_PACKAGE));
+        // (and in the split step with a write-through bundle, fx_split_wt: nothing dirty for the boundary behind this kernel)
+        const bool wt = MEGA || (!OBST && fx_split_wt(P.mode)) ||
+                        (FX_TAIL_IN_KERNEL(G, false) && fuse.host_result != nullptr && (fuse.tail() & FX_TAIL_PACKAGE));
         const double cv[FX_COEFF_ROWS] = {s0, ss0, .5 * sss0, cl3, cl4, cl5, L.c0, L.c1, L.c2, L.c3, L.c4, L.c5,
                                           tau};  // tau: PolynomialTrajectory.delta_tau of the lateral polynomial (reactive_planner.py:161-171)
 #pragma unroll

@@ -295,8 +295,12 @@ __device__ __forceinline__ void finish_candidate(const ProblemRegs &P, const Dev
     constexpr bool TAIL = FX_TAIL_IN_KERNEL(G, EXTRA);
     // MEGA (fx_step_kernel.h: the whole step in one launch): later phases of the SAME launch read what this one stores -- write-through
     const bool tail_mode = TAIL && fuse.host_result != nullptr && fuse.tail() != 0u;
-    const bool tail_pkg = MEGA || (tail_mode && (fuse.tail() & FX_TAIL_PACKAGE));
-    const bool out_wt = MEGA || tail_mode;
+    // Split step (deferred obstacle stage) with a write-through bundle: the obstacle kernel behind the boundary reads what this one
+    // stores, and what stays dirty in the L2s is written back AT the boundary, in front of that kernel's first wave -- so the
+    // per-candidate outputs leave with the planes, write-through, as in the one-launch step (a run-time choice: fx_split_wt)
+    const bool split_wt = !OBST && fx_split_wt(P.mode);
+    const bool tail_pkg = MEGA || split_wt || (tail_mode && (fuse.tail() & FX_TAIL_PACKAGE));
+    const bool out_wt = MEGA || split_wt || tail_mode;
     FX_GLOBAL double *__restrict__ planes = as_global(P.planes);
     const FX_GLOBAL double *__restrict__ obs_pos = as_global(P.obs_pos);
     const FX_GLOBAL double *__restrict__ obs_cov_inv = as_global(P.obs_cov_inv);
@@ -522,10 +526,10 @@ __device__ __forceinline__ void finish_candidate(const ProblemRegs &P, const Dev
         const int src = __ffsll((long long)live_mask) - 1;
         const unsigned lo = (unsigned)__shfl((int)(unsigned)(list_base & 0xffffffffULL), src);   // (lists stay below 2^31 entries)
         if (active && leader && costed)
-            st_out(as_global(P.obs_list) + (lo + __popcll(live_mask & ((1ULL << (tid & 63)) - 1ULL))), (int32_t)g, MEGA);
+            st_out(as_global(P.obs_list) + (lo + __popcll(live_mask & ((1ULL << (tid & 63)) - 1ULL))), (int32_t)g, MEGA || split_wt);
     }
     if (active && leader) {
-        if (defer) st_out(as_global(P.cost_tail) + g, tail, MEGA);
+        if (defer) st_out(as_global(P.cost_tail) + g, tail, MEGA || split_wt);
         st_out(as_global(P.cost) + g, costed ? (have_pre ? pre : total) : 0.0, out_wt);
         st_out(as_global(P.flags) + g, flags, out_wt);
         if (OBST && (P.mode & FX_MODE_ROAD_BOUNDARY)) as_global(P.bound_step)[g] = (selectable && off_road) ? (int)bound_step : -1;
@@ -552,9 +556,12 @@ __device__ __forceinline__ void finish_candidate(const ProblemRegs &P, const Dev
     const bool eligible = own && selectable && !(flags & (FX_FLAG_COLLISION | FX_FLAG_BOUNDARY)) && total == total;
     double bc = eligible ? total : INFINITY;
     long long bi = eligible ? (long long)(g + P.g_base) : 0x7fffffffffffffffLL;
+    // Deferred obstacle stage behind a selection kernel: the obstacle kernel owns this agent's partials (its totals are not known
+    // here), so nothing below reads an arg-min of this kernel -- neither the wave's nor the workgroup's is formed.
+    const bool no_argmin = defer && fuse.host_result == nullptr;
     // wave arg-min: candidate indices grow with the lane, so the (cost, index) minimum is the LOWEST lane that
     // holds the minimum cost -- a min-reduction of the cost alone plus one ballot
-    {
+    if (!no_argmin) {
         double m = bc;
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off));
@@ -562,8 +569,8 @@ __device__ __forceinline__ void finish_candidate(const ProblemRegs &P, const Dev
         const int src = hit ? __ffsll((long long)hit) - 1 : 0;
         bc = m;
         bi = hit ? __shfl(bi, src) : 0x7fffffffffffffffLL;
+        if (lane == 0) { red_cost[wave] = bc; red_idx[wave] = bi; }
     }
-    if (lane == 0) { red_cost[wave] = bc; red_idx[wave] = bi; }
     FX_STAMP(9);
     // tail mode: this wave's cost / flag / coefficient / plane stores are performed before the workgroup takes its ticket
     if (tail_mode) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -572,8 +579,9 @@ __device__ __forceinline__ void finish_candidate(const ProblemRegs &P, const Dev
     // theirs is the agent's last workgroup.
     if (wave != 0 && !tail_mode) return;
     if (wave == 0) {
-        for (int w = 1; w < (int)blockDim.x / 64; w++)
-            if (red_cost[w] < bc || (red_cost[w] == bc && red_idx[w] < bi)) { bc = red_cost[w]; bi = red_idx[w]; }
+        if (!no_argmin)
+            for (int w = 1; w < (int)blockDim.x / 64; w++)
+                if (red_cost[w] < bc || (red_cost[w] == bc && red_idx[w] < bi)) { bc = red_cost[w]; bi = red_idx[w]; }
         if (lane == 0 && !defer) {   // deferred obstacle stage: fx_obstacle_kernel owns this agent's partials
             // agent-scope stores: visible to whichever XCD runs the reducing workgroup without an L2 write-back
             __hip_atomic_store(as_global(P.part_cost) + blockIdx.x, bc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -823,7 +831,9 @@ __global__ __launch_bounds__(FX_BLOCK, WPE) void fx_eval_kernel(const DevProblem
     if (bundle && active && part == 0) {
         FX_GLOBAL double *__restrict__ co = as_global(P.coeffs) + g;
         // (write-through where the step's last workgroup gathers the winner package itself, fx_tail.h)
-        const bool wt = FX_TAIL_IN_KERNEL(G, EXTRA) && fuse.host_result != nullptr && (fuse.tail() & FX_TAIL_PACKAGE);
+        // (and in the split step with a write-through bundle, fx_split_wt: nothing dirty for the boundary behind this kernel)
+        const bool wt = (!OBST && fx_split_wt(P.mode)) ||
+                        (FX_TAIL_IN_KERNEL(G, EXTRA) && fuse.host_result != nullptr && (fuse.tail() & FX_TAIL_PACKAGE));
         const double cv[FX_COEFF_ROWS] = {cl0, cl1, cl2, cl3, cl4, cl5, L.c0, L.c1, L.c2, L.c3, L.c4, L.c5,
                                           tau};  // tau: PolynomialTrajectory.delta_tau of the lateral polynomial (reactive_planner.py:161-171)
 #pragma unroll

@@ -253,24 +253,34 @@ extern "C" hipError_t fx_launch_eval_grid(const DevProblem *d_probs, int n_agent
 // The obstacle stage as its own kernel (fx_obstacle_kernel.h): grid = (max tiles x chunks, n_agents), one wave per item,
 // dynamic LDS = CH * K * 48 B.
 extern "C" hipError_t fx_launch_obstacle(const DevProblem *d_probs, int n_agents, int max_items, size_t lds_bytes, int CH,
-                                         hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream, int wg_waves, int max_tiles) {
+                                         hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream, int wg_waves, int max_tiles,
+                                         const DevProblem *head) {
     // wg_waves > 0: one workgroup of wg_waves waves per tile (the chunks meet in LDS), grid = (max_tiles, n_agents)
+    // head (one agent): the HEAD kernels, with the step header in their leading arguments (fx_obstacle_kernel.h, ObstHead)
+    const bool hd = head && n_agents == 1;
+    const DevProblem none{};
+    const DevProblem &h = hd ? *head : none;
+#define FX_LAUNCH_K(CHv, WGv, HDv, grid, block)                                                                                         \
+    do {                                                                                                                            \
+        if (const hipError_t e_ = fx_allow_dynamic_lds<&fxk::fx_obstacle_kernel<CHv, 4, WGv, HDv>>(lds_bytes); e_ != hipSuccess) return e_; \
+        hipExtLaunchKernelGGL((fxk::fx_obstacle_kernel<CHv, 4, WGv, HDv>), grid, block, lds_bytes, stream, ev_start, ev_stop, 0, d_probs,   \
+                              h.obs_list, h.counters, h.obs_hot, h.C, h.S, h.K, h.mode);                                             \
+        return hipGetLastError();                                                                                                   \
+    } while (0)
 #define FX_LAUNCH(CHv)                                                                                                                \
     do {                                                                                                                            \
         if (wg_waves > 0) {                                                                                                         \
-            if (const hipError_t e_ = fx_allow_dynamic_lds<&fxk::fx_obstacle_kernel<CHv, 4, true>>(lds_bytes); e_ != hipSuccess) return e_; \
-            hipExtLaunchKernelGGL((fxk::fx_obstacle_kernel<CHv, 4, true>), dim3(max_tiles, n_agents), dim3(64 * wg_waves), lds_bytes, stream, \
-                                  ev_start, ev_stop, 0, d_probs);                                                                   \
-        } else {                                                                                                                    \
-            hipExtLaunchKernelGGL((fxk::fx_obstacle_kernel<CHv, 4, false>), dim3(max_items, n_agents), dim3(64), lds_bytes, stream, ev_start, \
-                                  ev_stop, 0, d_probs);                                                                             \
+            if (hd) FX_LAUNCH_K(CHv, true, true, dim3(max_tiles, n_agents), dim3(64 * wg_waves));                                     \
+            FX_LAUNCH_K(CHv, true, false, dim3(max_tiles, n_agents), dim3(64 * wg_waves));                                            \
         }                                                                                                                           \
-        return hipGetLastError();                                                                                                   \
+        if (hd) FX_LAUNCH_K(CHv, false, true, dim3(max_items, n_agents), dim3(64));                                                   \
+        FX_LAUNCH_K(CHv, false, false, dim3(max_items, n_agents), dim3(64));                                                          \
     } while (0)
     if (CH == 2) FX_LAUNCH(2);
     if (CH == 3) FX_LAUNCH(3);
     if (CH == 5) FX_LAUNCH(5);
 #undef FX_LAUNCH
+#undef FX_LAUNCH_K
     return hipErrorInvalidValue;
 }
 
@@ -312,15 +322,20 @@ extern "C" hipError_t fx_launch_step(const DevProblem *d_probs, int n_agents, in
     return hipErrorInvalidValue;
 }
 
+// head (as in fx_launch_obstacle): the host's copy of the ONE agent's problem, whose fields the kernel's first loads need travel
+// as leading kernel arguments (fx_select.h, SelectHead); nullptr for a batch.
 extern "C" hipError_t fx_launch_select(const DevProblem *d_probs, int n_agents, int64_t max_candidates, unsigned long long *host_result,
                                        unsigned long long seq, double *dev_winner, double *host_pkg, int pkg_stride, int pkg_plane_rows,
-                                       hipStream_t stream) {
+                                       hipStream_t stream, const DevProblem *head) {
     // one slice per ~4 096 candidates of the largest agent, at least 32 (the small-step tuning), a power of two, at most 512
     int slices = FX_SELECT_SLICES_MIN;
     while (slices < FX_SELECT_SLICES_MAX && (int64_t)slices * 4096 < max_candidates) slices *= 2;
     // batched launches: keep the grid around a thousand workgroups (every workgroup reduces all of an agent's partials)
     while (slices > FX_SELECT_SLICES_MIN && (int64_t)slices * n_agents > 2048) slices /= 2;
-    hipLaunchKernelGGL(fx_select_kernel, dim3(slices, n_agents), dim3(256), 0, stream, d_probs, host_result, seq, dev_winner,
+    const DevProblem none{};   // (the header's counts are 32-bit: a larger agent reads its problem like a batch)
+    const DevProblem &h = head && n_agents == 1 && head->C < ((int64_t)1 << 31) ? *head : none;
+    hipLaunchKernelGGL(fx_select_kernel, dim3(slices, n_agents), dim3(256), 0, stream, d_probs, h.flags, h.cost, h.part_cost, h.part_idx,
+                       (int32_t)h.C, (int32_t)((h.C + slices - 1) / slices), h.n_blocks, h.mode, h.counters, host_result, seq, dev_winner,
                        host_pkg, pkg_stride, pkg_plane_rows);
     return hipGetLastError();
 }

@@ -89,17 +89,29 @@ __device__ __forceinline__ double obs_four(double a, double b, double c, double 
 //     what the walk wrote;
 //   * what the selection phase reads is stored write-through.
 // The arithmetic is the same instruction sequence either way.
+// What the item's FIRST batch of loads (count, list entries, hot table) needs of the problem.  A launch for one agent carries it in
+// fx_obstacle_kernel's leading arguments, which the device build preloads into scalar registers (Makefile): that batch then goes
+// out beside the loads of the problem's other fields -- problem | (count, list, table) -> rows -- instead of behind them.
+struct ObstHead {
+    const int32_t *obs_list;
+    const unsigned long long *counters;
+    const double *obs_hot;
+    int64_t C;
+    int32_t S, K;
+    uint32_t mode;
+    __device__ __forceinline__ static ObstHead of(const DevProblem &P) { return ObstHead{P.obs_list, P.counters, P.obs_hot, P.C, P.S, P.K, P.mode}; }
+};
 template <int CH, bool WG, bool COH>
-__device__ __forceinline__ void fx_obstacle_body(const DevProblem &P, double *__restrict__ lds_all, const int tile, const int chunk,
-                                                 const long long n_live_known = -1) {
+__device__ __forceinline__ void fx_obstacle_body(const DevProblem &P, const ObstHead &H, double *__restrict__ lds_all, const int tile,
+                                                 const int chunk, const long long n_live_known = -1) {
     static_assert(!COH || !WG, "the one-launch step runs single-wave items");
     auto LD = [](auto p) { return *p; };
     auto ST = [](auto p, auto v) { if (COH) st_agent(p, v); else *p = v; };
-    const uint32_t mode = P.mode;
+    const uint32_t mode = H.mode;
     if (!(mode & FX_MODE_INT_DEFER_OBST)) return;
-    const int S = P.S, K = P.K;
+    const int S = H.S, K = H.K;
     const int NC = (S - 1 + CH - 1) / CH;
-    const int64_t C = P.C, ld = P.ld;
+    const int64_t C = H.C, ld = P.ld;
     const int n_wave = WG ? (int)(blockDim.x >> 6) : 1;
     const int64_t c0 = (int64_t)tile * 64;
     if (c0 >= C) return;
@@ -114,15 +126,15 @@ __device__ __forceinline__ void fx_obstacle_body(const DevProblem &P, double *__
     // The kernel's floor is a chain of dependent round trips (problem -> count -> list -> rows), so the count, the tile's list
     // entries and the chunk's slice of the hot table are requested TOGETHER: the list slot c0 + lane always exists (c0 < C <= ld);
     // past the list's end it holds whatever an earlier step left -- clamped to a valid candidate, loaded from, never stored for.
-    const FX_GLOBAL unsigned long long *cnt_live = as_global(P.counters) + FX_DCNT_LIVE;
+    const FX_GLOBAL unsigned long long *cnt_live = as_global(H.counters) + FX_DCNT_LIVE;
     unsigned long long n_live_raw = 0ULL;
     int32_t g_listed = 0;
     if (!COH) {
         n_live_raw = *cnt_live;
-        g_listed = as_global(P.obs_list)[c0 + lane];
+        g_listed = as_global(H.obs_list)[c0 + lane];
     } else {
         n_live_raw = (unsigned long long)n_live_known;
-        g_listed = ld_agent(as_global(P.obs_list) + (c0 + lane));
+        g_listed = ld_agent(as_global(H.obs_list) + (c0 + lane));
     }
 
     const int i_a = 1 + chunk * CH, i_b = min(S, i_a + CH);
@@ -132,7 +144,7 @@ __device__ __forceinline__ void fx_obstacle_body(const DevProblem &P, double *__
     // the chunk's slice of the hot table -> LDS: per (step, obstacle) the addends (cu, cw) as one 16-byte pair, then the hull
     // circles (hx2, hy2, hr2, ck) as 32 bytes; entry e of the slice is handled by lane e, e + 64, ... (two entries in flight).
     // The first round's loads go out here, its LDS writes follow the row requests below.
-    const auto hot_a = as_table<COH>(P.obs_hot) + (size_t)i_a * K * FX_HOT_STRIDE;   // (COH: constant address space, fx_device.h)
+    const auto hot_a = as_table<COH>(H.obs_hot) + (size_t)i_a * K * FX_HOT_STRIDE;   // (COH: constant address space, fx_device.h)
     fx_d2 *__restrict__ cc_tab = reinterpret_cast<fx_d2 *>(lds_dyn);   // [CH][K]
     double *__restrict__ circ_tab = lds_dyn + 2 * (size_t)CH * K;       // [CH][K][4]
     const int n_e = max((i_b - i_a) * K, 0);
@@ -433,14 +445,19 @@ __device__ __forceinline__ void fx_obstacle_body(const DevProblem &P, double *__
     FX_OSTAMP(15);
 }
 
-template <int CH, int WPS, bool WG = false>
-__global__ __launch_bounds__(WG ? 1024 : 64, WG ? FX_OBST_WG_WPE : WPS) void fx_obstacle_kernel(const DevProblem *__restrict__ probs) {
+// HEAD: the launch has one agent and the leading arguments are its step header (ObstHead; probs .. h_K are the 12 preloaded dwords);
+// a batched launch runs the HEAD = false kernel, which reads every agent's problem first, as before.
+template <int CH, int WPS, bool WG = false, bool HEAD = false>
+__global__ __launch_bounds__(WG ? 1024 : 64, WG ? FX_OBST_WG_WPE : WPS) void fx_obstacle_kernel(
+    const DevProblem *__restrict__ probs, const int32_t *h_obs_list, const unsigned long long *h_counters, const double *h_obs_hot, int64_t h_C,
+    int32_t h_S, int32_t h_K, uint32_t h_mode) {
     extern __shared__ __attribute__((aligned(16))) double lds_all[];  // per wave: (cu, cw) [CH][K][2] | hull circles [CH][K][4]
     const DevProblem &P = probs[blockIdx.y];
-    const int NC = (P.S - 1 + CH - 1) / CH;
+    const ObstHead H = HEAD ? ObstHead{h_obs_list, h_counters, h_obs_hot, h_C, h_S, h_K, h_mode} : ObstHead::of(P);
+    const int NC = (H.S - 1 + CH - 1) / CH;
     const int tile = WG ? (int)blockIdx.x : (int)(blockIdx.x / NC);
     const int chunk = WG ? (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(blockIdx.x - tile * NC);
-    fx_obstacle_body<CH, WG, false>(P, lds_all, tile, chunk);
+    fx_obstacle_body<CH, WG, false>(P, H, lds_all, tile, chunk);
 }
 
 }  // namespace fxk

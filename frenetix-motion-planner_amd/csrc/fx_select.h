@@ -28,12 +28,26 @@ __device__ __forceinline__ void fx_lex_wave_min(double &bc, long long &bi) {
 
 #define FX_SELECT_SLICES_MIN 32
 #define FX_SELECT_SLICES_MAX 512
+// What the body's FIRST batch of loads needs of the problem.  fx_select_kernel hands it over in its leading kernel arguments (which
+// the device build preloads into scalar registers, Makefile) when the launch has one agent: the batch then goes out with no scalar
+// load in front of it -- beside the loads of the problem's other fields instead of behind them.  per: candidates per slice.
+struct SelectHead {
+    const uint32_t *flags;
+    const double *cost, *part_cost;
+    const int64_t *part_idx;
+    const unsigned long long *counters;
+    int64_t C, per;
+    uint32_t mode;
+    __device__ __forceinline__ static SelectHead of(const DevProblem &P, int n_slices) {
+        return SelectHead{P.flags, P.cost, P.part_cost, P.part_idx, P.counters, P.C, (P.C + n_slices - 1) / n_slices, P.mode};
+    }
+};
 // The body, for workgroup `slice` of `n_slices` of agent `agent` (256 lanes).  COH (fx_step_kernel.h: the selection as the last
 // phase of a one-launch step): partials, flag words and costs were written by other workgroups of the launch that is still
 // running (agent-scope stores, acknowledged before the grid barrier) -- agent-scope loads; `n_part` = how many partials exist.
 template <bool COH>
-__device__ __forceinline__ void fx_select_body(const DevProblem &P, const int agent, const int slice, const int n_slices, const int n_part,
-                                               unsigned long long *host_result, unsigned long long seq, double *dev_winner,
+__device__ __forceinline__ void fx_select_body(const DevProblem &P, const SelectHead &H, const int agent, const int slice, const int n_slices,
+                                               const int n_part, unsigned long long *host_result, unsigned long long seq, double *dev_winner,
                                                double *host_pkg, int pkg_stride, int pkg_plane_rows) {
     __shared__ double sc[4];
     __shared__ long long si[4];
@@ -46,14 +60,14 @@ __device__ __forceinline__ void fx_select_body(const DevProblem &P, const int ag
     // Everything that does not depend on the winner is requested NOW, together with the partials -- the first eight (flag, cost)
     // pairs per thread of this workgroup's slice (the whole slice up to 2 048 candidates: planner-sized steps, config 3) and the
     // step's counters: the kernel is a chain of memory round trips, and these two used to be links of their own.
-    const bool count_mode = (P.mode & FX_MODE_COLLISION) != 0;
-    const int64_t per = (P.C + n_slices - 1) / n_slices;
-    const int64_t g0 = min(P.C, (int64_t)slice * per), g1 = min(P.C, g0 + per);
+    const bool count_mode = (H.mode & FX_MODE_COLLISION) != 0;
+    const int64_t per = H.per;
+    const int64_t g0 = min(H.C, (int64_t)slice * per), g1 = min(H.C, g0 + per);
     uint32_t f_pre[8];
     double c_pre[8];
     if (count_mode) {
-        const FX_GLOBAL uint32_t *__restrict__ fl = as_global(P.flags);
-        const FX_GLOBAL double *__restrict__ co = as_global(P.cost);
+        const FX_GLOBAL uint32_t *__restrict__ fl = as_global(H.flags);
+        const FX_GLOBAL double *__restrict__ co = as_global(H.cost);
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             const int64_t gu = g0 + tid + u * 256;
@@ -62,12 +76,12 @@ __device__ __forceinline__ void fx_select_body(const DevProblem &P, const int ag
         }
     }
     unsigned long long cnt_pre = 0ULL;
-    if (tid < FX_CNT_BEST_IDX) cnt_pre = LD(as_global(P.counters) + tid);   // (accumulated by the evaluation kernel, which is complete)
+    if (tid < FX_CNT_BEST_IDX) cnt_pre = LD(as_global(H.counters) + tid);   // (accumulated by the evaluation kernel, which is complete)
     {
         // the partials were written by the evaluation kernel, which is complete: plain loads, four per thread in flight
         // (device-coherent atomic loads, as the in-kernel selection needs them, serialise at ~1 us each)
-        const FX_GLOBAL double *__restrict__ pc = as_global(P.part_cost);
-        const FX_GLOBAL int64_t *__restrict__ pi = as_global(P.part_idx);
+        const FX_GLOBAL double *__restrict__ pc = as_global(H.part_cost);
+        const FX_GLOBAL int64_t *__restrict__ pi = as_global(H.part_idx);
         for (int b0 = tid; b0 < n_part; b0 += 4 * 256) {
             double c[4];
             long long ix[4];
@@ -92,8 +106,8 @@ __device__ __forceinline__ void fx_select_body(const DevProblem &P, const int ag
     const bool none = bi == 0x7fffffffffffffffLL;
     // colliding selectable candidates ordered before the winner (all of them when nothing is collision-free)
     if (count_mode) {
-        const FX_GLOBAL uint32_t *__restrict__ fl = as_global(P.flags);
-        const FX_GLOBAL double *__restrict__ co = as_global(P.cost);
+        const FX_GLOBAL uint32_t *__restrict__ fl = as_global(H.flags);
+        const FX_GLOBAL double *__restrict__ co = as_global(H.cost);
         unsigned int cnt = 0;
 #pragma unroll
         for (int u = 0; u < 8; u++) {   // the pairs requested at entry
@@ -163,10 +177,19 @@ __device__ __forceinline__ void fx_select_body(const DevProblem &P, const int ag
     }
 }
 
-__global__ __launch_bounds__(256) void fx_select_kernel(const DevProblem *__restrict__ probs, unsigned long long *host_result,
-                                                        unsigned long long seq, double *dev_winner, double *host_pkg, int pkg_stride,
-                                                        int pkg_plane_rows) {
+// The leading arguments are the step header (SelectHead; probs .. h_mode are preloaded: 14 dwords, what the hardware's user registers
+// hold beside the kernel-argument pointer), valid when the launch has one agent of fewer than 2^31 candidates -- any other launch
+// passes h_flags == nullptr and every workgroup reads its agent's problem first, as before.
+__global__ __launch_bounds__(256) void fx_select_kernel(const DevProblem *__restrict__ probs, const uint32_t *h_flags, const double *h_cost,
+                                                        const double *h_part_cost, const int64_t *h_part_idx, int32_t h_C, int32_t h_per,
+                                                        int32_t h_n_part, uint32_t h_mode, const unsigned long long *h_counters,
+                                                        unsigned long long *host_result, unsigned long long seq, double *dev_winner,
+                                                        double *host_pkg, int pkg_stride, int pkg_plane_rows) {
     const DevProblem &P = probs[blockIdx.y];
-    fx_select_body<false>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x, P.n_blocks, host_result, seq, dev_winner, host_pkg, pkg_stride,
-                          pkg_plane_rows);
+    if (h_flags)   // (a branch, not a select: the header's loads must not wait for the problem's)
+        fx_select_body<false>(P, SelectHead{h_flags, h_cost, h_part_cost, h_part_idx, h_counters, h_C, h_per, h_mode}, (int)blockIdx.y,
+                              (int)blockIdx.x, (int)gridDim.x, h_n_part, host_result, seq, dev_winner, host_pkg, pkg_stride, pkg_plane_rows);
+    else
+        fx_select_body<false>(P, SelectHead::of(P, (int)gridDim.x), (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x, P.n_blocks, host_result,
+                              seq, dev_winner, host_pkg, pkg_stride, pkg_plane_rows);
 }

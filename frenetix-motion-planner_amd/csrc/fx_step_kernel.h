@@ -114,7 +114,7 @@ __global__ __launch_bounds__(FX_BLOCK, 3) void fx_step_kernel(const DevProblem *
         const int n_items = n_tiles * NC;
         for (int item = (int)blockIdx.x * n_wave + wave; item < n_items; item += n_w) {
             const int grp = item / NC;
-            fx_obstacle_body<CH, false, true>(P, my_lds, grp, item - grp * NC, n_live);
+            fx_obstacle_body<CH, false, true>(P, ObstHead::of(P), my_lds, grp, item - grp * NC, n_live);
         }
     }
     (void)lane;
@@ -123,8 +123,8 @@ __global__ __launch_bounds__(FX_BLOCK, 3) void fx_step_kernel(const DevProblem *
     FX_MSTAMP(10);
 
     // ---- phase 3: selection; slices = the launch's workgroups of this agent ----
-    fx_select_body<true>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x, n_tiles, sa.host_result, sa.seq, sa.dev_winner, sa.host_pkg,
-                         sa.pkg_stride, sa.pkg_plane_rows);
+    fx_select_body<true>(P, SelectHead::of(P, (int)gridDim.x), (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x, n_tiles, sa.host_result, sa.seq, sa.dev_winner,
+                         sa.host_pkg, sa.pkg_stride, sa.pkg_plane_rows);
     FX_MSTAMP(11);
 }
 

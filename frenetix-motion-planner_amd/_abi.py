@@ -5,7 +5,7 @@ wrapper (oracle/oracle.py) can share the struct definitions.
 """
 import ctypes as C
 
-FX_ABI_VERSION = 14
+FX_ABI_VERSION = 15
 FX_READ_CHUNK_BYTES = 8 << 20   # fx_read_candidates_agent: bytes per chunk (ids + packed records)
 FX_LON_VELOCITY_KEEPING, FX_LON_STOP_POINT = 0, 1
 
@@ -165,10 +165,8 @@ class FxPredProbOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("prob", "prob_obs", "total", "best_index", "best_cost")]
 
 
-# the risk walk's decomposition and the responsibility cost as a weighted term (fxplan.h)
+# the responsibility cost as a weighted term (fxplan.h)
 BESIDE_STEP_COSTS = ("responsibility",)   # cost names the planner evaluates by a pass beside the plan step (PlanInputs refuses them)
-FX_RISK_DECOMP_WALK, FX_RISK_DECOMP_ITEMS = 0, 1
-RISK_DECOMPOSITIONS = {"walk": FX_RISK_DECOMP_WALK, "items": FX_RISK_DECOMP_ITEMS}
 
 
 class FxRespCostParams(C.Structure):

@@ -45,7 +45,7 @@ def exported_symbols():
         "fx_materialise_candidates_agent", "fx_read_materialised_agent", "fx_read_package_materialised", "fx_last_materialise_ms",
         "fx_sort_candidates_agent", "fx_sort_candidates_batch", "fx_read_ranked_agent", "fx_sort_views", "fx_last_sort_ms",
         "fx_eval_prediction_prob_agent", "fx_last_predprob_ms",
-        "fx_set_risk_decomposition", "fx_eval_responsibility_cost_agent",
+        "fx_eval_responsibility_cost_agent",
     ]
 
 
@@ -161,7 +161,6 @@ def lib():
         # (launcher hook of the tests, not part of fxplan.h: steps per chunk of the prediction-probability items, 0 = automatic)
         "fx_predprob_set_chunk_steps": ([C.c_int32], None),
         "fx_predprob_chunk_steps": ([C.c_int64, C.c_int32, C.c_int32], C.c_int32),
-        "fx_set_risk_decomposition": ([vp, C.c_int32], C.c_int32),
         "fx_eval_responsibility_cost_agent": ([vp, C.c_int32, C.POINTER(_abi.FxRiskParams), C.POINTER(_abi.FxRespCostParams), C.c_int64,
                                                pi64, C.POINTER(_abi.FxRespCostOutputs)], C.c_int32),
         # (hook of the tests, not part of fxplan.h: steps per chunk of the risk items, 0 = automatic)

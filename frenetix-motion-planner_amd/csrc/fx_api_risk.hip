@@ -11,10 +11,9 @@
 #include "fx_pass.h"
 #include "fx_risk_args.h"
 
-extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const FxRiskParams *params, double *out_ego, double *out_obst,
-                                     double *col, double *out_occ, const RiskCostArgs *cost, long long *out_idx, hipEvent_t ev_start,
-                                     hipEvent_t ev_stop, hipStream_t stream, const RiskItemArgs *items, const RespSumArgs *resp,
-                                     long long *resp_idx);
+extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const RiskItemArgs *items, double *out_ego, double *out_obst, double *col,
+                                     double *out_occ, const RiskCostArgs *cost, long long *out_idx, hipEvent_t ev_start,
+                                     hipEvent_t ev_stop, hipStream_t stream, const RespSumArgs *resp, long long *resp_idx);
 extern "C" hipError_t fx_launch_predprob(const PredProbArgs *args, long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
                                          hipStream_t stream);
 
@@ -44,7 +43,6 @@ struct FxRiskState {
     FxEventPair ev;          // around a pass's launches; read at once into the two times below
     float last_ms = 0.f;
     float last_pp_ms = -1.f;   // fx_eval_prediction_prob_agent
-    int decomposition = FX_RISK_DECOMP_WALK;   // fx_set_risk_decomposition
 };
 
 void fx_risk_release(FxRiskState *r) { delete r; }
@@ -184,8 +182,7 @@ struct RiskPass {
     size_t o_occ, o_col;                                                 // detail pass only
     size_t o_out, o_bh, o_resp, o_eobs, o_eoff, o_pst, o_voff, o_vert;   // cost pass only
     size_t o_pstep, o_pprob, o_pobs, o_ptot, o_pbest;                    // prediction-probability pass only
-    bool items = false;      // the walk in the item decomposition (fx_risk_items_kernel.h): `it`, its partials at o_part
-    RiskItemArgs it{};
+    RiskItemArgs it{};       // the items of the walk (fx_risk_kernel.h): their partials at o_part, the parameters at o_prm
     size_t o_part, o_prm;
     const FxRiskParams *prm;   // the call's parameters (risk_check)
     size_t o_rresp, o_rtot, o_rpred, o_rbest;                            // responsibility pass only
@@ -255,9 +252,6 @@ static int risk_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskPara
     return FX_OK;
 }
 
-// The scratch of the passes that work in items -- the per-step probabilities of fx_eval_prediction_prob_agent, the partials of the
-// risk items -- holds one batch of candidates: the batch bounds it to FX_PREDPROB_SCRATCH_BYTES where one candidate's share allows.
-#define FX_PREDPROB_SCRATCH_BYTES ((size_t)64 << 20)
 // Steps per chunk of the risk items (fx_item_chunk_steps, fx_pass.h), or what fx_risk_items_set_chunk_steps forces (tests: the
 // results do not depend on it)
 static std::atomic<int> fx_risk_items_chunk_forced{0};
@@ -269,10 +263,9 @@ extern "C" int32_t fx_risk_items_chunk_steps(int64_t n, int32_t S, int32_t K) {
 // The device block of a pass and the uploads every pass makes.  One grow-only allocation, every part 256-byte aligned; the plain
 // pass takes no room for the detail pass's columns, and only a pass with cost parameters for their outputs and tables.
 // pp_nb > 0: the prediction-probability pass with batches of pp_nb candidates -- room for its per-step scratch and outputs.
-// items: the walk runs in the item decomposition -- room for the partials of one batch, the batch sized so that they stay within
-// FX_PREDPROB_SCRATCH_BYTES where one candidate's share allows; need: the flags a candidate needs when no ids are given.
-// resp: the responsibility pass -- room for its outputs.
-static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, size_t pp_nb = 0, bool items = false,
+// Every other pass has a walk -- room for the partials of one batch of its items (fx_item_batch, fx_pass.h) and for the call's
+// parameters; need: the flags a candidate needs when no ids are given.  resp: the responsibility pass -- room for its outputs.
+static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, size_t pp_nb = 0,
                       uint32_t need = FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED, bool resp = false) {
     FxContext *c = q.c;
     FxRiskState *r = q.r;
@@ -298,17 +291,15 @@ static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, si
         q.o_pprob = lay.take(sizeof(double) * n1), q.o_pobs = lay.take(sizeof(double) * K * n1), q.o_ptot = lay.take(sizeof(double) * n1);
         q.o_pbest = lay.take(2 * sizeof(long long));
     }
-    q.items = items;
-    if (items) {
+    const bool walk = pp_nb == 0;
+    if (walk) {
         const size_t steps = (size_t)std::max(q.S - 1, 1), nv = detail ? 7 : 2;
         q.it.cs = fx_risk_items_chunk_steps(q.n, q.S, q.K);
         q.it.chunks = (int32_t)((steps + q.it.cs - 1) / q.it.cs);
         const size_t per_cand = sizeof(double) * nv * std::max<size_t>(K, 1) * (size_t)q.it.chunks;
-        size_t nb = std::max<size_t>(FX_PREDPROB_SCRATCH_BYTES / per_cand / 64, 1) * 64;   // whole tiles
-        nb = std::min(nb, (n1 + 63) / 64 * 64);
-        q.it.nb = (int64_t)nb;
+        q.it.nb = fx_item_batch(per_cand, q.n);
         q.it.need = need;
-        q.o_part = lay.take(per_cand * nb), q.o_prm = lay.take(sizeof(FxRiskParams));
+        q.o_part = lay.take(per_cand * (size_t)q.it.nb), q.o_prm = lay.take(sizeof(FxRiskParams));
     }
     if (resp) {
         q.o_rresp = lay.take(sizeof(double) * n1), q.o_rtot = lay.take(sizeof(double) * n1), q.o_rpred = lay.take(sizeof(double) * n1);
@@ -319,12 +310,12 @@ static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, si
     FX_TRY(r->block.ensure(lay.size()));
     FX_TRY(r->ev.ensure());
     q.base = r->block;
-    if (items) {
+    if (walk) {
         q.it.part = q.D(q.o_part);
         q.it.params = reinterpret_cast<const FxRiskParams *>(q.base + q.o_prm);
-        HIP_TRY(q.up(q.o_prm, q.prm, sizeof(FxRiskParams)));
     }
-    if (q.K > 0) {
+    if (q.K > 0) {   // (without an obstacle no kernel reads any of these)
+        if (walk) HIP_TRY(q.up(q.o_prm, q.prm, sizeof(FxRiskParams)));
         HIP_TRY(q.up(q.o_rec, q.rec.data(), sizeof(double) * q.rec.size()));
         HIP_TRY(q.up(q.o_obs, a.obs.data(), sizeof(double) * a.obs.size()));
         HIP_TRY(q.up(q.o_pos, a.pos.data(), sizeof(double) * a.pos.size()));
@@ -336,15 +327,14 @@ static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, si
 }
 
 // The launches of a pass (fx_launch_risk), the read-back of what the caller asked for, and the device time
-static int risk_run(RiskPass &q, const FxRiskParams &p, bool detail, const RiskCostArgs *ca, const FxRiskOutputs &out,
-                    const RespSumArgs *rs = nullptr) {
+static int risk_run(RiskPass &q, bool detail, const RiskCostArgs *ca, const FxRiskOutputs &out, const RespSumArgs *rs = nullptr) {
     FxContext *c = q.c;
     FxRiskState *r = q.r;
     const RiskWalkArgs w{q.planes, q.ld, q.S, q.n, q.d_ids(), q.flags, q.D(q.o_rec), q.D(q.o_obs),
                          q.D(q.o_pos), q.D(q.o_yaw), q.D(q.o_v), q.K, q.P};
     long long *d_idx = reinterpret_cast<long long *>(q.base + q.o_idx);
-    HIP_TRY(fx_launch_risk(&w, &p, q.D(q.o_ego), q.D(q.o_obst), detail ? q.D(q.o_col) : nullptr, detail ? q.D(q.o_occ) : nullptr, ca, d_idx,
-                           r->ev.e0, r->ev.e1, c->stream, q.items ? &q.it : nullptr, rs,
+    HIP_TRY(fx_launch_risk(&w, &q.it, q.D(q.o_ego), q.D(q.o_obst), detail ? q.D(q.o_col) : nullptr, detail ? q.D(q.o_occ) : nullptr, ca, d_idx,
+                           r->ev.e0, r->ev.e1, c->stream, rs,
                            rs ? reinterpret_cast<long long *>(q.base + q.o_rbest) : nullptr));
     const size_t nn = (size_t)q.n, Kn = (size_t)q.K * nn;
     HIP_TRY(q.down(out.ego_risk, q.o_ego, nn));
@@ -381,10 +371,10 @@ extern "C" int32_t fx_eval_risk_agent(FxContext *c, int32_t agent, const FxRiskP
                                       double *ego_risk, double *obst_risk, int64_t *min_risk_index) {
     RiskPass q;
     int rc = risk_check(q, c, agent, params, n_ids, ids, ego_risk && obst_risk && min_risk_index, false);
-    if (rc || (rc = risk_stage(q, false, nullptr, 0, q.r->decomposition == FX_RISK_DECOMP_ITEMS))) return rc;
+    if (rc || (rc = risk_stage(q, false, nullptr))) return rc;
     FxRiskOutputs out{};
     out.ego_risk = ego_risk, out.obst_risk = obst_risk, out.min_risk_index = min_risk_index;
-    return risk_run(q, *params, false, nullptr, out);
+    return risk_run(q, false, nullptr, out);
 }
 
 extern "C" int32_t fx_set_reach_sets_agent(FxContext *c, int32_t agent, int32_t n_entries, const int32_t *entry_obs,
@@ -496,21 +486,14 @@ extern "C" int32_t fx_eval_risk_costs_agent(FxContext *c, int32_t agent, const F
     int rc = risk_check(q, c, agent, params, n_ids, ids, out != nullptr, true);
     if (rc) return rc;
     if (cost) FX_TRY(risk_cost_check(q, cost));
-    if ((rc = risk_stage(q, true, cost, 0, q.r->decomposition == FX_RISK_DECOMP_ITEMS))) return rc;
+    if ((rc = risk_stage(q, true, cost))) return rc;
     RiskCostArgs ca{};
     if (cost) FX_TRY(risk_cost_args(q, cost, ca));
-    return risk_run(q, *params, true, cost ? &ca : nullptr, *out);
+    return risk_run(q, true, cost ? &ca : nullptr, *out);
 }
 
-extern "C" int32_t fx_set_risk_decomposition(FxContext *c, int32_t mode) {
-    if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
-    if (mode != FX_RISK_DECOMP_WALK && mode != FX_RISK_DECOMP_ITEMS) return set_err(FX_ERR_INVALID_ARGUMENT, "risk decomposition %d", mode);
-    risk_state(c)->decomposition = mode;
-    return FX_OK;
-}
-
-// The responsibility cost as a weighted term of the step's cost (fxplan.h): the detail pass in the item
-// decomposition, the responsibility part of the cost pass over its columns, and the re-sum with its arg-min.
+// The responsibility cost as a weighted term of the step's cost (fxplan.h): the detail pass, the
+// responsibility part of the cost pass over its columns, and the re-sum with its arg-min.
 extern "C" int32_t fx_eval_responsibility_cost_agent(FxContext *c, int32_t agent, const FxRiskParams *params, const FxRespCostParams *resp,
                                                      int64_t n_ids, const int64_t *ids, const FxRespCostOutputs *out) {
     FX_TRY(check_agent(c, agent));
@@ -539,7 +522,7 @@ extern "C" int32_t fx_eval_responsibility_cost_agent(FxContext *c, int32_t agent
         if (hp.cost_id[m] > FX_COST_PREDICTION) rs.at = m;
     }
     const uint32_t need = FX_FLAG_COSTED;
-    FX_TRY(risk_stage(q, true, &cost, 0, true, need, true));
+    FX_TRY(risk_stage(q, true, &cost, 0, need, true));
     RiskCostArgs ca{};
     FX_TRY(risk_cost_args(q, &cost, ca));
     if (!q.ids && q.n > 0) {
@@ -565,7 +548,7 @@ extern "C" int32_t fx_eval_responsibility_cost_agent(FxContext *c, int32_t agent
     rs.resp_out = q.D(q.o_rresp), rs.total = q.D(q.o_rtot);
     FxRiskOutputs ro{};
     ro.ego_risk = out->ego_risk, ro.obst_risk = out->obst_risk, ro.responsibility = out->resp, ro.total = out->total;
-    FX_TRY(risk_run(q, *params, true, &ca, ro, &rs));
+    FX_TRY(risk_run(q, true, &ca, ro, &rs));
     long long best[2] = {-1, 0};
     HIP_TRY(hipMemcpy(best, q.base + q.o_rbest, sizeof(best), hipMemcpyDeviceToHost));
     // (sparse set: the arg-min ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
@@ -576,7 +559,7 @@ extern "C" int32_t fx_eval_responsibility_cost_agent(FxContext *c, int32_t agent
 }
 
 // Collision probability as the prediction cost (fxplan.h).  The scratch holds the per-step probabilities of
-// one batch of candidates, [K][S - 1][batch]: the batch bounds it to FX_PREDPROB_SCRATCH_BYTES where one candidate's share allows.
+// one batch of candidates, [K][S - 1][batch] (fx_item_batch, fx_pass.h).
 extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, const FxPredProbParams *params, int64_t n_ids,
                                                  const int64_t *ids, const FxPredProbOutputs *out) {
     FX_TRY(check_agent(c, agent));
@@ -600,9 +583,7 @@ extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, co
         if (hp.cost_id[m] == FX_COST_PREDICTION) n_pred = m;
     if (n_pred < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "the cost list has no FX_COST_PREDICTION");
     const size_t per_cand = sizeof(double) * (size_t)std::max(q.K, 1) * (size_t)std::max(q.S - 1, 1);
-    const size_t n1 = (size_t)std::max<int64_t>(q.n, 1);
-    size_t nb = std::max<size_t>(FX_PREDPROB_SCRATCH_BYTES / per_cand / 64, 1) * 64;   // whole tiles
-    nb = std::min(nb, (n1 + 63) / 64 * 64);
+    const size_t nb = (size_t)fx_item_batch(per_cand, q.n);
     FX_TRY(risk_stage(q, false, nullptr, nb));
     FxRiskState *r = q.r;
     PredProbArgs a{};

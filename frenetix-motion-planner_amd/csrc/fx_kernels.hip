@@ -12,7 +12,6 @@
 #include "fx_step_kernel.h"
 #include "fx_risk_kernel.h"
 #include "fx_predprob_kernel.h"
-#include "fx_risk_items_kernel.h"
 #include "fx_gather_kernel.h"
 #include "fx_sort_kernel.h"
 #include "fx_selftest_kernel.h"
@@ -355,38 +354,29 @@ extern "C" hipError_t fx_launch_topk(const DevProblem *d_probs, int n_agents, in
     return hipGetLastError();
 }
 
-// trajectory risk (fx_risk_kernel.h; DESIGN.md sections 11 and 13) over the w.n listed candidates: the walk -- the plain one, or
-// with col / out_occ the detail one -- and the arg-min of ego + obst into out_idx[0]; then, cost != null, the cost pass over the
-// columns and the arg-min of its total into out_idx[1].  ev_start / ev_stop (may be null) bracket all of them.
-// items != null: the walk in the item decomposition (fx_risk_items_kernel.h), in batches of items->nb
-// candidates -- per batch the (tile, chunk, obstacle) items and the finish kernel -- into the same outputs.  resp != null: behind
-// the cost pass the re-sum of the step's cost with the responsibility term and its arg-min into resp_idx[0 .. 1].
-extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const FxRiskParams *params, double *out_ego, double *out_obst,
-                                     double *col, double *out_occ, const RiskCostArgs *cost, long long *out_idx, hipEvent_t ev_start,
-                                     hipEvent_t ev_stop, hipStream_t stream, const RiskItemArgs *items, const RespSumArgs *resp,
-                                     long long *resp_idx) {
+// trajectory risk (fx_risk_kernel.h; DESIGN.md sections 11, 13 and 17) over the w.n listed candidates: the walk in batches of
+// it.nb candidates -- per batch the (tile, chunk, obstacle) items and the finish kernel; the plain one, or with col / out_occ the
+// detail one -- and the arg-min of ego + obst into out_idx[0]; then, cost != null, the cost pass over the columns and the arg-min of
+// its total into out_idx[1]; then, resp != null, the re-sum of the step's cost with the responsibility term and its arg-min into
+// resp_idx[0 .. 1].  ev_start / ev_stop (may be null) bracket all of them.
+extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const RiskItemArgs *items, double *out_ego, double *out_obst, double *col,
+                                     double *out_occ, const RiskCostArgs *cost, long long *out_idx, hipEvent_t ev_start,
+                                     hipEvent_t ev_stop, hipStream_t stream, const RespSumArgs *resp, long long *resp_idx) {
     const RiskWalkArgs &w = *walk;
+    const RiskItemArgs &it = *items;
     if (ev_start) { hipError_t e = hipEventRecord(ev_start, stream); if (e != hipSuccess) return e; }
     const dim3 grid((unsigned)((w.n + 255) / 256));
-    if (items) {
-        const RiskItemArgs &it = *items;
-        for (int64_t j0 = 0; j0 < w.n; j0 += it.nb) {
-            const int64_t m = std::min<int64_t>(it.nb, w.n - j0);
-            const dim3 igrid((unsigned)((m + 63) / 64), (unsigned)it.chunks, (unsigned)w.K), fgrid((unsigned)((m + 255) / 256));
-            if (col) {
-                if (w.K > 0 && w.S > 1) hipLaunchKernelGGL(fxri::fx_risk_item_kernel<true>, igrid, dim3(64), 0, stream, w, it, j0);
-                hipLaunchKernelGGL(fxri::fx_risk_items_finish_kernel<true>, fgrid, dim3(256), 0, stream, w, it, j0, out_ego, out_obst, col, out_occ);
-            } else {
-                if (w.K > 0 && w.S > 1) hipLaunchKernelGGL(fxri::fx_risk_item_kernel<false>, igrid, dim3(64), 0, stream, w, it, j0);
-                hipLaunchKernelGGL(fxri::fx_risk_items_finish_kernel<false>, fgrid, dim3(256), 0, stream, w, it, j0, out_ego, out_obst, col, out_occ);
-            }
+    for (int64_t j0 = 0; j0 < w.n; j0 += it.nb) {
+        const int64_t m = std::min<int64_t>(it.nb, w.n - j0);
+        const dim3 igrid((unsigned)((m + 63) / 64), (unsigned)it.chunks, (unsigned)w.K), fgrid((unsigned)((m + 255) / 256));
+        if (col) {
+            if (w.K > 0 && w.S > 1) hipLaunchKernelGGL(fxrisk::fx_risk_item_kernel<true>, igrid, dim3(64), 0, stream, w, it, j0);
+            hipLaunchKernelGGL(fxrisk::fx_risk_items_finish_kernel<true>, fgrid, dim3(256), 0, stream, w, it, j0, out_ego, out_obst, col, out_occ);
+        } else {
+            if (w.K > 0 && w.S > 1) hipLaunchKernelGGL(fxrisk::fx_risk_item_kernel<false>, igrid, dim3(64), 0, stream, w, it, j0);
+            hipLaunchKernelGGL(fxrisk::fx_risk_items_finish_kernel<false>, fgrid, dim3(256), 0, stream, w, it, j0, out_ego, out_obst, col, out_occ);
         }
-    } else if (w.n > 0 && col)
-        hipLaunchKernelGGL(fxrisk::fx_risk_detail_kernel, grid, dim3(256), 0, stream, w.planes, w.ld, w.S, w.n, w.ids, w.flags, w.rec,
-                           w.obs, w.pos, w.yaw, w.vo, w.K, w.P, *params, out_ego, out_obst, col, out_occ);
-    else if (w.n > 0)
-        hipLaunchKernelGGL(fxrisk::fx_risk_kernel, grid, dim3(256), 0, stream, w.planes, w.ld, w.S, w.n, w.ids, w.flags, w.rec, w.obs,
-                           w.pos, w.yaw, w.vo, w.K, w.P, *params, out_ego, out_obst);
+    }
     hipLaunchKernelGGL(fxrisk::fx_risk_argmin_kernel, dim3(1), dim3(1024), 0, stream, out_ego, out_obst, w.n, w.ids, out_idx);
     if (cost) {
         if (w.n > 0) hipLaunchKernelGGL(fxrisk::fx_risk_cost_kernel, grid, dim3(256), 0, stream, *cost);
@@ -394,7 +384,7 @@ extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const FxRiskParam
                            out_idx + 1);
     }
     if (resp) {
-        if (w.n > 0) hipLaunchKernelGGL(fxri::fx_resp_finish_kernel, grid, dim3(256), 0, stream, *resp);
+        if (w.n > 0) hipLaunchKernelGGL(fxrisk::fx_resp_finish_kernel, grid, dim3(256), 0, stream, *resp);
         hipLaunchKernelGGL(fxpp::fx_predprob_argmin_kernel, dim3(1), dim3(1024), 0, stream, resp->total, w.n, w.ids, w.flags, resp_idx);
     }
     if (ev_stop) { hipError_t e = hipEventRecord(ev_stop, stream); if (e != hipSuccess) return e; }

@@ -43,6 +43,16 @@ inline int fx_item_chunk_steps(int64_t n, int S, int K, int forced) {
     return std::min(cs, steps);
 }
 
+// Candidates per batch of such a pass, whose scratch -- the per-step probabilities of fx_eval_prediction_prob_agent, the partials
+// of the risk items -- holds one batch at per_candidate_bytes each: whole tiles of 64; at most FX_ITEM_SCRATCH_BYTES of scratch
+// where one candidate's share allows; never more tiles than the call's n candidates have.  Pure: no HIP call.
+#define FX_ITEM_SCRATCH_BYTES ((size_t)64 << 20)
+inline int64_t fx_item_batch(size_t per_candidate_bytes, int64_t n) {
+    const size_t tiles = std::max<size_t>(FX_ITEM_SCRATCH_BYTES / per_candidate_bytes / 64, 1);
+    const size_t call = ((size_t)std::max<int64_t>(n, 1) + 63) / 64;
+    return (int64_t)(std::min(tiles, call) * 64);
+}
+
 // wait for everything on the context's stream; what stays unknown is what a caller's own stream may hold (FxContext.tail_work)
 inline int fx_drain(FxContext *c) {
     HIP_TRY(hipStreamSynchronize(c->stream));

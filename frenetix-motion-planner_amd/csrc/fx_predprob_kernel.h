@@ -5,8 +5,8 @@
 // The probability of one (obstacle, ego step) is fxrisk::step_probability in FX_RISK_PROB_MVN mode on the host's records
 // (fx_risk_kernel.h, fx_api_risk.hip build_records) -- that code is included and called, not restated.
 //
-// Decomposition.  fx_risk_kernel gives one lane the serial chain of all K (S - 1) records.  Here the work is spread over
-// (tile of 64 listed candidates) x (chunk of steps) x obstacle: one wave per item, grid = (tiles, chunks, K).  Obstacle and step
+// Decomposition.  The K (S - 1) records of a candidate are spread over (tile of 64 listed candidates) x (chunk of steps) x
+// obstacle, as the risk items of fx_risk_kernel.h are: one wave per item, grid = (tiles, chunks, K).  Obstacle and step
 // are wave-uniform, so are the record and the |rho| branch of the bivariate normal; only the 5 m gate diverges, and an item none
 // of whose lanes passes it costs three distances per step.
 //
@@ -104,25 +104,15 @@ __global__ __launch_bounds__(256) void fx_predprob_finish_kernel(const PredProbA
 __global__ __launch_bounds__(1024) void fx_predprob_argmin_kernel(const double *__restrict__ total, int64_t n,
                                                                   const int64_t *__restrict__ ids, const uint32_t *__restrict__ flags,
                                                                   long long *__restrict__ out) {
-    __shared__ double sc[16];
-    __shared__ long long si[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double bc = INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
-    for (int64_t j = tid; j < n; j += blockDim.x) {
-        const long long c = ids ? (long long)ids[j] : (long long)j;
+    double bc;
+    long long bi;
+    fx_lex_block_min(n, ids, [=](int64_t j, long long c, double &t) {
         const uint32_t f = flags[c];
-        const double t = total[j];
-        if (!(f & FX_FLAG_SELECTABLE) || (f & (FX_FLAG_COLLISION | FX_FLAG_BOUNDARY)) || t != t) continue;
-        if (fx_lex_less(t, c, bc, bi)) { bc = t; bi = c; }
-    }
-    fx_lex_wave_min(bc, bi);
-    if (lane == 0) { sc[wave] = bc; si[wave] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); w++)
-            if (fx_lex_less(sc[w], si[w], bc, bi)) { bc = sc[w]; bi = si[w]; }
-        const bool none = bi == 0x7fffffffffffffffLL;
+        t = total[j];
+        return (f & FX_FLAG_SELECTABLE) && !(f & (FX_FLAG_COLLISION | FX_FLAG_BOUNDARY)) && t == t;
+    }, bc, bi);
+    if (threadIdx.x == 0) {
+        const bool none = bi == FX_LEX_NONE;
         out[0] = none ? -1LL : bi;
         out[1] = __double_as_longlong(none ? (double)NAN : bc);
     }

@@ -1,6 +1,7 @@
 // fx_risk_args.h -- what the host code of the trajectory risk (fx_api_risk.hip), its launcher (fx_kernels.hip) and its kernels
 // (fx_risk_kernel.h) share: the layout of the records the host builds and the kernels read, the arguments of the candidate walk
-// and the argument blocks of the risk-cost kernel and of the prediction-probability pass.  DESIGN.md sections 11, 13 and 16.
+// and the argument blocks of the risk-cost kernel, the responsibility re-sum and the prediction-probability pass.  DESIGN.md
+// sections 11, 13, 16 and 17.
 #pragma once
 
 #include <stdint.h>
@@ -30,7 +31,7 @@
 #define FXO_NPOS 4
 #define FXO_STRIDE 8
 
-// arguments of the candidate walk (fx_risk_kernel / fx_risk_detail_kernel), device pointers
+// what the candidate walk (fx_risk_item_kernel / fx_risk_items_finish_kernel) reads, device pointers
 struct RiskWalkArgs {
     const double *planes;      // [FX_NUM_PLANES][S][ld] of the agent
     int64_t ld;
@@ -45,7 +46,7 @@ struct RiskWalkArgs {
     int32_t K, P;
 };
 
-// the item decomposition of the candidate walk (fx_risk_items_kernel.h), device pointers
+// the items of the candidate walk, device pointers
 struct RiskItemArgs {
     const FxRiskParams *params;// the call's parameters, in device memory
     double *part;              // [K][chunks][NV][nb] partials of one batch of nb candidates (NV = 2, detail 7)

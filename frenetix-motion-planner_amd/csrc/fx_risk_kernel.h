@@ -1,12 +1,28 @@
 // fx_risk_kernel.h -- trajectory risk (risk_costs.py:20-118, crash_angle_simplified) over the materialised bundle, and the
 // arg-min of ego + obstacle risk (reactive_planner.py:262-269, reactive_planner_cpp.py:404-413).  DESIGN.md section 11.
-// The same walk with calc_risk's per-obstacle results, and the risk-cost principles with the responsibility cost over them
-// (risk_costs.py:124-251, utility/responsibility.py).  DESIGN.md section 13.
+// With calc_risk's per-obstacle results, the risk-cost principles with the responsibility cost over them (risk_costs.py:124-251,
+// utility/responsibility.py), and the responsibility cost as a weighted term of the step's cost sum beside the
+// step.
 //
-// One lane per candidate.  Every lane walks the (obstacle, step) pairs in the same order, so everything indexed by them -- the
-// three obstacle means, the standardisation (sigma_x, sigma_y, rho), the |rho| branch of the bivariate normal and its node terms
-// -- is wave-uniform and comes from a record the host built once per call (fx_api_risk.hip; its layout, FXR_* / FXO_*, is in
-// fx_risk_args.h).  Only the 5 m gate diverges.
+// Decomposition.  The K (S - 1) (obstacle, step) pairs of a candidate are spread over (tile of 64 listed candidates) x (chunk of
+// steps) x obstacle: one wave per item, grid = (tiles, chunks, K), and one finish lane per candidate behind them.  Obstacle and
+// step are wave-uniform, so everything indexed by them -- the three obstacle means, the standardisation (sigma_x, sigma_y, rho),
+// the |rho| branch of the bivariate normal and its node terms -- comes from a record the host built once per call
+// (fx_api_risk.hip; its layout, FXR_* / FXO_*, is in fx_risk_args.h).  Only the 5 m gate diverges.
+//
+// Why the chunk size cannot change a bit.  Everything a candidate keeps of its per-step values is a maximum taken with fmax from
+// -inf -- associative and commutative bit for bit, NaN operands dropped on either side -- or the FIRST maximum of the probability
+// list with the harm that stands beside it (strict >): a chunk keeps its first maximum, and the chunks, combined in chunk order
+// with the same strict >, keep the first of those.  p_nan is an OR.  So the chunk size decides how many waves a call has and
+// nothing else, and no atomics are needed: an item owns its partials.
+//
+// Partials.  part [K][chunks][NV][nb] of one batch of nb candidates, candidate innermost: a wave stores 512 contiguous bytes per
+// value.  NV = 2 (plain pass: e_max, o_max) or 7 (detail: + he_max, ho_max, p_max, ho_at, p_nan as 0 / 1).  An item whose chunk
+// begins at or behind pl = min(S - 1, npos) of its obstacle ends at once and writes nothing; the finish kernel reads the
+// ceil(pl / cs) chunks that ran.
+//
+// Parameters.  FxRiskParams comes through a pointer into the pass's device block, not by value: the bins of angle_coef then are
+// scalar loads at wave-uniform addresses, where a by-value structure gets a private copy -- 280 bytes of scratch per lane.
 //
 // Bivariate normal upper probability BVNU(h, k, rho) = P(X > h, Y > k) after Genz (2004), Statistics and Computing 14:251-260:
 // Drezner-Wesolowsky Gauss-Legendre quadrature of the Plackett integral in asin(rho) with 6 / 12 / 20 nodes for |rho| < 0.3 /
@@ -131,7 +147,7 @@ __device__ __forceinline__ double step_probability(const FxRiskParams &p, const 
 }
 
 // harm of ego point (x, y, th, v) against a prediction (px, py, yo, vob) of an obstacle (harm_estimation.py:282-300): the ego's
-// and the obstacle's.  Shared by the candidate walk below and the item kernel of fx_risk_items_kernel.h.
+// and the obstacle's
 __device__ __forceinline__ void step_harm(const FxRiskParams &p, bool prot, double f_ego, double f_obs, double x, double y, double th,
                                           double v, double yo, double vob, double px, double py, double &he, double &ho) {
     const double pdof = (yo - th) + 3.141592653589793;
@@ -154,23 +170,91 @@ __device__ __forceinline__ void step_harm(const FxRiskParams &p, bool prot, doub
     }
 }
 
-// The candidate walk of lane j.  DETAIL = false: ego / obstacle risk (max over obstacles of max over steps of harm x probability),
-// harm evaluated only where the probability is not zero.  DETAIL = true adds what calc_risk returns per
-// obstacle -- col [4][K][n] = ego_risk_max | obst_risk_max | ego_harm_max | obst_harm_max, obstacle-major, so that the 64 lanes of a
-// wave store 512 contiguous bytes per column -- and obst_harm_occ [n]; the harm is then evaluated at every t < pl
-// (risk_costs.py:109-112 take the maxima of the whole harm lists).  The products and their order are the same in both.
+// the values of a chunk's partials (NV = 2: the first two)
+enum { P_EMAX = 0, P_OMAX = 1, P_HEMAX = 2, P_HOMAX = 3, P_PMAX = 4, P_HOAT = 5, P_PNAN = 6 };
+
+// a candidate of the batch that the pass evaluates: listed, or -- every candidate -- with all of it.need in its flags
+__device__ __forceinline__ bool selected(const RiskWalkArgs &w, const RiskItemArgs &it, int64_t c) {
+    return w.ids || (w.flags[c] & it.need) == it.need;
+}
+
+// One wave per (tile, chunk, obstacle): lanes = candidates j0 + 64 tile + lane of the batch [j0, j0 + nb), steps t = chunk cs ...
+// of obstacle blockIdx.z.  DETAIL = false: the maxima over the chunk of harm x probability, the harm evaluated only where the
+// probability is not zero.  DETAIL = true: the harm at every t < pl (risk_costs.py:109-112 take the maxima of
+// the whole harm lists), and the further partials of what calc_risk returns per obstacle.  The products and their order are the same
+// in both.
 template <bool DETAIL>
-__device__ __forceinline__ void risk_walk(const double *__restrict__ planes, int64_t ld, int S, int64_t n, const int64_t *__restrict__ ids,
-                                          const uint32_t *__restrict__ flags, const double *__restrict__ rec,
-                                          const double *__restrict__ obs, const double *__restrict__ pos,
-                                          const double *__restrict__ yaw, const double *__restrict__ vo, int K, int P,
-                                          const FxRiskParams &p, double *__restrict__ out_ego, double *__restrict__ out_obst,
-                                          double *__restrict__ col, double *__restrict__ out_occ) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const int64_t c = ids ? ids[j] : j;
-    const uint32_t need = FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED;
-    if (!ids && (flags[c] & need) != need) {
+__global__ __launch_bounds__(64) void fx_risk_item_kernel(const RiskWalkArgs w, const RiskItemArgs it, const int64_t j0) {
+    const int lane = threadIdx.x;
+    const FxRiskParams &p = *it.params;
+    const int k = blockIdx.z, S = w.S, NV = DETAIL ? 7 : 2;
+    const double *__restrict__ o = w.obs + (size_t)k * FXO_STRIDE;
+    const int pl = min(S - 1, (int)o[FXO_NPOS]);
+    const int t_a = (int)blockIdx.y * it.cs, t_b = min(pl, t_a + it.cs);
+    if (t_a >= t_b) return;   // (wave-uniform)
+    const int64_t jj = (int64_t)blockIdx.x * 64 + lane;
+    const int64_t j = j0 + jj;
+    if (jj >= it.nb || j >= w.n) return;
+    const int64_t c = w.ids ? w.ids[j] : j;
+    if (!selected(w, it, c)) return;   // (NaN rows from the finish kernel)
+    const int64_t ld = w.ld;
+    const double *__restrict__ X = w.planes + c, *__restrict__ Y = X + (size_t)S * ld, *__restrict__ TH = Y + (size_t)S * ld,
+                 *__restrict__ V = TH + (size_t)S * ld;
+    const bool prot = o[FXO_CLS] == (double)FX_RISK_CLASS_PROTECTED;
+    const double me = p.ego_mass, mo = o[FXO_MASS];
+    const double f_ego = mo / (me + mo), f_obs = me / (me + mo);
+    double e_max = -INFINITY, o_max = -INFINITY;
+    double he_max = -INFINITY, ho_max = -INFINITY, p_max = -INFINITY, ho_at = 0.0;   // DETAIL
+    bool p_nan = false;
+    for (int t = t_a; t < t_b; t++) {
+        const int i = t + 1;
+        const double *__restrict__ q = w.rec + ((size_t)k * S + i) * FXR_STRIDE;
+        const double prob = fxrisk::step_probability(p, q, X[(size_t)i * ld], Y[(size_t)i * ld], TH[(size_t)i * ld]);
+        double re = 0.0, ro = 0.0;
+        if (DETAIL || prob != 0.0) {
+            const size_t kt = (size_t)k * w.P + t;
+            double he, ho;
+            fxrisk::step_harm(p, prot, f_ego, f_obs, X[(size_t)t * ld], Y[(size_t)t * ld], TH[(size_t)t * ld], V[(size_t)t * ld], w.yaw[kt],
+                              w.vo[kt], w.pos[2 * kt], w.pos[2 * kt + 1], he, ho);
+            re = prob != 0.0 ? he * prob : 0.0;
+            ro = prob != 0.0 ? ho * prob : 0.0;
+            if (DETAIL) {
+                he_max = fmax(he_max, he);
+                ho_max = fmax(ho_max, ho);
+                p_nan = p_nan || prob != prob;
+                if (prob > p_max) { p_max = prob; ho_at = ho; }
+            }
+        }
+        e_max = fmax(e_max, re);
+        o_max = fmax(o_max, ro);
+    }
+    double *__restrict__ out = it.part + (((size_t)k * it.chunks + blockIdx.y) * NV) * (size_t)it.nb + jj;
+    out[(size_t)P_EMAX * it.nb] = e_max;
+    out[(size_t)P_OMAX * it.nb] = o_max;
+    if (DETAIL) {
+        out[(size_t)P_HEMAX * it.nb] = he_max;
+        out[(size_t)P_HOMAX * it.nb] = ho_max;
+        out[(size_t)P_PMAX * it.nb] = p_max;
+        out[(size_t)P_HOAT * it.nb] = ho_at;
+        out[(size_t)P_PNAN * it.nb] = p_nan ? 1.0 : 0.0;
+    }
+}
+
+// One lane per candidate of the batch: per obstacle the chunks in chunk order, then out_ego / out_obst [n] = the maximum over the
+// obstacles (0.0 without one, NaN where the candidate is not selected).  DETAIL adds col [4][K][n] = ego_risk_max | obst_risk_max |
+// ego_harm_max | obst_harm_max, obstacle-major, so that the 64 lanes of a wave store 512 contiguous bytes per column, and
+// obst_harm_occ [n].  (The detail entry point refuses an obstacle with pl <= 0: np.max of an empty list upstream.)
+template <bool DETAIL>
+__global__ __launch_bounds__(256) void fx_risk_items_finish_kernel(const RiskWalkArgs w, const RiskItemArgs it, const int64_t j0,
+                                                                  double *__restrict__ out_ego, double *__restrict__ out_obst,
+                                                                  double *__restrict__ col, double *__restrict__ out_occ) {
+    const int64_t jj = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t j = j0 + jj;
+    if (jj >= it.nb || j >= w.n) return;
+    const size_t n = (size_t)w.n, nb = (size_t)it.nb;
+    const int K = w.K, S = w.S, NV = DETAIL ? 7 : 2;
+    const int64_t c = w.ids ? w.ids[j] : j;
+    if (!selected(w, it, c)) {
         out_ego[j] = NAN;
         out_obst[j] = NAN;
         if (DETAIL) {
@@ -179,50 +263,30 @@ __device__ __forceinline__ void risk_walk(const double *__restrict__ planes, int
         }
         return;
     }
-    const double *X = planes + c, *Y = planes + (size_t)S * ld + c, *TH = planes + 2 * (size_t)S * ld + c,
-                 *V = planes + 3 * (size_t)S * ld + c;
-    const double me = p.ego_mass;
     double ego_best = -INFINITY, obst_best = -INFINITY, occ_best = -INFINITY;
     bool any = false;
     for (int k = 0; k < K; k++) {
-        const double *o = obs + (size_t)k * FXO_STRIDE;
-        const int npos = (int)o[FXO_NPOS];
-        const int pl = min(S - 1, npos);
-        if (pl <= 0) {   // (the detail entry point refuses such an obstacle: np.max of an empty list upstream)
+        const int pl = min(S - 1, (int)w.obs[(size_t)k * FXO_STRIDE + FXO_NPOS]);
+        if (pl <= 0) {
             if (DETAIL)
                 for (int q = 0; q < 4; q++) col[((size_t)q * K + k) * n + j] = 0.0;
             continue;
         }
-        const bool prot = o[FXO_CLS] == (double)FX_RISK_CLASS_PROTECTED;
-        const double mo = o[FXO_MASS];
-        const double f_ego = mo / (me + mo), f_obs = me / (me + mo);
+        const int nch = (pl + it.cs - 1) / it.cs;
         double e_max = -INFINITY, o_max = -INFINITY;
-        double he_max = -INFINITY, ho_max = -INFINITY, p_max = -INFINITY, ho_at = 0.0;   // DETAIL
+        double he_max = -INFINITY, ho_max = -INFINITY, p_max = -INFINITY, ho_at = 0.0;
         bool p_nan = false;
-        for (int t = 0; t < pl; t++) {
-            const int i = t + 1;
-            const double *q = rec + ((size_t)k * S + i) * FXR_STRIDE;
-            const double prob = step_probability(p, q, X[(size_t)i * ld], Y[(size_t)i * ld], TH[(size_t)i * ld]);
-            double re = 0.0, ro = 0.0;
-            if (DETAIL || prob != 0.0) {
-                // harm of ego point t against prediction t (harm_estimation.py:282-300)
-                const double x = X[(size_t)t * ld], y = Y[(size_t)t * ld], th = TH[(size_t)t * ld], v = V[(size_t)t * ld];
-                const size_t kt = (size_t)k * P + t;
-                const double yo = yaw[kt], vob = vo[kt], px = pos[2 * kt], py = pos[2 * kt + 1];
-                double he, ho;
-                step_harm(p, prot, f_ego, f_obs, x, y, th, v, yo, vob, px, py, he, ho);
-                re = prob != 0.0 ? he * prob : 0.0;
-                ro = prob != 0.0 ? ho * prob : 0.0;
-                if (DETAIL) {
-                    he_max = fmax(he_max, he);
-                    ho_max = fmax(ho_max, ho);
-                    // np.argmax: the FIRST maximum of the probability list (the entries behind pl are zeros)
-                    p_nan = p_nan || prob != prob;
-                    if (prob > p_max) { p_max = prob; ho_at = ho; }
-                }
+        for (int ch = 0; ch < nch; ch++) {
+            const double *__restrict__ in = it.part + (((size_t)k * it.chunks + ch) * NV) * nb + jj;
+            e_max = fmax(e_max, in[(size_t)P_EMAX * nb]);
+            o_max = fmax(o_max, in[(size_t)P_OMAX * nb]);
+            if (DETAIL) {
+                he_max = fmax(he_max, in[(size_t)P_HEMAX * nb]);
+                ho_max = fmax(ho_max, in[(size_t)P_HOMAX * nb]);
+                p_nan = p_nan || in[(size_t)P_PNAN * nb] != 0.0;
+                const double pm = in[(size_t)P_PMAX * nb];
+                if (pm > p_max) { p_max = pm; ho_at = in[(size_t)P_HOAT * nb]; }
             }
-            e_max = fmax(e_max, re);
-            o_max = fmax(o_max, ro);
         }
         ego_best = fmax(ego_best, e_max);
         obst_best = fmax(obst_best, o_max);
@@ -238,27 +302,6 @@ __device__ __forceinline__ void risk_walk(const double *__restrict__ planes, int
     out_ego[j] = any ? ego_best : 0.0;
     out_obst[j] = any ? obst_best : 0.0;
     if (DETAIL) out_occ[j] = any ? occ_best : 0.0;
-}
-
-// One lane per listed candidate: out_ego / out_obst [n] (NaN where the candidate is not selected)
-__global__ __launch_bounds__(256) void fx_risk_kernel(const double *__restrict__ planes, int64_t ld, int S, int64_t n,
-                                                      const int64_t *__restrict__ ids, const uint32_t *__restrict__ flags,
-                                                      const double *__restrict__ rec, const double *__restrict__ obs,
-                                                      const double *__restrict__ pos, const double *__restrict__ yaw,
-                                                      const double *__restrict__ vo, int K, int P, FxRiskParams p,
-                                                      double *__restrict__ out_ego, double *__restrict__ out_obst) {
-    risk_walk<false>(planes, ld, S, n, ids, flags, rec, obs, pos, yaw, vo, K, P, p, out_ego, out_obst, nullptr, nullptr);
-}
-
-// The same walk with the per-obstacle columns and obst_harm_occ (fx_eval_risk_costs_agent)
-__global__ __launch_bounds__(256) void fx_risk_detail_kernel(const double *__restrict__ planes, int64_t ld, int S, int64_t n,
-                                                             const int64_t *__restrict__ ids, const uint32_t *__restrict__ flags,
-                                                             const double *__restrict__ rec, const double *__restrict__ obs,
-                                                             const double *__restrict__ pos, const double *__restrict__ yaw,
-                                                             const double *__restrict__ vo, int K, int P, FxRiskParams p,
-                                                             double *__restrict__ out_ego, double *__restrict__ out_obst,
-                                                             double *__restrict__ col, double *__restrict__ out_occ) {
-    risk_walk<true>(planes, ld, S, n, ids, flags, rec, obs, pos, yaw, vo, K, P, p, out_ego, out_obst, col, out_occ);
 }
 
 // Risk-cost principles (risk_costs.py:124-251) over the columns of the detail pass: one lane per listed candidate streams the K
@@ -340,31 +383,54 @@ __global__ __launch_bounds__(256) void fx_risk_cost_kernel(const RiskCostArgs a)
     out[6 * n] = bh;
 }
 
+// The responsibility cost as one more weighted term of the step's cost sum: one lane per listed candidate re-sums the step's raw
+// cost rows (FX_MODE_WRITE_COSTMAP) with w_resp * resp inserted in front of entry a.at -- its place in the name-sorted list,
+// between `prediction` and `velocity_offset` -- in the order and with the operations of fx_predprob_finish_kernel: sum = -0.0;
+// sum += w * c per term; a deferred step (fx_obstacle_kernel.h) added the terms behind the prediction as ONE addend, which the new
+// term then joins.  The prediction entry is the step's own, or a.pred [n] (the prob of a collision-probability pass over the same
+// candidates).  resp [n] is row 4 of fx_risk_cost_kernel's output.
+__global__ __launch_bounds__(256) void fx_resp_finish_kernel(const RespSumArgs a) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= a.n) return;
+    const int64_t c = a.ids ? a.ids[j] : j;
+    if (!a.ids && (a.flags[c] & a.need) != a.need) {
+        a.resp_out[j] = NAN;
+        a.total[j] = NAN;
+        return;
+    }
+    const double resp = a.resp[j];
+    double sum = -0.0, tail = 0.0;
+    const bool defer = a.deferred && a.n_pred >= 0;
+    for (int m = 0; m <= a.n_cost; m++) {
+        if (m == a.at) {
+            const double t = a.w_resp * resp;
+            if (defer && m > a.n_pred) tail += t;
+            else sum += t;
+        }
+        if (m == a.n_cost) break;
+        const double cm = (m == a.n_pred && a.pred) ? a.pred[j] : a.costmap[(size_t)m * a.ld + c];
+        const double t = a.cost_w[m] * cm;
+        if (defer && m > a.n_pred) tail += t;
+        else sum += t;
+    }
+    if (defer) sum += tail;   // (never empty: the new term stands behind the prediction)
+    a.resp_out[j] = resp;
+    a.total[j] = 0.0 + sum;
+}
+
 // arg-min over the n entries of ego + obst (SUM) or of val = ego alone, NaN = not selected or not comparable, ties to the lower
 // candidate index, -1 when nothing is left: ONE workgroup of 1024 lanes, the lexicographic (cost, index) reduction of fx_select.h
 template <bool SUM>
 __device__ __forceinline__ void risk_argmin(const double *__restrict__ ego, const double *__restrict__ obst, int64_t n,
                                             const int64_t *__restrict__ ids, long long *__restrict__ out) {
-    __shared__ double sc[16];
-    __shared__ long long si[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double bc = INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
-    for (int64_t j = tid; j < n; j += blockDim.x) {
+    double bc;
+    long long bi;
+    fx_lex_block_min(n, ids, [=](int64_t j, long long, double &s) {
         const double e = ego[j], o = SUM ? obst[j] : 0.0;
-        if (e != e || o != o) continue;
-        const double s = SUM ? e + o : e;
-        const long long c = ids ? (long long)ids[j] : (long long)j;
-        if (fx_lex_less(s, c, bc, bi)) { bc = s; bi = c; }
-    }
-    fx_lex_wave_min(bc, bi);
-    if (lane == 0) { sc[wave] = bc; si[wave] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); w++)
-            if (fx_lex_less(sc[w], si[w], bc, bi)) { bc = sc[w]; bi = si[w]; }
-        out[0] = bi == 0x7fffffffffffffffLL ? -1LL : bi;
-    }
+        s = SUM ? e + o : e;
+        return e == e && o == o;
+    }, bc, bi);
+    if (threadIdx.x == 0) out[0] = bi == FX_LEX_NONE ? -1LL : bi;
 }
 
 __global__ __launch_bounds__(1024) void fx_risk_argmin_kernel(const double *__restrict__ ego, const double *__restrict__ obst, int64_t n,

@@ -25,6 +25,30 @@ __device__ __forceinline__ void fx_lex_wave_min(double &bc, long long &bi) {
         if (fx_lex_less(oc, oi, bc, bi)) { bc = oc; bi = oi; }
     }
 }
+// (cost, index) minimum over the n entries of a list by ONE workgroup of up to 1024 lanes: a strided scan, the wave reduction, and
+// the waves' results combined by thread 0 in wave order -- the result is valid in thread 0 alone.  entry(j, c, v): does entry j, of
+// candidate c = ids ? ids[j] : j, take part -- then v is its cost.  bi == FX_LEX_NONE: nothing took part.
+#define FX_LEX_NONE 0x7fffffffffffffffLL
+template <class Entry>
+__device__ __forceinline__ void fx_lex_block_min(int64_t n, const int64_t *__restrict__ ids, Entry entry, double &bc, long long &bi) {
+    __shared__ double sc[16];
+    __shared__ long long si[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    bc = INFINITY;
+    bi = FX_LEX_NONE;
+    for (int64_t j = tid; j < n; j += blockDim.x) {
+        const long long c = ids ? (long long)ids[j] : (long long)j;
+        double v;
+        if (!entry(j, c, v)) continue;
+        if (fx_lex_less(v, c, bc, bi)) { bc = v; bi = c; }
+    }
+    fx_lex_wave_min(bc, bi);
+    if (lane == 0) { sc[wave] = bc; si[wave] = bi; }
+    __syncthreads();
+    if (tid == 0)
+        for (int w = 1; w < (int)(blockDim.x >> 6); w++)
+            if (fx_lex_less(sc[w], si[w], bc, bi)) { bc = sc[w]; bi = si[w]; }
+}
 
 #define FX_SELECT_SLICES_MIN 32
 #define FX_SELECT_SLICES_MAX 512

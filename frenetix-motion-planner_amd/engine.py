@@ -966,15 +966,7 @@ class FrenetEngine(StepRegistry):
         """device time of the last `risk` / `risk_detail` / `risk_costs` / `responsibility_cost` call (its kernels)"""
         return float(lib().fx_last_risk_ms(self._ctx))
 
-    # -- the walk in the item decomposition, the responsibility cost as a weighted term (DESIGN.md section 17) --
-    def set_risk_decomposition(self, mode: str = "walk"):
-        """How `risk`, `risk_detail` and `risk_costs` evaluate the (obstacle, step) pairs: "walk" (the default), one lane per
-        candidate over all of them, or "items", one wave per (tile of 64 candidates, chunk of steps, obstacle).  Every output is
-        the same bit for bit in both (fx_set_risk_decomposition)."""
-        if mode not in _abi.RISK_DECOMPOSITIONS:
-            raise ValueError(f"risk decomposition {mode!r}: one of {sorted(_abi.RISK_DECOMPOSITIONS)}")
-        check(lib().fx_set_risk_decomposition(self._ctx, _abi.RISK_DECOMPOSITIONS[mode]))
-
+    # -- the responsibility cost as a weighted term (DESIGN.md section 17) --
     def responsibility_cost(self, params, cost_params, weight: float, ids=None, agent: int = 0, prediction: str = "step") -> dict:
         """The `responsibility` cost term (partial_cost_functions.py:359-387) for candidates of the last plan step, on the device
         (fx_eval_responsibility_cost_agent): resp [n], get_responsibility_cost over calc_risk's obst_risk_max in the mode of

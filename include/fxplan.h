@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 14
+#define FX_ABI_VERSION 15
 
 /* ---- status codes (planner.py / reactive_planner_cpp.py raise Python exceptions; the shim maps
  *      <0 -> ValueError, >0 -> RuntimeError, see SURVEY 8b "Error conventions") ---- */
@@ -742,16 +742,14 @@ int32_t fx_eval_prediction_prob_agent(FxContext *ctx, int32_t agent, const FxPre
 /* device time of the last fx_eval_prediction_prob_agent (all its kernels), ms; -1 before the first */
 double fx_last_predprob_ms(FxContext *ctx);
 
-/* ---- The risk walk in an item decomposition, and the responsibility cost as a weighted term of the step's cost (DESIGN.md
- *      section 17; additive within ABI 14).  Beside the plan step like the blocks above: nothing here runs unless called. ----
- * fx_set_risk_decomposition chooses how fx_eval_risk_agent and fx_eval_risk_costs_agent of the context evaluate the (obstacle,
- * step) pairs of a candidate: FX_RISK_DECOMP_WALK (the default) one lane per candidate over all of them; FX_RISK_DECOMP_ITEMS one
- * wave per (tile of 64 candidates, chunk of steps, obstacle) and a finish kernel that combines the chunks.  Every output of both
- * calls is the same bit for bit in both: all of them are maxima, or the first maximum of a list.  The partials of the items live
- * in the risk passes' device block (at most 64 MiB of it where one candidate's share allows; the candidates are batched). */
-enum { FX_RISK_DECOMP_WALK = 0, FX_RISK_DECOMP_ITEMS = 1 };
-int32_t fx_set_risk_decomposition(FxContext *ctx, int32_t mode);
-/* responsibility (partial_cost_functions.py:359-387): get_responsibility_cost over calc_risk's obst_risk_max of a candidate, times
+/* ---- The responsibility cost as a weighted term of the step's cost.  Beside the plan step like the
+ *      blocks above: nothing here runs unless called. ----
+ * ABI 15 removed the choice between two decompositions of the risk walk (a setter and its two constants), which changed no bit:
+ * every risk pass -- fx_eval_risk_agent, fx_eval_risk_costs_agent and the call below -- evaluates the (obstacle, step) pairs of a
+ * candidate with one wave per (tile of 64 candidates, chunk of steps, obstacle) and a finish kernel that combines the chunks.  The
+ * partials of these items live in the risk passes' device block (at most 64 MiB of it where one candidate's share allows; the
+ * candidates are batched).
+ * responsibility (partial_cost_functions.py:359-387): get_responsibility_cost over calc_risk's obst_risk_max of a candidate, times
  * its weight, as one more term of the weighted cost sum at its place in the name-sorted list -- behind `prediction`, in front of
  * `velocity_offset`.  The term inside the total never ran upstream (UNPINNED: DESIGN.md section 17); its per-candidate value is the
  * `responsibility` of fx_eval_risk_costs_agent. */
@@ -776,8 +774,8 @@ typedef struct FxRespCostOutputs {   /* rows in the order of ids, or [C] with id
  * evaluated step or when inputs were rewritten since it, for a step without FX_MODE_WRITE_COSTMAP, and without
  * FX_MODE_WRITE_BUNDLE unless every listed id lies in the agent's sparse set; FX_ERR_INVALID_ARGUMENT for what
  * fx_eval_risk_costs_agent refuses (an obstacle with min(S - 1, n_pos) == 0 among it), a zero or NaN weight, another
- * responsibility_mode, a NULL params, resp, out or output pointer.  K = 0 is legal: resp = 0 and total is the step's cost.  The
- * detail pass runs in the item decomposition whatever fx_set_risk_decomposition says.  Synchronous; fx_last_risk_ms covers it. */
+ * responsibility_mode, a NULL params, resp, out or output pointer.  K = 0 is legal: resp = 0 and total is the step's cost.
+ * Synchronous; fx_last_risk_ms covers it. */
 int32_t fx_eval_responsibility_cost_agent(FxContext *ctx, int32_t agent, const FxRiskParams *params, const FxRespCostParams *resp,
                                           int64_t n_ids, const int64_t *ids, const FxRespCostOutputs *out);
 

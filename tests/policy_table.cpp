@@ -9,6 +9,8 @@
 //      then      name ok <16 numbers of fx_step_info_ex> <one-launch step: CH blocks lds>   or   name err <code> <message>
 //      then      name launch <M_max S_max gen_rec_lds> <fx_generic_lds of them>   for a row the generic kernel runs
 //      at the end, per part list:  #layout <n> <bytes...> <offsets...> <size>   an FxBlockLayout walk (csrc/fx_pass.h)
+//      and the two rules of the passes that work in items (csrc/fx_pass.h):
+//                #items chunk <n> <S> <K> <forced> <fx_item_chunk_steps>   and   #items batch <per_candidate_bytes> <n> <fx_item_batch>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -91,5 +93,16 @@ int main() {
         for (size_t o : offs) std::cout << " " << o;
         std::cout << " " << lay.size() << "\n";
     }
+    // steps per chunk: the planner's grid and config 3 (as recorded on the device), a forced size beyond the horizon, a horizon of one sample
+    const long long chunk_calls[][4] = {{2176, 31, 8, 0}, {50388, 31, 20, 0}, {1, 31, 1, 99},  {2176, 31, 8, 99}, {50388, 31, 20, 99},
+                                        {1, 1, 0, 0},     {2176, 1, 8, 0},    {50388, 1, 20, 0}};
+    for (const auto &q : chunk_calls)
+        std::cout << "#items chunk " << q[0] << " " << q[1] << " " << q[2] << " " << q[3] << " "
+                  << fx_item_chunk_steps(q[0], (int)q[1], (int)q[2], (int)q[3]) << "\n";
+    // candidates per batch: two batches of the planner's grid, one tile for one candidate and for none, a ragged second tile, a share
+    // of a candidate beyond the bound
+    const std::pair<size_t, long long> batch_calls[] = {
+        {(size_t)7 * 20 * 30 * 8, 2176}, {100, 1}, {100, 0}, {100, 65}, {2 * FX_ITEM_SCRATCH_BYTES, 1000}};
+    for (const auto &q : batch_calls) std::cout << "#items batch " << q.first << " " << q.second << " " << fx_item_batch(q.first, q.second) << "\n";
     return 0;
 }

@@ -8,7 +8,8 @@ three answers next to the row, and the second test holds the pure sizing functio
 
 The same program prints, for the rows' agents, the generic kernel's LDS sizes (fx_generic_base_lds, fx_generic_lds) -- held here to the
 closed forms the launch sites spelled out before the rules were written once -- and walks of the passes' block layout (csrc/fx_pass.h,
-FxBlockLayout), held to its rule: every part at a multiple of 256 bytes, at least 8 bytes long, none overlapping."""
+FxBlockLayout), held to its rule: every part at a multiple of 256 bytes, at least 8 bytes long, none overlapping -- and the two
+rules of the passes that work in items (fx_item_chunk_steps, fx_item_batch), held to closed forms derived from their statements."""
 import importlib.util
 import json
 import os
@@ -55,13 +56,16 @@ def answers(tmp_path_factory):
     rows = recorded_rows()
     text = [row_text(r) for r in rows] + [row_text(r, second=True) for r in rows if "info_second" in r]
     out = subprocess.run([exe], input="\n".join(text) + "\n", capture_output=True, text=True, check=True).stdout
-    got, lds, launch, layouts = {}, {}, {}, []
+    got, lds, launch, layouts, items = {}, {}, {}, [], {}
     for line in out.splitlines():
         name, kind, rest = (line.split(" ", 2) + [""])[:3]
         if name == "#layout":
             v = [int(x) for x in line.split()[1:]]
             assert len(v) == 2 * v[0] + 2
             layouts.append((v[1:1 + v[0]], v[1 + v[0]:1 + 2 * v[0]], v[-1]))
+        elif name == "#items":
+            v = [int(x) for x in rest.split()]
+            items[(kind,) + tuple(v[:-1])] = v[-1]
         elif kind == "lds":
             v = [int(x) for x in rest.split()]
             lds[name] = [tuple(v[i:i + 6]) for i in range(0, len(v), 6)]
@@ -74,7 +78,7 @@ def answers(tmp_path_factory):
             code, msg = rest.split(" ", 1)
             got[name] = ("err", int(code), msg)
     assert len(got) == len(text) and len(lds) == len(text)
-    got["#lds"], got["#launch"], got["#layouts"] = lds, launch, layouts
+    got["#lds"], got["#launch"], got["#layouts"], got["#items"] = lds, launch, layouts, items
     return got
 
 
@@ -166,3 +170,19 @@ def test_block_layout_rule(answers):
         assert total == at and total % 256 == 0, (parts, offs, total)
         spans = sorted((o, o + max(b, 8)) for b, o in zip(parts, offs))
         assert all(e0 <= s1 for (_s0, e0), (s1, _e1) in zip(spans, spans[1:])), (parts, offs)
+
+
+def test_item_rules_closed_forms(answers):
+    """Steps per chunk: as many as keep a call at 4096 items or more -- one at the planner's grid (34 tiles x 8 obstacles x 15 pairs
+    of steps = 4080 items, too few to double), the whole horizon at config 3 -- a forced size capped at the horizon, one step where
+    there is none.  Candidates per batch: whole tiles of 64 within 64 MiB of scratch -- 64 MiB // 33600 B // 64 = 31 tiles -- never
+    fewer than one tile, never more tiles than the call has."""
+    items = answers["#items"]
+    want = {("chunk", 2176, 31, 8, 0): 1, ("chunk", 50388, 31, 20, 0): 30,
+            ("batch", 7 * 20 * 30 * 8, 2176): 1984, ("batch", 100, 1): 64, ("batch", 100, 0): 64, ("batch", 100, 65): 128,
+            ("batch", 2 * (64 << 20), 1000): 64}
+    for n, K in ((1, 1), (2176, 8), (50388, 20)):
+        want["chunk", n, 31, K, 99] = 30
+    for n, K in ((1, 0), (2176, 8), (50388, 20)):
+        want["chunk", n, 1, K, 0] = 1
+    assert items == want

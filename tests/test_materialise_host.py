@@ -169,4 +169,4 @@ def test_new_symbols_are_declared_and_exported():
         assert re.search(r"\b" + sym + r"\s*\(", hdr), f"{sym} is not declared in fxplan.h"
         assert sym in _lib.exported_symbols() and hasattr(L, sym), sym
         assert getattr(L, sym).argtypes is not None
-    assert _abi.FX_ABI_VERSION == 14 and L.fx_abi_version() == 14 and "#define FX_ABI_VERSION 14" in hdr
+    assert _abi.FX_ABI_VERSION == 15 and L.fx_abi_version() == 15 and "#define FX_ABI_VERSION 15" in hdr

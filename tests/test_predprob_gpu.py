@@ -313,12 +313,16 @@ def test_rewritten_inputs_are_refused():
 
 def test_device_bytes_without_the_pass():
     """a context that never calls the pass reports the device bytes it always did: nothing of the pass is allocated at creation,
-    by a plan step, by the obstacle tables or by risk(); the first call grows the risk passes' block, and only it"""
+    by a plan step, by the obstacle tables or by risk(); the first call takes its scratch -- [K][S - 1][whole tiles] doubles and
+    more -- from the risk passes' block, and only from it: it grows the block of a context that made no risk call, and behind
+    risk() over all candidates, whose items keep two partials per obstacle and step where the pass keeps one probability, the
+    block, which only grows, already holds it"""
     from frenetix_motion_planner_amd import risk
     from tests.test_risk_gpu import BASE, HARM, EGO
     inp = _make()
+    need = 8 * 8 * (inp.n_samples - 1) * (-(-inp.n_candidates // 64) * 64)
     seen = []
-    for call in (False, True):
+    for call in (False, True, None):   # None: the pass is the first call on the block
         with _engine(inp) as eng:
             b0 = eng.device_bytes
             eng.plan_step(inp)
@@ -327,11 +331,15 @@ def test_device_bytes_without_the_pass():
             preds, typ = _predictions(planes, flags, np.random.default_rng(7), n_obs=8)
             eng.set_risk_obstacles(risk.obstacle_tables(preds, typ))
             b1 = eng.device_bytes
+            if call is None:
+                eng.prediction_probability(EGO_L, EGO_W)
+                assert eng.device_bytes - b1 > need
+                continue
             eng.risk(risk.risk_params(BASE, HARM, **EGO))
             b2 = eng.device_bytes
             if call:
                 eng.prediction_probability(EGO_L, EGO_W)
-                assert eng.device_bytes > b2
+                assert eng.device_bytes >= b2 and eng.device_bytes - b1 > need
             seen.append((b0, b1, b2))
     assert seen[0] == seen[1]
 

@@ -114,6 +114,20 @@ def test_no_obstacles_is_zero_risk(step):
     assert np.all(ego[ids] == 0) and np.all(obst[ids] == 0) and idx == ids[0]
 
 
+@pytest.mark.parametrize("n", [1, 64, 65, 1024, 1025])
+def test_argmin_of_all_equal_is_the_lowest_id(step, n):
+    """The tie rule of the one-workgroup arg-min (1024 lanes), across lanes, waves and strides: without obstacles every listed
+    candidate has risk 0.0, and of a DESCENDING list the lowest id stands in the last lane that has an entry -- of the only wave,
+    the last of a full wave, the first of a second wave, the last lane of the workgroup, the first lane's second entry."""
+    from frenetix_motion_planner_amd import risk
+    eng, inp, flags, planes = step
+    eng.set_risk_obstacles(risk.obstacle_tables({}, {}))
+    ids = np.arange(inp.n_candidates - 1, inp.n_candidates - 1 - n, -1)
+    assert len(ids) == n and ids[-1] == ids.min() > 0
+    ego, obst, idx = eng.risk(risk.risk_params(BASE, HARM, **EGO), ids)
+    assert np.all(ego == 0) and np.all(obst == 0) and idx == ids[-1]
+
+
 def test_risk_needs_the_bundle():
     from frenetix_motion_planner_amd import synthetic, risk
     from frenetix_motion_planner_amd.engine import FrenetEngine, build_obstacle_hulls

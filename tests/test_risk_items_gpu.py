@@ -1,7 +1,11 @@
-"""The trajectory-risk walk in the item decomposition (fx_risk_items_kernel.h) against the walk itself: every
-output of risk(), risk_detail() and risk_costs() with set_risk_decomposition("items") is the one of "walk" on the same context,
-step and obstacles, bit for bit (np.array_equal, NaN rows equal) -- the walk is held to the restatement and the reference's own
-values by tests/test_risk_gpu.py, test_risk_costs_gpu.py and test_risk_golden.py.
+"""The items of the trajectory-risk walk (fx_risk_kernel.h): the chunk size changes no bit.  Every output of
+risk(), risk_detail() and risk_costs() with the automatic chunk size, with one step per chunk and with seven is the one with ONE
+chunk per obstacle -- the serial step order -- on the same context, step and obstacles, bit for bit (np.array_equal, NaN rows
+equal); so are the batches of the partials, an agent of a batch context and calls that share the block.
+
+These tests once held the item kernels to a second walk, one lane per candidate, which alone was held to the references; that walk
+is gone.  The item kernels are now held directly, at 1e-12, to the NumPy restatements and to the reference's own values by
+tests/test_risk_gpu.py, test_risk_costs_gpu.py and test_risk_golden.py, which run unedited on them.
 
 Why equality and not a tolerance: every per-step value comes from the same device function on the same operands, and what is kept
 of them is a maximum (fmax from -inf: associative and commutative bit for bit) or the first maximum of a list (strict >, chunks
@@ -40,7 +44,6 @@ def step():
     eng.plan_step(inp)
     _, flags = eng.costs()
     yield eng, inp, flags, _planes(eng)
-    eng.set_risk_decomposition("walk")
     eng.close()
 
 
@@ -81,7 +84,7 @@ def _calls(eng, params, cost, lists):
 
 @pytest.mark.parametrize("mode", list(MODES))
 @pytest.mark.parametrize("K", [0, 1, 3, 4])
-def test_items_equal_the_walk(step, K, mode):
+def test_chunk_size_changes_no_bit(step, K, mode):
     from frenetix_motion_planner_amd import risk
     from frenetix_motion_planner_amd._lib import lib
     eng, inp, flags, planes = step
@@ -106,23 +109,24 @@ def test_items_equal_the_walk(step, K, mode):
     params = risk.risk_params(modes, HARM, **EGO)
     # (lists spread over the whole grid: the 64 lanes of a tile hold candidates of every end time, velocity and offset)
     lists = {n: (None if n is None else ok[np.linspace(0, len(ok) - 1, n).astype(int)]) for n in COUNTS}
-    eng.set_risk_decomposition("walk")
-    want = _calls(eng, params, cost, lists)
-    if K and mode != "mahalanobis":
-        # the gate diverges inside a tile: of the first 64 listed candidates some come within 5 m of obstacle 0 and some never do
-        r0 = want[64, "detail"]["obst_risk_max"][:, 0]
-        assert (r0 > 0).any() and (r0 == 0).any()
-        assert (want[None, "detail"]["obst_risk_max"][ok][:, :3] > 0).any(axis=0).all()   # (every obstacle with a record is met by somebody)
-    if K >= 3:
-        assert np.nanmax(want[None, "detail"]["obst_harm_occ"]) > 0   # (a maximum above 0.001 somewhere: not a comparison of zeros)
-    eng.set_risk_decomposition("items")
     try:
+        lib().fx_risk_items_set_chunk_steps(S - 1)   # one chunk per obstacle: its steps in their serial order
+        assert lib().fx_risk_items_chunk_steps(C, S, max(K, 1)) == S - 1
+        want = _calls(eng, params, cost, lists)
+        if K and mode != "mahalanobis":
+            # the gate diverges inside a tile: of the first 64 listed candidates some come within 5 m of obstacle 0 and some never do
+            r0 = want[64, "detail"]["obst_risk_max"][:, 0]
+            assert (r0 > 0).any() and (r0 == 0).any()
+            assert (want[None, "detail"]["obst_risk_max"][ok][:, :3] > 0).any(axis=0).all()   # (every obstacle with a record is met by somebody)
+        if K >= 3:
+            assert np.nanmax(want[None, "detail"]["obst_harm_occ"]) > 0   # (a maximum above 0.001 somewhere: not a comparison of zeros)
+        lib().fx_risk_items_set_chunk_steps(0)   # the automatic size
         got = _calls(eng, params, cost, lists)
         for key, w in want.items():
             assert _same(got[key], w), key
         assert eng.last_risk_ms > 0
         some = {n: lists[n] for n in (65, None)}
-        for cs in (1, 7, S - 1):
+        for cs in (1, 7):
             lib().fx_risk_items_set_chunk_steps(cs)
             assert lib().fx_risk_items_chunk_steps(C, S, max(K, 1)) == cs
             got = _calls(eng, params, cost, some)
@@ -130,7 +134,6 @@ def test_items_equal_the_walk(step, K, mode):
                 assert _same(g, want[key]), (cs, key)
     finally:
         lib().fx_risk_items_set_chunk_steps(0)
-        eng.set_risk_decomposition("walk")
     full = want[None, "detail"]
     off = np.setdiff1d(np.arange(C), ok)
     assert all(np.all(np.isnan(full[q][off])) for q in COLS + ("ego_risk", "obst_harm_occ"))
@@ -163,7 +166,11 @@ def test_first_maximum_across_chunks():
         eng.set_risk_obstacles(risk.obstacle_tables(preds, typ))
         params = risk.risk_params(BASE, HARM, **EGO)
         ids = np.concatenate([still[:3], np.arange(0, inp.n_candidates, 29)])
-        walk = eng.risk_detail(params, ids)
+        try:
+            lib().fx_risk_items_set_chunk_steps(S - 1)   # one chunk: the steps in their serial order
+            walk = eng.risk_detail(params, ids)
+        finally:
+            lib().fx_risk_items_set_chunk_steps(0)
         sub = ids[:1]
         ref = rcr.calc_risk_detail(*[planes[n][sub] for n in ("x", "y", "theta", "v")], preds, typ, BASE, HARM, **EGO)
         # the precondition: a probability above the 0.001 of the rule, the first step's harm well below the horizon's largest
@@ -178,19 +185,24 @@ def test_first_maximum_across_chunks():
             assert len(tied) >= 2 and tied[0] == 0, (cs, prob)
         harm = rcr._harm(*[planes[n][sub] for n in ("x", "y", "theta", "v")], preds[7], "car", BASE, HARM, EGO["ego_mass"])[1][0]
         assert np.all(harm[1:] > harm[0])   # (any later tied step would give a larger harm: `>=` in a combine would show)
-        eng.set_risk_decomposition("items")
         try:
-            for cs in (0, 1, 7, S - 1):   # (1 and 7: the tied maximum lies in every chunk)
+            for cs in (0, 1, 7):   # (1 and 7: the tied maximum lies in every chunk)
                 lib().fx_risk_items_set_chunk_steps(cs)
                 assert _same(eng.risk_detail(params, ids), walk), cs
         finally:
             lib().fx_risk_items_set_chunk_steps(0)
 
 
+def _rows(res, rows):
+    """the per-candidate rows of a risk_detail result"""
+    return {k: v[rows] for k, v in res.items() if isinstance(v, np.ndarray)}
+
+
 def test_more_than_one_batch_of_partials(step):
     """The partials of one batch stay within 64 MiB: with K = 20 obstacles and one step per chunk a candidate's share of the detail
     pass is 7 values x 20 obstacles x 30 chunks x 8 bytes = 33 600 bytes, a batch holds 1 984 candidates (31 whole tiles) and the
-    2 176 candidates of the grid take two -- the second one ragged, 192 candidates in 3 tiles."""
+    2 176 candidates of the grid take two -- the second one ragged, 192 candidates in 3 tiles.  The base: the second batch's
+    candidates as a list of their own, which one batch holds."""
     from frenetix_motion_planner_amd import risk
     from frenetix_motion_planner_amd._lib import lib
     from tests.test_risk_gpu import _predictions
@@ -202,22 +214,29 @@ def test_more_than_one_batch_of_partials(step):
     params = risk.risk_params(BASE, HARM, **EGO)
     ok = np.nonzero((flags & NEED) == NEED)[0]
     assert ok.max() >= 1984   # (selected candidates in the second batch)
-    eng.set_risk_decomposition("walk")
-    want = eng.risk_detail(params), eng.risk_detail(params, np.arange(C)[::-1])
-    assert (want[0]["obst_risk_max"][ok[ok >= 1984]] > 0).any()
-    eng.set_risk_decomposition("items")
+    second = np.arange(1984, C)
+    sel = ok[ok >= 1984]
+    assert len(second) <= 1984
+    want = _rows(eng.risk_detail(params, second), slice(None))
+    assert (want["obst_risk_max"][sel - 1984] > 0).any()
     try:
         lib().fx_risk_items_set_chunk_steps(1)
-        assert _same(eng.risk_detail(params), want[0]) and _same(eng.risk_detail(params, np.arange(C)[::-1]), want[1])
+        full, rev = eng.risk_detail(params), eng.risk_detail(params, np.arange(C)[::-1])
     finally:
         lib().fx_risk_items_set_chunk_steps(0)
-        eng.set_risk_decomposition("walk")
+    assert _same(_rows(rev, C - 1 - second), want)                       # a listed candidate is evaluated whatever its flags say
+    assert _same(_rows(full, sel), _rows(want, sel - 1984))              # every candidate: the selected ones ...
+    off = np.setdiff1d(second, sel)
+    assert all(np.all(np.isnan(v)) for v in _rows(full, off).values())   # ... and NaN rows for the others
 
 
 def test_agent_of_a_batch_context():
+    """Agent 1 of a batch context returns what the same agent returns planned alone on a fresh engine"""
     from frenetix_motion_planner_amd import risk
     from frenetix_motion_planner_amd.engine import FrenetEngine
     inps = [_make(grid=(3, 5, 5)), _make(grid=(6, 7, 9), v0=8.0)]
+    params = risk.risk_params(BASE, HARM, **EGO)
+    cost = lambda: risk.risk_cost_params(WEIGHTS, responsibility=np.array([1.0, 0.0, 1.0]))
     with FrenetEngine(max_candidates=max(i.n_candidates for i in inps), device=0, max_agents=2) as eng:
         eng.plan_batch(inps)
         _, flags = eng.costs(1)
@@ -225,20 +244,23 @@ def test_agent_of_a_batch_context():
         ok = np.nonzero((flags & NEED) == NEED)[0]
         assert len(ok) > 64
         preds, typ = _obstacles(planes, ok, 3)
-        eng.set_risk_obstacles(risk.obstacle_tables(preds, typ), agent=1)
-        params = risk.risk_params(BASE, HARM, **EGO)
-        cost = lambda: risk.risk_cost_params(WEIGHTS, responsibility=np.array([1.0, 0.0, 1.0]))
-        want = [eng.risk(params, agent=1), eng.risk_detail(params, ok[:70], agent=1), eng.risk_costs(params, cost(), agent=1)]
-        assert np.nanmax(want[2]["obst_harm_occ"]) > 0
-        assert np.nanmax(want[1]["obst_risk_max"]) > 0
-        eng.set_risk_decomposition("items")
+        tabs = risk.obstacle_tables(preds, typ)
+        eng.set_risk_obstacles(tabs, agent=1)
         got = [eng.risk(params, agent=1), eng.risk_detail(params, ok[:70], agent=1), eng.risk_costs(params, cost(), agent=1)]
-        assert all(_same(g, w) for g, w in zip(got, want))
+    assert np.nanmax(got[2]["obst_harm_occ"]) > 0
+    assert np.nanmax(got[1]["obst_risk_max"]) > 0
+    with FrenetEngine(max_candidates=inps[1].n_candidates, device=0) as alone:
+        alone.plan_step(inps[1])
+        assert _same(alone.costs()[1], flags) and _same(_planes(alone), planes)   # (the same step: what the passes read)
+        alone.set_risk_obstacles(tabs)
+        want = [alone.risk(params), alone.risk_detail(params, ok[:70]), alone.risk_costs(params, cost())]
+    assert all(_same(g, w) for g, w in zip(got, want))
 
 
 def test_items_share_the_block():
-    """The partials live in the risk passes' grow-only block: the first items call grows it, a repetition and smaller calls do not,
-    and calls in either decomposition afterwards return what they return on a fresh engine (test_calls_share_one_block's property)."""
+    """The partials live in the risk passes' grow-only block: the first, largest call grows it, a repetition and smaller calls do
+    not, and the largest call returns, first and after the others, what it returns on a fresh engine (test_calls_share_one_block's
+    property)."""
     from frenetix_motion_planner_amd import risk
     from frenetix_motion_planner_amd.engine import FrenetEngine
     inp = _make(grid=(6, 7, 3), n_obstacles=2)
@@ -254,27 +276,14 @@ def test_items_share_the_block():
         calls = [lambda e: e.risk_costs(params, cost()), lambda e: e.risk(params, ok[::3]), lambda e: e.risk_detail(params, ok)]
         eng.set_risk_obstacles(tabs)
         b0 = eng.device_bytes
-        walk = [call(eng) for call in calls]
-        b1 = eng.device_bytes
-        eng.set_risk_decomposition("items")
         first = calls[0](eng)
         b2 = eng.device_bytes
-        assert b1 > b0 and b2 > b1
+        assert b2 > b0
         items = [first] + [call(eng) for call in calls[1:]] + [calls[0](eng)]
         assert eng.device_bytes == b2
-        eng.set_risk_decomposition("walk")
-        again = [call(eng) for call in calls]
-        assert eng.device_bytes == b2
-    assert all(_same(g, w) for g, w in zip(items, walk + walk[:1])) and all(_same(g, w) for g, w in zip(again, walk))
-    with FrenetEngine(max_candidates=inp.n_candidates, device=0) as fresh:   # only the items call, on a fresh engine
+    assert _same(items[-1], first)
+    with FrenetEngine(max_candidates=inp.n_candidates, device=0) as fresh:   # only the first call, on a fresh engine
         fresh.plan_step(inp)
         fresh.set_risk_obstacles(tabs)
-        fresh.set_risk_decomposition("items")
         assert fresh.device_bytes == b0
-        assert _same(calls[0](fresh), walk[0])
-
-
-def test_unknown_decomposition_is_refused(step):
-    eng = step[0]
-    with pytest.raises(ValueError):
-        eng.set_risk_decomposition("tiles")
+        assert _same(calls[0](fresh), first)

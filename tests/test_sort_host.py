@@ -122,7 +122,7 @@ def test_refusals_that_need_no_device():
     assert L.fx_sort_views(None, 0, C.byref(p), C.byref(a)) == _abi.FX_ERR_INVALID_ARGUMENT
     assert L.fx_last_sort_ms(None) == -1.0
     assert (a.value, b.value, p.value) == (7, 7, 5) and not idx.any()          # nothing was written
-    assert L.fx_abi_version() == _abi.FX_ABI_VERSION == 14                     # additive: the version stays
+    assert L.fx_abi_version() == _abi.FX_ABI_VERSION == 15                     # additive: the version stays
     for name in ("fx_sort_candidates_agent", "fx_sort_candidates_batch", "fx_read_ranked_agent", "fx_sort_views", "fx_last_sort_ms"):
         assert name in _lib.exported_symbols()
 

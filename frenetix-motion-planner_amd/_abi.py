@@ -165,6 +165,10 @@ class FxPredProbOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("prob", "prob_obs", "total", "best_index", "best_cost")]
 
 
+class FxPredProbBatchOutputs(C.Structure):   # (fx_eval_prediction_prob_batch)
+    _fields_ = [(n, C.c_void_p) for n in ("prob", "total", "best_index", "best_cost")]
+
+
 # the responsibility cost as a weighted term (fxplan.h)
 BESIDE_STEP_COSTS = ("responsibility",)   # cost names the planner evaluates by a pass beside the plan step (PlanInputs refuses them)
 

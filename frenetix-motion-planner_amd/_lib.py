@@ -44,7 +44,7 @@ def exported_symbols():
         "fx_set_reach_sets_agent", "fx_eval_risk_costs_agent",
         "fx_materialise_candidates_agent", "fx_read_materialised_agent", "fx_read_package_materialised", "fx_last_materialise_ms",
         "fx_sort_candidates_agent", "fx_sort_candidates_batch", "fx_read_ranked_agent", "fx_sort_views", "fx_last_sort_ms",
-        "fx_eval_prediction_prob_agent", "fx_last_predprob_ms",
+        "fx_eval_prediction_prob_agent", "fx_last_predprob_ms", "fx_eval_prediction_prob_batch",
         "fx_eval_responsibility_cost_agent",
     ]
 
@@ -158,8 +158,12 @@ def lib():
         "fx_eval_prediction_prob_agent": ([vp, C.c_int32, C.POINTER(_abi.FxPredProbParams), C.c_int64, pi64,
                                            C.POINTER(_abi.FxPredProbOutputs)], C.c_int32),
         "fx_last_predprob_ms": ([vp], C.c_double),
+        "fx_eval_prediction_prob_batch": ([vp, C.c_int32, pi32, C.POINTER(_abi.FxPredProbParams),
+                                           C.POINTER(_abi.FxPredProbBatchOutputs)], C.c_int32),
         # (launcher hook of the tests, not part of fxplan.h: steps per chunk of the prediction-probability items, 0 = automatic)
         "fx_predprob_set_chunk_steps": ([C.c_int32], None),
+        # (hook of the tests, not part of fxplan.h: bytes of scratch per round of the batched pass, 0 = FX_ITEM_SCRATCH_BYTES)
+        "fx_predprob_set_scratch_limit": ([C.c_int64], None),
         "fx_predprob_chunk_steps": ([C.c_int64, C.c_int32, C.c_int32], C.c_int32),
         "fx_eval_responsibility_cost_agent": ([vp, C.c_int32, C.POINTER(_abi.FxRiskParams), C.POINTER(_abi.FxRespCostParams), C.c_int64,
                                                pi64, C.POINTER(_abi.FxRespCostOutputs)], C.c_int32),

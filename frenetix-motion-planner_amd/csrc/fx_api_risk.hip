@@ -3,7 +3,8 @@
 // none, over the agent's sparse set: fx_api_materialise.hip); the reach sets of an agent and the detail /
 // risk-cost pass.  The two evaluations share one host path (RiskPass) and one device block.  Nothing of
 // this runs in a plan step.  The collision probability as the prediction cost (fx_predprob_kernel.h) is a third
-// entrance on the same host path: the same checks, records, uploads and block.
+// entrance on the same host path: the same checks, records, uploads and block; fx_eval_prediction_prob_batch
+// is that pass for several agents in one call: the same checks and records per agent, one staging buffer each for records and tables.
 #include <atomic>
 #include <cmath>
 #include <vector>
@@ -16,6 +17,12 @@ extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const RiskItemArg
                                      hipEvent_t ev_stop, hipStream_t stream, const RespSumArgs *resp, long long *resp_idx);
 extern "C" hipError_t fx_launch_predprob(const PredProbArgs *args, long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
                                          hipStream_t stream);
+// (weak, like the chunk rule below: a host-only program that links these files against launcher stubs of its own need not define
+// the launchers that came after it was written; fx_eval_prediction_prob_batch reports their absence)
+extern "C" __attribute__((weak)) hipError_t fx_launch_predprob_batch(const PredProbBatchArgs *t, const PredProbRound *rounds, int n_rounds,
+                                                                     long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                                                     hipStream_t stream);
+extern "C" __attribute__((weak)) int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K);   // (fx_kernels.hip: the rule, or what a test forces)
 
 namespace {
 // Gauss-Legendre nodes on [-1, 1], positive half: 6, 12 and 20 points (Genz 2004)
@@ -560,8 +567,9 @@ extern "C" int32_t fx_eval_responsibility_cost_agent(FxContext *c, int32_t agent
 
 // Collision probability as the prediction cost (fxplan.h).  The scratch holds the per-step probabilities of
 // one batch of candidates, [K][S - 1][batch] (fx_item_batch, fx_pass.h).
-extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, const FxPredProbParams *params, int64_t n_ids,
-                                                 const int64_t *ids, const FxPredProbOutputs *out) {
+// The checks of the pass for one agent, in the order the entry points report them; n_pred: where the cost list has its prediction
+static int predprob_check(RiskPass &q, FxContext *c, int32_t agent, const FxPredProbParams *params, int64_t n_ids, const int64_t *ids,
+                          bool have_out, int &n_pred) {
     FX_TRY(check_agent(c, agent));
     // (the planes and the cost map are the last EVALUATED step's: inputs rewritten since belong to a step that has not run -- the
     // condition of the sort and of the sparse set, fx_api_sort.hip / fx_api_materialise.hip)
@@ -573,27 +581,42 @@ extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, co
     rp.prot_model = rp.unprot_ego_model = FX_RISK_HARM_LOGISTIC;
     rp.ego_mass = 1.0;
     if (params) { rp.ego_length = params->ego_length; rp.ego_width = params->ego_width; }
-    RiskPass q;
-    FX_TRY(risk_check(q, c, agent, params ? &rp : nullptr, n_ids, ids, out != nullptr, false, false));
+    FX_TRY(risk_check(q, c, agent, params ? &rp : nullptr, n_ids, ids, have_out, false, false));
+    q.prm = nullptr;   // (rp is a local; this pass reads the footprint from its own parameters)
     if (params->source != FX_PRED_SOURCE_PROBABILITY && params->source != FX_PRED_SOURCE_STEP)
         return set_err(FX_ERR_INVALID_ARGUMENT, "source %d", params->source);
     const DevProblem &hp = c->h_probs[agent];
-    int n_pred = -1;
+    n_pred = -1;
     for (int m = 0; m < hp.n_cost; m++)
         if (hp.cost_id[m] == FX_COST_PREDICTION) n_pred = m;
     if (n_pred < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "the cost list has no FX_COST_PREDICTION");
+    return FX_OK;
+}
+
+// what the kernels read of a checked agent, but for the records, the scratch and the outputs
+static void predprob_args(const RiskPass &q, const FxPredProbParams *params, int n_pred, PredProbArgs &a) {
+    const DevProblem &hp = q.c->h_probs[q.agent];
+    a.planes = q.planes, a.ld = q.ld, a.S = q.S, a.K = q.K, a.n = q.n, a.flags = q.flags;
+    a.ego_length = params->ego_length, a.ego_width = params->ego_width, a.source = params->source;
+    a.costmap = q.sparse ? q.set.costmap : q.c->d_costmap + (size_t)FX_NUM_COSTS * q.s->cand_off;
+    a.n_cost = hp.n_cost, a.n_pred = n_pred;
+    // (a sparse set's rows were closed by the list kernel, which never defers)
+    a.deferred = (!q.sparse && (hp.mode & FX_MODE_INT_DEFER_OBST)) ? 1 : 0;
+    for (int m = 0; m < hp.n_cost; m++) a.cost_w[m] = hp.cost_w[m];
+}
+
+extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, const FxPredProbParams *params, int64_t n_ids,
+                                                 const int64_t *ids, const FxPredProbOutputs *out) {
+    RiskPass q;
+    int n_pred;
+    FX_TRY(predprob_check(q, c, agent, params, n_ids, ids, out != nullptr, n_pred));
     const size_t per_cand = sizeof(double) * (size_t)std::max(q.K, 1) * (size_t)std::max(q.S - 1, 1);
     const size_t nb = (size_t)fx_item_batch(per_cand, q.n);
     FX_TRY(risk_stage(q, false, nullptr, nb));
     FxRiskState *r = q.r;
     PredProbArgs a{};
-    a.planes = q.planes, a.ld = q.ld, a.S = q.S, a.K = q.K, a.n = q.n, a.ids = q.d_ids(), a.flags = q.flags, a.rec = q.D(q.o_rec);
-    a.ego_length = params->ego_length, a.ego_width = params->ego_width, a.source = params->source;
-    a.costmap = q.sparse ? q.set.costmap : c->d_costmap + (size_t)FX_NUM_COSTS * q.s->cand_off;
-    a.n_cost = hp.n_cost, a.n_pred = n_pred;
-    // (a sparse set's rows were closed by the list kernel, which never defers)
-    a.deferred = (!q.sparse && (hp.mode & FX_MODE_INT_DEFER_OBST)) ? 1 : 0;
-    for (int m = 0; m < hp.n_cost; m++) a.cost_w[m] = hp.cost_w[m];
+    predprob_args(q, params, n_pred, a);
+    a.ids = q.d_ids(), a.rec = q.D(q.o_rec);
     a.step = q.D(q.o_pstep), a.nb = (int64_t)nb;
     a.prob = q.D(q.o_pprob), a.prob_obs = out->prob_obs ? q.D(q.o_pobs) : nullptr, a.total = q.D(q.o_ptot);
     long long *d_best = reinterpret_cast<long long *>(q.base + q.o_pbest);
@@ -610,6 +633,136 @@ extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, co
     if (q.sparse && best[0] >= 0) best[0] = (long long)q.set.ids[best[0]];
     if (out->best_index) *out->best_index = (int64_t)best[0];
     if (out->best_cost) memcpy(out->best_cost, &best[1], sizeof(double));
+    return FX_OK;
+}
+
+// The same pass over every candidate of several agents in ONE call (fxplan.h).  Per agent the checks and
+// records of the call above; then all records and all tables in one staging buffer each, the rounds of fx_item_rounds (fx_pass.h)
+// over one scratch, and per round two launches whatever the agent count.  Runtime calls of a call with R rounds: 1 drain
+// (a synchronisation), 2 copies up (records, tables), 2 event records, 2 R + 1 launches, 3 copies down (prob, total, best),
+// 1 synchronisation -- none of them per agent.
+static std::atomic<long long> fx_predprob_scratch_forced{0};
+extern "C" void fx_predprob_set_scratch_limit(int64_t bytes) { fx_predprob_scratch_forced.store(bytes > 0 ? bytes : 0, std::memory_order_relaxed); }
+
+extern "C" int32_t fx_eval_prediction_prob_batch(FxContext *c, int32_t n_agents, const int32_t *agents, const FxPredProbParams *params,
+                                                 const FxPredProbBatchOutputs *out) {
+    if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
+    if (!params || !out) return set_err(FX_ERR_INVALID_ARGUMENT, "params or out is NULL");
+    if (n_agents < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d", n_agents);
+    if (n_agents == 0) return FX_OK;
+    if (!fx_launch_predprob_batch || !fx_predprob_chunk_steps) return set_err(FX_ERR_HIP, "built without the batched prediction-probability launcher");
+    if (!c->evaluated) return set_err(FX_ERR_NOT_READY, "no evaluated plan step");
+    if (n_agents > c->n_agents) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d of %d uploaded agents", n_agents, c->n_agents);
+    const size_t A = (size_t)n_agents;
+    std::vector<RiskPass> q(A);
+    std::vector<int> n_pred(A);
+    std::vector<char> listed((size_t)c->n_agents, 0);
+    for (size_t i = 0; i < A; i++) {
+        const int32_t agent = agents ? agents[i] : (int32_t)i;
+        if (agent >= 0 && agent < c->n_agents && listed[agent]) return set_err(FX_ERR_INVALID_ARGUMENT, "agent %d listed twice", agent);
+        if (const int rc = predprob_check(q[i], c, agent, params + i, 0, nullptr, true, n_pred[i])) {
+            char why[sizeof(g_err)];
+            snprintf(why, sizeof(why), "%s", g_err);
+            return set_err(rc, "agent %d: %s", agent, why);
+        }
+        listed[agent] = 1;
+    }
+    // records of all agents in one buffer; one candidate's share of the scratch: a probability per (obstacle, step), none where
+    // no item runs
+    std::vector<double> rec, one;
+    std::vector<size_t> rec_at(A), out_at(A);
+    std::vector<FxItemAgent> ia(A);
+    size_t rows_out = 0;
+    for (size_t i = 0; i < A; i++) {
+        const RiskPass &p = q[i];
+        rec_at[i] = rec.size();
+        out_at[i] = rows_out;
+        rows_out += (size_t)p.n;
+        const bool items = params[i].source == FX_PRED_SOURCE_PROBABILITY && p.K > 0 && p.S > 1;
+        if (items) {
+            build_records(*p.a, p.S, false, one);
+            rec.insert(rec.end(), one.begin(), one.end());
+        }
+        ia[i] = FxItemAgent{p.n, items ? sizeof(double) * (size_t)p.K * (size_t)(p.S - 1) : 0};
+    }
+    const long long forced = fx_predprob_scratch_forced.load(std::memory_order_relaxed);
+    const size_t limit = forced > 0 ? (size_t)forced : FX_ITEM_SCRATCH_BYTES;
+    const std::vector<FxItemSegment> segs = fx_item_rounds(ia.data(), n_agents, limit);
+    const size_t R = segs.size();
+    const int n_rounds = R ? segs.back().round + 1 : 0;
+    // the rounds' sizes: tiles x obstacles of all rows choose the chunk steps of each (fx_item_chunk_steps), the largest scratch
+    std::vector<PredProbRound> rounds((size_t)n_rounds, PredProbRound{0, 0, 0, 0});
+    std::vector<int64_t> tile_obst((size_t)n_rounds, 0);
+    size_t scratch = 0;
+    for (size_t k = 0; k < R; k++) {
+        const FxItemSegment &g = segs[k];
+        const size_t tiles = (size_t)(g.count + 63) / 64;
+        if (ia[g.agent].per_candidate_bytes) tile_obst[g.round] += (int64_t)tiles * q[g.agent].K;
+        scratch = std::max(scratch, g.scratch_off + tiles * 64 * ia[g.agent].per_candidate_bytes);
+    }
+    FxBlockLayout lay;
+    const size_t o_rec = lay.take(sizeof(double) * rec.size());
+    const size_t t_rows = 0, t_item0 = align_up(sizeof(PredProbRow) * R, 8), t_fin0 = t_item0 + sizeof(int64_t) * R,
+                 t_arow = t_fin0 + sizeof(int32_t) * R, t_size = t_arow + sizeof(int32_t) * A;
+    const size_t o_tab = lay.take(t_size), o_step = lay.take(scratch);
+    const size_t o_prob = lay.take(sizeof(double) * rows_out), o_tot = lay.take(sizeof(double) * rows_out);
+    const size_t o_best = lay.take(2 * sizeof(long long) * A);
+    FxRiskState *r = q[0].r;
+    HIP_TRY(hipSetDevice(c->device));
+    FX_TRY(fx_drain(c));
+    FX_TRY(r->block.ensure(lay.size()));
+    FX_TRY(r->ev.ensure());
+    char *base = r->block;
+    auto D = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    std::vector<char> tab(t_size, 0);
+    PredProbRow *rows = reinterpret_cast<PredProbRow *>(tab.data() + t_rows);
+    int64_t *item0 = reinterpret_cast<int64_t *>(tab.data() + t_item0);
+    int32_t *fin0 = reinterpret_cast<int32_t *>(tab.data() + t_fin0), *agent_row = reinterpret_cast<int32_t *>(tab.data() + t_arow);
+    for (size_t i = 0; i < A; i++) agent_row[i] = -1;
+    for (size_t k = 0; k < R; k++) {
+        const FxItemSegment &g = segs[k];
+        const RiskPass &p = q[g.agent];
+        PredProbRound &rd = rounds[g.round];
+        if (rd.n_rows == 0) rd.row0 = (int32_t)k;
+        rd.n_rows++;
+        PredProbRow &w = rows[k];
+        predprob_args(p, params + g.agent, n_pred[g.agent], w.a);
+        w.a.ids = nullptr, w.a.rec = D(o_rec) + rec_at[g.agent];
+        w.a.step = reinterpret_cast<double *>(base + o_step + g.scratch_off), w.a.nb = (g.count + 63) / 64 * 64;
+        w.a.prob = D(o_prob) + out_at[g.agent], w.a.prob_obs = nullptr, w.a.total = D(o_tot) + out_at[g.agent];
+        w.first = g.first, w.count = g.count;
+        const bool items = ia[g.agent].per_candidate_bytes != 0;
+        // (the round's tiles x obstacles as the candidates of ONE obstacle: the rule then sees the launch, not the agent)
+        w.cs = fx_predprob_chunk_steps(64 * tile_obst[g.round], p.S, 1);
+        w.chunks = items ? (std::max(p.S - 1, 1) + w.cs - 1) / w.cs : 0;
+        w.item0 = item0[k] = rd.items;
+        w.fin0 = fin0[k] = rd.fin_blocks;
+        rd.items += (w.a.nb / 64) * w.chunks * (int64_t)p.K;
+        rd.fin_blocks += (int32_t)((g.count + 255) / 256);
+        agent_row[g.agent] = (int32_t)k;
+    }
+    for (const PredProbRound &rd : rounds)
+        if (rd.items > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld items", (long long)rd.items);
+    if (!rec.empty()) HIP_TRY(hipMemcpyAsync(base + o_rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(base + o_tab, tab.data(), t_size, hipMemcpyHostToDevice, c->stream));
+    PredProbBatchArgs t{};
+    t.rows = reinterpret_cast<const PredProbRow *>(base + o_tab + t_rows);
+    t.item0 = reinterpret_cast<const int64_t *>(base + o_tab + t_item0);
+    t.fin0 = reinterpret_cast<const int32_t *>(base + o_tab + t_fin0);
+    t.agent_row = reinterpret_cast<const int32_t *>(base + o_tab + t_arow);
+    t.n_agents = n_agents;
+    long long *d_best = reinterpret_cast<long long *>(base + o_best);
+    HIP_TRY(fx_launch_predprob_batch(&t, rounds.data(), n_rounds, d_best, r->ev.e0, r->ev.e1, c->stream));
+    if (out->prob && rows_out) HIP_TRY(hipMemcpyAsync(out->prob, base + o_prob, sizeof(double) * rows_out, hipMemcpyDeviceToHost, c->stream));
+    if (out->total && rows_out) HIP_TRY(hipMemcpyAsync(out->total, base + o_tot, sizeof(double) * rows_out, hipMemcpyDeviceToHost, c->stream));
+    std::vector<long long> best(2 * A);
+    HIP_TRY(hipMemcpyAsync(best.data(), d_best, sizeof(long long) * 2 * A, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&r->last_pp_ms, r->ev.e0, r->ev.e1));
+    for (size_t i = 0; i < A; i++) {
+        if (out->best_index) out->best_index[i] = (int64_t)best[2 * i];
+        if (out->best_cost) memcpy(out->best_cost + i, &best[2 * i + 1], sizeof(double));
+    }
     return FX_OK;
 }
 

@@ -53,6 +53,40 @@ inline int64_t fx_item_batch(size_t per_candidate_bytes, int64_t n) {
     return (int64_t)(std::min(tiles, call) * 64);
 }
 
+// The rounds of such a pass over SEVERAL agents in one call (fx_eval_prediction_prob_batch): the scratch of one round holds
+// segments of candidates of one or more agents, at most `limit` bytes of it.  agents: per agent its n candidates and one
+// candidate's share of the scratch in bytes (0: the agent needs none).  The rule:
+//   * agents in call order, each agent's candidates ascending and contiguous;
+//   * a segment's scratch is whole tiles of 64 candidates, and every segment but an agent's last is whole tiles;
+//   * a round is closed only when the next tile does not fit; a tile that alone exceeds the limit is a round by itself
+//     (fx_item_batch's "at least one tile").
+// An agent has at most one segment per round; an agent without candidates has none.  Pure: no HIP call (tests/item_rounds.cpp).
+struct FxItemAgent {
+    int64_t n;
+    size_t per_candidate_bytes;
+};
+struct FxItemSegment {
+    int32_t agent, round;   // position in the call's list; rounds count from 0
+    int64_t first, count;   // candidates [first, first + count) of the agent
+    size_t scratch_off;     // bytes, from the start of the round's scratch
+};
+inline std::vector<FxItemSegment> fx_item_rounds(const FxItemAgent *agents, int n_agents, size_t limit) {
+    std::vector<FxItemSegment> segs;
+    int32_t round = 0;
+    size_t used = 0;
+    for (int a = 0; a < n_agents; a++) {
+        const size_t tile = 64 * agents[a].per_candidate_bytes;
+        for (int64_t j = 0; j < agents[a].n; j += 64) {
+            if (used > 0 && tile > limit - std::min(used, limit)) { round++; used = 0; }
+            const int64_t m = std::min<int64_t>(64, agents[a].n - j);
+            if (!segs.empty() && segs.back().agent == a && segs.back().round == round) segs.back().count += m;
+            else segs.push_back(FxItemSegment{(int32_t)a, round, j, m, used});
+            used += tile;
+        }
+    }
+    return segs;
+}
+
 // wait for everything on the context's stream; what stays unknown is what a caller's own stream may hold (FxContext.tail_work)
 inline int fx_drain(FxContext *c) {
     HIP_TRY(hipStreamSynchronize(c->stream));

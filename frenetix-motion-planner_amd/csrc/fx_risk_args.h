@@ -116,3 +116,27 @@ struct PredProbArgs {
     int64_t nb;
     double *prob, *prob_obs, *total;   // [n], [K][n], [n]
 };
+
+// The pass over several agents in one call (fx_eval_prediction_prob_batch): one row per (round, agent with
+// candidates in it) in device memory, the rows of a round consecutive and in call order (fx_item_rounds, fx_pass.h).
+struct PredProbRow {
+    PredProbArgs a;            // of the agent: ids and prob_obs null, n = C, prob / total the agent's rows of the call's outputs,
+                               // step the agent's segment of the round's scratch, nb = count rounded up to whole tiles
+    int64_t first, count;      // the agent's candidates of this round
+    int32_t cs, chunks;        // steps per chunk, chunks = ceil(max(S - 1, 1) / cs); chunks = 0: the row has no item
+    int64_t item0;             // first item of the row in the round's flat index; its items: (nb / 64) x chunks x K, tile fastest
+    int32_t fin0;              // first workgroup of the row in the round's finish launch; it has ceil(count / 256)
+};
+// where the tables of a call lie, device pointers; the host's copy says what a round launches
+struct PredProbBatchArgs {
+    const PredProbRow *rows;   // [n_rows], all rounds
+    const int64_t *item0;      // [n_rows] the rows' item0, compact: a wave looks its row up with one load
+    const int32_t *fin0;       // [n_rows] the rows' fin0
+    const int32_t *agent_row;  // [n_agents] a row of the agent (any of them: the arg-min reads total, n and flags), -1 without one
+    int32_t n_agents;
+};
+struct PredProbRound {         // host only
+    int32_t row0, n_rows;
+    int64_t items;             // of all its rows
+    int32_t fin_blocks;
+};

@@ -1037,9 +1037,34 @@ class FrenetEngine(StepRegistry):
         res["best_index"], res["best_cost"] = int(best_index[0]), float(best_cost[0])
         return res
 
+    def prediction_probability_batch(self, ego_lengths, ego_widths, agents=None, source: str = "probability") -> list:
+        """`prediction_probability` over every candidate of several agents of the last plan step in ONE call
+        (fx_eval_prediction_prob_batch): per listed agent a dict of prob, total [C of that agent], best_index
+        and best_cost, bit for bit what prediction_probability(agent=a) returns.  ego_lengths / ego_widths: one number for all or
+        one per listed agent; agents None: every agent of the last upload, in order; the obstacles are each agent's
+        `set_risk_obstacles`.  The arrays are views of the call's concatenated ones."""
+        if source not in _abi.PRED_SOURCES:
+            raise ValueError(f"source {source!r}: one of {sorted(_abi.PRED_SOURCES)}")
+        listed = list(range(len(self._inputs))) if agents is None else [int(a) for a in agents]
+        n = len(listed)
+        ln, wd = np.broadcast_to(np.asarray(ego_lengths, np.float64), (n,)), np.broadcast_to(np.asarray(ego_widths, np.float64), (n,))
+        params = (_abi.FxPredProbParams * max(n, 1))(*[_abi.FxPredProbParams(float(ln[i]), float(wd[i]), _abi.PRED_SOURCES[source])
+                                                       for i in range(n)])
+        # (an agent the library will refuse counts no rows: the refusal comes before anything is written)
+        counts = [self._inputs[a].n_candidates if 0 <= a < len(self._inputs) else 0 for a in listed]
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        prob, total = np.zeros(max(int(off[-1]), 1)), np.zeros(max(int(off[-1]), 1))
+        best_index, best_cost = np.full(max(n, 1), -1, np.int64), np.full(max(n, 1), np.nan)
+        out = _abi.FxPredProbBatchOutputs(prob.ctypes.data, total.ctypes.data, best_index.ctypes.data, best_cost.ctypes.data)
+        ids = np.ascontiguousarray(listed, dtype=np.int32)
+        check(lib().fx_eval_prediction_prob_batch(self._ctx, n, ids.ctypes.data_as(C.POINTER(C.c_int32)) if agents is not None else None,
+                                                  params, C.byref(out)))
+        return [dict(prob=prob[off[i]:off[i + 1]], total=total[off[i]:off[i + 1]], best_index=int(best_index[i]),
+                     best_cost=float(best_cost[i])) for i in range(n)]
+
     @property
     def last_predprob_ms(self) -> float:
-        """device time of the last `prediction_probability` call (its kernels); -1 before the first"""
+        """device time of the last `prediction_probability` / `prediction_probability_batch` call (its kernels); -1 before the first"""
         return float(lib().fx_last_predprob_ms(self._ctx))
 
     def topk(self, k: int):

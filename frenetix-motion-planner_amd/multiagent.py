@@ -88,6 +88,11 @@ def trajectory_as_prediction(states: Sequence, shape: dict, wb_rear_axle: float,
                 v_list=np.array([s.velocity for s in st]), shape=dict(shape))
 
 
+# AgentBatchHip(batched_passes=None): what the measurement of DESIGN.md section 18 decided (its decision rule: on only if the
+# batched call's wall p95 lies below the per-agent loop's wall p5 at both planner-sized workloads)
+BATCHED_PASSES_DEFAULT = False
+
+
 class AgentBatchHip:
     """The agents of one rank stepped together: one batched launch for every agent that plans in this step.
 
@@ -97,8 +102,14 @@ class AgentBatchHip:
     once per step by every rank when any agent of the simulation is split."""
 
     def __init__(self, agents: List[FrenetPlannerInterfaceHip], max_candidates: int, device: int = 0, max_ref_knots: int = 4096,
-                 max_obstacles: int = 64, engine=None, parts=None, slots=None, winner_exchange=None, pipeline_groups: Optional[int] = None):
-        """pipeline_groups: the agents are dealt to that many engine contexts (contiguous groups); a planning step prepares group
+                 max_obstacles: int = 64, engine=None, parts=None, slots=None, winner_exchange=None, pipeline_groups: Optional[int] = None,
+                 batched_passes: Optional[bool] = None):
+        """batched_passes: the collision-probability pass of the planners that weight it (prediction_cost="collision_probability")
+        runs for all of them in ONE engine.prediction_probability_batch call per engine group and step, behind the batched launch,
+        instead of one call per agent from plan_consume -- the same bits.  None: BATCHED_PASSES_DEFAULT, the
+        measurement's verdict.  Escalated levels, split agents, planners that also weight `responsibility` and engines without the
+        method keep their per-agent pass.
+        pipeline_groups: the agents are dealt to that many engine contexts (contiguous groups); a planning step prepares group
         0's inputs, launches it, prepares group 1's while group 0 evaluates, ... and consumes the results in the same order -- the
         host work of one group runs in the shadow of another group's kernels (planner-sized grids are host-bound: BASELINE config 4).
         None: 2 for four or more agents with planner-sized grids (<= 40 000 candidates each), else 1; an injected `engine`, a
@@ -144,9 +155,27 @@ class AgentBatchHip:
         for e in self.engines:
             if hasattr(e, "set_package"):   # every agent's winner arrives packaged with the result block: no read-back per agent
                 e.set_package(True)
+        self.batched_passes = BATCHED_PASSES_DEFAULT if batched_passes is None else bool(batched_passes)
         self.launches = 0
         self.escalations = 0
         self.last_batch_ms = 0.0
+
+    def _prediction_passes(self, eng, planners) -> list:
+        """Behind a batched launch of `planners` (in the launch's agent order) on `eng`: the collision-probability pass of those
+        that run it alone, in one call; per planner its dict for plan_consume, or None: the planner's own path."""
+        passes = [None] * len(planners)
+        if not self.batched_passes or not hasattr(eng, "prediction_probability_batch"):
+            return passes
+        js = [j for j, p in enumerate(planners) if p is not None and p.batched_prediction_pass()]
+        if not js:
+            return passes
+        for j in js:
+            planners[j].set_prediction_obstacles(eng, j)
+        res = eng.prediction_probability_batch([planners[j].vehicle_params.length for j in js],
+                                               [planners[j].vehicle_params.width for j in js], agents=js)
+        for j, r in zip(js, res):
+            passes[j] = r
+        return passes
 
     def _step_pipelined(self, global_timestep: int, predictions: Dict[int, dict]) -> Dict[int, Optional[list]]:
         """step() over several engine contexts: prepare and launch group after group, then consume in the same order."""
@@ -172,9 +201,11 @@ class AgentBatchHip:
                 results, packages = eng.plan_batch_end(token, yaws)
             else:   # a batch the packaged path does not take (sampling matrix, mixed horizons): the general call
                 results, packages = eng.plan_batch_packaged([inp for _, inp in planning], yaws)
+            passes = self._prediction_passes(eng, [a.planner for a, _ in planning])
             for j, (a, inp) in enumerate(planning):
                 p = a.planner
-                best = p.plan_consume(inp, results[j], eng, j, package=packages[j])
+                best = p.plan_consume(inp, results[j], eng, j, package=packages[j],
+                                      **({"prediction_pass": passes[j]} if passes[j] is not None else {}))
                 if best is None and p._sampling_min + 1 < p._sampling_max:
                     self.escalations += 1
                     pair = p.plan_escalate(t0)
@@ -217,10 +248,14 @@ class AgentBatchHip:
                 results = self.engine.plan_batch([inp for _, inp, _ in planning])
             self.launches += 1
             self.last_batch_ms = (time.time() - t0) * 1e3
+        # (a split agent's part is evaluated again for its one winner: its pass stays with that launch's plan_consume)
+        passes = self._prediction_passes(self.engine, [a.planner if self.parts[k][1] == 1 and results[j] is not None else None
+                                                       for j, (a, _, k) in enumerate(planning)])
 
-        def conclude(a, inp, res, j, packages=packages):
+        def conclude(a, inp, res, j, packages=packages, passes=passes):
             p = a.planner
-            best = (p.plan_consume(inp, res, self.engine, j, package=packages[j] if packages is not None else False)
+            best = (p.plan_consume(inp, res, self.engine, j, package=packages[j] if packages is not None else False,
+                                   **({"prediction_pass": passes[j]} if passes is not None and passes[j] is not None else {}))
                     if res is not None else None)
             if best is None and p._sampling_min + 1 < p._sampling_max:
                 self.escalations += 1
@@ -252,7 +287,7 @@ class AgentBatchHip:
                 res1 = self.engine.plan_batch([one for _, one in again])
                 self.launches += 1
                 for j1, (a, one) in enumerate(again):
-                    conclude(a, one, res1[j1], j1, None)
+                    conclude(a, one, res1[j1], j1, None, None)
         for a, _, _ in passive:
             sel, _ = a.finish_step(None, global_timestep)
             out[a.id] = sel[0] if sel is not None else None
@@ -273,8 +308,9 @@ class MultiAgentSimulation:
     def __init__(self, scenario: Scenario, config: Optional[PlannerConfig] = None, vehicle: Optional[VehicleParams] = None,
                  number_of_agents: int = -1, sampling_level: Optional[int] = None, device: int = 0, group=None,
                  use_road_boundary: bool = False, max_candidates: Optional[int] = None, engine_factory=None,
-                 pipeline_groups: Optional[int] = None, freeze_gc: bool = False):
-        """engine_factory: callable returning an engine object (tests inject a stand-in); default = FrenetEngine.
+                 pipeline_groups: Optional[int] = None, freeze_gc: bool = False, batched_passes: Optional[bool] = None):
+        """batched_passes: see AgentBatchHip.
+        engine_factory: callable returning an engine object (tests inject a stand-in); default = FrenetEngine.
         pipeline_groups: see AgentBatchHip (None = automatic; with an engine_factory: that many injected engines, default one).
         freeze_gc: take what exists once the simulation is set up out of the garbage collector's generations (gc.freeze(): a
         PROCESS-WIDE setting, so it is off unless asked for -- bench.py and the timing tools ask; close() undoes it)."""
@@ -312,7 +348,7 @@ class MultiAgentSimulation:
                                    engine=(([engine_factory() for _ in range(pipeline_groups)] if pipeline_groups and pipeline_groups > 1
                                             else engine_factory()) if engine_factory else None),
                                    parts=[(part, n_parts) for _, part, n_parts in my_items], slots=self.my_slots,
-                                   winner_exchange=self._exchange_winners if self.split else None)
+                                   winner_exchange=self._exchange_winners if self.split else None, batched_passes=batched_passes)
         self.S = self.batch.agents[0].planner.N + 1 if mine else int(self.config.planning_horizon / self.config.dt) + 1
         self.time_step = 0
         # planned trajectories of ALL agents, identical on every rank after the exchange: [agents][S][FIELDS]

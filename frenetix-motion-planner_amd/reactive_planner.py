@@ -312,17 +312,29 @@ class ReactivePlannerHip:
         step.apply_responsibility_cost(self._risk_model["params"], cp, float(self.cost_weights["responsibility"]),
                                        prediction="probability" if probability else "step")
 
-    def _apply_prediction_cost(self, step):
-        """the collision-probability pass over the step's costed candidates, installed as the step's cost override.  The tables it
-        sets on the engine carry placeholders for what the pass does not read; the planner's own risk paths (_eval_risk,
-        _risk_costs_on) set theirs through _set_risk_obstacles before every evaluation, a caller that uses engine.risk() directly
-        sets its own again.  step.result keeps the step's own best_index; the override's winner is step.best."""
+    def batched_prediction_pass(self) -> bool:
+        """True when this planner's pass beside the step is the collision probability alone: a batch of planners may then run
+        it for all of them in one call (multiagent.AgentBatchHip) and hand the result to plan_consume.  A planner that also weights
+        `responsibility` sums both in ONE override of its own pass and stays there."""
+        return self._check_prediction_cost() and not self._check_responsibility_cost()
+
+    def set_prediction_obstacles(self, engine, agent: int = 0):
+        """The obstacle tables of the collision-probability pass for the current predictions, set on `engine` for `agent`.  They
+        carry placeholders for what the pass does not read; the planner's own risk paths (_eval_risk, _risk_costs_on) set theirs
+        through _set_risk_obstacles before every evaluation, a caller that uses engine.risk() directly sets its own again."""
         from . import risk
         preds = (self.predictions if self.use_prediction else None) or {}
         # (of the tables only pos, cov, yaw, their lengths and the obstacle's length are read: no speeds, no obstacle types)
         tabs = risk.obstacle_tables({k: dict(p, v_list=np.zeros(len(p["pos_list"]))) for k, p in preds.items()}, {k: "car" for k in preds})
-        step.engine.set_risk_obstacles(tabs, step.agent)
-        step.apply_prediction_probability(self.vehicle_params.length, self.vehicle_params.width)
+        engine.set_risk_obstacles(tabs, agent)
+
+    def _apply_prediction_cost(self, step, result=None):
+        """the collision-probability pass over the step's costed candidates, installed as the step's cost override.  result: the
+        pass already ran for this step in a batched call that set the tables (set_prediction_obstacles) -- its dict for this agent.
+        step.result keeps the step's own best_index; the override's winner is step.best."""
+        if result is None:
+            self.set_prediction_obstacles(step.engine, step.agent)
+        step.apply_prediction_probability(self.vehicle_params.length, self.vehicle_params.width, result=result)
 
     def set_fallback_selector(self, selector: Optional[Callable]):
         """What happens at the LAST sampling level when no feasible candidate is collision-free.  The reference's Python
@@ -656,14 +668,15 @@ class ReactivePlannerHip:
         self._stop_point_s = stop_point_s
         return self._inputs_for_level(self._sampling_min, stop_point_s)
 
-    def plan_consume(self, inputs: PlanInputs, res: dict, engine, agent: int = 0, package=False):
+    def plan_consume(self, inputs: PlanInputs, res: dict, engine, agent: int = 0, package=False, prediction_pass=None):
         """Take this planner's share of a batched launch (first sampling level); returns the chosen trajectory
         (materialised -- the batch engine's buffers are reused) or None when the level has to escalate.
         package: the winner as the batched call already packaged it (engine.plan_batch_packaged; None = nothing found);
-        False: read it here."""
+        False: read it here.  prediction_pass: this agent's dict of an engine.prediction_probability_batch call over this launch
+        (batched_prediction_pass planners only); None: the planner runs its own pass."""
         if package is False:
             package = engine.package(agent, self.x_0.yaw_rate) if getattr(engine, "packaging", False) and inputs.write_bundle else None
-        best = self._consume_result(inputs, res, engine, agent, package, self._sampling_min)
+        best = self._consume_result(inputs, res, engine, agent, package, self._sampling_min, prediction_pass=prediction_pass)
         if best is not None:
             best.materialise()
         return best
@@ -782,7 +795,7 @@ class ReactivePlannerHip:
             self.msg_logger.warning("No optimal trajectory available. Select lowest risk trajectory!")
         return chosen
 
-    def _consume_result(self, inputs: PlanInputs, res: dict, engine, agent: int, package=None, samp_lvl=None):
+    def _consume_result(self, inputs: PlanInputs, res: dict, engine, agent: int, package=None, samp_lvl=None, prediction_pass=None):
         if self.last_step is not None:
             self.last_step.invalidate()
         step = PlanStepResult(engine, inputs, res, agent)
@@ -804,7 +817,7 @@ class ReactivePlannerHip:
         if responsibility:
             self._apply_responsibility_cost(step, probability)
         elif probability:
-            self._apply_prediction_cost(step)
+            self._apply_prediction_cost(step, prediction_pass)
         by_rank = bool(self.config.device_sort) and hasattr(engine, "ranked")
         if self._draw_traj_set or self.save_all_traj:
             self.all_traj = _LazySortedList(step, by_rank)

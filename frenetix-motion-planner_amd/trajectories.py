@@ -460,11 +460,12 @@ class PlanStepResult:
         if rk is not None and not np.isnan(rk[0][t.uniqueId]):
             t.__dict__["_ego_risk"], t.__dict__["_obst_risk"] = float(rk[0][t.uniqueId]), float(rk[1][t.uniqueId])
 
-    def apply_prediction_probability(self, ego_length: float, ego_width: float):
+    def apply_prediction_probability(self, ego_length: float, ego_width: float, result=None):
         """Run engine.prediction_probability over every candidate of this step -- the obstacles are the ones of the engine's last
-        set_risk_obstacles -- and install its result as the cost override.  Returns the pass's dict."""
+        set_risk_obstacles -- and install its result as the cost override.  result: this agent's dict of a
+        prediction_probability_batch call over the same step, installed exactly as the computed one is.  Returns the pass's dict."""
         self._check()
-        r = self.engine.prediction_probability(ego_length, ego_width, agent=self.agent)
+        r = result if result is not None else self.engine.prediction_probability(ego_length, ego_width, agent=self.agent)
         self.set_cost_override(r["total"], r["prob"], r["best_index"])
         return r
 

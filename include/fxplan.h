@@ -739,8 +739,29 @@ typedef struct FxPredProbOutputs {       /* rows in the order of ids, or [C] wit
  * Synchronous; its part of the risk passes' device block is allocated on first use, only grows and is counted in fx_device_bytes. */
 int32_t fx_eval_prediction_prob_agent(FxContext *ctx, int32_t agent, const FxPredProbParams *params, int64_t n_ids, const int64_t *ids,
                                       const FxPredProbOutputs *out);
-/* device time of the last fx_eval_prediction_prob_agent (all its kernels), ms; -1 before the first */
+/* device time of the last fx_eval_prediction_prob_agent or fx_eval_prediction_prob_batch (all its kernels), ms; -1 before the first */
 double fx_last_predprob_ms(FxContext *ctx);
+
+/* The same pass over EVERY candidate of several agents of the last plan step in one call (additive within
+ * ABI 15): the ids == NULL form of fx_eval_prediction_prob_agent for each listed agent -- NaN rows for candidates without
+ * FX_FLAG_COSTED, which the arg-min skips -- with the agent's own params[i], its own fx_set_risk_obstacles_agent tables, C, S, K and
+ * cost list.  Every result is bit for bit what the per-agent call returns, whichever agents share a call.  Listed candidates,
+ * sparse sets and prob_obs stay with the per-agent call. */
+typedef struct FxPredProbBatchOutputs {  /* any pointer may be NULL */
+    double *prob, *total;                /* [sum of C over the listed agents], agent-major: the rows of agents[i] start at the sum of
+                                            C of agents[0..i) */
+    int64_t *best_index;                 /* [n_agents], as FxPredProbOutputs.best_index (index within the agent's shard; -1: none) */
+    double *best_cost;                   /* [n_agents] */
+} FxPredProbBatchOutputs;
+/* agents: n_agents distinct agents of the last upload in any order, or NULL: 0 .. n_agents - 1.  Everything is checked for every
+ * listed agent before anything is launched, uploaded or written to out, and the message names the first offending agent:
+ * FX_ERR_NOT_READY before the first evaluated step, when inputs were rewritten since it, and for an agent whose step ran without
+ * FX_MODE_WRITE_COSTMAP or without FX_MODE_WRITE_BUNDLE; FX_ERR_INVALID_ARGUMENT for NULL ctx, params or out, n_agents < 0 or above
+ * the uploaded agents, an agent out of range or listed twice, and per agent for what fx_eval_prediction_prob_agent refuses.
+ * n_agents == 0 returns FX_OK and touches nothing.  Synchronous; fx_last_predprob_ms covers it; its memory is the risk passes'
+ * device block (grow-only, counted in fx_device_bytes). */
+int32_t fx_eval_prediction_prob_batch(FxContext *ctx, int32_t n_agents, const int32_t *agents /* NULL: 0 .. n_agents-1 */,
+                                      const FxPredProbParams *params /* [n_agents] */, const FxPredProbBatchOutputs *out);
 
 /* ---- The responsibility cost as a weighted term of the step's cost.  Beside the plan step like the
  *      blocks above: nothing here runs unless called. ----

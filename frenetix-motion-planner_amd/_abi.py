@@ -181,6 +181,10 @@ class FxRespCostOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("resp", "total", "ego_risk", "obst_risk", "best_index", "best_cost")]
 
 
+class FxRespCostBatchOutputs(C.Structure):   # (fx_eval_responsibility_cost_batch)
+    _fields_ = [(n, C.c_void_p) for n in ("resp", "total", "ego_risk", "obst_risk", "best_index", "best_cost")]
+
+
 class FxRiskOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ego_risk", "obst_risk", "obst_harm_occ", "ego_risk_max", "obst_risk_max", "ego_harm_max",
                                           "obst_harm_max", "bayes", "equality", "maximin", "ego", "responsibility", "total",

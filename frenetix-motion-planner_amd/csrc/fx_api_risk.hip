@@ -4,7 +4,8 @@
 // risk-cost pass.  The two evaluations share one host path (RiskPass) and one device block.  Nothing of
 // this runs in a plan step.  The collision probability as the prediction cost (fx_predprob_kernel.h) is a third
 // entrance on the same host path: the same checks, records, uploads and block; fx_eval_prediction_prob_batch
-// is that pass for several agents in one call: the same checks and records per agent, one staging buffer each for records and tables.
+// is that pass for several agents in one call: the same checks and records per agent, one staging buffer each for records and tables;
+// fx_eval_responsibility_cost_batch is the responsibility pass for several agents in one call.
 #include <atomic>
 #include <cmath>
 #include <vector>
@@ -22,6 +23,9 @@ extern "C" hipError_t fx_launch_predprob(const PredProbArgs *args, long long *ou
 extern "C" __attribute__((weak)) hipError_t fx_launch_predprob_batch(const PredProbBatchArgs *t, const PredProbRound *rounds, int n_rounds,
                                                                      long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
                                                                      hipStream_t stream);
+extern "C" __attribute__((weak)) hipError_t fx_launch_risk_batch(const RiskBatchArgs *t, const RiskBatchRound *rounds, int n_rounds,
+                                                                 long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                                                 hipStream_t stream);
 extern "C" __attribute__((weak)) int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K);   // (fx_kernels.hip: the rule, or what a test forces)
 
 namespace {
@@ -442,11 +446,13 @@ static int risk_cost_check(const RiskPass &q, const FxRiskCostParams *cost) {
     return FX_OK;
 }
 
+// the argument block of a cost pass's kernel from where the pass's parts lie (q.base, q.o_*): no HIP call
+static void risk_cost_fill(const RiskPass &q, const FxRiskCostParams *cost, RiskCostArgs &ca);
+
 // the uploads of a staged cost pass and the argument block of its kernel
 static int risk_cost_args(const RiskPass &q, const FxRiskCostParams *cost, RiskCostArgs &ca) {
-    const FxAgentSlot &s = *q.s;
     const FxRiskAgent &a = *q.a;
-    const int S = q.S, K = q.K;
+    const int K = q.K;
     const int64_t n = q.n;
     const size_t nE = q.nE, nP = q.nP, nV = q.nV;
     if (cost->boundary_mode == FX_RISK_BOUNDARY_ARRAY && n > 0) HIP_TRY(q.up(q.o_bh, cost->boundary_harm, sizeof(double) * n));
@@ -460,6 +466,15 @@ static int risk_cost_args(const RiskPass &q, const FxRiskCostParams *cost, RiskC
             HIP_TRY(q.up(q.o_vert, a.rs_verts.data(), sizeof(double) * 2 * nV));
         }
     }
+    risk_cost_fill(q, cost, ca);
+    return FX_OK;
+}
+
+static void risk_cost_fill(const RiskPass &q, const FxRiskCostParams *cost, RiskCostArgs &ca) {
+    const FxAgentSlot &s = *q.s;
+    const int S = q.S, K = q.K;
+    const int64_t n = q.n;
+    const size_t nE = q.nE;
     ca.col = q.D(q.o_col);
     ca.n = n;
     ca.ids = q.d_ids();
@@ -484,7 +499,6 @@ static int risk_cost_args(const RiskPass &q, const FxRiskCostParams *cost, RiskC
     ca.eps = cost->maximin_eps;
     ca.scale = cost->maximin_scale;
     ca.out = q.D(q.o_out);
-    return FX_OK;
 }
 
 extern "C" int32_t fx_eval_risk_costs_agent(FxContext *c, int32_t agent, const FxRiskParams *params, const FxRiskCostParams *cost,
@@ -501,33 +515,54 @@ extern "C" int32_t fx_eval_risk_costs_agent(FxContext *c, int32_t agent, const F
 
 // The responsibility cost as a weighted term of the step's cost (fxplan.h): the detail pass, the
 // responsibility part of the cost pass over its columns, and the re-sum with its arg-min.
-extern "C" int32_t fx_eval_responsibility_cost_agent(FxContext *c, int32_t agent, const FxRiskParams *params, const FxRespCostParams *resp,
-                                                     int64_t n_ids, const int64_t *ids, const FxRespCostOutputs *out) {
+// The checks of the responsibility pass for one agent, in the order the entry points report them (the per-agent call and the
+// batched one); cost: the cost pass with the responsibility alone -- no boundary harm, total = the responsibility cost
+static int resp_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskParams *params, const FxRespCostParams *resp, int64_t n_ids,
+                      const int64_t *ids, bool have_out, FxRiskCostParams &cost) {
     FX_TRY(check_agent(c, agent));
     if (!fx_inputs_current(c))   // (the condition of fx_eval_prediction_prob_agent: the planes and cost rows are the last evaluated step's)
         return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
     if (!(c->slots[agent].mode & FX_MODE_WRITE_COSTMAP)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_COSTMAP");
-    RiskPass q;
-    FX_TRY(risk_check(q, c, agent, (params && resp) ? params : nullptr, n_ids, ids,
-                      out && out->resp && out->total && out->ego_risk && out->obst_risk && out->best_index && out->best_cost, true));
+    FX_TRY(risk_check(q, c, agent, (params && resp) ? params : nullptr, n_ids, ids, have_out, true));
     if (!(resp->weight != 0.0) || resp->weight != resp->weight) return set_err(FX_ERR_INVALID_ARGUMENT, "responsibility weight %g", resp->weight);
     if (resp->responsibility_mode != FX_RISK_RESP_ACTION_SPACE && resp->responsibility_mode != FX_RISK_RESP_REACH_SET)
         return set_err(FX_ERR_INVALID_ARGUMENT, "responsibility_mode %d", resp->responsibility_mode);
-    FxRiskCostParams cost{};   // the cost pass with the responsibility alone: no boundary harm, total = the responsibility cost
+    cost = FxRiskCostParams{};
     cost.weights[4] = 1.0;
     cost.maximin_scale = 1.0;
     cost.boundary_mode = FX_RISK_BOUNDARY_ZERO;
     cost.responsibility_mode = resp->responsibility_mode;
     cost.responsibility = resp->responsibility;
-    FX_TRY(risk_cost_check(q, &cost));
-    const DevProblem &hp = c->h_probs[agent];
-    RespSumArgs rs{};
+    return risk_cost_check(q, &cost);
+}
+
+// what the re-sum reads of a checked agent's cost list, but for the pointers into the pass's block
+static void resp_sum_fill(const RiskPass &q, const FxRespCostParams *resp, RespSumArgs &rs) {
+    const DevProblem &hp = q.c->h_probs[q.agent];
     rs.n_pred = -1;
     rs.at = hp.n_cost;   // in front of the first name behind "responsibility" in the sorted list
     for (int m = hp.n_cost - 1; m >= 0; m--) {
         if (hp.cost_id[m] == FX_COST_PREDICTION) rs.n_pred = m;
         if (hp.cost_id[m] > FX_COST_PREDICTION) rs.at = m;
     }
+    rs.n = q.n, rs.flags = q.flags, rs.need = FX_FLAG_COSTED;
+    rs.costmap = q.sparse ? q.set.costmap : q.c->d_costmap + (size_t)FX_NUM_COSTS * q.s->cand_off;
+    rs.ld = q.ld;
+    rs.n_cost = hp.n_cost;
+    // (a sparse set's rows were closed by the list kernel, which never defers)
+    rs.deferred = (!q.sparse && (hp.mode & FX_MODE_INT_DEFER_OBST)) ? 1 : 0;
+    for (int m = 0; m < hp.n_cost; m++) rs.cost_w[m] = hp.cost_w[m];
+    rs.w_resp = resp->weight;
+}
+
+extern "C" int32_t fx_eval_responsibility_cost_agent(FxContext *c, int32_t agent, const FxRiskParams *params, const FxRespCostParams *resp,
+                                                     int64_t n_ids, const int64_t *ids, const FxRespCostOutputs *out) {
+    RiskPass q;
+    FxRiskCostParams cost;
+    FX_TRY(resp_check(q, c, agent, params, resp, n_ids, ids,
+                      out && out->resp && out->total && out->ego_risk && out->obst_risk && out->best_index && out->best_cost, cost));
+    RespSumArgs rs{};
+    resp_sum_fill(q, resp, rs);
     const uint32_t need = FX_FLAG_COSTED;
     FX_TRY(risk_stage(q, true, &cost, 0, need, true));
     RiskCostArgs ca{};
@@ -542,16 +577,9 @@ extern "C" int32_t fx_eval_responsibility_cost_agent(FxContext *c, int32_t agent
         ca.ids = reinterpret_cast<const int64_t *>(q.base + q.o_ids);
     }
     if (resp->prediction && q.n > 0) HIP_TRY(q.up(q.o_rpred, resp->prediction, sizeof(double) * q.n));
-    rs.n = q.n, rs.ids = q.d_ids(), rs.flags = q.flags, rs.need = need;
+    rs.ids = q.d_ids();
     rs.resp = q.D(q.o_out) + 4 * (size_t)q.n;
     rs.pred = (resp->prediction && rs.n_pred >= 0) ? q.D(q.o_rpred) : nullptr;
-    rs.costmap = q.sparse ? q.set.costmap : c->d_costmap + (size_t)FX_NUM_COSTS * q.s->cand_off;
-    rs.ld = q.ld;
-    rs.n_cost = hp.n_cost;
-    // (a sparse set's rows were closed by the list kernel, which never defers)
-    rs.deferred = (!q.sparse && (hp.mode & FX_MODE_INT_DEFER_OBST)) ? 1 : 0;
-    for (int m = 0; m < hp.n_cost; m++) rs.cost_w[m] = hp.cost_w[m];
-    rs.w_resp = resp->weight;
     rs.resp_out = q.D(q.o_rresp), rs.total = q.D(q.o_rtot);
     FxRiskOutputs ro{};
     ro.ego_risk = out->ego_risk, ro.obst_risk = out->obst_risk, ro.responsibility = out->resp, ro.total = out->total;
@@ -762,6 +790,190 @@ extern "C" int32_t fx_eval_prediction_prob_batch(FxContext *c, int32_t n_agents,
     for (size_t i = 0; i < A; i++) {
         if (out->best_index) out->best_index[i] = (int64_t)best[2 * i];
         if (out->best_cost) memcpy(out->best_cost + i, &best[2 * i + 1], sizeof(double));
+    }
+    return FX_OK;
+}
+
+// The responsibility pass over every candidate of several agents in ONE call (fxplan.h).  Per agent the checks
+// of the per-agent entry (resp_check) and its records; then everything the kernels read -- FxRiskParams, records, obstacle tables,
+// responsibility vectors, prediction entries, reach-set tables, and the rows, compact arrays and per-agent argument blocks that
+// point at them -- in ONE staging buffer and one copy; the rounds of fx_item_rounds over one scratch with each row's steps per
+// chunk chosen from its agent's OWN size, as the per-agent call chooses them.  Runtime calls of a call with R rounds: 1 drain (a
+// synchronisation), 1 ensure of the block, 1 copy up, 2 event records, 2 R + 3 launches, 5 copies down (resp, total, ego_risk,
+// obst_risk, best), 1 synchronisation -- none of them per agent.
+static std::atomic<unsigned long long> fx_risk_batch_scratch_forced{0};
+extern "C" void fx_risk_batch_set_scratch_limit(size_t bytes) { fx_risk_batch_scratch_forced.store(bytes, std::memory_order_relaxed); }
+
+extern "C" int32_t fx_eval_responsibility_cost_batch(FxContext *c, int32_t n_agents, const int32_t *agents, const FxRiskParams *params,
+                                                     const FxRespCostParams *resp, const FxRespCostBatchOutputs *out) {
+    if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
+    if (!params || !resp || !out) return set_err(FX_ERR_INVALID_ARGUMENT, "params, resp or out is NULL");
+    if (n_agents < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d", n_agents);
+    if (n_agents == 0) return FX_OK;
+    if (!fx_launch_risk_batch) return set_err(FX_ERR_HIP, "built without the batched responsibility launcher");
+    const int32_t agent0 = agents ? agents[0] : 0;
+    if (!c->evaluated) return set_err(FX_ERR_NOT_READY, "agent %d: no evaluated plan step", agent0);
+    if (n_agents > c->n_agents) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d of %d uploaded agents", n_agents, c->n_agents);
+    const size_t A = (size_t)n_agents;
+    const bool have_out = out->resp && out->total && out->ego_risk && out->obst_risk && out->best_index && out->best_cost;
+    std::vector<RiskPass> q(A);
+    std::vector<FxRiskCostParams> cost(A);
+    std::vector<char> listed((size_t)c->n_agents, 0);
+    for (size_t i = 0; i < A; i++) {
+        const int32_t agent = agents ? agents[i] : (int32_t)i;
+        if (agent >= 0 && agent < c->n_agents && listed[agent]) return set_err(FX_ERR_INVALID_ARGUMENT, "agent %d listed twice", agent);
+        if (const int rc = resp_check(q[i], c, agent, params + i, resp + i, 0, nullptr, have_out, cost[i])) {
+            char why[sizeof(g_err)];
+            snprintf(why, sizeof(why), "%s", g_err);
+            return set_err(rc, "agent %d: %s", agent, why);
+        }
+        listed[agent] = 1;   // (without ids risk_check has refused a step that stored no bundle)
+    }
+    // ONE staging buffer, every part 16-byte aligned; the device's copy lies at o_stage of the block
+    std::vector<char> stage;
+    auto room = [&](size_t bytes) { const size_t o = stage.size(); stage.resize(o + align_up(std::max<size_t>(bytes, 8), 16), 0); return o; };
+    auto put = [&](const void *src, size_t bytes) { const size_t o = room(bytes); if (bytes) memcpy(stage.data() + o, src, bytes); return o; };
+    struct Parts { size_t prm, rec, obs, pos, yaw, v, resp, pred, eobs, eoff, pst, voff, vert, out_at, col_at; bool items, has_pred; };
+    std::vector<Parts> at(A);
+    std::vector<RespSumArgs> sums(A);
+    std::vector<FxItemAgent> ia(A);
+    std::vector<int32_t> cs(A), chunks(A), blk0(A);
+    std::vector<double> rec;
+    size_t rows_out = 0, col_doubles = 0;
+    int64_t blocks = 0;
+    for (size_t i = 0; i < A; i++) {
+        RiskPass &p = q[i];
+        const FxRiskAgent &a = *p.a;
+        Parts &t = at[i];
+        t = Parts{};
+        t.out_at = rows_out, t.col_at = col_doubles;
+        rows_out += (size_t)p.n;
+        col_doubles += 4 * (size_t)p.K * (size_t)p.n;
+        blk0[i] = (int32_t)blocks;
+        blocks += (p.n + 255) / 256;
+        t.prm = put(p.prm, sizeof(FxRiskParams));
+        if (p.K > 0) {
+            build_records(a, p.S, p.maha, rec);
+            t.rec = put(rec.data(), sizeof(double) * rec.size()), t.obs = put(a.obs.data(), sizeof(double) * a.obs.size());
+            t.pos = put(a.pos.data(), sizeof(double) * a.pos.size()), t.yaw = put(a.yaw.data(), sizeof(double) * a.yaw.size());
+            t.v = put(a.v.data(), sizeof(double) * a.v.size());
+            if (resp[i].responsibility_mode == FX_RISK_RESP_ACTION_SPACE) t.resp = put(resp[i].responsibility, sizeof(double) * p.K);
+        }
+        if (resp[i].responsibility_mode == FX_RISK_RESP_REACH_SET) {
+            p.nE = a.rs_obs.size(), p.nP = a.rs_step.size(), p.nV = a.rs_verts.size() / 2;
+            t.eobs = put(a.rs_obs.data(), sizeof(int32_t) * p.nE), t.eoff = put(a.rs_off.data(), sizeof(int32_t) * a.rs_off.size());
+            t.pst = put(a.rs_step.data(), sizeof(int32_t) * p.nP), t.voff = put(a.rs_voff.data(), sizeof(int32_t) * a.rs_voff.size());
+            t.vert = put(a.rs_verts.data(), sizeof(double) * a.rs_verts.size());
+        }
+        resp_sum_fill(p, resp + i, sums[i]);
+        t.has_pred = resp[i].prediction && sums[i].n_pred >= 0 && p.n > 0;
+        if (t.has_pred) t.pred = put(resp[i].prediction, sizeof(double) * (size_t)p.n);
+        // steps per chunk from the agent's OWN size: what fx_eval_responsibility_cost_agent chooses for it
+        t.items = p.K > 0 && p.S > 1;
+        cs[i] = fx_risk_items_chunk_steps(p.n, p.S, p.K);
+        chunks[i] = (std::max(p.S - 1, 1) + cs[i] - 1) / cs[i];
+        ia[i] = FxItemAgent{p.n, t.items ? sizeof(double) * 7 * (size_t)p.K * (size_t)chunks[i] : 0};
+    }
+    if (blocks > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "%lld workgroups of candidates", (long long)blocks);
+    const unsigned long long forced = fx_risk_batch_scratch_forced.load(std::memory_order_relaxed);
+    const std::vector<FxItemSegment> segs = fx_item_rounds(ia.data(), n_agents, forced ? (size_t)forced : FX_ITEM_SCRATCH_BYTES);
+    const size_t R = segs.size();
+    const int n_rounds = R ? segs.back().round + 1 : 0;
+    std::vector<RiskBatchRound> rounds((size_t)n_rounds, RiskBatchRound{0, 0, 0, 0});
+    const size_t t_rows = room(sizeof(RiskBatchRow) * R), t_item0 = room(sizeof(int64_t) * R), t_fin0 = room(sizeof(int32_t) * R),
+                 t_cost = room(sizeof(RiskCostArgs) * A), t_sum = room(sizeof(RespSumArgs) * A), t_blk0 = put(blk0.data(), sizeof(int32_t) * A);
+    size_t scratch = 0;
+    for (size_t k = 0; k < R; k++) {   // the rows' counts (their pointers follow when the block is there)
+        const FxItemSegment &g = segs[k];
+        const size_t tiles = (size_t)(g.count + 63) / 64;
+        RiskBatchRound &rd = rounds[g.round];
+        RiskBatchRow w{};
+        if (rd.n_rows == 0) rd.row0 = (int32_t)k;
+        rd.n_rows++;
+        w.first = g.first, w.count = g.count;
+        w.it.nb = (int64_t)tiles * 64, w.it.cs = cs[g.agent], w.it.chunks = chunks[g.agent], w.it.need = FX_FLAG_COSTED;
+        w.items = at[g.agent].items ? 1 : 0;
+        w.item0 = rd.items;
+        w.fin0 = rd.fin_blocks;
+        if (w.items) rd.items += (int64_t)tiles * chunks[g.agent] * (int64_t)q[g.agent].K;
+        rd.fin_blocks += (int32_t)((g.count + 255) / 256);
+        scratch = std::max(scratch, g.scratch_off + tiles * 64 * ia[g.agent].per_candidate_bytes);
+        memcpy(stage.data() + t_rows + sizeof(RiskBatchRow) * k, &w, sizeof(w));
+        memcpy(stage.data() + t_item0 + sizeof(int64_t) * k, &w.item0, sizeof(int64_t));
+        memcpy(stage.data() + t_fin0 + sizeof(int32_t) * k, &w.fin0, sizeof(int32_t));
+    }
+    for (const RiskBatchRound &rd : rounds)
+        if (rd.items > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld items", (long long)rd.items);
+    FxBlockLayout lay;
+    const size_t o_stage = lay.take(stage.size()), o_part = lay.take(scratch), o_col = lay.take(sizeof(double) * col_doubles);
+    const size_t o_ego = lay.take(sizeof(double) * rows_out), o_obst = lay.take(sizeof(double) * rows_out), o_occ = lay.take(sizeof(double) * rows_out);
+    const size_t o_out = lay.take(sizeof(double) * 7 * rows_out), o_rresp = lay.take(sizeof(double) * rows_out);
+    const size_t o_rtot = lay.take(sizeof(double) * rows_out), o_best = lay.take(2 * sizeof(long long) * A);
+    FxRiskState *r = q[0].r;
+    HIP_TRY(hipSetDevice(c->device));
+    FX_TRY(fx_drain(c));
+    FX_TRY(r->block.ensure(lay.size()));
+    FX_TRY(r->ev.ensure());
+    char *base = r->block;
+    auto D = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    std::vector<RiskWalkArgs> walk(A);
+    for (size_t i = 0; i < A; i++) {   // the per-agent argument blocks: the cost kernel's and the re-sum's
+        RiskPass &p = q[i];
+        const Parts &t = at[i];
+        const size_t s0 = o_stage;
+        walk[i] = RiskWalkArgs{p.planes, p.ld, p.S, p.n, nullptr, p.flags, D(s0 + t.rec), D(s0 + t.obs), D(s0 + t.pos), D(s0 + t.yaw),
+                               D(s0 + t.v), p.K, p.P};
+        p.base = base;
+        p.o_col = o_col + sizeof(double) * t.col_at, p.o_out = o_out + sizeof(double) * 7 * t.out_at;
+        p.o_ids = p.o_bh = s0, p.o_resp = s0 + t.resp;
+        p.o_eobs = s0 + t.eobs, p.o_eoff = s0 + t.eoff, p.o_pst = s0 + t.pst, p.o_voff = s0 + t.voff, p.o_vert = s0 + t.vert;
+        RiskCostArgs ca{};
+        risk_cost_fill(p, &cost[i], ca);
+        RespSumArgs &rs = sums[i];
+        rs.ids = nullptr;
+        rs.resp = D(p.o_out) + 4 * (size_t)p.n;
+        rs.pred = t.has_pred ? D(s0 + t.pred) : nullptr;
+        rs.resp_out = D(o_rresp) + t.out_at, rs.total = D(o_rtot) + t.out_at;
+        memcpy(stage.data() + t_cost + sizeof(RiskCostArgs) * i, &ca, sizeof(ca));
+        memcpy(stage.data() + t_sum + sizeof(RespSumArgs) * i, &rs, sizeof(rs));
+    }
+    for (size_t k = 0; k < R; k++) {
+        const FxItemSegment &g = segs[k];
+        const Parts &t = at[g.agent];
+        RiskBatchRow w;
+        memcpy(&w, stage.data() + t_rows + sizeof(RiskBatchRow) * k, sizeof(w));
+        w.w = walk[g.agent];
+        w.it.params = reinterpret_cast<const FxRiskParams *>(base + o_stage + t.prm);
+        w.it.part = reinterpret_cast<double *>(base + o_part + g.scratch_off);
+        w.ego = D(o_ego) + t.out_at, w.obst = D(o_obst) + t.out_at, w.occ = D(o_occ) + t.out_at;
+        w.col = D(o_col) + t.col_at;
+        memcpy(stage.data() + t_rows + sizeof(RiskBatchRow) * k, &w, sizeof(w));
+    }
+    HIP_TRY(hipMemcpyAsync(base + o_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, c->stream));
+    RiskBatchArgs t{};
+    t.rows = reinterpret_cast<const RiskBatchRow *>(base + o_stage + t_rows);
+    t.item0 = reinterpret_cast<const int64_t *>(base + o_stage + t_item0);
+    t.fin0 = reinterpret_cast<const int32_t *>(base + o_stage + t_fin0);
+    t.cost = reinterpret_cast<const RiskCostArgs *>(base + o_stage + t_cost);
+    t.sum = reinterpret_cast<const RespSumArgs *>(base + o_stage + t_sum);
+    t.blk0 = reinterpret_cast<const int32_t *>(base + o_stage + t_blk0);
+    t.n_agents = n_agents, t.blocks = (int32_t)blocks;
+    long long *d_best = reinterpret_cast<long long *>(base + o_best);
+    HIP_TRY(fx_launch_risk_batch(&t, rounds.data(), n_rounds, d_best, r->ev.e0, r->ev.e1, c->stream));
+    if (rows_out) {
+        const size_t bytes = sizeof(double) * rows_out;
+        HIP_TRY(hipMemcpyAsync(out->resp, base + o_rresp, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out->total, base + o_rtot, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out->ego_risk, base + o_ego, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out->obst_risk, base + o_obst, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    std::vector<long long> best(2 * A);
+    HIP_TRY(hipMemcpyAsync(best.data(), d_best, sizeof(long long) * 2 * A, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&r->last_ms, r->ev.e0, r->ev.e1));
+    for (size_t i = 0; i < A; i++) {
+        out->best_index[i] = (int64_t)best[2 * i];
+        memcpy(out->best_cost + i, &best[2 * i + 1], sizeof(double));
     }
     return FX_OK;
 }

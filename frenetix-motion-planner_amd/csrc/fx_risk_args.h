@@ -1,7 +1,7 @@
 // fx_risk_args.h -- what the host code of the trajectory risk (fx_api_risk.hip), its launcher (fx_kernels.hip) and its kernels
 // (fx_risk_kernel.h) share: the layout of the records the host builds and the kernels read, the arguments of the candidate walk
-// and the argument blocks of the risk-cost kernel, the responsibility re-sum and the prediction-probability pass.  DESIGN.md
-// sections 11, 13, 16 and 17.
+// and the argument blocks of the risk-cost kernel, the responsibility re-sum and the prediction-probability pass, and the row
+// tables of the two passes that take several agents in one call.  DESIGN.md sections 11, 13, 16, 17, 18 and 19.
 #pragma once
 
 #include <stdint.h>
@@ -136,6 +136,36 @@ struct PredProbBatchArgs {
     int32_t n_agents;
 };
 struct PredProbRound {         // host only
+    int32_t row0, n_rows;
+    int64_t items;             // of all its rows
+    int32_t fin_blocks;
+};
+
+// The responsibility pass over several agents in one call (fx_eval_responsibility_cost_batch): the table of
+// the prediction-probability batch with the walk's arguments in the rows.  One row per (round, agent with candidates in it), the
+// rows of a round consecutive and in call order (fx_item_rounds, fx_pass.h).
+struct RiskBatchRow {
+    RiskWalkArgs w;            // of the agent: ids null, n = C
+    RiskItemArgs it;           // of the agent: need = FX_FLAG_COSTED, params its FxRiskParams in the block, part its segment of the
+                               // round's scratch [K][chunks][7][nb], nb = count rounded up to whole tiles, cs / chunks of its OWN size
+    int64_t first, count;      // the agent's candidates of this round
+    int64_t item0;             // first item of the row in the round's flat index; its items: (nb / 64) x chunks x K, tile fastest
+    int32_t fin0;              // first workgroup of the row in the round's finish launch; it has ceil(count / 256)
+    int32_t items;             // 0: the row runs no item (K = 0 or S = 1)
+    double *ego, *obst, *occ;  // [C] of the agent: what the finish kernel writes
+    double *col;               // [4][K][C] of the agent
+};
+// where the tables of a call lie, device pointers; the host's copy says what the launches behind the rounds cover
+struct RiskBatchArgs {
+    const RiskBatchRow *rows;  // [n_rows], all rounds
+    const int64_t *item0;      // [n_rows] the rows' item0, compact: a wave looks its row up with one load
+    const int32_t *fin0;       // [n_rows] the rows' fin0
+    const RiskCostArgs *cost;  // [n_agents] of the cost kernel, ids null: every row is evaluated
+    const RespSumArgs *sum;    // [n_agents] of the re-sum and the arg-min
+    const int32_t *blk0;       // [n_agents] first workgroup of 256 of the agent in the cost and re-sum launches; it has ceil(C / 256)
+    int32_t n_agents, blocks;  // blocks: of all agents
+};
+struct RiskBatchRound {        // host only
     int32_t row0, n_rows;
     int64_t items;             // of all its rows
     int32_t fin_blocks;

@@ -245,10 +245,9 @@ __global__ __launch_bounds__(64) void fx_risk_item_kernel(const RiskWalkArgs w, 
 // ego_harm_max | obst_harm_max, obstacle-major, so that the 64 lanes of a wave store 512 contiguous bytes per column, and
 // obst_harm_occ [n].  (The detail entry point refuses an obstacle with pl <= 0: np.max of an empty list upstream.)
 template <bool DETAIL>
-__global__ __launch_bounds__(256) void fx_risk_items_finish_kernel(const RiskWalkArgs w, const RiskItemArgs it, const int64_t j0,
-                                                                  double *__restrict__ out_ego, double *__restrict__ out_obst,
-                                                                  double *__restrict__ col, double *__restrict__ out_occ) {
-    const int64_t jj = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void items_finish_body(const RiskWalkArgs &w, const RiskItemArgs &it, const int64_t j0, const int64_t jj,
+                                                  double *__restrict__ out_ego, double *__restrict__ out_obst,
+                                                  double *__restrict__ col, double *__restrict__ out_occ) {
     const int64_t j = j0 + jj;
     if (jj >= it.nb || j >= w.n) return;
     const size_t n = (size_t)w.n, nb = (size_t)it.nb;
@@ -303,20 +302,26 @@ __global__ __launch_bounds__(256) void fx_risk_items_finish_kernel(const RiskWal
     out_obst[j] = any ? obst_best : 0.0;
     if (DETAIL) out_occ[j] = any ? occ_best : 0.0;
 }
+template <bool DETAIL>
+__global__ __launch_bounds__(256) void fx_risk_items_finish_kernel(const RiskWalkArgs w, const RiskItemArgs it, const int64_t j0,
+                                                                  double *__restrict__ out_ego, double *__restrict__ out_obst,
+                                                                  double *__restrict__ col, double *__restrict__ out_occ) {
+    items_finish_body<DETAIL>(w, it, j0, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, out_ego, out_obst, col, out_occ);
+}
 
 // Risk-cost principles (risk_costs.py:124-251) over the columns of the detail pass: one lane per listed candidate streams the K
 // obstacles and accumulates as it goes -- no per-lane array, nothing in scratch.  Every lane walks the reach-set parts in the
 // same order, so the part tables and the vertices are wave-uniform loads; the crossing test has no branch.
 // out [7][n] = bayes | equality | maximin | ego | responsibility | total | boundary_harm (NaN where the candidate is not selected)
-__global__ __launch_bounds__(256) void fx_risk_cost_kernel(const RiskCostArgs a) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// every: ids == null evaluates every row, as the identity list would (the batched responsibility pass)
+__device__ __forceinline__ void cost_body(const RiskCostArgs &a, const int64_t j, const bool every) {
     if (j >= a.n) return;
     const size_t n = (size_t)a.n;
     const int64_t c = a.ids ? a.ids[j] : j;
     const uint32_t fl = a.flags[c];
     const uint32_t need = FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED;
     double *__restrict__ out = a.out + j;
-    if (!a.ids && (fl & need) != need) {
+    if (!every && !a.ids && (fl & need) != need) {
 #pragma unroll
         for (int q = 0; q < 7; q++) out[q * n] = NAN;
         return;
@@ -382,6 +387,9 @@ __global__ __launch_bounds__(256) void fx_risk_cost_kernel(const RiskCostArgs a)
     out[5 * n] = (((a.w[0] * bayes + a.w[1] * equal) + a.w[2] * maximin) + a.w[3] * ego) + a.w[4] * resp;
     out[6 * n] = bh;
 }
+__global__ __launch_bounds__(256) void fx_risk_cost_kernel(const RiskCostArgs a) {
+    cost_body(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, false);
+}
 
 // The responsibility cost as one more weighted term of the step's cost sum: one lane per listed candidate re-sums the step's raw
 // cost rows (FX_MODE_WRITE_COSTMAP) with w_resp * resp inserted in front of entry a.at -- its place in the name-sorted list,
@@ -389,8 +397,7 @@ __global__ __launch_bounds__(256) void fx_risk_cost_kernel(const RiskCostArgs a)
 // sum += w * c per term; a deferred step (fx_obstacle_kernel.h) added the terms behind the prediction as ONE addend, which the new
 // term then joins.  The prediction entry is the step's own, or a.pred [n] (the prob of a collision-probability pass over the same
 // candidates).  resp [n] is row 4 of fx_risk_cost_kernel's output.
-__global__ __launch_bounds__(256) void fx_resp_finish_kernel(const RespSumArgs a) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void resp_sum_body(const RespSumArgs &a, const int64_t j) {
     if (j >= a.n) return;
     const int64_t c = a.ids ? a.ids[j] : j;
     if (!a.ids && (a.flags[c] & a.need) != a.need) {
@@ -417,6 +424,9 @@ __global__ __launch_bounds__(256) void fx_resp_finish_kernel(const RespSumArgs a
     a.resp_out[j] = resp;
     a.total[j] = 0.0 + sum;
 }
+__global__ __launch_bounds__(256) void fx_resp_finish_kernel(const RespSumArgs a) {
+    resp_sum_body(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
 
 // arg-min over the n entries of ego + obst (SUM) or of val = ego alone, NaN = not selected or not comparable, ties to the lower
 // candidate index, -1 when nothing is left: ONE workgroup of 1024 lanes, the lexicographic (cost, index) reduction of fx_select.h
@@ -442,6 +452,119 @@ __global__ __launch_bounds__(1024) void fx_risk_argmin_kernel(const double *__re
 __global__ __launch_bounds__(1024) void fx_risk_cost_argmin_kernel(const double *__restrict__ val, int64_t n, const int64_t *__restrict__ ids,
                                                                    long long *__restrict__ out) {
     risk_argmin<false>(val, nullptr, n, ids, out);
+}
+
+// ---- the responsibility pass of several agents in one call (fx_eval_responsibility_cost_batch) ----
+// The row of flat index `at` (an item of the item launch, a workgroup of the other launches) among n_rows rows whose first indices
+// `first0` ascend: the last row that starts at or before `at` (fx_predprob_kernel.h row_of).  A row without
+// an item shares its first index with the row behind it, which is the one found.  One load per 64 rows and a ballot: `at` is
+// wave-uniform, so is the answer.
+template <typename T>
+__device__ __forceinline__ int batch_row_of(const T *__restrict__ first0, const int n_rows, const int64_t at) {
+    const int lane = threadIdx.x & 63;
+    int r = 0;
+    for (int b = 0; b < n_rows; b += 64) r += __popcll(__ballot(b + lane < n_rows && (int64_t)first0[b + lane] <= at));
+    return __builtin_amdgcn_readfirstlane(r - 1);
+}
+
+// One wave per item of a round: grid.x = the round's items exactly.  rows, item0: of the round.  Tile, chunk and obstacle of the
+// item come from blockIdx alone, so the row's fields, the record and FxRiskParams are scalar loads; from there on the loop of
+// fx_risk_item_kernel<true> with ids == null in its own text (that kernel is to stay what it is), the same seven partials in the
+// same layout [K][chunks][7][nb] of the row's segment.
+__global__ __launch_bounds__(64) void fx_risk_batch_item_kernel(const RiskBatchRow *__restrict__ rows, const int64_t *__restrict__ item0,
+                                                                const int n_rows) {
+    const int64_t at = blockIdx.x;
+    const RiskBatchRow &r = rows[batch_row_of(item0, n_rows, at)];
+    const RiskWalkArgs &w = r.w;
+    const RiskItemArgs &it = r.it;
+    const FxRiskParams &p = *it.params;
+    const int64_t local = at - r.item0, tiles = it.nb / 64, rest = local / tiles;
+    const int lane = threadIdx.x, S = w.S;
+    const int k = (int)(rest / it.chunks), ch = (int)(rest % it.chunks);
+    const double *__restrict__ o = w.obs + (size_t)k * FXO_STRIDE;
+    const int pl = min(S - 1, (int)o[FXO_NPOS]);
+    const int t_a = ch * it.cs, t_b = min(pl, t_a + it.cs);
+    if (t_a >= t_b) return;   // (wave-uniform)
+    const int64_t jj = (local % tiles) * 64 + lane;
+    if (jj >= r.count) return;   // (count <= nb, first + count <= n)
+    const int64_t c = r.first + jj;
+    if ((w.flags[c] & it.need) != it.need) return;   // (NaN rows from the finish kernel)
+    const int64_t ld = w.ld;
+    const double *__restrict__ X = w.planes + c, *__restrict__ Y = X + (size_t)S * ld, *__restrict__ TH = Y + (size_t)S * ld,
+                 *__restrict__ V = TH + (size_t)S * ld;
+    const bool prot = o[FXO_CLS] == (double)FX_RISK_CLASS_PROTECTED;
+    const double me = p.ego_mass, mo = o[FXO_MASS];
+    const double f_ego = mo / (me + mo), f_obs = me / (me + mo);
+    double e_max = -INFINITY, o_max = -INFINITY, he_max = -INFINITY, ho_max = -INFINITY, p_max = -INFINITY, ho_at = 0.0;
+    bool p_nan = false;
+    for (int t = t_a; t < t_b; t++) {
+        const int i = t + 1;
+        const double *__restrict__ q = w.rec + ((size_t)k * S + i) * FXR_STRIDE;
+        const double prob = fxrisk::step_probability(p, q, X[(size_t)i * ld], Y[(size_t)i * ld], TH[(size_t)i * ld]);
+        const size_t kt = (size_t)k * w.P + t;
+        double he, ho;
+        fxrisk::step_harm(p, prot, f_ego, f_obs, X[(size_t)t * ld], Y[(size_t)t * ld], TH[(size_t)t * ld], V[(size_t)t * ld], w.yaw[kt],
+                          w.vo[kt], w.pos[2 * kt], w.pos[2 * kt + 1], he, ho);
+        const double re = prob != 0.0 ? he * prob : 0.0;
+        const double ro = prob != 0.0 ? ho * prob : 0.0;
+        he_max = fmax(he_max, he);
+        ho_max = fmax(ho_max, ho);
+        p_nan = p_nan || prob != prob;
+        if (prob > p_max) { p_max = prob; ho_at = ho; }
+        e_max = fmax(e_max, re);
+        o_max = fmax(o_max, ro);
+    }
+    const size_t nb = (size_t)it.nb;
+    double *__restrict__ out = it.part + (((size_t)k * it.chunks + ch) * 7) * nb + jj;
+    out[(size_t)P_EMAX * nb] = e_max;
+    out[(size_t)P_OMAX * nb] = o_max;
+    out[(size_t)P_HEMAX * nb] = he_max;
+    out[(size_t)P_HOMAX * nb] = ho_max;
+    out[(size_t)P_PMAX * nb] = p_max;
+    out[(size_t)P_HOAT * nb] = ho_at;
+    out[(size_t)P_PNAN * nb] = p_nan ? 1.0 : 0.0;
+}
+
+// One lane per (row, candidate) of a round: grid.x = the rows' workgroups of 256; the chunk combination of
+// fx_risk_items_finish_kernel<true> (the same function) into the agent's columns
+__global__ __launch_bounds__(256) void fx_risk_batch_finish_kernel(const RiskBatchRow *__restrict__ rows, const int32_t *__restrict__ fin0,
+                                                                   const int n_rows) {
+    const RiskBatchRow &r = rows[batch_row_of(fin0, n_rows, (int64_t)blockIdx.x)];
+    const int64_t jj = (int64_t)(blockIdx.x - r.fin0) * blockDim.x + threadIdx.x;
+    if (jj < r.count) items_finish_body<true>(r.w, r.it, r.first, jj, r.ego, r.obst, r.col, r.occ);
+}
+
+// Behind the last round, one launch each over all listed agents: one lane per (agent, candidate), the agent of a workgroup found
+// through blk0[]; the cost kernel's and the re-sum's own functions on the agent's argument block
+__global__ __launch_bounds__(256) void fx_risk_batch_cost_kernel(const RiskCostArgs *__restrict__ cost, const int32_t *__restrict__ blk0,
+                                                                 const int n_agents) {
+    const int a = batch_row_of(blk0, n_agents, (int64_t)blockIdx.x);
+    cost_body(cost[a], (int64_t)(blockIdx.x - blk0[a]) * blockDim.x + threadIdx.x, true);
+}
+__global__ __launch_bounds__(256) void fx_risk_batch_sum_kernel(const RespSumArgs *__restrict__ sum, const int32_t *__restrict__ blk0,
+                                                                const int n_agents) {
+    const int a = batch_row_of(blk0, n_agents, (int64_t)blockIdx.x);
+    resp_sum_body(sum[a], (int64_t)(blockIdx.x - blk0[a]) * blockDim.x + threadIdx.x);
+}
+
+// One workgroup of 1024 lanes per listed agent, the predicate of fx_predprob_argmin_kernel over the agent's total: selectable,
+// neither colliding nor off the road, NaN skipped; out[2 agent] = index (-1: none), out[2 agent + 1] = the cost's bits
+__global__ __launch_bounds__(1024) void fx_risk_batch_argmin_kernel(const RespSumArgs *__restrict__ sum, long long *__restrict__ out) {
+    const RespSumArgs &a = sum[blockIdx.x];
+    const double *__restrict__ total = a.total;
+    const uint32_t *__restrict__ flags = a.flags;
+    double bc;
+    long long bi;
+    fx_lex_block_min(a.n, nullptr, [=](int64_t j, long long c, double &t) {
+        const uint32_t f = flags[c];
+        t = total[j];
+        return (f & FX_FLAG_SELECTABLE) && !(f & (FX_FLAG_COLLISION | FX_FLAG_BOUNDARY)) && t == t;
+    }, bc, bi);
+    if (threadIdx.x == 0) {
+        const bool none = bi == FX_LEX_NONE;
+        out[2 * blockIdx.x] = none ? -1LL : bi;
+        out[2 * blockIdx.x + 1] = __double_as_longlong(none ? (double)NAN : bc);
+    }
 }
 
 }  // namespace fxrisk

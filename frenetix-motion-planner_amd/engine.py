@@ -963,7 +963,8 @@ class FrenetEngine(StepRegistry):
 
     @property
     def last_risk_ms(self) -> float:
-        """device time of the last `risk` / `risk_detail` / `risk_costs` / `responsibility_cost` call (its kernels)"""
+        """device time of the last `risk` / `risk_detail` / `risk_costs` / `responsibility_cost` / `responsibility_cost_batch` call
+        (its kernels)"""
         return float(lib().fx_last_risk_ms(self._ctx))
 
     # -- the responsibility cost as a weighted term (DESIGN.md section 17) --
@@ -1006,6 +1007,55 @@ class FrenetEngine(StepRegistry):
         res["best_index"], res["best_cost"] = int(best_index[0]), float(best_cost[0])
         res["prediction"] = pred   # (the prediction entry that was summed instead of the step's own, or None)
         return res
+
+    def responsibility_cost_batch(self, params, cost_params, weights, agents=None, prediction: str = "step") -> list:
+        """`responsibility_cost` over every candidate of several agents of the last plan step in ONE call
+        (fx_eval_responsibility_cost_batch): per listed agent the dict responsibility_cost(agent=a) returns,
+        bit for bit -- resp, total, ego_risk, obst_risk [C of that agent] as views of the call's concatenated arrays, best_index,
+        best_cost, prediction.  params, cost_params, weights: one per listed agent; agents None: every agent of the last upload,
+        in order; obstacles and reach sets are each agent's `set_risk_obstacles` / `set_reach_sets`.  prediction "probability":
+        ONE `prediction_probability_batch` over the same agents first (ego length and width of each params), each agent's prob
+        as its prediction entry; a sequence of the two words, one per listed agent: that call over the "probability" ones."""
+        listed = list(range(len(self._inputs))) if agents is None else [int(a) for a in agents]
+        n = len(listed)
+        kinds = [prediction] * n if isinstance(prediction, str) else list(prediction)
+        if len(kinds) != n or any(k not in ("step", "probability") for k in kinds):
+            raise ValueError(f"prediction {prediction!r}: 'step' or 'probability', or one of them per listed agent")
+        params, cost_params, weights = list(params), list(cost_params), [float(w) for w in weights]
+        if not (len(params) == len(cost_params) == len(weights) == n):
+            raise ValueError(f"{len(params)} params, {len(cost_params)} cost_params and {len(weights)} weights for {n} agents")
+        for a, cp, w in zip(listed, cost_params, weights):   # (the refusals of responsibility_cost, before any call)
+            K = getattr(self, "_risk_K", {}).get(a, 0)
+            lens = getattr(cp, "_lengths", {})
+            if lens.get("responsibility", K) != K:
+                raise ValueError(f"agent {a}: responsibility has {lens['responsibility']} entries for {K} obstacles")
+            if not w or np.isnan(w):
+                raise ValueError(f"agent {a}: responsibility weight {w!r}: a non-zero number")
+            if cp.responsibility_mode not in (_abi.FX_RISK_RESP_ACTION_SPACE, _abi.FX_RISK_RESP_REACH_SET):
+                raise ValueError(f"agent {a}: responsibility_mode {cp.responsibility_mode}: the action-space factors or 'reach_set'")
+        preds = [None] * n
+        js = [i for i in range(n) if kinds[i] == "probability"]
+        if js:
+            pp = self.prediction_probability_batch([params[i].ego_length for i in js], [params[i].ego_width for i in js],
+                                                   agents=[listed[i] for i in js])
+            for i, r in zip(js, pp):
+                preds[i] = np.ascontiguousarray(r["prob"])
+        prm = (_abi.FxRiskParams * max(n, 1))(*params)
+        rps = (_abi.FxRespCostParams * max(n, 1))(*[
+            _abi.FxRespCostParams(weights[i], int(cost_params[i].responsibility_mode), cost_params[i].responsibility,
+                                  preds[i].ctypes.data if preds[i] is not None and len(preds[i]) else None) for i in range(n)])
+        # (an agent the library will refuse counts no rows: the refusal comes before anything is written)
+        counts = [self._inputs[a].n_candidates if 0 <= a < len(self._inputs) else 0 for a in listed]
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        res = {k: np.zeros(max(int(off[-1]), 1)) for k in ("resp", "total", "ego_risk", "obst_risk")}
+        best_index, best_cost = np.full(max(n, 1), -1, np.int64), np.full(max(n, 1), np.nan)
+        out = _abi.FxRespCostBatchOutputs(*[res[k].ctypes.data for k in ("resp", "total", "ego_risk", "obst_risk")],
+                                          best_index.ctypes.data, best_cost.ctypes.data)
+        ids = np.ascontiguousarray(listed, dtype=np.int32)
+        check(lib().fx_eval_responsibility_cost_batch(self._ctx, n, ids.ctypes.data_as(C.POINTER(C.c_int32)) if agents is not None else None,
+                                                      prm, rps, C.byref(out)))
+        return [dict({k: a[off[i]:off[i + 1]] for k, a in res.items()}, best_index=int(best_index[i]), best_cost=float(best_cost[i]),
+                     prediction=preds[i]) for i in range(n)]
 
     # -- collision probability as the prediction cost (DESIGN.md section 16) --
     def prediction_probability(self, ego_length: float, ego_width: float, ids=None, agent: int = 0, per_obstacle: bool = False,

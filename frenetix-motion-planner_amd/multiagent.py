@@ -91,6 +91,8 @@ def trajectory_as_prediction(states: Sequence, shape: dict, wb_rear_axle: float,
 # AgentBatchHip(batched_passes=None): what the measurement of DESIGN.md section 18 decided (its decision rule: on only if the
 # batched call's wall p95 lies below the per-agent loop's wall p5 at both planner-sized workloads)
 BATCHED_PASSES_DEFAULT = False
+# AgentBatchHip(batched_responsibility=None): the same rule for the responsibility pass of a whole batch
+BATCHED_RESPONSIBILITY_DEFAULT = False
 
 
 class AgentBatchHip:
@@ -103,8 +105,15 @@ class AgentBatchHip:
 
     def __init__(self, agents: List[FrenetPlannerInterfaceHip], max_candidates: int, device: int = 0, max_ref_knots: int = 4096,
                  max_obstacles: int = 64, engine=None, parts=None, slots=None, winner_exchange=None, pipeline_groups: Optional[int] = None,
-                 batched_passes: Optional[bool] = None):
-        """batched_passes: the collision-probability pass of the planners that weight it (prediction_cost="collision_probability")
+                 batched_passes: Optional[bool] = None, batched_responsibility: Optional[bool] = None):
+        """batched_responsibility: independent of batched_passes -- the responsibility pass of the planners that weight the term
+        runs for all of them in ONE engine.responsibility_cost_batch call per engine group and step, behind the batched launch:
+        each such planner sets its tables (prepare_responsibility_cost), the call runs over those whose preparation returns
+        parameters -- with the collision probability as the prediction entry for those that run that pass too, one
+        prediction_probability_batch for that subset -- and each gets its dict through plan_consume; the same bits (DESIGN.md
+        section 19).  None: BATCHED_RESPONSIBILITY_DEFAULT.  A planner whose preparation returns None, escalated levels, split agents
+        and engines without the method keep the per-agent path.
+        batched_passes: the collision-probability pass of the planners that weight it (prediction_cost="collision_probability")
         runs for all of them in ONE engine.prediction_probability_batch call per engine group and step, behind the batched launch,
         instead of one call per agent from plan_consume -- the same bits.  None: BATCHED_PASSES_DEFAULT, the
         measurement's verdict.  Escalated levels, split agents, planners that also weight `responsibility` and engines without the
@@ -156,6 +165,7 @@ class AgentBatchHip:
             if hasattr(e, "set_package"):   # every agent's winner arrives packaged with the result block: no read-back per agent
                 e.set_package(True)
         self.batched_passes = BATCHED_PASSES_DEFAULT if batched_passes is None else bool(batched_passes)
+        self.batched_responsibility = BATCHED_RESPONSIBILITY_DEFAULT if batched_responsibility is None else bool(batched_responsibility)
         self.launches = 0
         self.escalations = 0
         self.last_batch_ms = 0.0
@@ -173,6 +183,30 @@ class AgentBatchHip:
             planners[j].set_prediction_obstacles(eng, j)
         res = eng.prediction_probability_batch([planners[j].vehicle_params.length for j in js],
                                                [planners[j].vehicle_params.width for j in js], agents=js)
+        for j, r in zip(js, res):
+            passes[j] = r
+        return passes
+
+    def _responsibility_passes(self, eng, planners, inputs) -> list:
+        """Behind a batched launch of `planners` (in the launch's agent order, with their inputs) on `eng`: the responsibility pass
+        of those that weight the term and whose preparation returns parameters, in one call; per planner its dict for
+        plan_consume, or None: the planner's own path."""
+        passes = [None] * len(planners)
+        if not self.batched_responsibility or not hasattr(eng, "responsibility_cost_batch"):
+            return passes
+        js, preps = [], []
+        for j, p in enumerate(planners):
+            if p is None or not p.batched_responsibility_pass():
+                continue
+            prep = p.prepare_responsibility_cost(eng, j, inputs[j].n_samples)
+            if prep is not None:
+                js.append(j)
+                preps.append(prep)
+        if not js:
+            return passes
+        kinds = ["probability" if planners[j]._check_prediction_cost() else "step" for j in js]
+        res = eng.responsibility_cost_batch([q[0] for q in preps], [q[1] for q in preps], [q[2] for q in preps], agents=js,
+                                            prediction=kinds)
         for j, r in zip(js, res):
             passes[j] = r
         return passes
@@ -202,10 +236,12 @@ class AgentBatchHip:
             else:   # a batch the packaged path does not take (sampling matrix, mixed horizons): the general call
                 results, packages = eng.plan_batch_packaged([inp for _, inp in planning], yaws)
             passes = self._prediction_passes(eng, [a.planner for a, _ in planning])
+            rpasses = self._responsibility_passes(eng, [a.planner for a, _ in planning], [inp for _, inp in planning])
             for j, (a, inp) in enumerate(planning):
                 p = a.planner
                 best = p.plan_consume(inp, results[j], eng, j, package=packages[j],
-                                      **({"prediction_pass": passes[j]} if passes[j] is not None else {}))
+                                      **({"prediction_pass": passes[j]} if passes[j] is not None else {}),
+                                      **({"responsibility_pass": rpasses[j]} if rpasses[j] is not None else {}))
                 if best is None and p._sampling_min + 1 < p._sampling_max:
                     self.escalations += 1
                     pair = p.plan_escalate(t0)
@@ -251,11 +287,14 @@ class AgentBatchHip:
         # (a split agent's part is evaluated again for its one winner: its pass stays with that launch's plan_consume)
         passes = self._prediction_passes(self.engine, [a.planner if self.parts[k][1] == 1 and results[j] is not None else None
                                                        for j, (a, _, k) in enumerate(planning)])
+        rpasses = self._responsibility_passes(self.engine, [a.planner if self.parts[k][1] == 1 and results[j] is not None else None
+                                                            for j, (a, _, k) in enumerate(planning)], [inp for _, inp, _ in planning])
 
-        def conclude(a, inp, res, j, packages=packages, passes=passes):
+        def conclude(a, inp, res, j, packages=packages, passes=passes, rpasses=rpasses):
             p = a.planner
             best = (p.plan_consume(inp, res, self.engine, j, package=packages[j] if packages is not None else False,
-                                   **({"prediction_pass": passes[j]} if passes is not None and passes[j] is not None else {}))
+                                   **({"prediction_pass": passes[j]} if passes is not None and passes[j] is not None else {}),
+                                   **({"responsibility_pass": rpasses[j]} if rpasses is not None and rpasses[j] is not None else {}))
                     if res is not None else None)
             if best is None and p._sampling_min + 1 < p._sampling_max:
                 self.escalations += 1
@@ -287,7 +326,7 @@ class AgentBatchHip:
                 res1 = self.engine.plan_batch([one for _, one in again])
                 self.launches += 1
                 for j1, (a, one) in enumerate(again):
-                    conclude(a, one, res1[j1], j1, None, None)
+                    conclude(a, one, res1[j1], j1, None, None, None)
         for a, _, _ in passive:
             sel, _ = a.finish_step(None, global_timestep)
             out[a.id] = sel[0] if sel is not None else None
@@ -308,8 +347,9 @@ class MultiAgentSimulation:
     def __init__(self, scenario: Scenario, config: Optional[PlannerConfig] = None, vehicle: Optional[VehicleParams] = None,
                  number_of_agents: int = -1, sampling_level: Optional[int] = None, device: int = 0, group=None,
                  use_road_boundary: bool = False, max_candidates: Optional[int] = None, engine_factory=None,
-                 pipeline_groups: Optional[int] = None, freeze_gc: bool = False, batched_passes: Optional[bool] = None):
-        """batched_passes: see AgentBatchHip.
+                 pipeline_groups: Optional[int] = None, freeze_gc: bool = False, batched_passes: Optional[bool] = None,
+                 batched_responsibility: Optional[bool] = None):
+        """batched_passes, batched_responsibility: see AgentBatchHip.
         engine_factory: callable returning an engine object (tests inject a stand-in); default = FrenetEngine.
         pipeline_groups: see AgentBatchHip (None = automatic; with an engine_factory: that many injected engines, default one).
         freeze_gc: take what exists once the simulation is set up out of the garbage collector's generations (gc.freeze(): a
@@ -348,7 +388,8 @@ class MultiAgentSimulation:
                                    engine=(([engine_factory() for _ in range(pipeline_groups)] if pipeline_groups and pipeline_groups > 1
                                             else engine_factory()) if engine_factory else None),
                                    parts=[(part, n_parts) for _, part, n_parts in my_items], slots=self.my_slots,
-                                   winner_exchange=self._exchange_winners if self.split else None, batched_passes=batched_passes)
+                                   winner_exchange=self._exchange_winners if self.split else None, batched_passes=batched_passes,
+                                   batched_responsibility=batched_responsibility)
         self.S = self.batch.agents[0].planner.N + 1 if mine else int(self.config.planning_horizon / self.config.dt) + 1
         self.time_step = 0
         # planned trajectories of ALL agents, identical on every rank after the exchange: [agents][S][FIELDS]

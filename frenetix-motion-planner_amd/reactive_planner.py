@@ -288,34 +288,53 @@ class ReactivePlannerHip:
                              "(PlannerConfig.sparse_bundle_k = 0), not a select-only step")
         return True
 
-    def _apply_responsibility_cost(self, step, probability: bool):
-        """the responsibility pass over the step's candidates, installed as the step's cost override together with -- probability
-        -- the collision probability as the prediction entry: ONE override.  Upstream's condition (partial_cost_functions.py:371):
-        without predictions, or in reach-set mode without a reach set, the term is 0.0 for every candidate and no pass runs:
-        costMap["responsibility"] is (0.0, 0.0) and the step's costs and orders stay its own."""
+    def prepare_responsibility_cost(self, engine, agent: int, n_samples: int):
+        """The preparation of the responsibility pass on `engine` for `agent`: the obstacle tables of the current predictions, the
+        reach-set tables or the action-space vector.  Returns (FxRiskParams, risk_cost_params, weight) for the pass, or None where
+        upstream's condition (partial_cost_functions.py:371) lets no pass run: without predictions, or in reach-set mode without a
+        reach set."""
+        from types import SimpleNamespace
         from . import risk
         preds = self.predictions if self.use_prediction else None
         mode = self.config.responsibility_mode
         if preds is None or (mode == "reach_set" and self.reach_set is None):
-            if probability:
-                self._apply_prediction_cost(step)
-            step.set_cost_extras({"responsibility": (np.zeros(step.inputs.n_candidates), float(self.cost_weights["responsibility"]))})
-            return
-        tabs = self._set_risk_obstacles(step)
+            return None
+        tabs = self._set_risk_obstacles(SimpleNamespace(engine=engine, agent=agent))
         if mode == "action_space":
             resp = risk.action_space_responsibility(preds, self.x_0.position, self.x_0.orientation)
         else:
             sets = self.reach_set.reach_sets[self.x_0.time_step]
-            step.engine.set_reach_sets(risk.reach_set_tables(sets, tabs["keys"], self.dT, step.inputs.n_samples), step.agent)
+            engine.set_reach_sets(risk.reach_set_tables(sets, tabs["keys"], self.dT, n_samples), agent)
             resp = "reach_set"
         cp = risk.risk_cost_params([0.0, 0.0, 0.0, 0.0, 1.0], responsibility=resp)
-        step.apply_responsibility_cost(self._risk_model["params"], cp, float(self.cost_weights["responsibility"]),
-                                       prediction="probability" if probability else "step")
+        return self._risk_model["params"], cp, float(self.cost_weights["responsibility"])
+
+    def _apply_responsibility_cost(self, step, probability: bool, result=None):
+        """the responsibility pass over the step's candidates, installed as the step's cost override together with -- probability
+        -- the collision probability as the prediction entry: ONE override.  Where the preparation lets no pass run the term is
+        0.0 for every candidate: costMap["responsibility"] is (0.0, 0.0) and the step's costs and orders stay its own.  result: the
+        pass already ran for this step in a batched call behind this planner's preparation -- its dict for this agent."""
+        if result is not None:
+            step.apply_responsibility_cost(None, None, float(self.cost_weights["responsibility"]), result=result)
+            return
+        prep = self.prepare_responsibility_cost(step.engine, step.agent, step.inputs.n_samples)
+        if prep is None:
+            if probability:
+                self._apply_prediction_cost(step)
+            step.set_cost_extras({"responsibility": (np.zeros(step.inputs.n_candidates), float(self.cost_weights["responsibility"]))})
+            return
+        step.apply_responsibility_cost(*prep, prediction="probability" if probability else "step")
+
+    def batched_responsibility_pass(self) -> bool:
+        """True when this planner weights `responsibility`: a batch of planners may then prepare each of them
+        (prepare_responsibility_cost) and run the pass for all in one call (multiagent.AgentBatchHip),
+        handing each its dict through plan_consume."""
+        return self._check_responsibility_cost()
 
     def batched_prediction_pass(self) -> bool:
         """True when this planner's pass beside the step is the collision probability alone: a batch of planners may then run
         it for all of them in one call (multiagent.AgentBatchHip) and hand the result to plan_consume.  A planner that also weights
-        `responsibility` sums both in ONE override of its own pass and stays there."""
+        `responsibility` sums both in ONE override of the responsibility pass: batched_responsibility_pass."""
         return self._check_prediction_cost() and not self._check_responsibility_cost()
 
     def set_prediction_obstacles(self, engine, agent: int = 0):
@@ -668,15 +687,18 @@ class ReactivePlannerHip:
         self._stop_point_s = stop_point_s
         return self._inputs_for_level(self._sampling_min, stop_point_s)
 
-    def plan_consume(self, inputs: PlanInputs, res: dict, engine, agent: int = 0, package=False, prediction_pass=None):
+    def plan_consume(self, inputs: PlanInputs, res: dict, engine, agent: int = 0, package=False, prediction_pass=None,
+                     responsibility_pass=None):
         """Take this planner's share of a batched launch (first sampling level); returns the chosen trajectory
         (materialised -- the batch engine's buffers are reused) or None when the level has to escalate.
         package: the winner as the batched call already packaged it (engine.plan_batch_packaged; None = nothing found);
         False: read it here.  prediction_pass: this agent's dict of an engine.prediction_probability_batch call over this launch
-        (batched_prediction_pass planners only); None: the planner runs its own pass."""
+        (batched_prediction_pass planners only); None: the planner runs its own pass.  responsibility_pass: the same for an
+        engine.responsibility_cost_batch call behind this planner's prepare_responsibility_cost."""
         if package is False:
             package = engine.package(agent, self.x_0.yaw_rate) if getattr(engine, "packaging", False) and inputs.write_bundle else None
-        best = self._consume_result(inputs, res, engine, agent, package, self._sampling_min, prediction_pass=prediction_pass)
+        best = self._consume_result(inputs, res, engine, agent, package, self._sampling_min, prediction_pass=prediction_pass,
+                                    responsibility_pass=responsibility_pass)
         if best is not None:
             best.materialise()
         return best
@@ -795,7 +817,8 @@ class ReactivePlannerHip:
             self.msg_logger.warning("No optimal trajectory available. Select lowest risk trajectory!")
         return chosen
 
-    def _consume_result(self, inputs: PlanInputs, res: dict, engine, agent: int, package=None, samp_lvl=None, prediction_pass=None):
+    def _consume_result(self, inputs: PlanInputs, res: dict, engine, agent: int, package=None, samp_lvl=None, prediction_pass=None,
+                        responsibility_pass=None):
         if self.last_step is not None:
             self.last_step.invalidate()
         step = PlanStepResult(engine, inputs, res, agent)
@@ -815,7 +838,7 @@ class ReactivePlannerHip:
             raise ValueError("prediction_cost='collision_probability' and cost_weights['responsibility'] need a plan step that stored "
                              "the bundle and the cost map")
         if responsibility:
-            self._apply_responsibility_cost(step, probability)
+            self._apply_responsibility_cost(step, probability, responsibility_pass)
         elif probability:
             self._apply_prediction_cost(step, prediction_pass)
         by_rank = bool(self.config.device_sort) and hasattr(engine, "ranked")

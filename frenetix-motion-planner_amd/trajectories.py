@@ -442,13 +442,15 @@ class PlanStepResult:
             weights.append(w)
         return names, raw, np.array(weights, np.float64)
 
-    def apply_responsibility_cost(self, params, cost_params, weight: float, prediction: str = "step"):
+    def apply_responsibility_cost(self, params, cost_params, weight: float, prediction: str = "step", result=None):
         """Run engine.responsibility_cost over every candidate of this step -- the obstacles and reach sets are the engine's last
         ones -- and install its result: total and best as the cost override, costMap["responsibility"], and _ego_risk /
         _obst_risk of every sample of the step (partial_cost_functions.py:373-374).  prediction "probability": the collision
-        probability replaces the step's prediction entry in the same override.  Returns the pass's dict."""
+        probability replaces the step's prediction entry in the same override.  result: this agent's dict of a
+        responsibility_cost_batch call over the same step, installed exactly as the computed one is.  Returns the pass's dict."""
         self._check()
-        r = self.engine.responsibility_cost(params, cost_params, weight, agent=self.agent, prediction=prediction)
+        r = result if result is not None else self.engine.responsibility_cost(params, cost_params, weight, agent=self.agent,
+                                                                              prediction=prediction)
         pred = r["prediction"] if r["prediction"] is not None else np.full(len(r["total"]), np.nan)
         self.set_cost_override(r["total"], pred, r["best_index"], extras={"responsibility": (r["resp"], weight)})
         self._risk = (r["ego_risk"], r["obst_risk"])

@@ -800,6 +800,25 @@ typedef struct FxRespCostOutputs {   /* rows in the order of ids, or [C] with id
 int32_t fx_eval_responsibility_cost_agent(FxContext *ctx, int32_t agent, const FxRiskParams *params, const FxRespCostParams *resp,
                                           int64_t n_ids, const int64_t *ids, const FxRespCostOutputs *out);
 
+/* The same pass over EVERY candidate of several agents of the last plan step in one call (additive within
+ * ABI 15): the ids == NULL form of fx_eval_responsibility_cost_agent for each listed agent -- NaN rows for candidates without
+ * FX_FLAG_COSTED -- with the agent's own params[i] and resp[i] (weight, mode, responsibility [K of that agent], prediction [C of
+ * that agent] or NULL), its own fx_set_risk_obstacles_agent and fx_set_reach_sets_agent tables, C, S, K, cost list and deferred-sum
+ * mode.  Every output is bit for bit what the per-agent call returns, whichever agents share a call and in whatever order. */
+typedef struct FxRespCostBatchOutputs {      /* no pointer may be NULL */
+    double *resp, *total, *ego_risk, *obst_risk;  /* [sum of C over the listed agents], agent-major, as FxPredProbBatchOutputs */
+    int64_t *best_index;                          /* [n_agents], as FxRespCostOutputs.best_index */
+    double *best_cost;                            /* [n_agents] */
+} FxRespCostBatchOutputs;
+/* agents: as in fx_eval_prediction_prob_batch.  Everything is checked for every listed agent before anything is launched, uploaded,
+ * allocated or written to out, and the message names the first offending agent: FX_ERR_INVALID_ARGUMENT for NULL ctx, params, resp,
+ * out or output pointer, n_agents < 0 or above the uploaded agents, an agent out of range or listed twice; per agent what
+ * fx_eval_responsibility_cost_agent refuses, with its codes.  n_agents == 0 returns FX_OK and touches nothing.  Synchronous;
+ * fx_last_risk_ms covers it; its memory is the risk passes' device block (grow-only, counted in fx_device_bytes). */
+int32_t fx_eval_responsibility_cost_batch(FxContext *ctx, int32_t n_agents, const int32_t *agents /* NULL: 0 .. n_agents-1 */,
+                                          const FxRiskParams *params /* [n_agents] */, const FxRespCostParams *resp /* [n_agents] */,
+                                          const FxRespCostBatchOutputs *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,10 @@ class FxRespCostBatchOutputs(C.Structure):   # (fx_eval_responsibility_cost_batc
     _fields_ = [(n, C.c_void_p) for n in ("resp", "total", "ego_risk", "obst_risk", "best_index", "best_cost")]
 
 
+class FxRiskBatchOutputs(C.Structure):   # (fx_eval_risk_batch)
+    _fields_ = [(n, C.c_void_p) for n in ("ego_risk", "obst_risk", "min_risk_index")]
+
+
 class FxRiskOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ego_risk", "obst_risk", "obst_harm_occ", "ego_risk_max", "obst_risk_max", "ego_harm_max",
                                           "obst_harm_max", "bayes", "equality", "maximin", "ego", "responsibility", "total",

@@ -5,7 +5,8 @@
 // this runs in a plan step.  The collision probability as the prediction cost (fx_predprob_kernel.h) is a third
 // entrance on the same host path: the same checks, records, uploads and block; fx_eval_prediction_prob_batch
 // is that pass for several agents in one call: the same checks and records per agent, one staging buffer each for records and tables;
-// fx_eval_responsibility_cost_batch is the responsibility pass for several agents in one call.
+// fx_eval_responsibility_cost_batch is the responsibility pass for several agents in one call, and
+// fx_eval_risk_batch the plain risk pass for several agents, each with an id list or none.
 #include <atomic>
 #include <cmath>
 #include <vector>
@@ -26,6 +27,9 @@ extern "C" __attribute__((weak)) hipError_t fx_launch_predprob_batch(const PredP
 extern "C" __attribute__((weak)) hipError_t fx_launch_risk_batch(const RiskBatchArgs *t, const RiskBatchRound *rounds, int n_rounds,
                                                                  long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
                                                                  hipStream_t stream);
+extern "C" __attribute__((weak)) hipError_t fx_launch_risk_list_batch(const RiskListBatchArgs *t, const RiskBatchRound *rounds, int n_rounds,
+                                                                      long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                                                      hipStream_t stream);
 extern "C" __attribute__((weak)) int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K);   // (fx_kernels.hip: the rule, or what a test forces)
 
 namespace {
@@ -974,6 +978,158 @@ extern "C" int32_t fx_eval_responsibility_cost_batch(FxContext *c, int32_t n_age
     for (size_t i = 0; i < A; i++) {
         out->best_index[i] = (int64_t)best[2 * i];
         memcpy(out->best_cost + i, &best[2 * i + 1], sizeof(double));
+    }
+    return FX_OK;
+}
+
+// The plain risk pass -- fx_eval_risk_agent -- of several agents in ONE call, each with its own id list or none (fxplan.h; DESIGN.md
+// section 20).  Per agent the checks of the per-agent entry (risk_check: it resolves planes, ld, flags and the positions of listed
+// candidates in a sparse set) and its records; then everything the kernels read -- FxRiskParams, records, obstacle tables, id lists
+// (or sparse positions), rows and compact arrays -- in ONE staging buffer and one copy; the rounds of fx_item_rounds over one scratch
+// with each row's steps per chunk chosen from its agent's OWN list length, as the per-agent call chooses them.  Runtime calls of a
+// call with R rounds: 1 drain (a synchronisation), 1 ensure of the block, 1 copy up, 2 event records, 2 R + 1 launches, 3 copies
+// down (ego_risk, obst_risk, min_risk_index), 1 synchronisation -- none of them per agent.
+extern "C" int32_t fx_eval_risk_batch(FxContext *c, int32_t n_agents, const int32_t *agents, const FxRiskParams *params, const int64_t *n_ids,
+                                      const int64_t *const *ids, const FxRiskBatchOutputs *out) {
+    if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
+    if (!params || !out) return set_err(FX_ERR_INVALID_ARGUMENT, "params or out is NULL");
+    if (!out->ego_risk || !out->obst_risk || !out->min_risk_index) return set_err(FX_ERR_INVALID_ARGUMENT, "an output pointer is NULL");
+    if (n_agents < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d", n_agents);
+    if (n_agents == 0) return FX_OK;
+    if (!fx_launch_risk_list_batch) return set_err(FX_ERR_HIP, "built without the batched risk launcher");
+    const int32_t agent0 = agents ? agents[0] : 0;
+    if (!c->evaluated) return set_err(FX_ERR_NOT_READY, "agent %d: no evaluated plan step", agent0);
+    if (n_agents > c->n_agents) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d of %d uploaded agents", n_agents, c->n_agents);
+    // (the batch is made behind a plan step of all its agents: inputs rewritten since belong to a step that has not run)
+    if (!fx_inputs_current(c))
+        return set_err(FX_ERR_NOT_READY, "agent %d: the inputs were rewritten since the last evaluation (fx_update_state): evaluate first", agent0);
+    const size_t A = (size_t)n_agents;
+    std::vector<RiskPass> q(A);
+    std::vector<char> listed((size_t)c->n_agents, 0);
+    for (size_t i = 0; i < A; i++) {
+        const int32_t agent = agents ? agents[i] : (int32_t)i;
+        if (agent >= 0 && agent < c->n_agents && listed[agent]) return set_err(FX_ERR_INVALID_ARGUMENT, "agent %d listed twice", agent);
+        const int64_t n_i = n_ids ? n_ids[i] : 0;
+        const int64_t *ids_i = (n_ids && ids) ? ids[i] : nullptr;
+        if (const int rc = risk_check(q[i], c, agent, params + i, n_i, ids_i, true, false)) {
+            char why[sizeof(g_err)];
+            snprintf(why, sizeof(why), "%s", g_err);
+            return set_err(rc, "agent %d: %s", agent, why);
+        }
+        listed[agent] = 1;
+    }
+    // ONE staging buffer, every part 16-byte aligned; the device's copy lies at o_stage of the block
+    std::vector<char> stage;
+    auto room = [&](size_t bytes) { const size_t o = stage.size(); stage.resize(o + align_up(std::max<size_t>(bytes, 8), 16), 0); return o; };
+    auto put = [&](const void *src, size_t bytes) { const size_t o = room(bytes); if (bytes) memcpy(stage.data() + o, src, bytes); return o; };
+    struct Parts { size_t prm, rec, obs, pos, yaw, v, ids, out_at; bool items; };
+    std::vector<Parts> at(A);
+    std::vector<FxItemAgent> ia(A);
+    std::vector<int32_t> cs(A), chunks(A);
+    std::vector<double> rec;
+    size_t rows_out = 0;
+    for (size_t i = 0; i < A; i++) {
+        const RiskPass &p = q[i];
+        const FxRiskAgent &a = *p.a;
+        Parts &t = at[i];
+        t = Parts{};
+        t.out_at = rows_out;
+        rows_out += (size_t)p.n;
+        t.prm = put(p.prm, sizeof(FxRiskParams));
+        if (p.K > 0) {
+            build_records(a, p.S, p.maha, rec);
+            t.rec = put(rec.data(), sizeof(double) * rec.size()), t.obs = put(a.obs.data(), sizeof(double) * a.obs.size());
+            t.pos = put(a.pos.data(), sizeof(double) * a.pos.size()), t.yaw = put(a.yaw.data(), sizeof(double) * a.yaw.size());
+            t.v = put(a.v.data(), sizeof(double) * a.v.size());
+        }
+        if (p.ids) t.ids = put(p.sparse ? p.pos.data() : p.ids, sizeof(int64_t) * (size_t)p.n);
+        // steps per chunk from the agent's OWN list length: what fx_eval_risk_agent chooses for it
+        t.items = p.K > 0 && p.S > 1;
+        cs[i] = fx_risk_items_chunk_steps(p.n, p.S, p.K);
+        chunks[i] = (std::max(p.S - 1, 1) + cs[i] - 1) / cs[i];
+        ia[i] = FxItemAgent{p.n, t.items ? sizeof(double) * 2 * (size_t)std::max(p.K, 1) * (size_t)chunks[i] : 0};
+    }
+    const unsigned long long forced = fx_risk_batch_scratch_forced.load(std::memory_order_relaxed);
+    const std::vector<FxItemSegment> segs = fx_item_rounds(ia.data(), n_agents, forced ? (size_t)forced : FX_ITEM_SCRATCH_BYTES);
+    const size_t R = segs.size();
+    const int n_rounds = R ? segs.back().round + 1 : 0;
+    std::vector<RiskBatchRound> rounds((size_t)n_rounds, RiskBatchRound{0, 0, 0, 0});
+    std::vector<RiskBatchRow> rows(R);
+    std::vector<int32_t> agent_row(A, -1);
+    const size_t t_rows = room(sizeof(RiskBatchRow) * R), t_item0 = room(sizeof(int64_t) * R), t_fin0 = room(sizeof(int32_t) * R),
+                 t_arow = room(sizeof(int32_t) * A);
+    size_t scratch = 0;
+    for (size_t k = 0; k < R; k++) {   // the rows' counts (their pointers follow when the block is there)
+        const FxItemSegment &g = segs[k];
+        const size_t tiles = (size_t)(g.count + 63) / 64;
+        RiskBatchRound &rd = rounds[g.round];
+        RiskBatchRow &w = rows[k];
+        w = RiskBatchRow{};
+        if (rd.n_rows == 0) rd.row0 = (int32_t)k;
+        rd.n_rows++;
+        w.first = g.first, w.count = g.count;
+        w.it.nb = (int64_t)tiles * 64, w.it.cs = cs[g.agent], w.it.chunks = chunks[g.agent];
+        w.it.need = FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED;
+        w.items = at[g.agent].items ? 1 : 0;
+        w.item0 = rd.items;
+        w.fin0 = rd.fin_blocks;
+        if (w.items) rd.items += (int64_t)tiles * chunks[g.agent] * (int64_t)q[g.agent].K;
+        const int64_t fin = (int64_t)rd.fin_blocks + (g.count + 255) / 256;
+        if (fin > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld workgroups of candidates", (long long)fin);
+        rd.fin_blocks = (int32_t)fin;
+        scratch = std::max(scratch, g.scratch_off + tiles * 64 * ia[g.agent].per_candidate_bytes);
+        agent_row[g.agent] = (int32_t)k;
+    }
+    for (const RiskBatchRound &rd : rounds)
+        if (rd.items > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld items", (long long)rd.items);
+    FxBlockLayout lay;
+    const size_t o_stage = lay.take(stage.size()), o_part = lay.take(scratch);
+    const size_t o_ego = lay.take(sizeof(double) * rows_out), o_obst = lay.take(sizeof(double) * rows_out);
+    const size_t o_idx = lay.take(sizeof(long long) * A);
+    FxRiskState *r = q[0].r;
+    HIP_TRY(hipSetDevice(c->device));
+    FX_TRY(fx_drain(c));
+    FX_TRY(r->block.ensure(lay.size()));
+    FX_TRY(r->ev.ensure());
+    char *base = r->block;
+    auto D = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    for (size_t k = 0; k < R; k++) {
+        const FxItemSegment &g = segs[k];
+        const RiskPass &p = q[g.agent];
+        const Parts &t = at[g.agent];
+        const size_t s0 = o_stage;
+        RiskBatchRow &w = rows[k];
+        w.w = RiskWalkArgs{p.planes, p.ld, p.S, p.n, p.ids ? reinterpret_cast<const int64_t *>(base + s0 + t.ids) : nullptr, p.flags,
+                           D(s0 + t.rec), D(s0 + t.obs), D(s0 + t.pos), D(s0 + t.yaw), D(s0 + t.v), p.K, p.P};
+        w.it.params = reinterpret_cast<const FxRiskParams *>(base + s0 + t.prm);
+        w.it.part = reinterpret_cast<double *>(base + o_part + g.scratch_off);
+        w.ego = D(o_ego) + t.out_at, w.obst = D(o_obst) + t.out_at;
+        memcpy(stage.data() + t_item0 + sizeof(int64_t) * k, &w.item0, sizeof(int64_t));
+        memcpy(stage.data() + t_fin0 + sizeof(int32_t) * k, &w.fin0, sizeof(int32_t));
+    }
+    if (R) memcpy(stage.data() + t_rows, rows.data(), sizeof(RiskBatchRow) * R);
+    memcpy(stage.data() + t_arow, agent_row.data(), sizeof(int32_t) * A);
+    HIP_TRY(hipMemcpyAsync(base + o_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, c->stream));
+    RiskListBatchArgs t{};
+    t.rows = reinterpret_cast<const RiskBatchRow *>(base + o_stage + t_rows);
+    t.item0 = reinterpret_cast<const int64_t *>(base + o_stage + t_item0);
+    t.fin0 = reinterpret_cast<const int32_t *>(base + o_stage + t_fin0);
+    t.agent_row = reinterpret_cast<const int32_t *>(base + o_stage + t_arow);
+    t.n_agents = n_agents;
+    long long *d_idx = reinterpret_cast<long long *>(base + o_idx);
+    HIP_TRY(fx_launch_risk_list_batch(&t, rounds.data(), n_rounds, d_idx, r->ev.e0, r->ev.e1, c->stream));
+    if (rows_out) {
+        HIP_TRY(hipMemcpyAsync(out->ego_risk, base + o_ego, sizeof(double) * rows_out, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out->obst_risk, base + o_obst, sizeof(double) * rows_out, hipMemcpyDeviceToHost, c->stream));
+    }
+    std::vector<long long> idx(A, -1);
+    HIP_TRY(hipMemcpyAsync(idx.data(), d_idx, sizeof(long long) * A, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&r->last_ms, r->ev.e0, r->ev.e1));
+    for (size_t i = 0; i < A; i++) {
+        // (sparse set: the arg-min ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
+        if (q[i].sparse && idx[i] >= 0) idx[i] = (long long)q[i].set.ids[idx[i]];
+        out->min_risk_index[i] = (int64_t)idx[i];
     }
     return FX_OK;
 }

@@ -466,6 +466,29 @@ extern "C" hipError_t fx_launch_risk_batch(const RiskBatchArgs *t, const RiskBat
     return hipSuccess;
 }
 
+// the plain risk pass over several agents in one call, each with an id list or none (fx_risk_kernel.h): per
+// round ONE item launch over the flat items of all its rows and ONE finish launch, then one arg-min launch with a workgroup per
+// agent -- 2 R + 1 launches.  t: the device tables; rounds: the host's account of them (fx_api_risk.hip builds both).
+// ev_start / ev_stop bracket all launches.
+extern "C" hipError_t fx_launch_risk_list_batch(const RiskListBatchArgs *t, const RiskBatchRound *rounds, int n_rounds, long long *out_idx,
+                                                hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream) {
+    hipError_t e;
+    if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
+    for (int r = 0; r < n_rounds; r++) {
+        const RiskBatchRound &q = rounds[r];
+        if (q.items > 0)
+            hipLaunchKernelGGL(fxrisk::fx_risk_list_batch_item_kernel, dim3((unsigned)q.items), dim3(64), 0, stream, t->rows + q.row0,
+                               t->item0 + q.row0, q.n_rows);
+        hipLaunchKernelGGL(fxrisk::fx_risk_list_batch_finish_kernel, dim3((unsigned)q.fin_blocks), dim3(256), 0, stream, t->rows + q.row0,
+                           t->fin0 + q.row0, q.n_rows);
+    }
+    hipLaunchKernelGGL(fxrisk::fx_risk_list_batch_argmin_kernel, dim3((unsigned)t->n_agents), dim3(1024), 0, stream, t->rows, t->agent_row,
+                       out_idx);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
 // batched candidate read-back (fx_gather_kernel.h): one workgroup per listed candidate
 extern "C" hipError_t fx_launch_gather_candidates(const GatherArgs *args, const int64_t *d_ids, int64_t n, unsigned long long *d_out,
                                                   hipStream_t stream) {

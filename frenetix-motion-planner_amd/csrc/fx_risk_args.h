@@ -1,7 +1,7 @@
 // fx_risk_args.h -- what the host code of the trajectory risk (fx_api_risk.hip), its launcher (fx_kernels.hip) and its kernels
 // (fx_risk_kernel.h) share: the layout of the records the host builds and the kernels read, the arguments of the candidate walk
 // and the argument blocks of the risk-cost kernel, the responsibility re-sum and the prediction-probability pass, and the row
-// tables of the two passes that take several agents in one call.  DESIGN.md sections 11, 13, 16, 17, 18 and 19.
+// tables of the three passes that take several agents in one call.  DESIGN.md sections 11, 13, 16, 17, 18, 19 and 20.
 #pragma once
 
 #include <stdint.h>
@@ -169,4 +169,17 @@ struct RiskBatchRound {        // host only
     int32_t row0, n_rows;
     int64_t items;             // of all its rows
     int32_t fin_blocks;
+};
+
+// The plain risk pass over several agents in one call, each with an id list or none (fx_eval_risk_batch):
+// the rows are RiskBatchRow as above -- its layout is the existing batch kernels' -- with, per agent, w.ids its list in the block
+// (positions in its sparse set where the step stored no bundle) or null, w.n the list's length or C, first / count list positions,
+// it.need = VALID | FEASIBLE | RETURNED, it.part [K][chunks][2][nb], ego / obst the agent's rows of the call's concatenated
+// outputs, occ and col null.  The rounds are RiskBatchRound.
+struct RiskListBatchArgs {
+    const RiskBatchRow *rows;  // [n_rows], all rounds
+    const int64_t *item0;      // [n_rows] the rows' item0, compact
+    const int32_t *fin0;       // [n_rows] the rows' fin0
+    const int32_t *agent_row;  // [n_agents] a row of the agent (any of them: the arg-min reads ego, obst, w.n and w.ids), -1 without one
+    int32_t n_agents;
 };

@@ -567,4 +567,80 @@ __global__ __launch_bounds__(1024) void fx_risk_batch_argmin_kernel(const RespSu
     }
 }
 
+// ---- the plain risk pass of several agents in one call, with or without id lists (fx_eval_risk_batch) ----
+// One wave per item of a round, as fx_risk_batch_item_kernel finds it; lane jj of a row handles list position first + jj: the
+// candidate ids[first + jj] of a row with a list -- evaluated whatever its flags, as selected() has it -- or candidate first + jj,
+// which then needs all of it.need.  The choice is the row's, so wave-uniform.  From there on the loop of fx_risk_item_kernel<false>
+// in its own text (that kernel is to stay what it is): the harm only where the probability is not zero, the two partials in the
+// layout [K][chunks][2][nb] of the row's segment.  FxRiskParams through the row's pointer, never by value.
+__global__ __launch_bounds__(64) void fx_risk_list_batch_item_kernel(const RiskBatchRow *__restrict__ rows, const int64_t *__restrict__ item0,
+                                                                     const int n_rows) {
+    const int64_t at = blockIdx.x;
+    const RiskBatchRow &r = rows[batch_row_of(item0, n_rows, at)];
+    const RiskWalkArgs &w = r.w;
+    const RiskItemArgs &it = r.it;
+    const FxRiskParams &p = *it.params;
+    const int64_t local = at - r.item0, tiles = it.nb / 64, rest = local / tiles;
+    const int lane = threadIdx.x, S = w.S;
+    const int k = (int)(rest / it.chunks), ch = (int)(rest % it.chunks);
+    const double *__restrict__ o = w.obs + (size_t)k * FXO_STRIDE;
+    const int pl = min(S - 1, (int)o[FXO_NPOS]);
+    const int t_a = ch * it.cs, t_b = min(pl, t_a + it.cs);
+    if (t_a >= t_b) return;   // (wave-uniform)
+    const int64_t jj = (local % tiles) * 64 + lane;
+    if (jj >= r.count) return;   // (count <= nb, first + count <= n)
+    const int64_t c = w.ids ? w.ids[r.first + jj] : r.first + jj;
+    if (!selected(w, it, c)) return;   // (NaN rows from the finish kernel)
+    const int64_t ld = w.ld;
+    const double *__restrict__ X = w.planes + c, *__restrict__ Y = X + (size_t)S * ld, *__restrict__ TH = Y + (size_t)S * ld,
+                 *__restrict__ V = TH + (size_t)S * ld;
+    const bool prot = o[FXO_CLS] == (double)FX_RISK_CLASS_PROTECTED;
+    const double me = p.ego_mass, mo = o[FXO_MASS];
+    const double f_ego = mo / (me + mo), f_obs = me / (me + mo);
+    double e_max = -INFINITY, o_max = -INFINITY;
+    for (int t = t_a; t < t_b; t++) {
+        const int i = t + 1;
+        const double *__restrict__ q = w.rec + ((size_t)k * S + i) * FXR_STRIDE;
+        const double prob = fxrisk::step_probability(p, q, X[(size_t)i * ld], Y[(size_t)i * ld], TH[(size_t)i * ld]);
+        double re = 0.0, ro = 0.0;
+        if (prob != 0.0) {
+            const size_t kt = (size_t)k * w.P + t;
+            double he, ho;
+            fxrisk::step_harm(p, prot, f_ego, f_obs, X[(size_t)t * ld], Y[(size_t)t * ld], TH[(size_t)t * ld], V[(size_t)t * ld], w.yaw[kt],
+                              w.vo[kt], w.pos[2 * kt], w.pos[2 * kt + 1], he, ho);
+            re = he * prob;
+            ro = ho * prob;
+        }
+        e_max = fmax(e_max, re);
+        o_max = fmax(o_max, ro);
+    }
+    const size_t nb = (size_t)it.nb;
+    double *__restrict__ out = it.part + (((size_t)k * it.chunks + ch) * 2) * nb + jj;
+    out[(size_t)P_EMAX * nb] = e_max;
+    out[(size_t)P_OMAX * nb] = o_max;
+}
+
+// One lane per (row, list position) of a round: the chunk combination of fx_risk_items_finish_kernel<false> (the same function)
+// into the agent's rows of the call's concatenated outputs
+__global__ __launch_bounds__(256) void fx_risk_list_batch_finish_kernel(const RiskBatchRow *__restrict__ rows, const int32_t *__restrict__ fin0,
+                                                                        const int n_rows) {
+    const RiskBatchRow &r = rows[batch_row_of(fin0, n_rows, (int64_t)blockIdx.x)];
+    const int64_t jj = (int64_t)(blockIdx.x - r.fin0) * blockDim.x + threadIdx.x;
+    if (jj < r.count) items_finish_body<false>(r.w, r.it, r.first, jj, r.ego, r.obst, nullptr, nullptr);
+}
+
+// One workgroup of 1024 lanes per listed agent: fx_risk_argmin_kernel's reduction over the agent's rows -- the candidate INDEX of
+// the minimum of ego + obst, ties to the lower candidate index whatever the list's order, -1 when nothing is left (or the agent
+// has no row: agent_row < 0)
+__global__ __launch_bounds__(1024) void fx_risk_list_batch_argmin_kernel(const RiskBatchRow *__restrict__ rows, const int32_t *__restrict__ agent_row,
+                                                                         long long *__restrict__ out) {
+    const int row = agent_row[blockIdx.x];
+    if (row < 0) {   // (uniform over the workgroup)
+        if (threadIdx.x == 0) out[blockIdx.x] = -1LL;
+        return;
+    }
+    const RiskBatchRow &r = rows[row];
+    risk_argmin<true>(r.ego, r.obst, r.w.n, r.w.ids, out + blockIdx.x);
+}
+
 }  // namespace fxrisk

@@ -911,6 +911,35 @@ class FrenetEngine(StepRegistry):
                                        C.byref(idx)))
         return ego[:n], obst[:n], int(idx.value)
 
+    def risk_batch(self, params, ids=None, agents=None) -> list:
+        """`risk` of several agents of the last plan step in ONE call (fx_eval_risk_batch): per listed agent
+        the (ego_risk, obst_risk, min_risk_index) that risk(params_a, ids_a, agent=a) returns, bit for bit; the arrays are views of
+        the call's concatenated ones.  params: one FxRiskParams for all or one per listed agent; ids: None (no agent has a list) or
+        per listed agent None (every candidate) or an int array; agents None: every agent of the last upload, in order; the
+        obstacles are each agent's `set_risk_obstacles`."""
+        listed = list(range(len(self._inputs))) if agents is None else [int(a) for a in agents]
+        n = len(listed)
+        params = [params] * n if isinstance(params, _abi.FxRiskParams) else list(params)
+        ids = [None] * n if ids is None else [None if x is None else np.ascontiguousarray(x, dtype=np.int64) for x in ids]
+        if len(params) != n or len(ids) != n:
+            raise ValueError(f"{len(params)} params and {len(ids)} id lists for {n} agents")
+        prm = (_abi.FxRiskParams * max(n, 1))(*params)
+        pi64 = C.POINTER(C.c_int64)
+        n_ids = np.array([0 if x is None else len(x) for x in ids] + [0], dtype=np.int64)
+        backs = [None if x is None else (x if len(x) else np.zeros(1, np.int64)) for x in ids]   # (an empty list is a list: never NULL)
+        idp = (pi64 * max(n, 1))(*[C.cast(None, pi64) if x is None else x.ctypes.data_as(pi64) for x in backs])
+        # (an agent the library will refuse counts no rows: the refusal comes before anything is written)
+        counts = [(self._inputs[a].n_candidates if 0 <= a < len(self._inputs) else 0) if x is None else len(x) for a, x in zip(listed, ids)]
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        ego, obst = np.zeros(max(int(off[-1]), 1)), np.zeros(max(int(off[-1]), 1))
+        idx = np.full(max(n, 1), -1, np.int64)
+        out = _abi.FxRiskBatchOutputs(ego.ctypes.data, obst.ctypes.data, idx.ctypes.data)
+        al = np.ascontiguousarray(listed, dtype=np.int32)
+        any_list = any(x is not None for x in ids)
+        check(lib().fx_eval_risk_batch(self._ctx, n, al.ctypes.data_as(C.POINTER(C.c_int32)) if agents is not None else None, prm,
+                                       n_ids.ctypes.data_as(pi64) if any_list else None, idp if any_list else None, C.byref(out)))
+        return [(ego[off[i]:off[i + 1]], obst[off[i]:off[i + 1]], int(idx[i])) for i in range(n)]
+
     def set_reach_sets(self, tables: dict, agent: int = 0):
         """Reach-set tables (risk.reach_set_tables) for the reach-set responsibility of the next `risk_costs` calls of this
         agent.  Call it after set_risk_obstacles: the entries index that call's obstacles, and new obstacles clear them."""
@@ -963,8 +992,8 @@ class FrenetEngine(StepRegistry):
 
     @property
     def last_risk_ms(self) -> float:
-        """device time of the last `risk` / `risk_detail` / `risk_costs` / `responsibility_cost` / `responsibility_cost_batch` call
-        (its kernels)"""
+        """device time of the last `risk` / `risk_batch` / `risk_detail` / `risk_costs` / `responsibility_cost` /
+        `responsibility_cost_batch` call (its kernels)"""
         return float(lib().fx_last_risk_ms(self._ctx))
 
     # -- the responsibility cost as a weighted term (DESIGN.md section 17) --

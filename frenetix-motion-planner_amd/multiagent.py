@@ -93,6 +93,9 @@ def trajectory_as_prediction(states: Sequence, shape: dict, wb_rear_axle: float,
 BATCHED_PASSES_DEFAULT = False
 # AgentBatchHip(batched_responsibility=None): the same rule for the responsibility pass of a whole batch
 BATCHED_RESPONSIBILITY_DEFAULT = False
+# AgentBatchHip(batched_risk=None): the planners' risk evaluations (log_risk, the min-risk selections) of a whole batch in one
+# call; turning it on is a later change, after that section's measurement has been read
+BATCHED_RISK_DEFAULT = False
 
 
 class AgentBatchHip:
@@ -105,8 +108,15 @@ class AgentBatchHip:
 
     def __init__(self, agents: List[FrenetPlannerInterfaceHip], max_candidates: int, device: int = 0, max_ref_knots: int = 4096,
                  max_obstacles: int = 64, engine=None, parts=None, slots=None, winner_exchange=None, pipeline_groups: Optional[int] = None,
-                 batched_passes: Optional[bool] = None, batched_responsibility: Optional[bool] = None):
-        """batched_responsibility: independent of batched_passes -- the responsibility pass of the planners that weight the term
+                 batched_passes: Optional[bool] = None, batched_responsibility: Optional[bool] = None,
+                 batched_risk: Optional[bool] = None):
+        """batched_risk: per engine group and step plan_consume runs for every planning agent first, then ONE engine.risk_batch
+        over the agents whose planner still needs a risk evaluation of its step (ReactivePlannerHip.risk_request: the winner for
+        log_risk, every candidate for the "min_risk" fallback of a single-level planner and for emergency_mode "min_risk"), then
+        plan_finish / finish_step for every agent in the order they run in anyway -- the same bits.  None:
+        BATCHED_RISK_DEFAULT.  Escalated levels, split agents, planners with sparse_bundle_k > 0, callable selectors,
+        "min_risk_cost" and engines without the method keep the per-agent path.
+        batched_responsibility: independent of batched_passes -- the responsibility pass of the planners that weight the term
         runs for all of them in ONE engine.responsibility_cost_batch call per engine group and step, behind the batched launch:
         each such planner sets its tables (prepare_responsibility_cost), the call runs over those whose preparation returns
         parameters -- with the collision probability as the prediction entry for those that run that pass too, one
@@ -166,9 +176,46 @@ class AgentBatchHip:
                 e.set_package(True)
         self.batched_passes = BATCHED_PASSES_DEFAULT if batched_passes is None else bool(batched_passes)
         self.batched_responsibility = BATCHED_RESPONSIBILITY_DEFAULT if batched_responsibility is None else bool(batched_responsibility)
+        self.batched_risk = BATCHED_RISK_DEFAULT if batched_risk is None else bool(batched_risk)
         self.launches = 0
         self.escalations = 0
         self.last_batch_ms = 0.0
+
+    def _conclude(self, eng, todo, t0, global_timestep, out, batch_risk: bool = True):
+        """Behind a batched launch on `eng`: todo = [(agent, its index in the launch, consume)] in launch order, consume(defer)
+        being the agent's plan_consume.  Per agent consume, then escalate or finish, then finish_step -- or, with batched_risk on
+        an engine that has risk_batch, consume for all, ONE risk_batch over those whose planner asks for an evaluation
+        (risk_request; a planner that escalates does not: its next level runs on its own engine), and then the rest per agent in
+        the same order.  batch_risk False: the per-agent path whatever the flag."""
+        def finish(a, best):
+            p = a.planner
+            if best is None and p._sampling_min + 1 < p._sampling_max:
+                self.escalations += 1
+                pair = p.plan_escalate(t0)   # the whole next level on the planner's own engine (identical on every replica)
+            else:
+                pair = p.plan_finish(best, t0)
+            sel, _ = a.finish_step(pair, global_timestep)
+            out[a.id] = sel
+
+        if not (batch_risk and self.batched_risk and hasattr(eng, "risk_batch")):
+            for a, j, consume in todo:
+                finish(a, consume(False))
+            return
+        bests = [consume(True) for a, j, consume in todo]
+        asked = []
+        for (a, j, _), best in zip(todo, bests):
+            p = a.planner
+            if best is None and p._sampling_min + 1 < p._sampling_max:
+                continue
+            req = p.risk_request(best)
+            if req is not None:
+                asked.append((p, j, req))
+        if asked:
+            res = eng.risk_batch([req[0] for _, _, req in asked], [req[1] for _, _, req in asked], agents=[j for _, j, _ in asked])
+            for (p, _, req), r in zip(asked, res):
+                p.hand_risk_result(req[1], r)
+        for (a, j, _), best in zip(todo, bests):
+            finish(a, best)
 
     def _prediction_passes(self, eng, planners) -> list:
         """Behind a batched launch of `planners` (in the launch's agent order) on `eng`: the collision-probability pass of those
@@ -237,18 +284,14 @@ class AgentBatchHip:
                 results, packages = eng.plan_batch_packaged([inp for _, inp in planning], yaws)
             passes = self._prediction_passes(eng, [a.planner for a, _ in planning])
             rpasses = self._responsibility_passes(eng, [a.planner for a, _ in planning], [inp for _, inp in planning])
-            for j, (a, inp) in enumerate(planning):
-                p = a.planner
-                best = p.plan_consume(inp, results[j], eng, j, package=packages[j],
-                                      **({"prediction_pass": passes[j]} if passes[j] is not None else {}),
-                                      **({"responsibility_pass": rpasses[j]} if rpasses[j] is not None else {}))
-                if best is None and p._sampling_min + 1 < p._sampling_max:
-                    self.escalations += 1
-                    pair = p.plan_escalate(t0)
-                else:
-                    pair = p.plan_finish(best, t0)
-                sel, _ = a.finish_step(pair, global_timestep)
-                out[a.id] = sel
+            def consume(defer, a, inp, j, eng=eng, results=results, packages=packages, passes=passes, rpasses=rpasses):
+                return a.planner.plan_consume(inp, results[j], eng, j, package=packages[j],
+                                              **({"prediction_pass": passes[j]} if passes[j] is not None else {}),
+                                              **({"responsibility_pass": rpasses[j]} if rpasses[j] is not None else {}),
+                                              **({"defer_risk": True} if defer else {}))
+
+            self._conclude(eng, [(a, j, lambda defer, a=a, inp=inp, j=j, consume=consume: consume(defer, a, inp, j))
+                                 for j, (a, inp) in enumerate(planning)], t0, global_timestep, out)
         if launched:
             self.last_batch_ms = (time.time() - t0) * 1e3
         for a, _ in passive:
@@ -290,24 +333,20 @@ class AgentBatchHip:
         rpasses = self._responsibility_passes(self.engine, [a.planner if self.parts[k][1] == 1 and results[j] is not None else None
                                                             for j, (a, _, k) in enumerate(planning)], [inp for _, inp, _ in planning])
 
-        def conclude(a, inp, res, j, packages=packages, passes=passes, rpasses=rpasses):
-            p = a.planner
-            best = (p.plan_consume(inp, res, self.engine, j, package=packages[j] if packages is not None else False,
-                                   **({"prediction_pass": passes[j]} if passes is not None and passes[j] is not None else {}),
-                                   **({"responsibility_pass": rpasses[j]} if rpasses is not None and rpasses[j] is not None else {}))
+        def consume(defer, a, inp, res, j, packages=packages, passes=passes, rpasses=rpasses):
+            return (a.planner.plan_consume(inp, res, self.engine, j, package=packages[j] if packages is not None else False,
+                                           **({"prediction_pass": passes[j]} if passes is not None and passes[j] is not None else {}),
+                                           **({"responsibility_pass": rpasses[j]} if rpasses is not None and rpasses[j] is not None else {}),
+                                           **({"defer_risk": True} if defer else {}))
                     if res is not None else None)
-            if best is None and p._sampling_min + 1 < p._sampling_max:
-                self.escalations += 1
-                pair = p.plan_escalate(t0)   # the whole next level on the planner's own engine (identical on every replica)
-            else:
-                pair = p.plan_finish(best, t0)
-            sel, _ = a.finish_step(pair, global_timestep)
-            out[a.id] = sel
+
+        def conclude(a, inp, res, j, *tables):   # one agent on the per-agent path (a split agent's part and its winner)
+            self._conclude(self.engine, [(a, j, lambda defer: consume(defer, a, inp, res, j, *tables))], t0, global_timestep, out,
+                           batch_risk=False)
 
         split = [(j, a, inp, k) for j, (a, inp, k) in enumerate(planning) if self.parts[k][1] > 1]
-        for j, (a, inp, k) in enumerate(planning):
-            if self.parts[k][1] == 1:
-                conclude(a, inp, results[j], j)
+        self._conclude(self.engine, [(a, j, lambda defer, a=a, inp=inp, j=j: consume(defer, a, inp, results[j], j))
+                                     for j, (a, inp, k) in enumerate(planning) if self.parts[k][1] == 1], t0, global_timestep, out)
         if self.winner_exchange is not None:
             # the parts of a split agent meet: ONE all-gather of (slot, cost, global index) per rank item, every rank takes
             # the same lexicographic minimum; then every replica evaluates the one winning candidate (the same launch on
@@ -348,8 +387,8 @@ class MultiAgentSimulation:
                  number_of_agents: int = -1, sampling_level: Optional[int] = None, device: int = 0, group=None,
                  use_road_boundary: bool = False, max_candidates: Optional[int] = None, engine_factory=None,
                  pipeline_groups: Optional[int] = None, freeze_gc: bool = False, batched_passes: Optional[bool] = None,
-                 batched_responsibility: Optional[bool] = None):
-        """batched_passes, batched_responsibility: see AgentBatchHip.
+                 batched_responsibility: Optional[bool] = None, batched_risk: Optional[bool] = None):
+        """batched_passes, batched_responsibility, batched_risk: see AgentBatchHip.
         engine_factory: callable returning an engine object (tests inject a stand-in); default = FrenetEngine.
         pipeline_groups: see AgentBatchHip (None = automatic; with an engine_factory: that many injected engines, default one).
         freeze_gc: take what exists once the simulation is set up out of the garbage collector's generations (gc.freeze(): a
@@ -389,7 +428,7 @@ class MultiAgentSimulation:
                                             else engine_factory()) if engine_factory else None),
                                    parts=[(part, n_parts) for _, part, n_parts in my_items], slots=self.my_slots,
                                    winner_exchange=self._exchange_winners if self.split else None, batched_passes=batched_passes,
-                                   batched_responsibility=batched_responsibility)
+                                   batched_responsibility=batched_responsibility, batched_risk=batched_risk)
         self.S = self.batch.agents[0].planner.N + 1 if mine else int(self.config.planning_horizon / self.config.dt) + 1
         self.time_step = 0
         # planned trajectories of ALL agents, identical on every rank after the exchange: [agents][S][FIELDS]

@@ -137,6 +137,11 @@ class ReactivePlannerHip:
         self.fallback_selector: Optional[Callable] = None   # last-level selection among colliding candidates (set_fallback_selector)
         self._risk_model = None             # set_risk_model: (risk.json, harm_parameters.json, obstacle types, ego mass)
         self._risk_cost_weights = None      # set_risk_cost_weights: (weights, responsibility mode)
+        # a batch of planners evaluates the risk of all of them in one call (risk_request / hand_risk_result)
+        self._risk_defer = False            # plan_consume(defer_risk=True): the "min_risk" fallback waits for the batch's call
+        self._risk_pending = None           # the step whose "min_risk" fallback waits
+        self._risk_handed = None            # (step, ids or None, (ego_risk, obst_risk, min_risk_index)) handed in for that step
+        self._stopping_choice = None        # (step, the stopping selection over it): chosen once per step
         self.reach_set = None               # set_reach_set
         self.occlusion_module = None       # planner.py:99 (set_occlusion_module)
         self.use_occ_model = False
@@ -395,9 +400,65 @@ class ReactivePlannerHip:
         """(ego_risk, obst_risk, min_risk_index) of the step's candidates `ids` on the device under the risk model"""
         if self._risk_model is None:
             raise ValueError("no risk model: call set_risk_model first")
+        handed = self._handed_risk(step, ids)
+        if handed is not None:
+            return handed
         self._set_risk_obstacles(step)
         step.materialise(ids)   # (a step without a bundle: the risk pass reads the listed candidates' rows from its sparse set)
         return step.engine.risk(self._risk_model["params"], np.asarray(ids, np.int64), step.agent)
+
+    # -- the same evaluations for a batch of planners in ONE call (multiagent.AgentBatchHip, DESIGN.md section 20) --
+    def _handed_risk(self, step, ids):
+        """the result handed in for exactly this evaluation of `step` (hand_risk_result), or None.  ids None: the whole-candidate
+        form"""
+        h = self._risk_handed
+        if h is None or h[0] is not step or (h[1] is None) != (ids is None):
+            return None
+        return h[2] if ids is None or np.array_equal(h[1], np.asarray(ids, np.int64)) else None
+
+    def _risk_batchable(self, step) -> bool:
+        """a batched call can stand for this planner's risk evaluations of `step`: the step stored everything they read"""
+        return (self._risk_model is not None and self.config.sparse_bundle_k == 0 and step is not None
+                and bool(step.inputs.write_bundle and step.inputs.write_costmap))
+
+    def risk_request(self, optimal_trajectory):
+        """After plan_consume(defer_risk=True) returned `optimal_trajectory`: the ONE risk evaluation of the step that
+        plan_finish(optimal_trajectory, ...) will make, as (FxRiskParams, ids) for engine.risk_batch -- ids None is the
+        whole-candidate form, which selects exactly _fallback_ids (the "min_risk" fallback of a single-level planner,
+        emergency_mode "min_risk"), a one-id list is the winner (log_risk) -- or None when it makes none, or one a batch cannot
+        stand for.  The obstacle tables of the current predictions are set on the step's engine (host work only).  The branches
+        are plan_finish's, in its order: standstill, stopping selection, min-risk selection, log_risk."""
+        step = self.last_step
+        if not self._risk_batchable(step):
+            return None
+        ids = False
+        opt = optimal_trajectory
+        if opt is None and self._risk_pending is step:
+            ids = None
+        else:
+            if opt is None and self.x_0.velocity <= 0.1:
+                return None   # (the standstill sample is no candidate of the step)
+            if opt is None and self.config.emergency_mode == "stopping" and self.config.emergency_selection:
+                opt = self._select_stopping(step)
+            if opt is None and self.config.emergency_mode == "min_risk" and self.config.emergency_selection:
+                ids = None
+            elif opt is not None and self.config.log_risk and getattr(opt, "_step", None) is step and opt._ego_risk is None:
+                ids = np.array([opt.uniqueId], np.int64)
+        if ids is False or (ids is None and len(self._fallback_ids(step)) == 0):
+            return None
+        self._set_risk_obstacles(step)
+        return self._risk_model["params"], ids
+
+    def hand_risk_result(self, ids, result):
+        """The (ego_risk, obst_risk, min_risk_index) of the evaluation risk_request asked for (its ids), made elsewhere: plan_finish
+        takes it where it would have called engine.risk"""
+        self._risk_handed = (self.last_step, ids, result)
+
+    def _select_stopping(self, step):
+        """_select_stopping_trajectory of `step`, chosen once (risk_request looks at what plan_finish will select)"""
+        if self._stopping_choice is None or self._stopping_choice[0] is not step:
+            self._stopping_choice = (step, self._select_stopping_trajectory(step, self.x_cl[1][0]))
+        return self._stopping_choice[1]
 
     def set_reach_set(self, reach_set):
         """planner.py:219: the reachable-set module whose `reach_sets[x_0.time_step]` (obstacle id -> list of {time_t: polygon})
@@ -469,7 +530,11 @@ class ReactivePlannerHip:
         ids = self._fallback_ids(step)
         if len(ids) == 0:
             return None
-        ego, obst, g = self._eval_risk(step, ids)
+        handed = self._handed_risk(step, None)
+        if handed is not None:   # (the whole-candidate form selects exactly `ids`: rows by candidate index, the same arg-min)
+            ego, obst, g = handed[0][ids], handed[1][ids], handed[2]
+        else:
+            ego, obst, g = self._eval_risk(step, ids)
         if g < 0:
             return None
         chosen = step.sample(int(g))
@@ -688,17 +753,23 @@ class ReactivePlannerHip:
         return self._inputs_for_level(self._sampling_min, stop_point_s)
 
     def plan_consume(self, inputs: PlanInputs, res: dict, engine, agent: int = 0, package=False, prediction_pass=None,
-                     responsibility_pass=None):
+                     responsibility_pass=None, defer_risk: bool = False):
         """Take this planner's share of a batched launch (first sampling level); returns the chosen trajectory
         (materialised -- the batch engine's buffers are reused) or None when the level has to escalate.
         package: the winner as the batched call already packaged it (engine.plan_batch_packaged; None = nothing found);
         False: read it here.  prediction_pass: this agent's dict of an engine.prediction_probability_batch call over this launch
         (batched_prediction_pass planners only); None: the planner runs its own pass.  responsibility_pass: the same for an
-        engine.responsibility_cost_batch call behind this planner's prepare_responsibility_cost."""
+        engine.responsibility_cost_batch call behind this planner's prepare_responsibility_cost.  defer_risk: the caller makes
+        the planners' risk evaluations in one call -- a "min_risk" fallback of this level then returns None here and waits:
+        risk_request says what to evaluate, hand_risk_result takes the result, plan_finish selects."""
         if package is False:
             package = engine.package(agent, self.x_0.yaw_rate) if getattr(engine, "packaging", False) and inputs.write_bundle else None
-        best = self._consume_result(inputs, res, engine, agent, package, self._sampling_min, prediction_pass=prediction_pass,
-                                    responsibility_pass=responsibility_pass)
+        self._risk_defer = bool(defer_risk)
+        try:
+            best = self._consume_result(inputs, res, engine, agent, package, self._sampling_min, prediction_pass=prediction_pass,
+                                        responsibility_pass=responsibility_pass)
+        finally:
+            self._risk_defer = False
         if best is not None:
             best.materialise()
         return best
@@ -716,6 +787,13 @@ class ReactivePlannerHip:
     def plan_finish(self, optimal_trajectory, t0: float):
         """reactive_planner.py:99-130: packaging, standstill fallback, logging hook."""
         self.planning_time = time.time() - t0
+        if optimal_trajectory is None and self._risk_pending is not None and self._risk_pending is self.last_step:
+            # the "min_risk" fallback that plan_consume(defer_risk=True) left waiting: what _fallback would have returned there
+            optimal_trajectory = self._min_risk_sample(self.last_step)
+            if optimal_trajectory is not None:
+                self.msg_logger.warning("No optimal trajectory available. Select lowest risk trajectory!")
+                optimal_trajectory.materialise()
+        self._risk_pending = None
 
         self.trajectory_pair = self._compute_trajectory_pair(optimal_trajectory) if optimal_trajectory is not None else None
         if self.trajectory_pair is not None:
@@ -727,7 +805,7 @@ class ReactivePlannerHip:
         # (reactive_planner_cpp.py:404-413; the "risk" mode needs the harm model and stays outside)
         if optimal_trajectory is None and self.config.emergency_mode == "stopping" and self.config.emergency_selection \
                 and self.last_step is not None:
-            optimal_trajectory = self._select_stopping_trajectory(self.last_step, self.x_cl[1][0])
+            optimal_trajectory = self._select_stopping(self.last_step)
             if optimal_trajectory is not None:
                 self.msg_logger.warning("No optimal trajectory available. Select stopping trajectory!")
                 self.trajectory_pair = self._compute_trajectory_pair(optimal_trajectory)
@@ -808,6 +886,9 @@ class ReactivePlannerHip:
         if len(ids) == 0:
             return None
         if isinstance(self.fallback_selector, str) and self.fallback_selector == "min_risk":
+            if self._risk_defer and self._risk_batchable(step):
+                self._risk_pending = step   # (the batch evaluates it with the other planners' -- risk_request; plan_finish selects)
+                return None
             chosen = self._min_risk_sample(step)    # the device's risk pass and arg-min (set_risk_model)
         elif isinstance(self.fallback_selector, str) and self.fallback_selector == "min_risk_cost":
             chosen = self._min_risk_cost_sample(step)
@@ -821,6 +902,7 @@ class ReactivePlannerHip:
                         responsibility_pass=None):
         if self.last_step is not None:
             self.last_step.invalidate()
+        self._risk_pending = self._risk_handed = self._stopping_choice = None   # (they belong to the step before)
         step = PlanStepResult(engine, inputs, res, agent)
         step.retain = self.config.retain_samples
         step.package = package

@@ -819,6 +819,31 @@ int32_t fx_eval_responsibility_cost_batch(FxContext *ctx, int32_t n_agents, cons
                                           const FxRiskParams *params /* [n_agents] */, const FxRespCostParams *resp /* [n_agents] */,
                                           const FxRespCostBatchOutputs *out);
 
+/* ---- The risk of listed candidates for several agents in one call (additive within ABI 15) ----
+ * fx_eval_risk_agent(ctx, agents[i], &params[i], n_ids[i], ids[i], ...) for each listed agent: an agent with a list gets the
+ * n_ids[i] listed candidates in that order, evaluated whatever their flags; an agent without one (ids[i] NULL with n_ids[i] == 0,
+ * or n_ids NULL: no agent has a list) every candidate, NaN rows for those that lack VALID, FEASIBLE or RETURNED.  An agent whose
+ * step stored no bundle takes part with a list inside its sparse set (fx_materialise_candidates_agent), as in the per-agent call.
+ * Every output is bit for bit what the per-agent call returns, whichever agents and forms share a call and in whatever order.  The
+ * detail and cost passes (fx_eval_risk_costs_agent) stay per agent. */
+typedef struct FxRiskBatchOutputs {      /* no pointer may be NULL */
+    double *ego_risk, *obst_risk;        /* [sum of n_a], agent-major; n_a = n_ids[i], or C of the agent without a list */
+    int64_t *min_risk_index;             /* [n_agents], as fx_eval_risk_agent's: a candidate index, ties to the lower candidate
+                                            index whatever the list's order; -1: none */
+} FxRiskBatchOutputs;
+/* agents: as in fx_eval_prediction_prob_batch.  Everything is checked for every listed agent before anything is launched, uploaded,
+ * allocated or written to out, and the message names the first offending agent: FX_ERR_INVALID_ARGUMENT for NULL ctx, params, out
+ * or output pointer, n_agents < 0 or above the uploaded agents, an agent out of range or listed twice, n_ids[i] > 0 with ids[i]
+ * NULL; per agent what fx_eval_risk_agent refuses, with its codes (a step without FX_MODE_WRITE_BUNDLE and an id outside the sparse
+ * set: FX_ERR_NOT_READY).  Unlike the per-agent call, the batch also refuses (FX_ERR_NOT_READY) inputs rewritten since the last
+ * evaluation (fx_update_state): it is made behind a plan step of all its agents.  n_agents == 0 returns FX_OK and touches nothing.
+ * Synchronous; fx_last_risk_ms covers it; its memory is the risk passes' device block (grow-only, counted in fx_device_bytes). */
+int32_t fx_eval_risk_batch(FxContext *ctx, int32_t n_agents, const int32_t *agents /* NULL: 0 .. n_agents-1 */,
+                           const FxRiskParams *params /* [n_agents] */,
+                           const int64_t *n_ids /* [n_agents], or NULL: no agent has a list */,
+                           const int64_t *const *ids /* [n_agents], ids[i] NULL with n_ids[i] == 0: every candidate */,
+                           const FxRiskBatchOutputs *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,7 +148,9 @@ int32_t fx_upload_batch(FxContext *c, int32_t n_agents, const FxProblem *probs) 
             sl.off_hot = ar.off; hot = ar.host_slot<double>((size_t)S * p->K * FX_HOT_STRIDE, &dhot, &ok);
             d.obs_rec = dev; d.obs_pmask = dpm; d.obs_hmask = dhm; d.obs_hot = dhot;
             sl.dyn_end = ar.off;
-            // the raw predictions: read on the device only by the generic kernel's windowed costs, kept for re-packing
+            // the raw predictions: kept for re-packing; read on the device only by the lane parts of a candidate that start behind
+            // the step at which it left the projection domain (finish_candidate: more than one lane per candidate, obstacle stage
+            // inside the walk) -- fx_update_state stages them for such a plan
             sl.off_pos = ar.off; d.obs_pos = ar.put(p->obs_pos, (size_t)2 * p->K * p->P, &ok);
             sl.off_cov = ar.off; d.obs_cov_inv = ar.put(p->obs_cov_inv, (size_t)4 * p->K * p->P, &ok);
             sl.off_npred = ar.off; d.obs_npred = ar.put(p->obs_npred, p->K, &ok);
@@ -456,8 +458,12 @@ int32_t fx_update_state(FxContext *c, int32_t agent, const FxStateUpdate *u) {
                                                 reinterpret_cast<unsigned long long *>(c->h_in + sl.off_pm),
                                                 reinterpret_cast<unsigned long long *>(c->h_in + sl.off_hm),
                                                 reinterpret_cast<double *>(c->h_in + sl.off_hot));
-        // the generic kernel also reads the raw predictions (windowed costs); the grid kernel only the packed tables
-        touch(sl.off_rec, (c->plan.use_grid ? sl.dyn_end : sl.raw_end) - sl.off_rec);
+        // The walk reads the packed tables.  The raw predictions have ONE reader on the device, in the grid and the generic kernel
+        // alike: with more than one lane per candidate and the obstacle stage inside the walk, a lane part that starts behind the
+        // step at which its candidate left the projection domain re-sums its prediction cost from them (fx_eval_kernel.h,
+        // finish_candidate).  They are staged with the tables when the update brought new ones and the plan has that reader.
+        const bool raw_read = new_obs && c->plan.G > 1 && !c->plan.split;
+        touch(sl.off_rec, (raw_read ? sl.raw_end : sl.dyn_end) - sl.off_rec);
     }
     c->probs_dirty = true;
     return FX_OK;

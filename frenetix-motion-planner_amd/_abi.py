@@ -189,6 +189,12 @@ class FxRiskBatchOutputs(C.Structure):   # (fx_eval_risk_batch, DESIGN.md sectio
     _fields_ = [(n, C.c_void_p) for n in ("ego_risk", "obst_risk", "min_risk_index")]
 
 
+class FxRiskCostBatchOutputs(C.Structure):   # (fx_eval_risk_costs_batch)
+    _fields_ = [(n, C.c_void_p) for n in ("ego_risk", "obst_risk", "obst_harm_occ", "ego_risk_max", "obst_risk_max", "ego_harm_max",
+                                          "obst_harm_max", "bayes", "equality", "maximin", "ego", "responsibility", "total",
+                                          "boundary_harm", "min_risk_index", "min_cost_index")]
+
+
 class FxRiskOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ego_risk", "obst_risk", "obst_harm_occ", "ego_risk_max", "obst_risk_max", "ego_harm_max",
                                           "obst_harm_max", "bayes", "equality", "maximin", "ego", "responsibility", "total",

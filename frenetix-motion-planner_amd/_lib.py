@@ -46,7 +46,7 @@ def exported_symbols():
         "fx_sort_candidates_agent", "fx_sort_candidates_batch", "fx_read_ranked_agent", "fx_sort_views", "fx_last_sort_ms",
         "fx_eval_prediction_prob_agent", "fx_last_predprob_ms", "fx_eval_prediction_prob_batch",
         "fx_eval_responsibility_cost_agent", "fx_eval_responsibility_cost_batch",
-        "fx_eval_risk_batch",
+        "fx_eval_risk_batch", "fx_eval_risk_costs_batch",
     ]
 
 
@@ -172,6 +172,10 @@ def lib():
                                                C.POINTER(_abi.FxRespCostBatchOutputs)], C.c_int32),
         "fx_eval_risk_batch": ([vp, C.c_int32, pi32, C.POINTER(_abi.FxRiskParams), pi64, C.POINTER(pi64),
                                 C.POINTER(_abi.FxRiskBatchOutputs)], C.c_int32),
+        "fx_eval_risk_costs_batch": ([vp, C.c_int32, pi32, C.POINTER(_abi.FxRiskParams), C.POINTER(C.POINTER(_abi.FxRiskCostParams)), pi64,
+                                      C.POINTER(pi64), C.POINTER(_abi.FxRiskCostBatchOutputs)], C.c_int32),
+        # (hook of the tests, not part of fxplan.h: the rounds of scratch of the last fx_eval_risk_costs_batch call)
+        "fx_last_risk_costs_batch_rounds": ([vp], C.c_int32),
         # (hook of the tests, not part of fxplan.h: bytes of scratch per round of the batched passes, 0 = FX_ITEM_SCRATCH_BYTES)
         "fx_risk_batch_set_scratch_limit": ([C.c_size_t], None),
         # (hook of the tests, not part of fxplan.h: steps per chunk of the risk items, 0 = automatic)

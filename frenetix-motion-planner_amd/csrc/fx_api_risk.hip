@@ -6,9 +6,11 @@
 // entrance on the same host path: the same checks, records, uploads and block; fx_eval_prediction_prob_batch
 // is that pass for several agents in one call: the same checks and records per agent, one staging buffer each for records and tables;
 // fx_eval_responsibility_cost_batch is the responsibility pass for several agents in one call, and
-// fx_eval_risk_batch the plain risk pass for several agents, each with an id list or none.
+// fx_eval_risk_batch the plain risk pass for several agents, each with an id list or none, and
+// fx_eval_risk_costs_batch the detail and cost passes for several agents, with lists and cost parameters each.
 #include <atomic>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 #include "fx_pass.h"
@@ -30,6 +32,9 @@ extern "C" __attribute__((weak)) hipError_t fx_launch_risk_batch(const RiskBatch
 extern "C" __attribute__((weak)) hipError_t fx_launch_risk_list_batch(const RiskListBatchArgs *t, const RiskBatchRound *rounds, int n_rounds,
                                                                       long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
                                                                       hipStream_t stream);
+extern "C" __attribute__((weak)) hipError_t fx_launch_risk_costs_batch(const RiskCostBatchArgs *t, const RiskBatchRound *rounds, int n_rounds,
+                                                                       long long *out_idx, long long *cost_idx, hipEvent_t ev_start,
+                                                                       hipEvent_t ev_stop, hipStream_t stream);
 extern "C" __attribute__((weak)) int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K);   // (fx_kernels.hip: the rule, or what a test forces)
 
 namespace {
@@ -58,6 +63,7 @@ struct FxRiskState {
     FxEventPair ev;          // around a pass's launches; read at once into the two times below
     float last_ms = 0.f;
     float last_pp_ms = -1.f;   // fx_eval_prediction_prob_agent
+    int32_t last_rounds = -1;  // fx_eval_risk_costs_batch: the rounds of scratch of the last call
 };
 
 void fx_risk_release(FxRiskState *r) { delete r; }
@@ -1133,6 +1139,246 @@ extern "C" int32_t fx_eval_risk_batch(FxContext *c, int32_t n_agents, const int3
     }
     return FX_OK;
 }
+
+// The detail and cost passes -- fx_eval_risk_costs_agent -- of several agents in ONE call, each with its own id list or none and
+// its own cost parameters or none (fxplan.h).  Per agent the checks of the per-agent entry (risk_check with
+// the detail flag, risk_cost_check) and its records; then everything the kernels read -- FxRiskParams, records, obstacle tables, id
+// lists (or sparse positions), boundary-harm arrays, responsibility vectors, reach-set tables, rows, compact arrays and the cost
+// kernel's argument blocks (risk_cost_fill) -- in ONE staging buffer and one copy; the rounds of fx_item_rounds over one scratch
+// with each row's steps per chunk chosen from its agent's OWN list length.  The columns and the principles lie per agent as the
+// per-agent kernels' functions index them ([4][K][n] and [7][n]); the caller's are concatenated per column, so a last launch lays
+// the column blocks out that way on the device, and the small principle block is laid out on the host.  Runtime calls of a call
+// with R rounds: 1 drain (a synchronisation), 1 ensure of the block, 1 copy up, 2 event records, 2 R + 4 launches (2 R + 1 where no
+// agent has cost parameters and no column is asked for), at most 9 copies down (ego_risk, obst_risk, obst_harm_occ, the four
+// columns, the principle block, the two arg-mins), 1 synchronisation -- none of them per agent.
+extern "C" int32_t fx_eval_risk_costs_batch(FxContext *c, int32_t n_agents, const int32_t *agents, const FxRiskParams *params,
+                                            const FxRiskCostParams *const *cost, const int64_t *n_ids, const int64_t *const *ids,
+                                            const FxRiskCostBatchOutputs *out) {
+    if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
+    if (!params || !out) return set_err(FX_ERR_INVALID_ARGUMENT, "params or out is NULL");
+    if (n_agents < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d", n_agents);
+    if (n_agents == 0) return FX_OK;
+    if (!fx_launch_risk_costs_batch) return set_err(FX_ERR_HIP, "built without the batched risk-cost launcher");
+    const int32_t agent0 = agents ? agents[0] : 0;
+    if (!c->evaluated) return set_err(FX_ERR_NOT_READY, "agent %d: no evaluated plan step", agent0);
+    if (n_agents > c->n_agents) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d of %d uploaded agents", n_agents, c->n_agents);
+    // (the batch is made behind a plan step of all its agents: inputs rewritten since belong to a step that has not run)
+    if (!fx_inputs_current(c))
+        return set_err(FX_ERR_NOT_READY, "agent %d: the inputs were rewritten since the last evaluation (fx_update_state): evaluate first", agent0);
+    const size_t A = (size_t)n_agents;
+    std::vector<RiskPass> q(A);
+    std::vector<char> listed((size_t)c->n_agents, 0);
+    for (size_t i = 0; i < A; i++) {
+        const int32_t agent = agents ? agents[i] : (int32_t)i;
+        if (agent >= 0 && agent < c->n_agents && listed[agent]) return set_err(FX_ERR_INVALID_ARGUMENT, "agent %d listed twice", agent);
+        const int64_t n_i = n_ids ? n_ids[i] : 0;
+        const int64_t *ids_i = (n_ids && ids) ? ids[i] : nullptr;
+        int rc = risk_check(q[i], c, agent, params + i, n_i, ids_i, true, true);
+        if (!rc && cost && cost[i]) rc = risk_cost_check(q[i], cost[i]);
+        if (rc) {
+            char why[sizeof(g_err)];
+            snprintf(why, sizeof(why), "%s", g_err);
+            return set_err(rc, "agent %d: %s", agent, why);
+        }
+        listed[agent] = 1;
+    }
+    // ONE staging buffer, every part 16-byte aligned; the device's copy lies at o_stage of the block
+    std::vector<char> stage;
+    auto room = [&](size_t bytes) { const size_t o = stage.size(); stage.resize(o + align_up(std::max<size_t>(bytes, 8), 16), 0); return o; };
+    auto put = [&](const void *src, size_t bytes) { const size_t o = room(bytes); if (bytes) memcpy(stage.data() + o, src, bytes); return o; };
+    struct Parts { size_t prm, rec, obs, pos, yaw, v, ids, bh, resp, eobs, eoff, pst, voff, vert, out_at, col_at, cout_at; int ci; bool items; };
+    std::vector<Parts> at(A);
+    std::vector<FxItemAgent> ia(A);
+    std::vector<int32_t> cs(A), chunks(A), blk0;
+    std::vector<double> rec;
+    size_t rows_out = 0, col_doubles = 0, rows_cost = 0;
+    int64_t blocks = 0;
+    for (size_t i = 0; i < A; i++) {
+        RiskPass &p = q[i];
+        const FxRiskAgent &a = *p.a;
+        const FxRiskCostParams *cp = cost ? cost[i] : nullptr;
+        Parts &t = at[i];
+        t = Parts{};
+        t.out_at = rows_out, t.col_at = col_doubles, t.cout_at = rows_cost, t.ci = -1;
+        rows_out += (size_t)p.n;
+        col_doubles += 4 * (size_t)p.K * (size_t)p.n;
+        t.prm = put(p.prm, sizeof(FxRiskParams));
+        if (p.K > 0) {
+            build_records(a, p.S, p.maha, rec);
+            t.rec = put(rec.data(), sizeof(double) * rec.size()), t.obs = put(a.obs.data(), sizeof(double) * a.obs.size());
+            t.pos = put(a.pos.data(), sizeof(double) * a.pos.size()), t.yaw = put(a.yaw.data(), sizeof(double) * a.yaw.size());
+            t.v = put(a.v.data(), sizeof(double) * a.v.size());
+        }
+        if (p.ids) t.ids = put(p.sparse ? p.pos.data() : p.ids, sizeof(int64_t) * (size_t)p.n);
+        if (cp) {   // (what risk_stage and risk_cost_args take and upload for a cost pass)
+            t.ci = (int)blk0.size();
+            blk0.push_back((int32_t)blocks);
+            blocks += (p.n + 255) / 256;
+            rows_cost += (size_t)p.n;
+            if (cp->boundary_mode == FX_RISK_BOUNDARY_ARRAY) t.bh = put(cp->boundary_harm, sizeof(double) * (size_t)p.n);
+            if (cp->responsibility_mode == FX_RISK_RESP_ACTION_SPACE && p.K > 0) t.resp = put(cp->responsibility, sizeof(double) * p.K);
+            if (cp->responsibility_mode == FX_RISK_RESP_REACH_SET) {
+                p.nE = a.rs_obs.size(), p.nP = a.rs_step.size(), p.nV = a.rs_verts.size() / 2;
+                t.eobs = put(a.rs_obs.data(), sizeof(int32_t) * p.nE), t.eoff = put(a.rs_off.data(), sizeof(int32_t) * a.rs_off.size());
+                t.pst = put(a.rs_step.data(), sizeof(int32_t) * p.nP), t.voff = put(a.rs_voff.data(), sizeof(int32_t) * a.rs_voff.size());
+                t.vert = put(a.rs_verts.data(), sizeof(double) * a.rs_verts.size());
+            }
+        }
+        // steps per chunk from the agent's OWN list length: what fx_eval_risk_costs_agent chooses for it
+        t.items = p.K > 0 && p.S > 1;
+        cs[i] = fx_risk_items_chunk_steps(p.n, p.S, p.K);
+        chunks[i] = (std::max(p.S - 1, 1) + cs[i] - 1) / cs[i];
+        ia[i] = FxItemAgent{p.n, t.items ? sizeof(double) * 7 * (size_t)p.K * (size_t)chunks[i] : 0};
+    }
+    const size_t NC = blk0.size();
+    if (blocks > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "%lld workgroups of candidates", (long long)blocks);
+    // the caller's columns are concatenated per column: where one is asked for, a last launch lays the agents' [4][K][n] blocks out
+    // that way on the device (RiskCopySeg: one plane of one agent, 1 024 doubles per workgroup), and each column comes down in one copy
+    double *const cols[4] = {out->ego_risk_max, out->obst_risk_max, out->ego_harm_max, out->obst_harm_max};
+    const bool any_col = (cols[0] || cols[1] || cols[2] || cols[3]) && col_doubles > 0;
+    const size_t NS = any_col ? 4 * A : 0, T = col_doubles / 4;
+    std::vector<int32_t> seg_blk0(NS);
+    int64_t seg_blocks = 0;
+    for (size_t k = 0; k < NS; k++) {
+        seg_blk0[k] = (int32_t)seg_blocks;
+        seg_blocks += ((int64_t)q[k / 4].K * q[k / 4].n + 1023) / 1024;
+        if (seg_blocks > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "%lld workgroups of column values", (long long)seg_blocks);
+    }
+    const unsigned long long forced = fx_risk_batch_scratch_forced.load(std::memory_order_relaxed);
+    const std::vector<FxItemSegment> segs = fx_item_rounds(ia.data(), n_agents, forced ? (size_t)forced : FX_ITEM_SCRATCH_BYTES);
+    const size_t R = segs.size();
+    const int n_rounds = R ? segs.back().round + 1 : 0;
+    std::vector<RiskBatchRound> rounds((size_t)n_rounds, RiskBatchRound{0, 0, 0, 0});
+    std::vector<RiskBatchRow> rows(R);
+    std::vector<int32_t> agent_row(A, -1);
+    const size_t t_rows = room(sizeof(RiskBatchRow) * R), t_item0 = room(sizeof(int64_t) * R), t_fin0 = room(sizeof(int32_t) * R),
+                 t_arow = room(sizeof(int32_t) * A), t_cost = room(sizeof(RiskCostArgs) * NC), t_blk0 = put(blk0.data(), sizeof(int32_t) * NC),
+                 t_seg = room(sizeof(RiskCopySeg) * NS), t_sblk = put(seg_blk0.data(), sizeof(int32_t) * NS);
+    size_t scratch = 0;
+    for (size_t k = 0; k < R; k++) {   // the rows' counts (their pointers follow when the block is there)
+        const FxItemSegment &g = segs[k];
+        const size_t tiles = (size_t)(g.count + 63) / 64;
+        RiskBatchRound &rd = rounds[g.round];
+        RiskBatchRow &w = rows[k];
+        w = RiskBatchRow{};
+        if (rd.n_rows == 0) rd.row0 = (int32_t)k;
+        rd.n_rows++;
+        w.first = g.first, w.count = g.count;
+        w.it.nb = (int64_t)tiles * 64, w.it.cs = cs[g.agent], w.it.chunks = chunks[g.agent];
+        w.it.need = FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED;
+        w.items = at[g.agent].items ? 1 : 0;
+        w.item0 = rd.items;
+        w.fin0 = rd.fin_blocks;
+        if (w.items) rd.items += (int64_t)tiles * chunks[g.agent] * (int64_t)q[g.agent].K;
+        const int64_t fin = (int64_t)rd.fin_blocks + (g.count + 255) / 256;
+        if (fin > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld workgroups of candidates", (long long)fin);
+        rd.fin_blocks = (int32_t)fin;
+        scratch = std::max(scratch, g.scratch_off + tiles * 64 * ia[g.agent].per_candidate_bytes);
+        agent_row[g.agent] = (int32_t)k;
+    }
+    for (const RiskBatchRound &rd : rounds)
+        if (rd.items > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld items", (long long)rd.items);
+    FxBlockLayout lay;
+    const size_t o_stage = lay.take(stage.size()), o_part = lay.take(scratch), o_col = lay.take(sizeof(double) * col_doubles);
+    const size_t o_cat = lay.take(any_col ? sizeof(double) * col_doubles : 0);
+    const size_t o_ego = lay.take(sizeof(double) * rows_out), o_obst = lay.take(sizeof(double) * rows_out), o_occ = lay.take(sizeof(double) * rows_out);
+    const size_t o_out = lay.take(sizeof(double) * 7 * rows_cost), o_idx = lay.take(sizeof(long long) * (A + NC));
+    FxRiskState *r = q[0].r;
+    HIP_TRY(hipSetDevice(c->device));
+    FX_TRY(fx_drain(c));
+    FX_TRY(r->block.ensure(lay.size()));
+    FX_TRY(r->ev.ensure());
+    char *base = r->block;
+    auto D = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
+    const size_t s0 = o_stage;
+    for (size_t i = 0; i < A; i++) {   // the cost kernel's argument blocks, from where the agent's parts lie
+        const Parts &t = at[i];
+        if (t.ci < 0) continue;
+        RiskPass &p = q[i];
+        p.base = base;
+        p.o_col = o_col + sizeof(double) * t.col_at, p.o_out = o_out + sizeof(double) * 7 * t.cout_at;
+        p.o_ids = s0 + t.ids, p.o_bh = s0 + t.bh, p.o_resp = s0 + t.resp;
+        p.o_eobs = s0 + t.eobs, p.o_eoff = s0 + t.eoff, p.o_pst = s0 + t.pst, p.o_voff = s0 + t.voff, p.o_vert = s0 + t.vert;
+        RiskCostArgs ca{};
+        risk_cost_fill(p, cost[i], ca);
+        memcpy(stage.data() + t_cost + sizeof(RiskCostArgs) * (size_t)t.ci, &ca, sizeof(ca));
+    }
+    for (size_t k = 0; k < R; k++) {
+        const FxItemSegment &g = segs[k];
+        const RiskPass &p = q[g.agent];
+        const Parts &t = at[g.agent];
+        RiskBatchRow &w = rows[k];
+        w.w = RiskWalkArgs{p.planes, p.ld, p.S, p.n, p.ids ? reinterpret_cast<const int64_t *>(base + s0 + t.ids) : nullptr, p.flags,
+                           D(s0 + t.rec), D(s0 + t.obs), D(s0 + t.pos), D(s0 + t.yaw), D(s0 + t.v), p.K, p.P};
+        w.it.params = reinterpret_cast<const FxRiskParams *>(base + s0 + t.prm);
+        w.it.part = reinterpret_cast<double *>(base + o_part + g.scratch_off);
+        w.ego = D(o_ego) + t.out_at, w.obst = D(o_obst) + t.out_at, w.occ = D(o_occ) + t.out_at;
+        w.col = D(o_col) + t.col_at;
+        memcpy(stage.data() + t_item0 + sizeof(int64_t) * k, &w.item0, sizeof(int64_t));
+        memcpy(stage.data() + t_fin0 + sizeof(int32_t) * k, &w.fin0, sizeof(int32_t));
+    }
+    if (R) memcpy(stage.data() + t_rows, rows.data(), sizeof(RiskBatchRow) * R);
+    memcpy(stage.data() + t_arow, agent_row.data(), sizeof(int32_t) * A);
+    for (size_t k = 0; k < NS; k++) {   // plane k % 4 of agent k / 4: from its block to its place in that column of the call
+        const Parts &pt = at[k / 4];
+        const size_t Kn = (size_t)q[k / 4].K * (size_t)q[k / 4].n;
+        const RiskCopySeg g{D(o_col) + pt.col_at + (k % 4) * Kn, D(o_cat) + (k % 4) * T + pt.col_at / 4, (int64_t)Kn};
+        memcpy(stage.data() + t_seg + sizeof(RiskCopySeg) * k, &g, sizeof(g));
+    }
+    HIP_TRY(hipMemcpyAsync(base + o_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, c->stream));
+    RiskCostBatchArgs t{};
+    t.rows = reinterpret_cast<const RiskBatchRow *>(base + o_stage + t_rows);
+    t.item0 = reinterpret_cast<const int64_t *>(base + o_stage + t_item0);
+    t.fin0 = reinterpret_cast<const int32_t *>(base + o_stage + t_fin0);
+    t.agent_row = reinterpret_cast<const int32_t *>(base + o_stage + t_arow);
+    t.cost = reinterpret_cast<const RiskCostArgs *>(base + o_stage + t_cost);
+    t.blk0 = reinterpret_cast<const int32_t *>(base + o_stage + t_blk0);
+    t.n_agents = n_agents, t.n_cost = (int32_t)NC, t.blocks = (int32_t)blocks;
+    t.seg = reinterpret_cast<const RiskCopySeg *>(base + o_stage + t_seg);
+    t.seg_blk0 = reinterpret_cast<const int32_t *>(base + o_stage + t_sblk);
+    t.n_seg = (int32_t)NS, t.seg_blocks = (int32_t)seg_blocks;
+    long long *d_idx = reinterpret_cast<long long *>(base + o_idx);
+    HIP_TRY(fx_launch_risk_costs_batch(&t, rounds.data(), n_rounds, d_idx, d_idx + A, r->ev.e0, r->ev.e1, c->stream));
+    auto down = [&](double *dst, size_t o, size_t count) {
+        return (dst && count) ? hipMemcpyAsync(dst, base + o, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIP_TRY(down(out->ego_risk, o_ego, rows_out));
+    HIP_TRY(down(out->obst_risk, o_obst, rows_out));
+    HIP_TRY(down(out->obst_harm_occ, o_occ, rows_out));
+    if (any_col)
+        for (int k = 0; k < 4; k++) HIP_TRY(down(cols[k], o_cat + sizeof(double) * k * T, T));
+    // the principles: an agent without cost parameters has rows in the caller's arrays that stay unwritten, so the (small) block
+    // [7][n] per agent comes down into memory of the call and is laid out from there (uninitialised: every double read below has
+    // been written by a kernel and copied)
+    double *const pr[7] = {out->bayes, out->equality, out->maximin, out->ego, out->responsibility, out->total, out->boundary_harm};
+    bool any_pr = false;
+    for (double *x : pr) any_pr = any_pr || x;
+    const size_t n_out = any_pr ? 7 * rows_cost : 0;
+    const std::unique_ptr<double[]> h_out(n_out ? new double[n_out] : nullptr);
+    HIP_TRY(down(h_out.get(), o_out, n_out));
+    std::vector<long long> idx(A + NC, -1);
+    HIP_TRY(hipMemcpyAsync(idx.data(), d_idx, sizeof(long long) * (A + NC), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&r->last_ms, r->ev.e0, r->ev.e1));
+    r->last_rounds = n_rounds;
+    for (size_t i = 0; i < A; i++) {
+        const Parts &pt = at[i];
+        const size_t nn = (size_t)q[i].n;
+        if (pt.ci >= 0 && h_out)
+            for (int k = 0; k < 7; k++)
+                if (pr[k] && nn) memcpy(pr[k] + pt.out_at, h_out.get() + 7 * pt.cout_at + k * nn, sizeof(double) * nn);
+        // (sparse set: the arg-mins ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
+        long long ri = idx[i], ci = pt.ci >= 0 ? idx[A + (size_t)pt.ci] : -1;
+        if (q[i].sparse && ri >= 0) ri = (long long)q[i].set.ids[ri];
+        if (q[i].sparse && ci >= 0) ci = (long long)q[i].set.ids[ci];
+        if (out->min_risk_index) out->min_risk_index[i] = (int64_t)ri;
+        if (out->min_cost_index) out->min_cost_index[i] = (int64_t)ci;
+    }
+    return FX_OK;
+}
+
+// (hook of the tests, not part of fxplan.h: the rounds of scratch the last fx_eval_risk_costs_batch call took; -1 before the first)
+extern "C" int32_t fx_last_risk_costs_batch_rounds(FxContext *c) { return (c && c->risk) ? c->risk->last_rounds : -1; }
 
 extern "C" double fx_last_predprob_ms(FxContext *c) { return (c && c->risk) ? (double)c->risk->last_pp_ms : -1.0; }
 

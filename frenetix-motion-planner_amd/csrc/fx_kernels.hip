@@ -489,6 +489,42 @@ extern "C" hipError_t fx_launch_risk_list_batch(const RiskListBatchArgs *t, cons
     return hipSuccess;
 }
 
+// the detail and cost passes over several agents in one call, each with an id list or none and with cost parameters or none
+// (fx_risk_kernel.h): per round ONE item launch over the flat items of all its rows and ONE finish launch
+// (fx_risk_batch_finish_kernel, which serves as it stands), then the risk arg-min with a workgroup per agent
+// (fx_risk_list_batch_argmin_kernel, as it stands) and, where an agent has cost parameters, the cost kernel and the cost arg-min
+// once each over those agents, and, where the caller asked for a per-obstacle column, one launch that lays the agents' column blocks
+// into the call's concatenated columns -- 2 R + 4 launches at most.  out_idx [n_agents] the risk arg-min,
+// cost_idx [n_cost] the cost arg-min.  t: the device tables; rounds: the host's account of them (fx_api_risk.hip builds both).
+// ev_start / ev_stop bracket all launches.
+extern "C" hipError_t fx_launch_risk_costs_batch(const RiskCostBatchArgs *t, const RiskBatchRound *rounds, int n_rounds, long long *out_idx,
+                                                 long long *cost_idx, hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream) {
+    hipError_t e;
+    if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
+    for (int r = 0; r < n_rounds; r++) {
+        const RiskBatchRound &q = rounds[r];
+        if (q.items > 0)
+            hipLaunchKernelGGL(fxrisk::fx_risk_costs_batch_item_kernel, dim3((unsigned)q.items), dim3(64), 0, stream, t->rows + q.row0,
+                               t->item0 + q.row0, q.n_rows);
+        hipLaunchKernelGGL(fxrisk::fx_risk_batch_finish_kernel, dim3((unsigned)q.fin_blocks), dim3(256), 0, stream, t->rows + q.row0,
+                           t->fin0 + q.row0, q.n_rows);
+    }
+    hipLaunchKernelGGL(fxrisk::fx_risk_list_batch_argmin_kernel, dim3((unsigned)t->n_agents), dim3(1024), 0, stream, t->rows, t->agent_row,
+                       out_idx);
+    if (t->n_cost > 0) {
+        if (t->blocks > 0)
+            hipLaunchKernelGGL(fxrisk::fx_risk_costs_batch_cost_kernel, dim3((unsigned)t->blocks), dim3(256), 0, stream, t->cost, t->blk0,
+                               t->n_cost);
+        hipLaunchKernelGGL(fxrisk::fx_risk_costs_batch_argmin_kernel, dim3((unsigned)t->n_cost), dim3(1024), 0, stream, t->cost, cost_idx);
+    }
+    if (t->seg_blocks > 0)
+        hipLaunchKernelGGL(fxrisk::fx_risk_costs_batch_gather_kernel, dim3((unsigned)t->seg_blocks), dim3(256), 0, stream, t->seg, t->seg_blk0,
+                           t->n_seg);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
 // batched candidate read-back (fx_gather_kernel.h): one workgroup per listed candidate
 extern "C" hipError_t fx_launch_gather_candidates(const GatherArgs *args, const int64_t *d_ids, int64_t n, unsigned long long *d_out,
                                                   hipStream_t stream) {

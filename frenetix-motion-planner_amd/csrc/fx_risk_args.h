@@ -1,7 +1,7 @@
 // fx_risk_args.h -- what the host code of the trajectory risk (fx_api_risk.hip), its launcher (fx_kernels.hip) and its kernels
 // (fx_risk_kernel.h) share: the layout of the records the host builds and the kernels read, the arguments of the candidate walk
 // and the argument blocks of the risk-cost kernel, the responsibility re-sum and the prediction-probability pass, and the row
-// tables of the three passes that take several agents in one call.  DESIGN.md sections 11, 13, 16, 17, 18, 19 and 20.
+// tables of the four passes that take several agents in one call.  DESIGN.md sections 11, 13, 16, 17, 18, 19, 20 and 21.
 #pragma once
 
 #include <stdint.h>
@@ -182,4 +182,28 @@ struct RiskListBatchArgs {
     const int32_t *fin0;       // [n_rows] the rows' fin0
     const int32_t *agent_row;  // [n_agents] a row of the agent (any of them: the arg-min reads ego, obst, w.n and w.ids), -1 without one
     int32_t n_agents;
+};
+
+// The detail and cost passes over several agents in one call, each with an id list or none and with cost parameters or none
+// (fx_eval_risk_costs_batch): the rows are RiskBatchRow with the lists of section 20 in w.ids and the
+// detail pass's parts -- it.part [K][chunks][7][nb], occ the agent's rows of the call's concatenated outputs, col the agent's
+// [4][K][n] -- and the rounds RiskBatchRound.  The cost pass runs over the agents that have cost parameters alone.
+// The caller's columns are concatenated per column -- agent i's [K_i][n_i] at the sum of K_b n_b of the agents before it -- while
+// items_finish_body and cost_body index an agent's four columns as ONE block [4][K][n]: a segment is one plane of one agent.
+struct RiskCopySeg {
+    const double *src;         // [n] plane q of the agent's block
+    double *dst;               // its place in column q of the call
+    int64_t n;                 // K n of the agent
+};
+struct RiskCostBatchArgs {
+    const RiskBatchRow *rows;  // [n_rows], all rounds
+    const int64_t *item0;      // [n_rows] the rows' item0, compact
+    const int32_t *fin0;       // [n_rows] the rows' fin0
+    const int32_t *agent_row;  // [n_agents] a row of the agent, -1 without one
+    const RiskCostArgs *cost;  // [n_cost] of the agents with cost parameters, in call order; ids the agent's list or null
+    const int32_t *blk0;       // [n_cost] first workgroup of 256 of the agent in the cost launch; it has ceil(n / 256)
+    int32_t n_agents, n_cost, blocks;   // blocks: of all agents with cost parameters
+    const RiskCopySeg *seg;    // [n_seg] the agents' column planes on their way into the call's concatenated columns, or null
+    const int32_t *seg_blk0;   // [n_seg] first workgroup of the segment in the gather launch; it has ceil(n / 1024)
+    int32_t n_seg, seg_blocks; // seg_blocks 0: the caller asked for no column
 };

@@ -2,7 +2,7 @@
 // arg-min of ego + obstacle risk (reactive_planner.py:262-269, reactive_planner_cpp.py:404-413).  DESIGN.md section 11.
 // With calc_risk's per-obstacle results, the risk-cost principles with the responsibility cost over them (risk_costs.py:124-251,
 // utility/responsibility.py), and the responsibility cost as a weighted term of the step's cost sum beside the
-// step.
+// step.  Behind them the forms of these passes for several agents in one call (DESIGN.md sections 19 - 21).
 //
 // Decomposition.  The K (S - 1) (obstacle, step) pairs of a candidate are spread over (tile of 64 listed candidates) x (chunk of
 // steps) x obstacle: one wave per item, grid = (tiles, chunks, K), and one finish lane per candidate behind them.  Obstacle and
@@ -641,6 +641,101 @@ __global__ __launch_bounds__(1024) void fx_risk_list_batch_argmin_kernel(const R
     }
     const RiskBatchRow &r = rows[row];
     risk_argmin<true>(r.ego, r.obst, r.w.n, r.w.ids, out + blockIdx.x);
+}
+
+// ---- the detail and cost passes of several agents in one call, with or without id lists (fx_eval_risk_costs_batch; DESIGN.md
+// section 21) ----
+// One wave per item of a round, as fx_risk_batch_item_kernel finds it; lane jj of a row handles list position first + jj: the
+// candidate ids[first + jj] of a row with a list -- evaluated whatever its flags, as selected() has it -- or candidate first + jj,
+// which then needs all of it.need.  The choice is the row's, so wave-uniform, and the index load stands in front of the walk: once
+// the four plane pointers are formed neither the list pointer nor the index is live in the loop.  From there on the loop of
+// fx_risk_item_kernel<true> in its own text (that kernel is to stay what it is): the harm at every t < pl, the seven partials in
+// the layout [K][chunks][7][nb] of the row's segment.  FxRiskParams through the row's pointer, never by value.
+__global__ __launch_bounds__(64) void fx_risk_costs_batch_item_kernel(const RiskBatchRow *__restrict__ rows, const int64_t *__restrict__ item0,
+                                                                      const int n_rows) {
+    const int64_t at = blockIdx.x;
+    const RiskBatchRow &r = rows[batch_row_of(item0, n_rows, at)];
+    const RiskWalkArgs &w = r.w;
+    const RiskItemArgs &it = r.it;
+    const FxRiskParams &p = *it.params;
+    const int64_t local = at - r.item0, tiles = it.nb / 64, rest = local / tiles;
+    const int lane = threadIdx.x, S = w.S;
+    const int k = (int)(rest / it.chunks), ch = (int)(rest % it.chunks);
+    const double *__restrict__ o = w.obs + (size_t)k * FXO_STRIDE;
+    const int pl = min(S - 1, (int)o[FXO_NPOS]);
+    const int t_a = ch * it.cs, t_b = min(pl, t_a + it.cs);
+    if (t_a >= t_b) return;   // (wave-uniform)
+    const int64_t jj = (local % tiles) * 64 + lane;
+    if (jj >= r.count) return;   // (count <= nb, first + count <= n)
+    const int64_t c = w.ids ? w.ids[r.first + jj] : r.first + jj;
+    if (!selected(w, it, c)) return;   // (NaN rows from the finish kernel)
+    const int64_t ld = w.ld;
+    const double *__restrict__ X = w.planes + c, *__restrict__ Y = X + (size_t)S * ld, *__restrict__ TH = Y + (size_t)S * ld,
+                 *__restrict__ V = TH + (size_t)S * ld;
+    const bool prot = o[FXO_CLS] == (double)FX_RISK_CLASS_PROTECTED;
+    const double me = p.ego_mass, mo = o[FXO_MASS];
+    const double f_ego = mo / (me + mo), f_obs = me / (me + mo);
+    double e_max = -INFINITY, o_max = -INFINITY, he_max = -INFINITY, ho_max = -INFINITY, p_max = -INFINITY, ho_at = 0.0;
+    bool p_nan = false;
+    for (int t = t_a; t < t_b; t++) {
+        const int i = t + 1;
+        const double *__restrict__ q = w.rec + ((size_t)k * S + i) * FXR_STRIDE;
+        const double prob = fxrisk::step_probability(p, q, X[(size_t)i * ld], Y[(size_t)i * ld], TH[(size_t)i * ld]);
+        const size_t kt = (size_t)k * w.P + t;
+        double he, ho;
+        fxrisk::step_harm(p, prot, f_ego, f_obs, X[(size_t)t * ld], Y[(size_t)t * ld], TH[(size_t)t * ld], V[(size_t)t * ld], w.yaw[kt],
+                          w.vo[kt], w.pos[2 * kt], w.pos[2 * kt + 1], he, ho);
+        const double re = prob != 0.0 ? he * prob : 0.0;
+        const double ro = prob != 0.0 ? ho * prob : 0.0;
+        he_max = fmax(he_max, he);
+        ho_max = fmax(ho_max, ho);
+        p_nan = p_nan || prob != prob;
+        if (prob > p_max) { p_max = prob; ho_at = ho; }
+        e_max = fmax(e_max, re);
+        o_max = fmax(o_max, ro);
+    }
+    const size_t nb = (size_t)it.nb;
+    double *__restrict__ out = it.part + (((size_t)k * it.chunks + ch) * 7) * nb + jj;
+    out[(size_t)P_EMAX * nb] = e_max;
+    out[(size_t)P_OMAX * nb] = o_max;
+    out[(size_t)P_HEMAX * nb] = he_max;
+    out[(size_t)P_HOMAX * nb] = ho_max;
+    out[(size_t)P_PMAX * nb] = p_max;
+    out[(size_t)P_HOAT * nb] = ho_at;
+    out[(size_t)P_PNAN * nb] = p_nan ? 1.0 : 0.0;
+}
+
+// (The finish launch of a round is fx_risk_batch_finish_kernel as it stands: items_finish_body<true> reads the row's list through
+// w.ids.  The risk arg-min is fx_risk_list_batch_argmin_kernel as it stands.)
+
+// Behind the last round, one launch over the agents WITH cost parameters (cost [n_cost], compact, in call order): one lane per
+// (agent, list position), the agent of a workgroup found through blk0[]; the cost kernel's own function with the per-agent call's
+// rule for an agent without a list (every = false: NaN rows where a flag of VALID, FEASIBLE, RETURNED is missing)
+__global__ __launch_bounds__(256) void fx_risk_costs_batch_cost_kernel(const RiskCostArgs *__restrict__ cost, const int32_t *__restrict__ blk0,
+                                                                       const int n_cost) {
+    const int a = batch_row_of(blk0, n_cost, (int64_t)blockIdx.x);
+    cost_body(cost[a], (int64_t)(blockIdx.x - blk0[a]) * blockDim.x + threadIdx.x, false);
+}
+
+// One workgroup of 1024 lanes per agent with cost parameters: fx_risk_cost_argmin_kernel's reduction over the agent's totals -- the
+// candidate INDEX of the minimum, ties to the lower candidate index whatever the list's order, NaN skipped, -1 when nothing is left
+__global__ __launch_bounds__(1024) void fx_risk_costs_batch_argmin_kernel(const RiskCostArgs *__restrict__ cost, long long *__restrict__ out) {
+    const RiskCostArgs &a = cost[blockIdx.x];
+    risk_argmin<false>(a.out + 5 * (size_t)a.n, nullptr, a.n, a.ids, out + blockIdx.x);
+}
+
+// Behind them, where the caller asked for a column: the agents' column planes into the call's concatenated columns, which then
+// come down in one copy each.  One workgroup per 1 024 doubles of a segment, the segment found through blk0[]
+__global__ __launch_bounds__(256) void fx_risk_costs_batch_gather_kernel(const RiskCopySeg *__restrict__ seg, const int32_t *__restrict__ blk0,
+                                                                         const int n_seg) {
+    const int s = batch_row_of(blk0, n_seg, (int64_t)blockIdx.x);
+    const RiskCopySeg &g = seg[s];
+    const int64_t j0 = (int64_t)(blockIdx.x - blk0[s]) * 1024 + threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int64_t j = j0 + 256 * u;
+        if (j < g.n) g.dst[j] = g.src[j];
+    }
 }
 
 }  // namespace fxrisk

@@ -990,10 +990,80 @@ class FrenetEngine(StepRegistry):
         skipped, -1 when nothing is left)."""
         return self._risk_costs(params, cost_params, ids, agent)
 
+    def _risk_costs_batch(self, params, cost_params, ids, agents) -> list:
+        listed = list(range(len(self._inputs))) if agents is None else [int(a) for a in agents]
+        n = len(listed)
+        params = [params] * n if isinstance(params, _abi.FxRiskParams) else list(params)
+        costs = [cost_params] * n if cost_params is None or isinstance(cost_params, _abi.FxRiskCostParams) else list(cost_params)
+        ids = [None] * n if ids is None else [None if x is None else np.ascontiguousarray(x, dtype=np.int64) for x in ids]
+        if len(params) != n or len(ids) != n or len(costs) != n:
+            raise ValueError(f"{len(params)} params, {len(costs)} cost params and {len(ids)} id lists for {n} agents")
+        # (an agent the library will refuse counts no rows: the refusal comes before anything is written)
+        counts = [(self._inputs[a].n_candidates if 0 <= a < len(self._inputs) else 0) if x is None else len(x) for a, x in zip(listed, ids)]
+        Ks = [getattr(self, "_risk_K", {}).get(a, 0) for a in listed]
+        for a, m, K, cp in zip(listed, counts, Ks, costs):   # the arrays behind the structures' pointers must cover what the library reads
+            lens = getattr(cp, "_lengths", {}) if cp is not None else {}
+            if lens.get("boundary_harm", m) != m:
+                raise ValueError(f"agent {a}: boundary_harm has {lens['boundary_harm']} entries for {m} candidates")
+            if lens.get("responsibility", K) != K:
+                raise ValueError(f"agent {a}: responsibility has {lens['responsibility']} entries for {K} obstacles")
+        prm = (_abi.FxRiskParams * max(n, 1))(*params)
+        pi64, pcp = C.POINTER(C.c_int64), C.POINTER(_abi.FxRiskCostParams)
+        cpp = (pcp * max(n, 1))(*[C.cast(None, pcp) if cp is None else C.pointer(cp) for cp in costs])
+        n_ids = np.array([0 if x is None else len(x) for x in ids] + [0], dtype=np.int64)
+        backs = [None if x is None else (x if len(x) else np.zeros(1, np.int64)) for x in ids]   # (an empty list is a list: never NULL)
+        idp = (pi64 * max(n, 1))(*[C.cast(None, pi64) if x is None else x.ctypes.data_as(pi64) for x in backs])
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        coff = np.concatenate([[0], np.cumsum([K * m for K, m in zip(Ks, counts)])]).astype(np.int64)
+        any_cost = any(cp is not None for cp in costs)
+        names = ["ego_risk", "obst_risk", "obst_harm_occ"]
+        cols = ["ego_risk_max", "obst_risk_max", "ego_harm_max", "obst_harm_max"]
+        cost_names = list(_abi.RISK_COST_NAMES) + ["total", "boundary_harm"]
+        flat = {k: np.zeros(max(int(off[-1]), 1)) for k in names + (cost_names if any_cost else [])}
+        flat.update({k: np.zeros(max(int(coff[-1]), 1)) for k in cols})
+        idx = np.full((2, max(n, 1)), -1, np.int64)
+        out = _abi.FxRiskCostBatchOutputs()
+        for k, a in flat.items():
+            setattr(out, k, a.ctypes.data)
+        out.min_risk_index, out.min_cost_index = idx[0].ctypes.data, idx[1].ctypes.data
+        al = np.ascontiguousarray(listed, dtype=np.int32)
+        any_list = any(x is not None for x in ids)
+        check(lib().fx_eval_risk_costs_batch(self._ctx, n, al.ctypes.data_as(C.POINTER(C.c_int32)) if agents is not None else None, prm,
+                                             cpp if any_cost else None, n_ids.ctypes.data_as(pi64) if any_list else None,
+                                             idp if any_list else None, C.byref(out)))
+        res = []
+        for i in range(n):
+            m, K = counts[i], Ks[i]
+            d = {k: flat[k][off[i]:off[i + 1]] for k in names + (cost_names if costs[i] is not None else [])}
+            d.update({k: flat[k][coff[i]:coff[i + 1]].reshape(K, m).T for k in cols})   # [n, K] views of the obstacle-major columns
+            d["min_risk_index"] = int(idx[0, i])
+            if costs[i] is not None:
+                d["min_cost_index"] = int(idx[1, i])
+            res.append(d)
+        return res
+
+    def risk_detail_batch(self, params, ids=None, agents=None) -> list:
+        """`risk_detail` of several agents of the last plan step in ONE call (fx_eval_risk_costs_batch): per
+        listed agent the dict risk_detail(params_a, ids_a, agent=a) returns, bit for bit; the arrays and the [n, K] column views
+        are views of the call's concatenated ones.  params, ids, agents as in `risk_batch`."""
+        return self._risk_costs_batch(params, None, ids, agents)
+
+    def risk_costs_batch(self, params, cost_params, ids=None, agents=None) -> list:
+        """`risk_costs` of several agents of the last plan step in ONE call (fx_eval_risk_costs_batch): per
+        listed agent the dict risk_costs(params_a, cost_params_a, ids_a, agent=a) returns, bit for bit.  cost_params: one
+        FxRiskCostParams for all or one per listed agent, None for an agent that gets the detail alone; params, ids, agents as in
+        `risk_batch`; obstacles and reach sets are each agent's `set_risk_obstacles` / `set_reach_sets`."""
+        return self._risk_costs_batch(params, cost_params, ids, agents)
+
+    @property
+    def last_risk_costs_batch_rounds(self) -> int:
+        """rounds of scratch the last `risk_detail_batch` / `risk_costs_batch` call took (-1 before the first)"""
+        return int(lib().fx_last_risk_costs_batch_rounds(self._ctx))
+
     @property
     def last_risk_ms(self) -> float:
-        """device time of the last `risk` / `risk_batch` / `risk_detail` / `risk_costs` / `responsibility_cost` /
-        `responsibility_cost_batch` call (its kernels)"""
+        """device time of the last `risk` / `risk_batch` / `risk_detail` / `risk_costs` / `risk_detail_batch` / `risk_costs_batch` /
+        `responsibility_cost` / `responsibility_cost_batch` call (its kernels)"""
         return float(lib().fx_last_risk_ms(self._ctx))
 
     # -- the responsibility cost as a weighted term (DESIGN.md section 17) --

@@ -96,6 +96,9 @@ BATCHED_RESPONSIBILITY_DEFAULT = False
 # AgentBatchHip(batched_risk=None): the planners' risk evaluations (log_risk, the min-risk selections) of a whole batch in one
 # call; turning it on is a later change, after that section's measurement has been read
 BATCHED_RISK_DEFAULT = False
+# AgentBatchHip(batched_risk_costs=None): the planners' "min_risk_cost" fallbacks of a whole batch in one call (DESIGN.md section
+# 21); off like the others, whatever that section's measurement says
+BATCHED_RISK_COSTS_DEFAULT = False
 
 
 class AgentBatchHip:
@@ -109,13 +112,18 @@ class AgentBatchHip:
     def __init__(self, agents: List[FrenetPlannerInterfaceHip], max_candidates: int, device: int = 0, max_ref_knots: int = 4096,
                  max_obstacles: int = 64, engine=None, parts=None, slots=None, winner_exchange=None, pipeline_groups: Optional[int] = None,
                  batched_passes: Optional[bool] = None, batched_responsibility: Optional[bool] = None,
-                 batched_risk: Optional[bool] = None):
-        """batched_risk: per engine group and step plan_consume runs for every planning agent first, then ONE engine.risk_batch
+                 batched_risk: Optional[bool] = None, batched_risk_costs: Optional[bool] = None):
+        """batched_risk_costs: independent of batched_risk and made at the same place -- ONE engine.risk_costs_batch over the
+        agents whose planner left a "min_risk_cost" fallback of its step waiting (ReactivePlannerHip.risk_cost_request: every
+        VALID & FEASIBLE & RETURNED candidate, the planner's weights and responsibility mode), between plan_consume and
+        plan_finish -- the same bits.  None: BATCHED_RISK_COSTS_DEFAULT.  Escalated levels, split agents,
+        planners with sparse_bundle_k > 0, callable selectors and engines without the method keep the per-agent path.
+        batched_risk: per engine group and step plan_consume runs for every planning agent first, then ONE engine.risk_batch
         over the agents whose planner still needs a risk evaluation of its step (ReactivePlannerHip.risk_request: the winner for
         log_risk, every candidate for the "min_risk" fallback of a single-level planner and for emergency_mode "min_risk"), then
         plan_finish / finish_step for every agent in the order they run in anyway -- the same bits.  None:
         BATCHED_RISK_DEFAULT.  Escalated levels, split agents, planners with sparse_bundle_k > 0, callable selectors,
-        "min_risk_cost" and engines without the method keep the per-agent path.
+        "min_risk_cost" (see batched_risk_costs) and engines without the method keep the per-agent path.
         batched_responsibility: independent of batched_passes -- the responsibility pass of the planners that weight the term
         runs for all of them in ONE engine.responsibility_cost_batch call per engine group and step, behind the batched launch:
         each such planner sets its tables (prepare_responsibility_cost), the call runs over those whose preparation returns
@@ -177,6 +185,7 @@ class AgentBatchHip:
         self.batched_passes = BATCHED_PASSES_DEFAULT if batched_passes is None else bool(batched_passes)
         self.batched_responsibility = BATCHED_RESPONSIBILITY_DEFAULT if batched_responsibility is None else bool(batched_responsibility)
         self.batched_risk = BATCHED_RISK_DEFAULT if batched_risk is None else bool(batched_risk)
+        self.batched_risk_costs = BATCHED_RISK_COSTS_DEFAULT if batched_risk_costs is None else bool(batched_risk_costs)
         self.launches = 0
         self.escalations = 0
         self.last_batch_ms = 0.0
@@ -186,7 +195,9 @@ class AgentBatchHip:
         being the agent's plan_consume.  Per agent consume, then escalate or finish, then finish_step -- or, with batched_risk on
         an engine that has risk_batch, consume for all, ONE risk_batch over those whose planner asks for an evaluation
         (risk_request; a planner that escalates does not: its next level runs on its own engine), and then the rest per agent in
-        the same order.  batch_risk False: the per-agent path whatever the flag."""
+        the same order; with batched_risk_costs on an engine that has risk_costs_batch, ONE risk_costs_batch over those whose
+        planner left a "min_risk_cost" fallback waiting (risk_cost_request) at the same place.  batch_risk False: the per-agent
+        path whatever the flags."""
         def finish(a, best):
             p = a.planner
             if best is None and p._sampling_min + 1 < p._sampling_max:
@@ -197,19 +208,30 @@ class AgentBatchHip:
             sel, _ = a.finish_step(pair, global_timestep)
             out[a.id] = sel
 
-        if not (batch_risk and self.batched_risk and hasattr(eng, "risk_batch")):
+        use_risk = batch_risk and self.batched_risk and hasattr(eng, "risk_batch")
+        use_costs = batch_risk and self.batched_risk_costs and hasattr(eng, "risk_costs_batch")
+        if not (use_risk or use_costs):
             for a, j, consume in todo:
                 finish(a, consume(False))
             return
         bests = [consume(True) for a, j, consume in todo]
-        asked = []
+        asked, cost_asked = [], []
         for (a, j, _), best in zip(todo, bests):
             p = a.planner
             if best is None and p._sampling_min + 1 < p._sampling_max:
                 continue
-            req = p.risk_request(best)
+            creq = p.risk_cost_request(best) if use_costs and hasattr(p, "risk_cost_request") else None
+            if creq is not None:
+                cost_asked.append((p, j, creq))
+                continue
+            req = p.risk_request(best) if use_risk else None
             if req is not None:
                 asked.append((p, j, req))
+        if cost_asked:
+            res = eng.risk_costs_batch([req[0] for _, _, req in cost_asked], [req[1] for _, _, req in cost_asked],
+                                       [req[2] for _, _, req in cost_asked], agents=[j for _, j, _ in cost_asked])
+            for (p, _, req), r in zip(cost_asked, res):
+                p.hand_risk_cost_result(req[2], r)
         if asked:
             res = eng.risk_batch([req[0] for _, _, req in asked], [req[1] for _, _, req in asked], agents=[j for _, j, _ in asked])
             for (p, _, req), r in zip(asked, res):
@@ -387,8 +409,9 @@ class MultiAgentSimulation:
                  number_of_agents: int = -1, sampling_level: Optional[int] = None, device: int = 0, group=None,
                  use_road_boundary: bool = False, max_candidates: Optional[int] = None, engine_factory=None,
                  pipeline_groups: Optional[int] = None, freeze_gc: bool = False, batched_passes: Optional[bool] = None,
-                 batched_responsibility: Optional[bool] = None, batched_risk: Optional[bool] = None):
-        """batched_passes, batched_responsibility, batched_risk: see AgentBatchHip.
+                 batched_responsibility: Optional[bool] = None, batched_risk: Optional[bool] = None,
+                 batched_risk_costs: Optional[bool] = None):
+        """batched_passes, batched_responsibility, batched_risk, batched_risk_costs: see AgentBatchHip.
         engine_factory: callable returning an engine object (tests inject a stand-in); default = FrenetEngine.
         pipeline_groups: see AgentBatchHip (None = automatic; with an engine_factory: that many injected engines, default one).
         freeze_gc: take what exists once the simulation is set up out of the garbage collector's generations (gc.freeze(): a
@@ -428,7 +451,8 @@ class MultiAgentSimulation:
                                             else engine_factory()) if engine_factory else None),
                                    parts=[(part, n_parts) for _, part, n_parts in my_items], slots=self.my_slots,
                                    winner_exchange=self._exchange_winners if self.split else None, batched_passes=batched_passes,
-                                   batched_responsibility=batched_responsibility, batched_risk=batched_risk)
+                                   batched_responsibility=batched_responsibility, batched_risk=batched_risk,
+                                   batched_risk_costs=batched_risk_costs)
         self.S = self.batch.agents[0].planner.N + 1 if mine else int(self.config.planning_horizon / self.config.dt) + 1
         self.time_step = 0
         # planned trajectories of ALL agents, identical on every rank after the exchange: [agents][S][FIELDS]

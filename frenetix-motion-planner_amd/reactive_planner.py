@@ -142,6 +142,9 @@ class ReactivePlannerHip:
         self._risk_pending = None           # the step whose "min_risk" fallback waits
         self._risk_handed = None            # (step, ids or None, (ego_risk, obst_risk, min_risk_index)) handed in for that step
         self._stopping_choice = None        # (step, the stopping selection over it): chosen once per step
+        # ... and the "min_risk_cost" fallback of all of them (risk_cost_request / hand_risk_cost_result)
+        self._risk_cost_pending = None      # the step whose "min_risk_cost" fallback waits
+        self._risk_cost_handed = None       # (step, ids, the risk_costs dict) handed in for that step
         self.reach_set = None               # set_reach_set
         self.occlusion_module = None       # planner.py:99 (set_occlusion_module)
         self.use_occ_model = False
@@ -431,6 +434,8 @@ class ReactivePlannerHip:
         step = self.last_step
         if not self._risk_batchable(step):
             return None
+        if optimal_trajectory is None and self._risk_cost_pending is step:
+            return None   # (plan_finish selects by risk cost first -- risk_cost_request; what may follow it runs on the planner's own path)
         ids = False
         opt = optimal_trajectory
         if opt is None and self._risk_pending is step:
@@ -453,6 +458,25 @@ class ReactivePlannerHip:
         """The (ego_risk, obst_risk, min_risk_index) of the evaluation risk_request asked for (its ids), made elsewhere: plan_finish
         takes it where it would have called engine.risk"""
         self._risk_handed = (self.last_step, ids, result)
+
+    def risk_cost_request(self, optimal_trajectory):
+        """After plan_consume(defer_risk=True) returned `optimal_trajectory`: the "min_risk_cost" fallback of the step that waits
+        for plan_finish, as (FxRiskParams, FxRiskCostParams, ids) for engine.risk_costs_batch -- ids every VALID & FEASIBLE &
+        RETURNED candidate, as _min_risk_cost_sample lists them -- or None when none waits.  The host work of that evaluation is
+        done here: the obstacle tables of the current predictions, the reach-set tables or the action-space vector."""
+        step = self.last_step
+        if optimal_trajectory is not None or step is None or self._risk_cost_pending is not step:
+            return None
+        ids = self._fallback_ids(step)
+        if len(ids) == 0:
+            return None
+        params, cp = self._risk_cost_setup(step)
+        return params, cp, ids
+
+    def hand_risk_cost_result(self, ids, result):
+        """The risk_costs dict of the evaluation risk_cost_request asked for (its ids), made elsewhere: _min_risk_cost_sample
+        takes it where it would have called engine.risk_costs"""
+        self._risk_cost_handed = (self.last_step, np.asarray(ids, np.int64), result)
 
     def _select_stopping(self, step):
         """_select_stopping_trajectory of `step`, chosen once (risk_request looks at what plan_finish will select)"""
@@ -488,6 +512,14 @@ class ReactivePlannerHip:
         return self._risk_costs_on(self.last_step, ids)
 
     def _risk_costs_on(self, step, ids):
+        params, cp = self._risk_cost_setup(step)
+        if ids is not None:
+            step.materialise(ids)   # (a step without a bundle: see _eval_risk)
+        return step.engine.risk_costs(params, cp, None if ids is None else np.asarray(ids, np.int64), step.agent)
+
+    def _risk_cost_setup(self, step):
+        """the host work in front of a risk-cost evaluation of `step`: obstacle tables, reach-set tables or the action-space vector
+        set on the step's engine; (FxRiskParams, FxRiskCostParams) of the call"""
         from . import risk
         if self._risk_model is None or self._risk_cost_weights is None:
             raise ValueError("no risk model: call set_risk_model and set_risk_cost_weights first")
@@ -503,10 +535,7 @@ class ReactivePlannerHip:
             sets = self.reach_set.reach_sets[self.x_0.time_step]
             step.engine.set_reach_sets(risk.reach_set_tables(sets, tabs["keys"], self.dT, step.inputs.n_samples), step.agent)
             resp = "reach_set"
-        cp = risk.risk_cost_params(weights, boundary_harm="step", harm_coeff=step.harm_coeff, responsibility=resp)
-        if ids is not None:
-            step.materialise(ids)   # (a step without a bundle: see _eval_risk)
-        return step.engine.risk_costs(m["params"], cp, None if ids is None else np.asarray(ids, np.int64), step.agent)
+        return m["params"], risk.risk_cost_params(weights, boundary_harm="step", harm_coeff=step.harm_coeff, responsibility=resp)
 
     @staticmethod
     def _fallback_ids(step):
@@ -517,7 +546,11 @@ class ReactivePlannerHip:
         ids = self._fallback_ids(step)
         if len(ids) == 0:
             return None
-        res = self._risk_costs_on(step, ids)
+        h = self._risk_cost_handed
+        if h is not None and h[0] is step and np.array_equal(h[1], ids):
+            res = h[2]
+        else:
+            res = self._risk_costs_on(step, ids)
         g = res["min_cost_index"]
         if g < 0:
             return None
@@ -761,7 +794,9 @@ class ReactivePlannerHip:
         (batched_prediction_pass planners only); None: the planner runs its own pass.  responsibility_pass: the same for an
         engine.responsibility_cost_batch call behind this planner's prepare_responsibility_cost.  defer_risk: the caller makes
         the planners' risk evaluations in one call -- a "min_risk" fallback of this level then returns None here and waits:
-        risk_request says what to evaluate, hand_risk_result takes the result, plan_finish selects."""
+        risk_request says what to evaluate, hand_risk_result takes the result, plan_finish selects.  A "min_risk_cost" fallback
+        of this level waits in the same way (risk_cost_request, hand_risk_cost_result); without a handed result plan_finish
+        makes the planner's own call."""
         if package is False:
             package = engine.package(agent, self.x_0.yaw_rate) if getattr(engine, "packaging", False) and inputs.write_bundle else None
         self._risk_defer = bool(defer_risk)
@@ -794,6 +829,13 @@ class ReactivePlannerHip:
                 self.msg_logger.warning("No optimal trajectory available. Select lowest risk trajectory!")
                 optimal_trajectory.materialise()
         self._risk_pending = None
+        if optimal_trajectory is None and self._risk_cost_pending is not None and self._risk_cost_pending is self.last_step:
+            # the same for a "min_risk_cost" fallback left waiting
+            optimal_trajectory = self._min_risk_cost_sample(self.last_step)
+            if optimal_trajectory is not None:
+                self.msg_logger.warning("No optimal trajectory available. Select lowest risk trajectory!")
+                optimal_trajectory.materialise()
+        self._risk_cost_pending = None
 
         self.trajectory_pair = self._compute_trajectory_pair(optimal_trajectory) if optimal_trajectory is not None else None
         if self.trajectory_pair is not None:
@@ -891,6 +933,9 @@ class ReactivePlannerHip:
                 return None
             chosen = self._min_risk_sample(step)    # the device's risk pass and arg-min (set_risk_model)
         elif isinstance(self.fallback_selector, str) and self.fallback_selector == "min_risk_cost":
+            if self._risk_defer and self._risk_batchable(step) and self._risk_cost_weights is not None:
+                self._risk_cost_pending = step   # (the batch evaluates it with the other planners' -- risk_cost_request)
+                return None
             chosen = self._min_risk_cost_sample(step)
         else:
             chosen = self.fallback_selector(_LazySamples(step, ids))
@@ -903,6 +948,7 @@ class ReactivePlannerHip:
         if self.last_step is not None:
             self.last_step.invalidate()
         self._risk_pending = self._risk_handed = self._stopping_choice = None   # (they belong to the step before)
+        self._risk_cost_pending = self._risk_cost_handed = None
         step = PlanStepResult(engine, inputs, res, agent)
         step.retain = self.config.retain_samples
         step.package = package

@@ -825,7 +825,7 @@ int32_t fx_eval_responsibility_cost_batch(FxContext *ctx, int32_t n_agents, cons
  * or n_ids NULL: no agent has a list) every candidate, NaN rows for those that lack VALID, FEASIBLE or RETURNED.  An agent whose
  * step stored no bundle takes part with a list inside its sparse set (fx_materialise_candidates_agent), as in the per-agent call.
  * Every output is bit for bit what the per-agent call returns, whichever agents and forms share a call and in whatever order.  The
- * detail and cost passes (fx_eval_risk_costs_agent) stay per agent. */
+ * detail and cost passes of a batch: fx_eval_risk_costs_batch below. */
 typedef struct FxRiskBatchOutputs {      /* no pointer may be NULL */
     double *ego_risk, *obst_risk;        /* [sum of n_a], agent-major; n_a = n_ids[i], or C of the agent without a list */
     int64_t *min_risk_index;             /* [n_agents], as fx_eval_risk_agent's: a candidate index, ties to the lower candidate
@@ -843,6 +843,34 @@ int32_t fx_eval_risk_batch(FxContext *ctx, int32_t n_agents, const int32_t *agen
                            const int64_t *n_ids /* [n_agents], or NULL: no agent has a list */,
                            const int64_t *const *ids /* [n_agents], ids[i] NULL with n_ids[i] == 0: every candidate */,
                            const FxRiskBatchOutputs *out);
+
+/* ---- Risk detail and risk costs for several agents in one call (additive within ABI 15) ----
+ * fx_eval_risk_costs_agent(ctx, agents[i], &params[i], cost[i], n_ids[i], ids[i], ...) for each listed agent, each with its own
+ * obstacle and reach-set tables, its own list or none (as in fx_eval_risk_batch: n_a = n_ids[i], or C without a list) and its own
+ * FxRiskCostParams or none -- weights, boundary mode, boundary_harm [n_a], responsibility [K_a], responsibility mode.  An agent
+ * whose step stored no bundle takes part with a list inside its sparse set, as in the per-agent call.  Every output is bit for bit
+ * what the per-agent call returns, whichever agents and forms share a call and in whatever order. */
+typedef struct FxRiskCostBatchOutputs {   /* any pointer may be NULL, as in FxRiskOutputs */
+    double *ego_risk, *obst_risk, *obst_harm_occ;                        /* [sum of n_a], agent-major */
+    double *ego_risk_max, *obst_risk_max, *ego_harm_max, *obst_harm_max; /* agent i: [K_i][n_i] at offset sum_{b<i} K_b n_b */
+    double *bayes, *equality, *maximin, *ego, *responsibility, *total, *boundary_harm;   /* [sum of n_a]; rows of an agent
+                                                                            without cost parameters are left unwritten */
+    int64_t *min_risk_index;   /* [n_agents] */
+    int64_t *min_cost_index;   /* [n_agents]; -1 for an agent without cost parameters */
+} FxRiskCostBatchOutputs;
+/* agents: as in fx_eval_prediction_prob_batch.  Everything is checked for every listed agent before anything is launched, uploaded,
+ * allocated or written to out, and the message names the first offending agent: FX_ERR_INVALID_ARGUMENT for NULL ctx, params or
+ * out, n_agents < 0 or above the uploaded agents, an agent out of range or listed twice, n_ids[i] > 0 with ids[i] NULL; per agent
+ * what fx_eval_risk_costs_agent refuses, with its codes (an obstacle with min(S - 1, n_pos) == 0, the reach-set and cost-mode
+ * checks; a step without FX_MODE_WRITE_BUNDLE and an id outside the sparse set: FX_ERR_NOT_READY).  Like fx_eval_risk_batch it
+ * also refuses (FX_ERR_NOT_READY) inputs rewritten since the last evaluation (fx_update_state).  n_agents == 0 returns FX_OK and
+ * touches nothing.  Synchronous; fx_last_risk_ms covers it; its memory is the risk passes' device block (grow-only, counted in
+ * fx_device_bytes). */
+int32_t fx_eval_risk_costs_batch(FxContext *ctx, int32_t n_agents, const int32_t *agents /* NULL: 0 .. n_agents-1 */,
+                                 const FxRiskParams *params /* [n_agents] */,
+                                 const FxRiskCostParams *const *cost /* [n_agents], entry NULL: detail only; or NULL: all detail only */,
+                                 const int64_t *n_ids /* [n_agents] or NULL */, const int64_t *const *ids,
+                                 const FxRiskCostBatchOutputs *out);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,7 @@
 // risk-cost pass.  The two evaluations share one host path (RiskPass) and one device block.  Nothing of
 // this runs in a plan step.  The collision probability as the prediction cost (fx_predprob_kernel.h) is a third
 // entrance on the same host path: the same checks, records, uploads and block; fx_eval_prediction_prob_batch
-// is that pass for several agents in one call: the same checks and records per agent, one staging buffer each for records and tables;
+// is that pass for several agents in one call: the same checks and records per agent, one staging buffer for records and tables;
 // fx_eval_responsibility_cost_batch is the responsibility pass for several agents in one call, and
 // fx_eval_risk_batch the plain risk pass for several agents, each with an id list or none, and
 // fx_eval_risk_costs_batch the detail and cost passes for several agents, with lists and cost parameters each.
@@ -23,16 +23,16 @@ extern "C" hipError_t fx_launch_predprob(const PredProbArgs *args, long long *ou
                                          hipStream_t stream);
 // (weak, like the chunk rule below: a host-only program that links these files against launcher stubs of its own need not define
 // the launchers that came after it was written; fx_eval_prediction_prob_batch reports their absence)
-extern "C" __attribute__((weak)) hipError_t fx_launch_predprob_batch(const PredProbBatchArgs *t, const PredProbRound *rounds, int n_rounds,
+extern "C" __attribute__((weak)) hipError_t fx_launch_predprob_batch(const PredProbBatchArgs *t, const FxItemRound *rounds, int n_rounds,
                                                                      long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
                                                                      hipStream_t stream);
-extern "C" __attribute__((weak)) hipError_t fx_launch_risk_batch(const RiskBatchArgs *t, const RiskBatchRound *rounds, int n_rounds,
+extern "C" __attribute__((weak)) hipError_t fx_launch_risk_batch(const RiskBatchArgs *t, const FxItemRound *rounds, int n_rounds,
                                                                  long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
                                                                  hipStream_t stream);
-extern "C" __attribute__((weak)) hipError_t fx_launch_risk_list_batch(const RiskListBatchArgs *t, const RiskBatchRound *rounds, int n_rounds,
+extern "C" __attribute__((weak)) hipError_t fx_launch_risk_list_batch(const RiskListBatchArgs *t, const FxItemRound *rounds, int n_rounds,
                                                                       long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
                                                                       hipStream_t stream);
-extern "C" __attribute__((weak)) hipError_t fx_launch_risk_costs_batch(const RiskCostBatchArgs *t, const RiskBatchRound *rounds, int n_rounds,
+extern "C" __attribute__((weak)) hipError_t fx_launch_risk_costs_batch(const RiskCostBatchArgs *t, const FxItemRound *rounds, int n_rounds,
                                                                        long long *out_idx, long long *cost_idx, hipEvent_t ev_start,
                                                                        hipEvent_t ev_stop, hipStream_t stream);
 extern "C" __attribute__((weak)) int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K);   // (fx_kernels.hip: the rule, or what a test forces)
@@ -281,6 +281,27 @@ extern "C" int32_t fx_risk_items_chunk_steps(int64_t n, int32_t S, int32_t K) {
     return fx_item_chunk_steps(n, S, K, fx_risk_items_chunk_forced.load(std::memory_order_relaxed));
 }
 
+// What every pass does before it touches the device: the stream drained, the passes' one block at `bytes` or more, the events
+static int risk_block(FxContext *c, FxRiskState *r, size_t bytes, char *&base) {
+    HIP_TRY(hipSetDevice(c->device));
+    FX_TRY(fx_drain(c));
+    FX_TRY(r->block.ensure(bytes));
+    FX_TRY(r->ev.ensure());
+    base = r->block;
+    return FX_OK;
+}
+
+// The end of every pass: its n arg-min words come down behind its outputs, the ONE synchronisation, the device time into *ms
+static int risk_end(FxContext *c, FxRiskState *r, const void *d_idx, long long *idx, size_t n, float *ms) {
+    HIP_TRY(hipMemcpyAsync(idx, d_idx, sizeof(long long) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(ms, r->ev.e0, r->ev.e1));
+    return FX_OK;
+}
+// ... and the candidate an arg-min names: over a sparse set it ran over positions, which grow with the candidate index -- the
+// same winner, the same tie rule
+static int64_t risk_winner(const RiskPass &q, long long i) { return (q.sparse && i >= 0) ? q.set.ids[i] : (int64_t)i; }
+
 // The device block of a pass and the uploads every pass makes.  One grow-only allocation, every part 256-byte aligned; the plain
 // pass takes no room for the detail pass's columns, and only a pass with cost parameters for their outputs and tables.
 // pp_nb > 0: the prediction-probability pass with batches of pp_nb candidates -- room for its per-step scratch and outputs.
@@ -326,11 +347,7 @@ static int risk_stage(RiskPass &q, bool detail, const FxRiskCostParams *cost, si
         q.o_rresp = lay.take(sizeof(double) * n1), q.o_rtot = lay.take(sizeof(double) * n1), q.o_rpred = lay.take(sizeof(double) * n1);
         q.o_rbest = lay.take(2 * sizeof(long long));
     }
-    HIP_TRY(hipSetDevice(c->device));
-    FX_TRY(fx_drain(c));
-    FX_TRY(r->block.ensure(lay.size()));
-    FX_TRY(r->ev.ensure());
-    q.base = r->block;
+    FX_TRY(risk_block(c, r, lay.size(), q.base));
     if (walk) {
         q.it.part = q.D(q.o_part);
         q.it.params = reinterpret_cast<const FxRiskParams *>(q.base + q.o_prm);
@@ -377,14 +394,9 @@ static int risk_run(RiskPass &q, bool detail, const RiskCostArgs *ca, const FxRi
         HIP_TRY(q.down(out.total, q.o_rtot, nn));
     }
     long long idx[2] = {-1, -1};   // (the second one: the cost pass's arg-min)
-    HIP_TRY(hipMemcpyAsync(idx, d_idx, sizeof(long long) * (ca ? 2 : 1), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&r->last_ms, r->ev.e0, r->ev.e1));
-    // (sparse set: the arg-min ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
-    for (long long &i : idx)
-        if (q.sparse && i >= 0) i = (long long)q.set.ids[i];
-    if (out.min_risk_index) *out.min_risk_index = (int64_t)idx[0];
-    if (out.min_cost_index) *out.min_cost_index = (int64_t)idx[1];
+    FX_TRY(risk_end(c, r, d_idx, idx, ca ? 2 : 1, &r->last_ms));
+    if (out.min_risk_index) *out.min_risk_index = risk_winner(q, idx[0]);
+    if (out.min_cost_index) *out.min_cost_index = risk_winner(q, idx[1]);
     return FX_OK;
 }
 
@@ -456,8 +468,44 @@ static int risk_cost_check(const RiskPass &q, const FxRiskCostParams *cost) {
     return FX_OK;
 }
 
-// the argument block of a cost pass's kernel from where the pass's parts lie (q.base, q.o_*): no HIP call
-static void risk_cost_fill(const RiskPass &q, const FxRiskCostParams *cost, RiskCostArgs &ca);
+// where the parts of a cost pass lie on the device: the per-agent pass has them in its block (risk_stage), a batched call in its
+// staging buffer and its outputs
+struct RiskCostPtrs {
+    const double *col;         // [4][K][n] of the detail pass
+    const int64_t *ids;        // the list the walk got, or null
+    const double *bh, *resp;   // the caller's boundary harm [n] and responsibility vector [K]
+    const int32_t *eobs, *eoff, *pst, *voff;   // the reach-set tables
+    const double *vert;
+    double *out;               // [7][n]
+};
+
+// the argument block of a cost pass's kernel from what risk_check established of the agent and where the parts lie: no HIP call
+static void risk_cost_fill(const RiskPass &q, const FxRiskCostParams *cost, const RiskCostPtrs &d, RiskCostArgs &ca) {
+    ca.col = d.col;
+    ca.n = q.n;
+    ca.ids = d.ids;
+    ca.flags = q.flags;
+    ca.planes = q.planes;
+    ca.ld = q.ld;
+    ca.S = q.S;
+    ca.K = q.K;
+    ca.bh_in = cost->boundary_mode == FX_RISK_BOUNDARY_ARRAY ? d.bh : nullptr;
+    ca.bstep = (cost->boundary_mode == FX_RISK_BOUNDARY_STEP && (q.s->mode & FX_MODE_ROAD_BOUNDARY)) ? q.bstep : nullptr;
+    ca.bh_c = cost->boundary_c;
+    ca.bh_s = cost->boundary_s;
+    ca.resp_mode = cost->responsibility_mode;
+    ca.n_entries = (int32_t)q.nE;
+    ca.resp = d.resp;
+    ca.entry_obs = d.eobs;
+    ca.entry_off = d.eoff;
+    ca.part_step = d.pst;
+    ca.vert_off = d.voff;
+    ca.verts = d.vert;
+    for (int k = 0; k < 5; k++) ca.w[k] = cost->weights[k];
+    ca.eps = cost->maximin_eps;
+    ca.scale = cost->maximin_scale;
+    ca.out = d.out;
+}
 
 // the uploads of a staged cost pass and the argument block of its kernel
 static int risk_cost_args(const RiskPass &q, const FxRiskCostParams *cost, RiskCostArgs &ca) {
@@ -476,39 +524,9 @@ static int risk_cost_args(const RiskPass &q, const FxRiskCostParams *cost, RiskC
             HIP_TRY(q.up(q.o_vert, a.rs_verts.data(), sizeof(double) * 2 * nV));
         }
     }
-    risk_cost_fill(q, cost, ca);
+    risk_cost_fill(q, cost, RiskCostPtrs{q.D(q.o_col), q.d_ids(), q.D(q.o_bh), q.D(q.o_resp), q.I(q.o_eobs), q.I(q.o_eoff), q.I(q.o_pst),
+                                         q.I(q.o_voff), q.D(q.o_vert), q.D(q.o_out)}, ca);
     return FX_OK;
-}
-
-static void risk_cost_fill(const RiskPass &q, const FxRiskCostParams *cost, RiskCostArgs &ca) {
-    const FxAgentSlot &s = *q.s;
-    const int S = q.S, K = q.K;
-    const int64_t n = q.n;
-    const size_t nE = q.nE;
-    ca.col = q.D(q.o_col);
-    ca.n = n;
-    ca.ids = q.d_ids();
-    ca.flags = q.flags;
-    ca.planes = q.planes;
-    ca.ld = q.ld;
-    ca.S = S;
-    ca.K = K;
-    ca.bh_in = cost->boundary_mode == FX_RISK_BOUNDARY_ARRAY ? q.D(q.o_bh) : nullptr;
-    ca.bstep = (cost->boundary_mode == FX_RISK_BOUNDARY_STEP && (s.mode & FX_MODE_ROAD_BOUNDARY)) ? q.bstep : nullptr;
-    ca.bh_c = cost->boundary_c;
-    ca.bh_s = cost->boundary_s;
-    ca.resp_mode = cost->responsibility_mode;
-    ca.n_entries = (int32_t)nE;
-    ca.resp = q.D(q.o_resp);
-    ca.entry_obs = q.I(q.o_eobs);
-    ca.entry_off = q.I(q.o_eoff);
-    ca.part_step = q.I(q.o_pst);
-    ca.vert_off = q.I(q.o_voff);
-    ca.verts = q.D(q.o_vert);
-    for (int k = 0; k < 5; k++) ca.w[k] = cost->weights[k];
-    ca.eps = cost->maximin_eps;
-    ca.scale = cost->maximin_scale;
-    ca.out = q.D(q.o_out);
 }
 
 extern "C" int32_t fx_eval_risk_costs_agent(FxContext *c, int32_t agent, const FxRiskParams *params, const FxRiskCostParams *cost,
@@ -596,9 +614,7 @@ extern "C" int32_t fx_eval_responsibility_cost_agent(FxContext *c, int32_t agent
     FX_TRY(risk_run(q, true, &ca, ro, &rs));
     long long best[2] = {-1, 0};
     HIP_TRY(hipMemcpy(best, q.base + q.o_rbest, sizeof(best), hipMemcpyDeviceToHost));
-    // (sparse set: the arg-min ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
-    if (q.sparse && best[0] >= 0) best[0] = (long long)q.set.ids[best[0]];
-    *out->best_index = (int64_t)best[0];
+    *out->best_index = risk_winner(q, best[0]);
     memcpy(out->best_cost, &best[1], sizeof(double));
     return FX_OK;
 }
@@ -664,312 +680,358 @@ extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, co
     HIP_TRY(q.down(out->prob_obs, q.o_pobs, (size_t)q.K * nn));
     HIP_TRY(q.down(out->total, q.o_ptot, nn));
     long long best[2] = {-1, 0};
-    HIP_TRY(hipMemcpyAsync(best, d_best, sizeof(best), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&r->last_pp_ms, r->ev.e0, r->ev.e1));
-    // (sparse set: the arg-min ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
-    if (q.sparse && best[0] >= 0) best[0] = (long long)q.set.ids[best[0]];
-    if (out->best_index) *out->best_index = (int64_t)best[0];
+    FX_TRY(risk_end(c, r, d_best, best, 2, &r->last_pp_ms));
+    if (out->best_index) *out->best_index = risk_winner(q, best[0]);
     if (out->best_cost) memcpy(out->best_cost, &best[1], sizeof(double));
     return FX_OK;
 }
 
-// The same pass over every candidate of several agents in ONE call (fxplan.h).  Per agent the checks and
-// records of the call above; then all records and all tables in one staging buffer each, the rounds of fx_item_rounds (fx_pass.h)
-// over one scratch, and per round two launches whatever the agent count.  Runtime calls of a call with R rounds: 1 drain
-// (a synchronisation), 2 copies up (records, tables), 2 event records, 2 R + 1 launches, 3 copies down (prob, total, best),
-// 1 synchronisation -- none of them per agent.
-static std::atomic<long long> fx_predprob_scratch_forced{0};
-extern "C" void fx_predprob_set_scratch_limit(int64_t bytes) { fx_predprob_scratch_forced.store(bytes > 0 ? bytes : 0, std::memory_order_relaxed); }
+// ---- Several agents in ONE call (fxplan.h; DESIGN.md sections 18 to 21) ----
+// The four entries at the end make the same call, each for its pass, out of these pieces: batch_front (the refusals that need no
+// device, then the per-agent entry's own checks agent by agent); RiskStage (ONE staging buffer for everything the kernels read and
+// one copy up); risk_put_agent / risk_put_cost (what an agent uploads); risk_item_share (its steps per chunk and scratch share);
+// fx_item_rounds and fx_item_table (fx_pass.h: the rounds over one scratch, the rows' and rounds' sizes, the capacity refusals);
+// risk_block; risk_fill_rows; risk_cost_fill; risk_end and risk_winner.  None of them makes a runtime call per agent.
 
-extern "C" int32_t fx_eval_prediction_prob_batch(FxContext *c, int32_t n_agents, const int32_t *agents, const FxPredProbParams *params,
-                                                 const FxPredProbBatchOutputs *out) {
+// The front of a call: the refusals in the order the entries report them.  missing: what of the call's own arguments is NULL, or
+// null; no_launcher: the launcher the library was linked without, or null; name_agent: the refusal of a context without an
+// evaluated step names the first agent; current: the call needs the inputs of the last evaluation (fx_inputs_current).  check is
+// the per-agent entry's check of agent `agent`, the i-th of the call, into q[i]; its refusal is reported as "agent <agent>: ...".
+// n_agents == 0 returns FX_OK with nothing touched: the caller returns then too.
+template <class Check>
+static int batch_front(FxContext *c, const char *missing, int32_t n_agents, const int32_t *agents, const char *no_launcher, bool name_agent,
+                       bool current, std::vector<RiskPass> &q, Check check) {
     if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
-    if (!params || !out) return set_err(FX_ERR_INVALID_ARGUMENT, "params or out is NULL");
+    if (missing) return set_err(FX_ERR_INVALID_ARGUMENT, "%s", missing);
     if (n_agents < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d", n_agents);
     if (n_agents == 0) return FX_OK;
-    if (!fx_launch_predprob_batch || !fx_predprob_chunk_steps) return set_err(FX_ERR_HIP, "built without the batched prediction-probability launcher");
-    if (!c->evaluated) return set_err(FX_ERR_NOT_READY, "no evaluated plan step");
+    if (no_launcher) return set_err(FX_ERR_HIP, "built without the batched %s launcher", no_launcher);
+    const int32_t agent0 = agents ? agents[0] : 0;
+    if (!c->evaluated)
+        return name_agent ? set_err(FX_ERR_NOT_READY, "agent %d: no evaluated plan step", agent0) : set_err(FX_ERR_NOT_READY, "no evaluated plan step");
     if (n_agents > c->n_agents) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d of %d uploaded agents", n_agents, c->n_agents);
-    const size_t A = (size_t)n_agents;
-    std::vector<RiskPass> q(A);
-    std::vector<int> n_pred(A);
+    // (a batch is made behind a plan step of all its agents: inputs rewritten since belong to a step that has not run)
+    if (current && !fx_inputs_current(c))
+        return set_err(FX_ERR_NOT_READY, "agent %d: the inputs were rewritten since the last evaluation (fx_update_state): evaluate first", agent0);
+    q.resize((size_t)n_agents);
     std::vector<char> listed((size_t)c->n_agents, 0);
-    for (size_t i = 0; i < A; i++) {
+    for (size_t i = 0; i < q.size(); i++) {
         const int32_t agent = agents ? agents[i] : (int32_t)i;
         if (agent >= 0 && agent < c->n_agents && listed[agent]) return set_err(FX_ERR_INVALID_ARGUMENT, "agent %d listed twice", agent);
-        if (const int rc = predprob_check(q[i], c, agent, params + i, 0, nullptr, true, n_pred[i])) {
+        if (const int rc = check(q[i], i, agent)) {
             char why[sizeof(g_err)];
             snprintf(why, sizeof(why), "%s", g_err);
             return set_err(rc, "agent %d: %s", agent, why);
         }
-        listed[agent] = 1;
+        listed[agent] = 1;   // (the check has refused an agent out of range)
     }
-    // records of all agents in one buffer; one candidate's share of the scratch: a probability per (obstacle, step), none where
-    // no item runs
-    std::vector<double> rec, one;
-    std::vector<size_t> rec_at(A), out_at(A);
+    return FX_OK;
+}
+
+// The ONE staging buffer of a call, every part 16-byte aligned and at least 8 bytes; offsets count from its start, and the
+// device's copy lies at the start of the block.
+struct RiskStage {
+    std::vector<char> bytes;
+    size_t room(size_t n) { const size_t o = bytes.size(); bytes.resize(o + align_up(std::max<size_t>(n, 8), 16), 0); return o; }
+    size_t put(const void *src, size_t n) { const size_t o = room(n); if (n) memcpy(bytes.data() + o, src, n); return o; }
+    template <class T> size_t put(const std::vector<T> &v) { return put(v.data(), sizeof(T) * v.size()); }
+};
+
+// What every agent of a risk pass uploads (risk_stage, for one agent): its FxRiskParams, records and obstacle tables, and its id
+// list or the list's positions in its sparse set.  rec: the records' buffer, reused from agent to agent.
+struct RiskAgentAt { size_t prm, rec, obs, pos, yaw, v, ids; };
+static RiskAgentAt risk_put_agent(RiskStage &st, const RiskPass &p, std::vector<double> &rec) {
+    const FxRiskAgent &a = *p.a;
+    RiskAgentAt t{};
+    t.prm = st.put(p.prm, sizeof(FxRiskParams));
+    if (p.K > 0) {   // (without an obstacle no kernel reads any of these)
+        build_records(a, p.S, p.maha, rec);
+        t.rec = st.put(rec), t.obs = st.put(a.obs), t.pos = st.put(a.pos), t.yaw = st.put(a.yaw), t.v = st.put(a.v);
+    }
+    if (p.ids) t.ids = st.put(p.sparse ? p.pos.data() : p.ids, sizeof(int64_t) * (size_t)p.n);
+    return t;
+}
+// ... and what its cost pass uploads on top (risk_stage and risk_cost_args, for one agent): the caller's boundary harm and
+// responsibility vector, the reach-set tables; it counts the latter into p
+struct RiskCostAt { size_t bh, resp, eobs, eoff, pst, voff, vert; };
+static RiskCostAt risk_put_cost(RiskStage &st, RiskPass &p, const FxRiskCostParams *cp) {
+    const FxRiskAgent &a = *p.a;
+    RiskCostAt t{};
+    if (cp->boundary_mode == FX_RISK_BOUNDARY_ARRAY) t.bh = st.put(cp->boundary_harm, sizeof(double) * (size_t)p.n);
+    if (cp->responsibility_mode == FX_RISK_RESP_ACTION_SPACE && p.K > 0) t.resp = st.put(cp->responsibility, sizeof(double) * p.K);
+    if (cp->responsibility_mode == FX_RISK_RESP_REACH_SET) {
+        p.nE = a.rs_obs.size(), p.nP = a.rs_step.size(), p.nV = a.rs_verts.size() / 2;
+        t.eobs = st.put(a.rs_obs), t.eoff = st.put(a.rs_off), t.pst = st.put(a.rs_step), t.voff = st.put(a.rs_voff), t.vert = st.put(a.rs_verts);
+    }
+    return t;
+}
+
+// Steps per chunk of an agent's items from its OWN size, as the per-agent entry chooses them, and one candidate's share of the
+// scratch -- nv partials per (obstacle, chunk) -- none where the agent runs no item (K = 0 or S = 1)
+struct RiskItemShare {
+    int32_t cs, chunks;
+    int64_t per_tile;   // items per tile of 64 candidates
+};
+static FxItemAgent risk_item_share(const RiskPass &p, int nv, RiskItemShare &sh) {
+    const bool items = p.K > 0 && p.S > 1;
+    sh.cs = fx_risk_items_chunk_steps(p.n, p.S, p.K);
+    sh.chunks = (std::max(p.S - 1, 1) + sh.cs - 1) / sh.cs;
+    sh.per_tile = items ? (int64_t)sh.chunks * p.K : 0;
+    return FxItemAgent{p.n, items ? sizeof(double) * (size_t)nv * (size_t)p.K * (size_t)sh.chunks : 0};
+}
+
+// an agent of a batched risk pass: where its parts lie in the stage, its items, and its rows of the call's outputs (in doubles)
+struct RiskBatchAgent {
+    RiskAgentAt at;
+    RiskCostAt cost;
+    RiskItemShare sh;
+    size_t out_at, col_at;   // of [n] per agent; of [4][K][n] per agent
+    int ci;                  // its place among the agents with a cost pass, -1 without one
+    size_t cout_at;          // of [n] per agent with a cost pass
+};
+
+static std::atomic<long long> fx_predprob_scratch_forced{0};
+extern "C" void fx_predprob_set_scratch_limit(int64_t bytes) { fx_predprob_scratch_forced.store(bytes > 0 ? bytes : 0, std::memory_order_relaxed); }
+static std::atomic<unsigned long long> fx_risk_batch_scratch_forced{0};
+extern "C" void fx_risk_batch_set_scratch_limit(size_t bytes) { fx_risk_batch_scratch_forced.store(bytes, std::memory_order_relaxed); }
+
+// the rounds and the table of a batched risk pass from its agents' shares
+static int risk_batch_table(const std::vector<FxItemAgent> &ia, const std::vector<RiskBatchAgent> &ag, std::vector<FxItemSegment> &segs,
+                            FxItemTable &tab) {
+    const unsigned long long forced = fx_risk_batch_scratch_forced.load(std::memory_order_relaxed);
+    segs = fx_item_rounds(ia.data(), (int)ia.size(), forced ? (size_t)forced : FX_ITEM_SCRATCH_BYTES);
+    std::vector<int64_t> per_tile(segs.size());
+    for (size_t k = 0; k < segs.size(); k++) per_tile[k] = ag[segs[k].agent].sh.per_tile;
+    return fx_item_table(segs, ia.data(), (int)ia.size(), per_tile.data(), tab);
+}
+
+// The device tables of a call in the stage: room for them while the stage is laid out, and -- the block is there, the rows have
+// their pointers -- their contents and where the device's copy has them (d_stage: its start)
+struct BatchTableAt { size_t rows, item0, fin0, arow; };
+template <class Row>
+static BatchTableAt batch_table_room(RiskStage &st, size_t R, size_t A) {
+    BatchTableAt t;
+    t.rows = st.room(sizeof(Row) * R), t.item0 = st.room(sizeof(int64_t) * R), t.fin0 = st.room(sizeof(int32_t) * R);
+    t.arow = st.room(sizeof(int32_t) * A);
+    return t;
+}
+template <class Row>
+static BatchTable<Row> batch_table_put(RiskStage &st, const BatchTableAt &t, const std::vector<Row> &rows, const FxItemTable &tab,
+                                       const char *d_stage) {
+    const size_t R = rows.size(), A = tab.agent_row.size();
+    if (R) {
+        memcpy(st.bytes.data() + t.rows, rows.data(), sizeof(Row) * R);
+        memcpy(st.bytes.data() + t.item0, tab.item0.data(), sizeof(int64_t) * R);
+        memcpy(st.bytes.data() + t.fin0, tab.fin0.data(), sizeof(int32_t) * R);
+    }
+    memcpy(st.bytes.data() + t.arow, tab.agent_row.data(), sizeof(int32_t) * A);
+    return BatchTable<Row>{reinterpret_cast<const Row *>(d_stage + t.rows), reinterpret_cast<const int64_t *>(d_stage + t.item0),
+                           reinterpret_cast<const int32_t *>(d_stage + t.fin0), reinterpret_cast<const int32_t *>(d_stage + t.arow), (int32_t)A};
+}
+
+// The rows of a batched risk pass: each segment's counts from the table and its agent's pointers from where the agent's parts lie
+// in the device's copy of the stage (d_stage), its segment of the round's scratch (d_part) and its rows of the call's outputs
+// (occ, col: null in the plain pass).  need: the flags a candidate of an agent without a list needs.
+static std::vector<RiskBatchRow> risk_fill_rows(const std::vector<FxItemSegment> &segs, const FxItemTable &tab, const std::vector<RiskPass> &q,
+                                                const std::vector<RiskBatchAgent> &ag, uint32_t need, char *d_stage, char *d_part,
+                                                double *ego, double *obst, double *occ, double *col) {
+    std::vector<RiskBatchRow> rows(segs.size(), RiskBatchRow{});
+    auto D = [&](size_t o) { return reinterpret_cast<double *>(d_stage + o); };
+    for (size_t k = 0; k < segs.size(); k++) {
+        const FxItemSegment &g = segs[k];
+        const RiskPass &p = q[g.agent];
+        const RiskBatchAgent &b = ag[g.agent];
+        const RiskAgentAt &t = b.at;
+        RiskBatchRow &w = rows[k];
+        w.w = RiskWalkArgs{p.planes, p.ld, p.S, p.n, p.ids ? reinterpret_cast<const int64_t *>(d_stage + t.ids) : nullptr, p.flags,
+                           D(t.rec), D(t.obs), D(t.pos), D(t.yaw), D(t.v), p.K, p.P};
+        w.it.params = reinterpret_cast<const FxRiskParams *>(d_stage + t.prm);
+        w.it.part = reinterpret_cast<double *>(d_part + g.scratch_off);
+        w.it.nb = tab.nb[k], w.it.cs = b.sh.cs, w.it.chunks = b.sh.chunks, w.it.need = need;
+        w.first = g.first, w.count = g.count;
+        w.item0 = tab.item0[k], w.fin0 = tab.fin0[k], w.items = b.sh.per_tile ? 1 : 0;
+        w.ego = ego + b.out_at, w.obst = obst + b.out_at, w.occ = occ ? occ + b.out_at : nullptr;
+        w.col = col ? col + b.col_at : nullptr;
+    }
+    return rows;
+}
+
+// where the parts of an agent's cost pass lie in a batched call: in the device's copy of the stage, but for its columns and outputs
+static RiskCostPtrs risk_batch_cost_ptrs(const char *d_stage, const RiskPass &p, const RiskBatchAgent &b, const double *col, double *out) {
+    auto D = [&](size_t o) { return reinterpret_cast<const double *>(d_stage + o); };
+    auto I = [&](size_t o) { return reinterpret_cast<const int32_t *>(d_stage + o); };
+    return RiskCostPtrs{col, p.ids ? reinterpret_cast<const int64_t *>(d_stage + b.at.ids) : nullptr, D(b.cost.bh), D(b.cost.resp),
+                        I(b.cost.eobs), I(b.cost.eoff), I(b.cost.pst), I(b.cost.voff), D(b.cost.vert), out};
+}
+
+// The prediction-probability pass over every candidate of several agents: the checks of
+// fx_eval_prediction_prob_agent (predprob_check); the stage holds the records of the agents that run items and the tables; a
+// row's steps per chunk come from its ROUND's tiles x obstacles, not from its agent.  Runtime calls of a call with R rounds: 1
+// drain (a synchronisation), 1 ensure of the block, 1 copy up, 2 event records, 2 R + 1 launches, 3 copies down (prob, total,
+// best), 1 synchronisation.
+extern "C" int32_t fx_eval_prediction_prob_batch(FxContext *c, int32_t n_agents, const int32_t *agents, const FxPredProbParams *params,
+                                                 const FxPredProbBatchOutputs *out) {
+    std::vector<RiskPass> q;
+    std::vector<int> n_pred;   // (sized in the check: the front has accepted n_agents by then)
+    const int rc = batch_front(c, (!params || !out) ? "params or out is NULL" : nullptr, n_agents, agents,
+                               (fx_launch_predprob_batch && fx_predprob_chunk_steps) ? nullptr : "prediction-probability", false, false, q,
+                               [&](RiskPass &p, size_t i, int32_t agent) {
+        n_pred.resize(q.size());
+        return predprob_check(p, c, agent, params + i, 0, nullptr, true, n_pred[i]);
+    });
+    if (rc || n_agents == 0) return rc;
+    const size_t A = (size_t)n_agents;
+    // one candidate's share of the scratch: a probability per (obstacle, step), none where no item runs
+    RiskStage st;
+    std::vector<double> rec;
+    std::vector<size_t> rec_at(A, 0), out_at(A);
     std::vector<FxItemAgent> ia(A);
     size_t rows_out = 0;
     for (size_t i = 0; i < A; i++) {
         const RiskPass &p = q[i];
-        rec_at[i] = rec.size();
         out_at[i] = rows_out;
         rows_out += (size_t)p.n;
         const bool items = params[i].source == FX_PRED_SOURCE_PROBABILITY && p.K > 0 && p.S > 1;
         if (items) {
-            build_records(*p.a, p.S, false, one);
-            rec.insert(rec.end(), one.begin(), one.end());
+            build_records(*p.a, p.S, false, rec);
+            rec_at[i] = st.put(rec);
         }
         ia[i] = FxItemAgent{p.n, items ? sizeof(double) * (size_t)p.K * (size_t)(p.S - 1) : 0};
     }
     const long long forced = fx_predprob_scratch_forced.load(std::memory_order_relaxed);
-    const size_t limit = forced > 0 ? (size_t)forced : FX_ITEM_SCRATCH_BYTES;
-    const std::vector<FxItemSegment> segs = fx_item_rounds(ia.data(), n_agents, limit);
+    const std::vector<FxItemSegment> segs = fx_item_rounds(ia.data(), n_agents, forced > 0 ? (size_t)forced : FX_ITEM_SCRATCH_BYTES);
     const size_t R = segs.size();
-    const int n_rounds = R ? segs.back().round + 1 : 0;
-    // the rounds' sizes: tiles x obstacles of all rows choose the chunk steps of each (fx_item_chunk_steps), the largest scratch
-    std::vector<PredProbRound> rounds((size_t)n_rounds, PredProbRound{0, 0, 0, 0});
-    std::vector<int64_t> tile_obst((size_t)n_rounds, 0);
-    size_t scratch = 0;
+    // the tiles x obstacles of all rows of a round choose the steps per chunk of each (fx_item_chunk_steps): as the candidates of
+    // ONE obstacle, so that the rule sees the launch, not the agent
+    std::vector<int64_t> tile_obst(R ? (size_t)segs.back().round + 1 : 0, 0), per_tile(R);
+    std::vector<int32_t> cs(R), chunks(R);
+    for (const FxItemSegment &g : segs)
+        if (ia[g.agent].per_candidate_bytes) tile_obst[g.round] += (g.count + 63) / 64 * q[g.agent].K;
     for (size_t k = 0; k < R; k++) {
-        const FxItemSegment &g = segs[k];
-        const size_t tiles = (size_t)(g.count + 63) / 64;
-        if (ia[g.agent].per_candidate_bytes) tile_obst[g.round] += (int64_t)tiles * q[g.agent].K;
-        scratch = std::max(scratch, g.scratch_off + tiles * 64 * ia[g.agent].per_candidate_bytes);
+        const RiskPass &p = q[segs[k].agent];
+        cs[k] = fx_predprob_chunk_steps(64 * tile_obst[segs[k].round], p.S, 1);
+        chunks[k] = ia[segs[k].agent].per_candidate_bytes ? (std::max(p.S - 1, 1) + cs[k] - 1) / cs[k] : 0;
+        per_tile[k] = (int64_t)chunks[k] * p.K;
     }
+    FxItemTable tab;
+    FX_TRY(fx_item_table(segs, ia.data(), n_agents, per_tile.data(), tab));
+    const BatchTableAt t_at = batch_table_room<PredProbRow>(st, R, A);
     FxBlockLayout lay;
-    const size_t o_rec = lay.take(sizeof(double) * rec.size());
-    const size_t t_rows = 0, t_item0 = align_up(sizeof(PredProbRow) * R, 8), t_fin0 = t_item0 + sizeof(int64_t) * R,
-                 t_arow = t_fin0 + sizeof(int32_t) * R, t_size = t_arow + sizeof(int32_t) * A;
-    const size_t o_tab = lay.take(t_size), o_step = lay.take(scratch);
+    const size_t o_stage = lay.take(st.bytes.size()), o_step = lay.take(tab.scratch);
     const size_t o_prob = lay.take(sizeof(double) * rows_out), o_tot = lay.take(sizeof(double) * rows_out);
     const size_t o_best = lay.take(2 * sizeof(long long) * A);
     FxRiskState *r = q[0].r;
-    HIP_TRY(hipSetDevice(c->device));
-    FX_TRY(fx_drain(c));
-    FX_TRY(r->block.ensure(lay.size()));
-    FX_TRY(r->ev.ensure());
-    char *base = r->block;
+    char *base;
+    FX_TRY(risk_block(c, r, lay.size(), base));
     auto D = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
-    std::vector<char> tab(t_size, 0);
-    PredProbRow *rows = reinterpret_cast<PredProbRow *>(tab.data() + t_rows);
-    int64_t *item0 = reinterpret_cast<int64_t *>(tab.data() + t_item0);
-    int32_t *fin0 = reinterpret_cast<int32_t *>(tab.data() + t_fin0), *agent_row = reinterpret_cast<int32_t *>(tab.data() + t_arow);
-    for (size_t i = 0; i < A; i++) agent_row[i] = -1;
+    std::vector<PredProbRow> rows(R, PredProbRow{});
     for (size_t k = 0; k < R; k++) {
         const FxItemSegment &g = segs[k];
-        const RiskPass &p = q[g.agent];
-        PredProbRound &rd = rounds[g.round];
-        if (rd.n_rows == 0) rd.row0 = (int32_t)k;
-        rd.n_rows++;
         PredProbRow &w = rows[k];
-        predprob_args(p, params + g.agent, n_pred[g.agent], w.a);
-        w.a.ids = nullptr, w.a.rec = D(o_rec) + rec_at[g.agent];
-        w.a.step = reinterpret_cast<double *>(base + o_step + g.scratch_off), w.a.nb = (g.count + 63) / 64 * 64;
+        predprob_args(q[g.agent], params + g.agent, n_pred[g.agent], w.a);
+        w.a.ids = nullptr, w.a.rec = D(o_stage + rec_at[g.agent]);
+        w.a.step = D(o_step + g.scratch_off), w.a.nb = tab.nb[k];
         w.a.prob = D(o_prob) + out_at[g.agent], w.a.prob_obs = nullptr, w.a.total = D(o_tot) + out_at[g.agent];
         w.first = g.first, w.count = g.count;
-        const bool items = ia[g.agent].per_candidate_bytes != 0;
-        // (the round's tiles x obstacles as the candidates of ONE obstacle: the rule then sees the launch, not the agent)
-        w.cs = fx_predprob_chunk_steps(64 * tile_obst[g.round], p.S, 1);
-        w.chunks = items ? (std::max(p.S - 1, 1) + w.cs - 1) / w.cs : 0;
-        w.item0 = item0[k] = rd.items;
-        w.fin0 = fin0[k] = rd.fin_blocks;
-        rd.items += (w.a.nb / 64) * w.chunks * (int64_t)p.K;
-        rd.fin_blocks += (int32_t)((g.count + 255) / 256);
-        agent_row[g.agent] = (int32_t)k;
+        w.cs = cs[k], w.chunks = chunks[k];
+        w.item0 = tab.item0[k], w.fin0 = tab.fin0[k];
     }
-    for (const PredProbRound &rd : rounds)
-        if (rd.items > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld items", (long long)rd.items);
-    if (!rec.empty()) HIP_TRY(hipMemcpyAsync(base + o_rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_tab, tab.data(), t_size, hipMemcpyHostToDevice, c->stream));
-    PredProbBatchArgs t{};
-    t.rows = reinterpret_cast<const PredProbRow *>(base + o_tab + t_rows);
-    t.item0 = reinterpret_cast<const int64_t *>(base + o_tab + t_item0);
-    t.fin0 = reinterpret_cast<const int32_t *>(base + o_tab + t_fin0);
-    t.agent_row = reinterpret_cast<const int32_t *>(base + o_tab + t_arow);
-    t.n_agents = n_agents;
+    const PredProbBatchArgs t = batch_table_put(st, t_at, rows, tab, base + o_stage);
+    HIP_TRY(hipMemcpyAsync(base + o_stage, st.bytes.data(), st.bytes.size(), hipMemcpyHostToDevice, c->stream));
     long long *d_best = reinterpret_cast<long long *>(base + o_best);
-    HIP_TRY(fx_launch_predprob_batch(&t, rounds.data(), n_rounds, d_best, r->ev.e0, r->ev.e1, c->stream));
+    HIP_TRY(fx_launch_predprob_batch(&t, tab.rounds.data(), (int)tab.rounds.size(), d_best, r->ev.e0, r->ev.e1, c->stream));
     if (out->prob && rows_out) HIP_TRY(hipMemcpyAsync(out->prob, base + o_prob, sizeof(double) * rows_out, hipMemcpyDeviceToHost, c->stream));
     if (out->total && rows_out) HIP_TRY(hipMemcpyAsync(out->total, base + o_tot, sizeof(double) * rows_out, hipMemcpyDeviceToHost, c->stream));
     std::vector<long long> best(2 * A);
-    HIP_TRY(hipMemcpyAsync(best.data(), d_best, sizeof(long long) * 2 * A, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&r->last_pp_ms, r->ev.e0, r->ev.e1));
+    FX_TRY(risk_end(c, r, d_best, best.data(), 2 * A, &r->last_pp_ms));
     for (size_t i = 0; i < A; i++) {
-        if (out->best_index) out->best_index[i] = (int64_t)best[2 * i];
+        if (out->best_index) out->best_index[i] = risk_winner(q[i], best[2 * i]);
         if (out->best_cost) memcpy(out->best_cost + i, &best[2 * i + 1], sizeof(double));
     }
     return FX_OK;
 }
 
-// The responsibility pass over every candidate of several agents in ONE call (fxplan.h).  Per agent the checks
-// of the per-agent entry (resp_check) and its records; then everything the kernels read -- FxRiskParams, records, obstacle tables,
-// responsibility vectors, prediction entries, reach-set tables, and the rows, compact arrays and per-agent argument blocks that
-// point at them -- in ONE staging buffer and one copy; the rounds of fx_item_rounds over one scratch with each row's steps per
-// chunk chosen from its agent's OWN size, as the per-agent call chooses them.  Runtime calls of a call with R rounds: 1 drain (a
-// synchronisation), 1 ensure of the block, 1 copy up, 2 event records, 2 R + 3 launches, 5 copies down (resp, total, ego_risk,
-// obst_risk, best), 1 synchronisation -- none of them per agent.
-static std::atomic<unsigned long long> fx_risk_batch_scratch_forced{0};
-extern "C" void fx_risk_batch_set_scratch_limit(size_t bytes) { fx_risk_batch_scratch_forced.store(bytes, std::memory_order_relaxed); }
-
+// The responsibility pass over every candidate of several agents: the checks of
+// fx_eval_responsibility_cost_agent (resp_check); every agent has the cost pass resp_check made of its parameters; beside the
+// shared parts the stage holds the prediction entries and the per-agent argument blocks of the cost kernel and the re-sum.
+// Runtime calls of a call with R rounds: 1 drain (a synchronisation), 1 ensure of the block, 1 copy up, 2 event records, 2 R + 3
+// launches, 5 copies down (resp, total, ego_risk, obst_risk, best), 1 synchronisation.
 extern "C" int32_t fx_eval_responsibility_cost_batch(FxContext *c, int32_t n_agents, const int32_t *agents, const FxRiskParams *params,
                                                      const FxRespCostParams *resp, const FxRespCostBatchOutputs *out) {
-    if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
-    if (!params || !resp || !out) return set_err(FX_ERR_INVALID_ARGUMENT, "params, resp or out is NULL");
-    if (n_agents < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d", n_agents);
-    if (n_agents == 0) return FX_OK;
-    if (!fx_launch_risk_batch) return set_err(FX_ERR_HIP, "built without the batched responsibility launcher");
-    const int32_t agent0 = agents ? agents[0] : 0;
-    if (!c->evaluated) return set_err(FX_ERR_NOT_READY, "agent %d: no evaluated plan step", agent0);
-    if (n_agents > c->n_agents) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d of %d uploaded agents", n_agents, c->n_agents);
-    const size_t A = (size_t)n_agents;
-    const bool have_out = out->resp && out->total && out->ego_risk && out->obst_risk && out->best_index && out->best_cost;
-    std::vector<RiskPass> q(A);
-    std::vector<FxRiskCostParams> cost(A);
-    std::vector<char> listed((size_t)c->n_agents, 0);
-    for (size_t i = 0; i < A; i++) {
-        const int32_t agent = agents ? agents[i] : (int32_t)i;
-        if (agent >= 0 && agent < c->n_agents && listed[agent]) return set_err(FX_ERR_INVALID_ARGUMENT, "agent %d listed twice", agent);
-        if (const int rc = resp_check(q[i], c, agent, params + i, resp + i, 0, nullptr, have_out, cost[i])) {
-            char why[sizeof(g_err)];
-            snprintf(why, sizeof(why), "%s", g_err);
-            return set_err(rc, "agent %d: %s", agent, why);
-        }
-        listed[agent] = 1;   // (without ids risk_check has refused a step that stored no bundle)
-    }
-    // ONE staging buffer, every part 16-byte aligned; the device's copy lies at o_stage of the block
-    std::vector<char> stage;
-    auto room = [&](size_t bytes) { const size_t o = stage.size(); stage.resize(o + align_up(std::max<size_t>(bytes, 8), 16), 0); return o; };
-    auto put = [&](const void *src, size_t bytes) { const size_t o = room(bytes); if (bytes) memcpy(stage.data() + o, src, bytes); return o; };
-    struct Parts { size_t prm, rec, obs, pos, yaw, v, resp, pred, eobs, eoff, pst, voff, vert, out_at, col_at; bool items, has_pred; };
-    std::vector<Parts> at(A);
+    std::vector<RiskPass> q;
+    std::vector<FxRiskCostParams> cost;   // (sized in the check: the front has accepted n_agents by then)
+    const bool have_out = out && out->resp && out->total && out->ego_risk && out->obst_risk && out->best_index && out->best_cost;
+    const int rc = batch_front(c, (!params || !resp || !out) ? "params, resp or out is NULL" : nullptr, n_agents, agents,
+                               fx_launch_risk_batch ? nullptr : "responsibility", true, false, q, [&](RiskPass &p, size_t i, int32_t agent) {
+        cost.resize(q.size());
+        return resp_check(p, c, agent, params + i, resp + i, 0, nullptr, have_out, cost[i]);   // (without ids it refuses a step that stored no bundle)
+    });
+    if (rc || n_agents == 0) return rc;
+    const size_t A = (size_t)n_agents, none = ~(size_t)0;
+    RiskStage st;
+    std::vector<RiskBatchAgent> ag(A);
     std::vector<RespSumArgs> sums(A);
     std::vector<FxItemAgent> ia(A);
-    std::vector<int32_t> cs(A), chunks(A), blk0(A);
+    std::vector<int32_t> blk0(A);
+    std::vector<size_t> pred_at(A, none);
     std::vector<double> rec;
     size_t rows_out = 0, col_doubles = 0;
     int64_t blocks = 0;
     for (size_t i = 0; i < A; i++) {
         RiskPass &p = q[i];
-        const FxRiskAgent &a = *p.a;
-        Parts &t = at[i];
-        t = Parts{};
-        t.out_at = rows_out, t.col_at = col_doubles;
+        RiskBatchAgent &b = ag[i];
+        b.out_at = b.cout_at = rows_out, b.col_at = col_doubles, b.ci = (int)i;
         rows_out += (size_t)p.n;
         col_doubles += 4 * (size_t)p.K * (size_t)p.n;
         blk0[i] = (int32_t)blocks;
         blocks += (p.n + 255) / 256;
-        t.prm = put(p.prm, sizeof(FxRiskParams));
-        if (p.K > 0) {
-            build_records(a, p.S, p.maha, rec);
-            t.rec = put(rec.data(), sizeof(double) * rec.size()), t.obs = put(a.obs.data(), sizeof(double) * a.obs.size());
-            t.pos = put(a.pos.data(), sizeof(double) * a.pos.size()), t.yaw = put(a.yaw.data(), sizeof(double) * a.yaw.size());
-            t.v = put(a.v.data(), sizeof(double) * a.v.size());
-            if (resp[i].responsibility_mode == FX_RISK_RESP_ACTION_SPACE) t.resp = put(resp[i].responsibility, sizeof(double) * p.K);
-        }
-        if (resp[i].responsibility_mode == FX_RISK_RESP_REACH_SET) {
-            p.nE = a.rs_obs.size(), p.nP = a.rs_step.size(), p.nV = a.rs_verts.size() / 2;
-            t.eobs = put(a.rs_obs.data(), sizeof(int32_t) * p.nE), t.eoff = put(a.rs_off.data(), sizeof(int32_t) * a.rs_off.size());
-            t.pst = put(a.rs_step.data(), sizeof(int32_t) * p.nP), t.voff = put(a.rs_voff.data(), sizeof(int32_t) * a.rs_voff.size());
-            t.vert = put(a.rs_verts.data(), sizeof(double) * a.rs_verts.size());
-        }
+        b.at = risk_put_agent(st, p, rec);
+        b.cost = risk_put_cost(st, p, &cost[i]);
         resp_sum_fill(p, resp + i, sums[i]);
-        t.has_pred = resp[i].prediction && sums[i].n_pred >= 0 && p.n > 0;
-        if (t.has_pred) t.pred = put(resp[i].prediction, sizeof(double) * (size_t)p.n);
-        // steps per chunk from the agent's OWN size: what fx_eval_responsibility_cost_agent chooses for it
-        t.items = p.K > 0 && p.S > 1;
-        cs[i] = fx_risk_items_chunk_steps(p.n, p.S, p.K);
-        chunks[i] = (std::max(p.S - 1, 1) + cs[i] - 1) / cs[i];
-        ia[i] = FxItemAgent{p.n, t.items ? sizeof(double) * 7 * (size_t)p.K * (size_t)chunks[i] : 0};
+        if (resp[i].prediction && sums[i].n_pred >= 0 && p.n > 0) pred_at[i] = st.put(resp[i].prediction, sizeof(double) * (size_t)p.n);
+        ia[i] = risk_item_share(p, 7, b.sh);
     }
     if (blocks > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "%lld workgroups of candidates", (long long)blocks);
-    const unsigned long long forced = fx_risk_batch_scratch_forced.load(std::memory_order_relaxed);
-    const std::vector<FxItemSegment> segs = fx_item_rounds(ia.data(), n_agents, forced ? (size_t)forced : FX_ITEM_SCRATCH_BYTES);
-    const size_t R = segs.size();
-    const int n_rounds = R ? segs.back().round + 1 : 0;
-    std::vector<RiskBatchRound> rounds((size_t)n_rounds, RiskBatchRound{0, 0, 0, 0});
-    const size_t t_rows = room(sizeof(RiskBatchRow) * R), t_item0 = room(sizeof(int64_t) * R), t_fin0 = room(sizeof(int32_t) * R),
-                 t_cost = room(sizeof(RiskCostArgs) * A), t_sum = room(sizeof(RespSumArgs) * A), t_blk0 = put(blk0.data(), sizeof(int32_t) * A);
-    size_t scratch = 0;
-    for (size_t k = 0; k < R; k++) {   // the rows' counts (their pointers follow when the block is there)
-        const FxItemSegment &g = segs[k];
-        const size_t tiles = (size_t)(g.count + 63) / 64;
-        RiskBatchRound &rd = rounds[g.round];
-        RiskBatchRow w{};
-        if (rd.n_rows == 0) rd.row0 = (int32_t)k;
-        rd.n_rows++;
-        w.first = g.first, w.count = g.count;
-        w.it.nb = (int64_t)tiles * 64, w.it.cs = cs[g.agent], w.it.chunks = chunks[g.agent], w.it.need = FX_FLAG_COSTED;
-        w.items = at[g.agent].items ? 1 : 0;
-        w.item0 = rd.items;
-        w.fin0 = rd.fin_blocks;
-        if (w.items) rd.items += (int64_t)tiles * chunks[g.agent] * (int64_t)q[g.agent].K;
-        rd.fin_blocks += (int32_t)((g.count + 255) / 256);
-        scratch = std::max(scratch, g.scratch_off + tiles * 64 * ia[g.agent].per_candidate_bytes);
-        memcpy(stage.data() + t_rows + sizeof(RiskBatchRow) * k, &w, sizeof(w));
-        memcpy(stage.data() + t_item0 + sizeof(int64_t) * k, &w.item0, sizeof(int64_t));
-        memcpy(stage.data() + t_fin0 + sizeof(int32_t) * k, &w.fin0, sizeof(int32_t));
-    }
-    for (const RiskBatchRound &rd : rounds)
-        if (rd.items > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld items", (long long)rd.items);
+    std::vector<FxItemSegment> segs;
+    FxItemTable tab;
+    FX_TRY(risk_batch_table(ia, ag, segs, tab));
+    const BatchTableAt t_at = batch_table_room<RiskBatchRow>(st, segs.size(), A);
+    const size_t t_cost = st.room(sizeof(RiskCostArgs) * A), t_sum = st.room(sizeof(RespSumArgs) * A), t_blk0 = st.put(blk0);
     FxBlockLayout lay;
-    const size_t o_stage = lay.take(stage.size()), o_part = lay.take(scratch), o_col = lay.take(sizeof(double) * col_doubles);
+    const size_t o_stage = lay.take(st.bytes.size()), o_part = lay.take(tab.scratch), o_col = lay.take(sizeof(double) * col_doubles);
     const size_t o_ego = lay.take(sizeof(double) * rows_out), o_obst = lay.take(sizeof(double) * rows_out), o_occ = lay.take(sizeof(double) * rows_out);
     const size_t o_out = lay.take(sizeof(double) * 7 * rows_out), o_rresp = lay.take(sizeof(double) * rows_out);
     const size_t o_rtot = lay.take(sizeof(double) * rows_out), o_best = lay.take(2 * sizeof(long long) * A);
     FxRiskState *r = q[0].r;
-    HIP_TRY(hipSetDevice(c->device));
-    FX_TRY(fx_drain(c));
-    FX_TRY(r->block.ensure(lay.size()));
-    FX_TRY(r->ev.ensure());
-    char *base = r->block;
+    char *base;
+    FX_TRY(risk_block(c, r, lay.size(), base));
     auto D = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
-    std::vector<RiskWalkArgs> walk(A);
+    char *const d_stage = base + o_stage;
+    std::vector<RiskCostArgs> cas(A, RiskCostArgs{});
     for (size_t i = 0; i < A; i++) {   // the per-agent argument blocks: the cost kernel's and the re-sum's
-        RiskPass &p = q[i];
-        const Parts &t = at[i];
-        const size_t s0 = o_stage;
-        walk[i] = RiskWalkArgs{p.planes, p.ld, p.S, p.n, nullptr, p.flags, D(s0 + t.rec), D(s0 + t.obs), D(s0 + t.pos), D(s0 + t.yaw),
-                               D(s0 + t.v), p.K, p.P};
-        p.base = base;
-        p.o_col = o_col + sizeof(double) * t.col_at, p.o_out = o_out + sizeof(double) * 7 * t.out_at;
-        p.o_ids = p.o_bh = s0, p.o_resp = s0 + t.resp;
-        p.o_eobs = s0 + t.eobs, p.o_eoff = s0 + t.eoff, p.o_pst = s0 + t.pst, p.o_voff = s0 + t.voff, p.o_vert = s0 + t.vert;
-        RiskCostArgs ca{};
-        risk_cost_fill(p, &cost[i], ca);
+        const RiskPass &p = q[i];
+        const RiskBatchAgent &b = ag[i];
+        double *const po = D(o_out) + 7 * b.out_at;
+        risk_cost_fill(p, &cost[i], risk_batch_cost_ptrs(d_stage, p, b, D(o_col) + b.col_at, po), cas[i]);
         RespSumArgs &rs = sums[i];
         rs.ids = nullptr;
-        rs.resp = D(p.o_out) + 4 * (size_t)p.n;
-        rs.pred = t.has_pred ? D(s0 + t.pred) : nullptr;
-        rs.resp_out = D(o_rresp) + t.out_at, rs.total = D(o_rtot) + t.out_at;
-        memcpy(stage.data() + t_cost + sizeof(RiskCostArgs) * i, &ca, sizeof(ca));
-        memcpy(stage.data() + t_sum + sizeof(RespSumArgs) * i, &rs, sizeof(rs));
+        rs.resp = po + 4 * (size_t)p.n;
+        rs.pred = pred_at[i] != none ? reinterpret_cast<const double *>(d_stage + pred_at[i]) : nullptr;
+        rs.resp_out = D(o_rresp) + b.out_at, rs.total = D(o_rtot) + b.out_at;
     }
-    for (size_t k = 0; k < R; k++) {
-        const FxItemSegment &g = segs[k];
-        const Parts &t = at[g.agent];
-        RiskBatchRow w;
-        memcpy(&w, stage.data() + t_rows + sizeof(RiskBatchRow) * k, sizeof(w));
-        w.w = walk[g.agent];
-        w.it.params = reinterpret_cast<const FxRiskParams *>(base + o_stage + t.prm);
-        w.it.part = reinterpret_cast<double *>(base + o_part + g.scratch_off);
-        w.ego = D(o_ego) + t.out_at, w.obst = D(o_obst) + t.out_at, w.occ = D(o_occ) + t.out_at;
-        w.col = D(o_col) + t.col_at;
-        memcpy(stage.data() + t_rows + sizeof(RiskBatchRow) * k, &w, sizeof(w));
-    }
-    HIP_TRY(hipMemcpyAsync(base + o_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, c->stream));
+    memcpy(st.bytes.data() + t_cost, cas.data(), sizeof(RiskCostArgs) * A);
+    memcpy(st.bytes.data() + t_sum, sums.data(), sizeof(RespSumArgs) * A);
+    const std::vector<RiskBatchRow> rows = risk_fill_rows(segs, tab, q, ag, FX_FLAG_COSTED, d_stage, base + o_part, D(o_ego), D(o_obst),
+                                                          D(o_occ), D(o_col));
     RiskBatchArgs t{};
-    t.rows = reinterpret_cast<const RiskBatchRow *>(base + o_stage + t_rows);
-    t.item0 = reinterpret_cast<const int64_t *>(base + o_stage + t_item0);
-    t.fin0 = reinterpret_cast<const int32_t *>(base + o_stage + t_fin0);
-    t.cost = reinterpret_cast<const RiskCostArgs *>(base + o_stage + t_cost);
-    t.sum = reinterpret_cast<const RespSumArgs *>(base + o_stage + t_sum);
-    t.blk0 = reinterpret_cast<const int32_t *>(base + o_stage + t_blk0);
-    t.n_agents = n_agents, t.blocks = (int32_t)blocks;
+    t.t = batch_table_put(st, t_at, rows, tab, d_stage);
+    t.cost = reinterpret_cast<const RiskCostArgs *>(d_stage + t_cost);
+    t.sum = reinterpret_cast<const RespSumArgs *>(d_stage + t_sum);
+    t.blk0 = reinterpret_cast<const int32_t *>(d_stage + t_blk0);
+    t.blocks = (int32_t)blocks;
+    HIP_TRY(hipMemcpyAsync(d_stage, st.bytes.data(), st.bytes.size(), hipMemcpyHostToDevice, c->stream));
     long long *d_best = reinterpret_cast<long long *>(base + o_best);
-    HIP_TRY(fx_launch_risk_batch(&t, rounds.data(), n_rounds, d_best, r->ev.e0, r->ev.e1, c->stream));
+    HIP_TRY(fx_launch_risk_batch(&t, tab.rounds.data(), (int)tab.rounds.size(), d_best, r->ev.e0, r->ev.e1, c->stream));
     if (rows_out) {
         const size_t bytes = sizeof(double) * rows_out;
         HIP_TRY(hipMemcpyAsync(out->resp, base + o_rresp, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -978,257 +1040,114 @@ extern "C" int32_t fx_eval_responsibility_cost_batch(FxContext *c, int32_t n_age
         HIP_TRY(hipMemcpyAsync(out->obst_risk, base + o_obst, bytes, hipMemcpyDeviceToHost, c->stream));
     }
     std::vector<long long> best(2 * A);
-    HIP_TRY(hipMemcpyAsync(best.data(), d_best, sizeof(long long) * 2 * A, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&r->last_ms, r->ev.e0, r->ev.e1));
+    FX_TRY(risk_end(c, r, d_best, best.data(), 2 * A, &r->last_ms));
     for (size_t i = 0; i < A; i++) {
-        out->best_index[i] = (int64_t)best[2 * i];
+        out->best_index[i] = risk_winner(q[i], best[2 * i]);
         memcpy(out->best_cost + i, &best[2 * i + 1], sizeof(double));
     }
     return FX_OK;
 }
 
-// The plain risk pass -- fx_eval_risk_agent -- of several agents in ONE call, each with its own id list or none (fxplan.h; DESIGN.md
-// section 20).  Per agent the checks of the per-agent entry (risk_check: it resolves planes, ld, flags and the positions of listed
-// candidates in a sparse set) and its records; then everything the kernels read -- FxRiskParams, records, obstacle tables, id lists
-// (or sparse positions), rows and compact arrays -- in ONE staging buffer and one copy; the rounds of fx_item_rounds over one scratch
-// with each row's steps per chunk chosen from its agent's OWN list length, as the per-agent call chooses them.  Runtime calls of a
-// call with R rounds: 1 drain (a synchronisation), 1 ensure of the block, 1 copy up, 2 event records, 2 R + 1 launches, 3 copies
-// down (ego_risk, obst_risk, min_risk_index), 1 synchronisation -- none of them per agent.
+// The id list of agent i of a call with lists, or none
+static int64_t batch_n_ids(const int64_t *n_ids, size_t i) { return n_ids ? n_ids[i] : 0; }
+static const int64_t *batch_ids(const int64_t *n_ids, const int64_t *const *ids, size_t i) { return (n_ids && ids) ? ids[i] : nullptr; }
+
+// The plain risk pass of several agents, each with its own id list or none: the checks of
+// fx_eval_risk_agent (risk_check: it resolves planes, ld, flags and the positions of listed candidates in a sparse set); nothing
+// in the stage but the shared parts.  Runtime calls of a call with R rounds: 1 drain (a synchronisation), 1 ensure of the block, 1
+// copy up, 2 event records, 2 R + 1 launches, 3 copies down (ego_risk, obst_risk, min_risk_index), 1 synchronisation.
 extern "C" int32_t fx_eval_risk_batch(FxContext *c, int32_t n_agents, const int32_t *agents, const FxRiskParams *params, const int64_t *n_ids,
                                       const int64_t *const *ids, const FxRiskBatchOutputs *out) {
-    if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
-    if (!params || !out) return set_err(FX_ERR_INVALID_ARGUMENT, "params or out is NULL");
-    if (!out->ego_risk || !out->obst_risk || !out->min_risk_index) return set_err(FX_ERR_INVALID_ARGUMENT, "an output pointer is NULL");
-    if (n_agents < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d", n_agents);
-    if (n_agents == 0) return FX_OK;
-    if (!fx_launch_risk_list_batch) return set_err(FX_ERR_HIP, "built without the batched risk launcher");
-    const int32_t agent0 = agents ? agents[0] : 0;
-    if (!c->evaluated) return set_err(FX_ERR_NOT_READY, "agent %d: no evaluated plan step", agent0);
-    if (n_agents > c->n_agents) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d of %d uploaded agents", n_agents, c->n_agents);
-    // (the batch is made behind a plan step of all its agents: inputs rewritten since belong to a step that has not run)
-    if (!fx_inputs_current(c))
-        return set_err(FX_ERR_NOT_READY, "agent %d: the inputs were rewritten since the last evaluation (fx_update_state): evaluate first", agent0);
+    std::vector<RiskPass> q;
+    const char *const missing = (!params || !out) ? "params or out is NULL"
+                                : (!out->ego_risk || !out->obst_risk || !out->min_risk_index) ? "an output pointer is NULL" : nullptr;
+    const int rc = batch_front(c, missing, n_agents, agents, fx_launch_risk_list_batch ? nullptr : "risk", true, true, q,
+                               [&](RiskPass &p, size_t i, int32_t agent) {
+        return risk_check(p, c, agent, params + i, batch_n_ids(n_ids, i), batch_ids(n_ids, ids, i), true, false);
+    });
+    if (rc || n_agents == 0) return rc;
     const size_t A = (size_t)n_agents;
-    std::vector<RiskPass> q(A);
-    std::vector<char> listed((size_t)c->n_agents, 0);
-    for (size_t i = 0; i < A; i++) {
-        const int32_t agent = agents ? agents[i] : (int32_t)i;
-        if (agent >= 0 && agent < c->n_agents && listed[agent]) return set_err(FX_ERR_INVALID_ARGUMENT, "agent %d listed twice", agent);
-        const int64_t n_i = n_ids ? n_ids[i] : 0;
-        const int64_t *ids_i = (n_ids && ids) ? ids[i] : nullptr;
-        if (const int rc = risk_check(q[i], c, agent, params + i, n_i, ids_i, true, false)) {
-            char why[sizeof(g_err)];
-            snprintf(why, sizeof(why), "%s", g_err);
-            return set_err(rc, "agent %d: %s", agent, why);
-        }
-        listed[agent] = 1;
-    }
-    // ONE staging buffer, every part 16-byte aligned; the device's copy lies at o_stage of the block
-    std::vector<char> stage;
-    auto room = [&](size_t bytes) { const size_t o = stage.size(); stage.resize(o + align_up(std::max<size_t>(bytes, 8), 16), 0); return o; };
-    auto put = [&](const void *src, size_t bytes) { const size_t o = room(bytes); if (bytes) memcpy(stage.data() + o, src, bytes); return o; };
-    struct Parts { size_t prm, rec, obs, pos, yaw, v, ids, out_at; bool items; };
-    std::vector<Parts> at(A);
+    RiskStage st;
+    std::vector<RiskBatchAgent> ag(A);
     std::vector<FxItemAgent> ia(A);
-    std::vector<int32_t> cs(A), chunks(A);
     std::vector<double> rec;
     size_t rows_out = 0;
     for (size_t i = 0; i < A; i++) {
-        const RiskPass &p = q[i];
-        const FxRiskAgent &a = *p.a;
-        Parts &t = at[i];
-        t = Parts{};
-        t.out_at = rows_out;
-        rows_out += (size_t)p.n;
-        t.prm = put(p.prm, sizeof(FxRiskParams));
-        if (p.K > 0) {
-            build_records(a, p.S, p.maha, rec);
-            t.rec = put(rec.data(), sizeof(double) * rec.size()), t.obs = put(a.obs.data(), sizeof(double) * a.obs.size());
-            t.pos = put(a.pos.data(), sizeof(double) * a.pos.size()), t.yaw = put(a.yaw.data(), sizeof(double) * a.yaw.size());
-            t.v = put(a.v.data(), sizeof(double) * a.v.size());
-        }
-        if (p.ids) t.ids = put(p.sparse ? p.pos.data() : p.ids, sizeof(int64_t) * (size_t)p.n);
-        // steps per chunk from the agent's OWN list length: what fx_eval_risk_agent chooses for it
-        t.items = p.K > 0 && p.S > 1;
-        cs[i] = fx_risk_items_chunk_steps(p.n, p.S, p.K);
-        chunks[i] = (std::max(p.S - 1, 1) + cs[i] - 1) / cs[i];
-        ia[i] = FxItemAgent{p.n, t.items ? sizeof(double) * 2 * (size_t)std::max(p.K, 1) * (size_t)chunks[i] : 0};
+        RiskBatchAgent &b = ag[i];
+        b.out_at = rows_out, b.col_at = b.cout_at = 0, b.ci = -1, b.cost = RiskCostAt{};
+        rows_out += (size_t)q[i].n;
+        b.at = risk_put_agent(st, q[i], rec);
+        ia[i] = risk_item_share(q[i], 2, b.sh);
     }
-    const unsigned long long forced = fx_risk_batch_scratch_forced.load(std::memory_order_relaxed);
-    const std::vector<FxItemSegment> segs = fx_item_rounds(ia.data(), n_agents, forced ? (size_t)forced : FX_ITEM_SCRATCH_BYTES);
-    const size_t R = segs.size();
-    const int n_rounds = R ? segs.back().round + 1 : 0;
-    std::vector<RiskBatchRound> rounds((size_t)n_rounds, RiskBatchRound{0, 0, 0, 0});
-    std::vector<RiskBatchRow> rows(R);
-    std::vector<int32_t> agent_row(A, -1);
-    const size_t t_rows = room(sizeof(RiskBatchRow) * R), t_item0 = room(sizeof(int64_t) * R), t_fin0 = room(sizeof(int32_t) * R),
-                 t_arow = room(sizeof(int32_t) * A);
-    size_t scratch = 0;
-    for (size_t k = 0; k < R; k++) {   // the rows' counts (their pointers follow when the block is there)
-        const FxItemSegment &g = segs[k];
-        const size_t tiles = (size_t)(g.count + 63) / 64;
-        RiskBatchRound &rd = rounds[g.round];
-        RiskBatchRow &w = rows[k];
-        w = RiskBatchRow{};
-        if (rd.n_rows == 0) rd.row0 = (int32_t)k;
-        rd.n_rows++;
-        w.first = g.first, w.count = g.count;
-        w.it.nb = (int64_t)tiles * 64, w.it.cs = cs[g.agent], w.it.chunks = chunks[g.agent];
-        w.it.need = FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED;
-        w.items = at[g.agent].items ? 1 : 0;
-        w.item0 = rd.items;
-        w.fin0 = rd.fin_blocks;
-        if (w.items) rd.items += (int64_t)tiles * chunks[g.agent] * (int64_t)q[g.agent].K;
-        const int64_t fin = (int64_t)rd.fin_blocks + (g.count + 255) / 256;
-        if (fin > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld workgroups of candidates", (long long)fin);
-        rd.fin_blocks = (int32_t)fin;
-        scratch = std::max(scratch, g.scratch_off + tiles * 64 * ia[g.agent].per_candidate_bytes);
-        agent_row[g.agent] = (int32_t)k;
-    }
-    for (const RiskBatchRound &rd : rounds)
-        if (rd.items > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld items", (long long)rd.items);
+    std::vector<FxItemSegment> segs;
+    FxItemTable tab;
+    FX_TRY(risk_batch_table(ia, ag, segs, tab));
+    const BatchTableAt t_at = batch_table_room<RiskBatchRow>(st, segs.size(), A);
     FxBlockLayout lay;
-    const size_t o_stage = lay.take(stage.size()), o_part = lay.take(scratch);
+    const size_t o_stage = lay.take(st.bytes.size()), o_part = lay.take(tab.scratch);
     const size_t o_ego = lay.take(sizeof(double) * rows_out), o_obst = lay.take(sizeof(double) * rows_out);
     const size_t o_idx = lay.take(sizeof(long long) * A);
     FxRiskState *r = q[0].r;
-    HIP_TRY(hipSetDevice(c->device));
-    FX_TRY(fx_drain(c));
-    FX_TRY(r->block.ensure(lay.size()));
-    FX_TRY(r->ev.ensure());
-    char *base = r->block;
+    char *base;
+    FX_TRY(risk_block(c, r, lay.size(), base));
     auto D = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
-    for (size_t k = 0; k < R; k++) {
-        const FxItemSegment &g = segs[k];
-        const RiskPass &p = q[g.agent];
-        const Parts &t = at[g.agent];
-        const size_t s0 = o_stage;
-        RiskBatchRow &w = rows[k];
-        w.w = RiskWalkArgs{p.planes, p.ld, p.S, p.n, p.ids ? reinterpret_cast<const int64_t *>(base + s0 + t.ids) : nullptr, p.flags,
-                           D(s0 + t.rec), D(s0 + t.obs), D(s0 + t.pos), D(s0 + t.yaw), D(s0 + t.v), p.K, p.P};
-        w.it.params = reinterpret_cast<const FxRiskParams *>(base + s0 + t.prm);
-        w.it.part = reinterpret_cast<double *>(base + o_part + g.scratch_off);
-        w.ego = D(o_ego) + t.out_at, w.obst = D(o_obst) + t.out_at;
-        memcpy(stage.data() + t_item0 + sizeof(int64_t) * k, &w.item0, sizeof(int64_t));
-        memcpy(stage.data() + t_fin0 + sizeof(int32_t) * k, &w.fin0, sizeof(int32_t));
-    }
-    if (R) memcpy(stage.data() + t_rows, rows.data(), sizeof(RiskBatchRow) * R);
-    memcpy(stage.data() + t_arow, agent_row.data(), sizeof(int32_t) * A);
-    HIP_TRY(hipMemcpyAsync(base + o_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, c->stream));
-    RiskListBatchArgs t{};
-    t.rows = reinterpret_cast<const RiskBatchRow *>(base + o_stage + t_rows);
-    t.item0 = reinterpret_cast<const int64_t *>(base + o_stage + t_item0);
-    t.fin0 = reinterpret_cast<const int32_t *>(base + o_stage + t_fin0);
-    t.agent_row = reinterpret_cast<const int32_t *>(base + o_stage + t_arow);
-    t.n_agents = n_agents;
+    const std::vector<RiskBatchRow> rows = risk_fill_rows(segs, tab, q, ag, FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED, base + o_stage,
+                                                          base + o_part, D(o_ego), D(o_obst), nullptr, nullptr);
+    const RiskListBatchArgs t = batch_table_put(st, t_at, rows, tab, base + o_stage);
+    HIP_TRY(hipMemcpyAsync(base + o_stage, st.bytes.data(), st.bytes.size(), hipMemcpyHostToDevice, c->stream));
     long long *d_idx = reinterpret_cast<long long *>(base + o_idx);
-    HIP_TRY(fx_launch_risk_list_batch(&t, rounds.data(), n_rounds, d_idx, r->ev.e0, r->ev.e1, c->stream));
+    HIP_TRY(fx_launch_risk_list_batch(&t, tab.rounds.data(), (int)tab.rounds.size(), d_idx, r->ev.e0, r->ev.e1, c->stream));
     if (rows_out) {
         HIP_TRY(hipMemcpyAsync(out->ego_risk, base + o_ego, sizeof(double) * rows_out, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(out->obst_risk, base + o_obst, sizeof(double) * rows_out, hipMemcpyDeviceToHost, c->stream));
     }
     std::vector<long long> idx(A, -1);
-    HIP_TRY(hipMemcpyAsync(idx.data(), d_idx, sizeof(long long) * A, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&r->last_ms, r->ev.e0, r->ev.e1));
-    for (size_t i = 0; i < A; i++) {
-        // (sparse set: the arg-min ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
-        if (q[i].sparse && idx[i] >= 0) idx[i] = (long long)q[i].set.ids[idx[i]];
-        out->min_risk_index[i] = (int64_t)idx[i];
-    }
+    FX_TRY(risk_end(c, r, d_idx, idx.data(), A, &r->last_ms));
+    for (size_t i = 0; i < A; i++) out->min_risk_index[i] = risk_winner(q[i], idx[i]);
     return FX_OK;
 }
 
-// The detail and cost passes -- fx_eval_risk_costs_agent -- of several agents in ONE call, each with its own id list or none and
-// its own cost parameters or none (fxplan.h).  Per agent the checks of the per-agent entry (risk_check with
-// the detail flag, risk_cost_check) and its records; then everything the kernels read -- FxRiskParams, records, obstacle tables, id
-// lists (or sparse positions), boundary-harm arrays, responsibility vectors, reach-set tables, rows, compact arrays and the cost
-// kernel's argument blocks (risk_cost_fill) -- in ONE staging buffer and one copy; the rounds of fx_item_rounds over one scratch
-// with each row's steps per chunk chosen from its agent's OWN list length.  The columns and the principles lie per agent as the
-// per-agent kernels' functions index them ([4][K][n] and [7][n]); the caller's are concatenated per column, so a last launch lays
-// the column blocks out that way on the device, and the small principle block is laid out on the host.  Runtime calls of a call
-// with R rounds: 1 drain (a synchronisation), 1 ensure of the block, 1 copy up, 2 event records, 2 R + 4 launches (2 R + 1 where no
-// agent has cost parameters and no column is asked for), at most 9 copies down (ego_risk, obst_risk, obst_harm_occ, the four
-// columns, the principle block, the two arg-mins), 1 synchronisation -- none of them per agent.
+// The detail and cost passes of several agents, each with its own id list or none and its own cost parameters or none (DESIGN.md
+// section 21): the checks of fx_eval_risk_costs_agent (risk_check with the detail flag, risk_cost_check); beside the shared parts
+// the stage holds the cost kernel's argument blocks of the agents that have cost parameters and the column segments.  The columns
+// and the principles lie per agent as the per-agent kernels' functions index them ([4][K][n] and [7][n]); the caller's are
+// concatenated per column, so a last launch lays the column blocks out that way on the device, and the small principle block is
+// laid out on the host.  Runtime calls of a call with R rounds: 1 drain (a synchronisation), 1 ensure of the block, 1 copy up, 2
+// event records, 2 R + 4 launches (2 R + 1 where no agent has cost parameters and no column is asked for), at most 9 copies down
+// (ego_risk, obst_risk, obst_harm_occ, the four columns, the principle block, the two arg-mins), 1 synchronisation.
 extern "C" int32_t fx_eval_risk_costs_batch(FxContext *c, int32_t n_agents, const int32_t *agents, const FxRiskParams *params,
                                             const FxRiskCostParams *const *cost, const int64_t *n_ids, const int64_t *const *ids,
                                             const FxRiskCostBatchOutputs *out) {
-    if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
-    if (!params || !out) return set_err(FX_ERR_INVALID_ARGUMENT, "params or out is NULL");
-    if (n_agents < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d", n_agents);
-    if (n_agents == 0) return FX_OK;
-    if (!fx_launch_risk_costs_batch) return set_err(FX_ERR_HIP, "built without the batched risk-cost launcher");
-    const int32_t agent0 = agents ? agents[0] : 0;
-    if (!c->evaluated) return set_err(FX_ERR_NOT_READY, "agent %d: no evaluated plan step", agent0);
-    if (n_agents > c->n_agents) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d of %d uploaded agents", n_agents, c->n_agents);
-    // (the batch is made behind a plan step of all its agents: inputs rewritten since belong to a step that has not run)
-    if (!fx_inputs_current(c))
-        return set_err(FX_ERR_NOT_READY, "agent %d: the inputs were rewritten since the last evaluation (fx_update_state): evaluate first", agent0);
+    std::vector<RiskPass> q;
+    const int rc = batch_front(c, (!params || !out) ? "params or out is NULL" : nullptr, n_agents, agents,
+                               fx_launch_risk_costs_batch ? nullptr : "risk-cost", true, true, q, [&](RiskPass &p, size_t i, int32_t agent) {
+        const int rc_i = risk_check(p, c, agent, params + i, batch_n_ids(n_ids, i), batch_ids(n_ids, ids, i), true, true);
+        return (!rc_i && cost && cost[i]) ? risk_cost_check(p, cost[i]) : rc_i;
+    });
+    if (rc || n_agents == 0) return rc;
     const size_t A = (size_t)n_agents;
-    std::vector<RiskPass> q(A);
-    std::vector<char> listed((size_t)c->n_agents, 0);
-    for (size_t i = 0; i < A; i++) {
-        const int32_t agent = agents ? agents[i] : (int32_t)i;
-        if (agent >= 0 && agent < c->n_agents && listed[agent]) return set_err(FX_ERR_INVALID_ARGUMENT, "agent %d listed twice", agent);
-        const int64_t n_i = n_ids ? n_ids[i] : 0;
-        const int64_t *ids_i = (n_ids && ids) ? ids[i] : nullptr;
-        int rc = risk_check(q[i], c, agent, params + i, n_i, ids_i, true, true);
-        if (!rc && cost && cost[i]) rc = risk_cost_check(q[i], cost[i]);
-        if (rc) {
-            char why[sizeof(g_err)];
-            snprintf(why, sizeof(why), "%s", g_err);
-            return set_err(rc, "agent %d: %s", agent, why);
-        }
-        listed[agent] = 1;
-    }
-    // ONE staging buffer, every part 16-byte aligned; the device's copy lies at o_stage of the block
-    std::vector<char> stage;
-    auto room = [&](size_t bytes) { const size_t o = stage.size(); stage.resize(o + align_up(std::max<size_t>(bytes, 8), 16), 0); return o; };
-    auto put = [&](const void *src, size_t bytes) { const size_t o = room(bytes); if (bytes) memcpy(stage.data() + o, src, bytes); return o; };
-    struct Parts { size_t prm, rec, obs, pos, yaw, v, ids, bh, resp, eobs, eoff, pst, voff, vert, out_at, col_at, cout_at; int ci; bool items; };
-    std::vector<Parts> at(A);
+    RiskStage st;
+    std::vector<RiskBatchAgent> ag(A);
     std::vector<FxItemAgent> ia(A);
-    std::vector<int32_t> cs(A), chunks(A), blk0;
+    std::vector<int32_t> blk0;
     std::vector<double> rec;
     size_t rows_out = 0, col_doubles = 0, rows_cost = 0;
     int64_t blocks = 0;
     for (size_t i = 0; i < A; i++) {
         RiskPass &p = q[i];
-        const FxRiskAgent &a = *p.a;
-        const FxRiskCostParams *cp = cost ? cost[i] : nullptr;
-        Parts &t = at[i];
-        t = Parts{};
-        t.out_at = rows_out, t.col_at = col_doubles, t.cout_at = rows_cost, t.ci = -1;
+        RiskBatchAgent &b = ag[i];
+        b.out_at = rows_out, b.col_at = col_doubles, b.cout_at = rows_cost, b.ci = -1, b.cost = RiskCostAt{};
         rows_out += (size_t)p.n;
         col_doubles += 4 * (size_t)p.K * (size_t)p.n;
-        t.prm = put(p.prm, sizeof(FxRiskParams));
-        if (p.K > 0) {
-            build_records(a, p.S, p.maha, rec);
-            t.rec = put(rec.data(), sizeof(double) * rec.size()), t.obs = put(a.obs.data(), sizeof(double) * a.obs.size());
-            t.pos = put(a.pos.data(), sizeof(double) * a.pos.size()), t.yaw = put(a.yaw.data(), sizeof(double) * a.yaw.size());
-            t.v = put(a.v.data(), sizeof(double) * a.v.size());
-        }
-        if (p.ids) t.ids = put(p.sparse ? p.pos.data() : p.ids, sizeof(int64_t) * (size_t)p.n);
-        if (cp) {   // (what risk_stage and risk_cost_args take and upload for a cost pass)
-            t.ci = (int)blk0.size();
+        b.at = risk_put_agent(st, p, rec);
+        if (cost && cost[i]) {
+            b.ci = (int)blk0.size();
             blk0.push_back((int32_t)blocks);
             blocks += (p.n + 255) / 256;
             rows_cost += (size_t)p.n;
-            if (cp->boundary_mode == FX_RISK_BOUNDARY_ARRAY) t.bh = put(cp->boundary_harm, sizeof(double) * (size_t)p.n);
-            if (cp->responsibility_mode == FX_RISK_RESP_ACTION_SPACE && p.K > 0) t.resp = put(cp->responsibility, sizeof(double) * p.K);
-            if (cp->responsibility_mode == FX_RISK_RESP_REACH_SET) {
-                p.nE = a.rs_obs.size(), p.nP = a.rs_step.size(), p.nV = a.rs_verts.size() / 2;
-                t.eobs = put(a.rs_obs.data(), sizeof(int32_t) * p.nE), t.eoff = put(a.rs_off.data(), sizeof(int32_t) * a.rs_off.size());
-                t.pst = put(a.rs_step.data(), sizeof(int32_t) * p.nP), t.voff = put(a.rs_voff.data(), sizeof(int32_t) * a.rs_voff.size());
-                t.vert = put(a.rs_verts.data(), sizeof(double) * a.rs_verts.size());
-            }
+            b.cost = risk_put_cost(st, p, cost[i]);
         }
-        // steps per chunk from the agent's OWN list length: what fx_eval_risk_costs_agent chooses for it
-        t.items = p.K > 0 && p.S > 1;
-        cs[i] = fx_risk_items_chunk_steps(p.n, p.S, p.K);
-        chunks[i] = (std::max(p.S - 1, 1) + cs[i] - 1) / cs[i];
-        ia[i] = FxItemAgent{p.n, t.items ? sizeof(double) * 7 * (size_t)p.K * (size_t)chunks[i] : 0};
+        ia[i] = risk_item_share(p, 7, b.sh);
     }
     const size_t NC = blk0.size();
     if (blocks > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "%lld workgroups of candidates", (long long)blocks);
@@ -1244,101 +1163,46 @@ extern "C" int32_t fx_eval_risk_costs_batch(FxContext *c, int32_t n_agents, cons
         seg_blocks += ((int64_t)q[k / 4].K * q[k / 4].n + 1023) / 1024;
         if (seg_blocks > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "%lld workgroups of column values", (long long)seg_blocks);
     }
-    const unsigned long long forced = fx_risk_batch_scratch_forced.load(std::memory_order_relaxed);
-    const std::vector<FxItemSegment> segs = fx_item_rounds(ia.data(), n_agents, forced ? (size_t)forced : FX_ITEM_SCRATCH_BYTES);
-    const size_t R = segs.size();
-    const int n_rounds = R ? segs.back().round + 1 : 0;
-    std::vector<RiskBatchRound> rounds((size_t)n_rounds, RiskBatchRound{0, 0, 0, 0});
-    std::vector<RiskBatchRow> rows(R);
-    std::vector<int32_t> agent_row(A, -1);
-    const size_t t_rows = room(sizeof(RiskBatchRow) * R), t_item0 = room(sizeof(int64_t) * R), t_fin0 = room(sizeof(int32_t) * R),
-                 t_arow = room(sizeof(int32_t) * A), t_cost = room(sizeof(RiskCostArgs) * NC), t_blk0 = put(blk0.data(), sizeof(int32_t) * NC),
-                 t_seg = room(sizeof(RiskCopySeg) * NS), t_sblk = put(seg_blk0.data(), sizeof(int32_t) * NS);
-    size_t scratch = 0;
-    for (size_t k = 0; k < R; k++) {   // the rows' counts (their pointers follow when the block is there)
-        const FxItemSegment &g = segs[k];
-        const size_t tiles = (size_t)(g.count + 63) / 64;
-        RiskBatchRound &rd = rounds[g.round];
-        RiskBatchRow &w = rows[k];
-        w = RiskBatchRow{};
-        if (rd.n_rows == 0) rd.row0 = (int32_t)k;
-        rd.n_rows++;
-        w.first = g.first, w.count = g.count;
-        w.it.nb = (int64_t)tiles * 64, w.it.cs = cs[g.agent], w.it.chunks = chunks[g.agent];
-        w.it.need = FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED;
-        w.items = at[g.agent].items ? 1 : 0;
-        w.item0 = rd.items;
-        w.fin0 = rd.fin_blocks;
-        if (w.items) rd.items += (int64_t)tiles * chunks[g.agent] * (int64_t)q[g.agent].K;
-        const int64_t fin = (int64_t)rd.fin_blocks + (g.count + 255) / 256;
-        if (fin > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld workgroups of candidates", (long long)fin);
-        rd.fin_blocks = (int32_t)fin;
-        scratch = std::max(scratch, g.scratch_off + tiles * 64 * ia[g.agent].per_candidate_bytes);
-        agent_row[g.agent] = (int32_t)k;
-    }
-    for (const RiskBatchRound &rd : rounds)
-        if (rd.items > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld items", (long long)rd.items);
+    std::vector<FxItemSegment> segs;
+    FxItemTable tab;
+    FX_TRY(risk_batch_table(ia, ag, segs, tab));
+    const BatchTableAt t_at = batch_table_room<RiskBatchRow>(st, segs.size(), A);
+    const size_t t_cost = st.room(sizeof(RiskCostArgs) * NC), t_blk0 = st.put(blk0), t_seg = st.room(sizeof(RiskCopySeg) * NS),
+                 t_sblk = st.put(seg_blk0);
     FxBlockLayout lay;
-    const size_t o_stage = lay.take(stage.size()), o_part = lay.take(scratch), o_col = lay.take(sizeof(double) * col_doubles);
+    const size_t o_stage = lay.take(st.bytes.size()), o_part = lay.take(tab.scratch), o_col = lay.take(sizeof(double) * col_doubles);
     const size_t o_cat = lay.take(any_col ? sizeof(double) * col_doubles : 0);
     const size_t o_ego = lay.take(sizeof(double) * rows_out), o_obst = lay.take(sizeof(double) * rows_out), o_occ = lay.take(sizeof(double) * rows_out);
     const size_t o_out = lay.take(sizeof(double) * 7 * rows_cost), o_idx = lay.take(sizeof(long long) * (A + NC));
     FxRiskState *r = q[0].r;
-    HIP_TRY(hipSetDevice(c->device));
-    FX_TRY(fx_drain(c));
-    FX_TRY(r->block.ensure(lay.size()));
-    FX_TRY(r->ev.ensure());
-    char *base = r->block;
+    char *base;
+    FX_TRY(risk_block(c, r, lay.size(), base));
     auto D = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
-    const size_t s0 = o_stage;
-    for (size_t i = 0; i < A; i++) {   // the cost kernel's argument blocks, from where the agent's parts lie
-        const Parts &t = at[i];
-        if (t.ci < 0) continue;
-        RiskPass &p = q[i];
-        p.base = base;
-        p.o_col = o_col + sizeof(double) * t.col_at, p.o_out = o_out + sizeof(double) * 7 * t.cout_at;
-        p.o_ids = s0 + t.ids, p.o_bh = s0 + t.bh, p.o_resp = s0 + t.resp;
-        p.o_eobs = s0 + t.eobs, p.o_eoff = s0 + t.eoff, p.o_pst = s0 + t.pst, p.o_voff = s0 + t.voff, p.o_vert = s0 + t.vert;
-        RiskCostArgs ca{};
-        risk_cost_fill(p, cost[i], ca);
-        memcpy(stage.data() + t_cost + sizeof(RiskCostArgs) * (size_t)t.ci, &ca, sizeof(ca));
-    }
-    for (size_t k = 0; k < R; k++) {
-        const FxItemSegment &g = segs[k];
-        const RiskPass &p = q[g.agent];
-        const Parts &t = at[g.agent];
-        RiskBatchRow &w = rows[k];
-        w.w = RiskWalkArgs{p.planes, p.ld, p.S, p.n, p.ids ? reinterpret_cast<const int64_t *>(base + s0 + t.ids) : nullptr, p.flags,
-                           D(s0 + t.rec), D(s0 + t.obs), D(s0 + t.pos), D(s0 + t.yaw), D(s0 + t.v), p.K, p.P};
-        w.it.params = reinterpret_cast<const FxRiskParams *>(base + s0 + t.prm);
-        w.it.part = reinterpret_cast<double *>(base + o_part + g.scratch_off);
-        w.ego = D(o_ego) + t.out_at, w.obst = D(o_obst) + t.out_at, w.occ = D(o_occ) + t.out_at;
-        w.col = D(o_col) + t.col_at;
-        memcpy(stage.data() + t_item0 + sizeof(int64_t) * k, &w.item0, sizeof(int64_t));
-        memcpy(stage.data() + t_fin0 + sizeof(int32_t) * k, &w.fin0, sizeof(int32_t));
-    }
-    if (R) memcpy(stage.data() + t_rows, rows.data(), sizeof(RiskBatchRow) * R);
-    memcpy(stage.data() + t_arow, agent_row.data(), sizeof(int32_t) * A);
+    char *const d_stage = base + o_stage;
+    std::vector<RiskCostArgs> cas(NC, RiskCostArgs{});
+    for (size_t i = 0; i < A; i++)   // the cost kernel's argument blocks of the agents that have cost parameters
+        if (ag[i].ci >= 0)
+            risk_cost_fill(q[i], cost[i], risk_batch_cost_ptrs(d_stage, q[i], ag[i], D(o_col) + ag[i].col_at, D(o_out) + 7 * ag[i].cout_at),
+                           cas[(size_t)ag[i].ci]);
+    if (NC) memcpy(st.bytes.data() + t_cost, cas.data(), sizeof(RiskCostArgs) * NC);
+    const std::vector<RiskBatchRow> rows = risk_fill_rows(segs, tab, q, ag, FX_FLAG_VALID | FX_FLAG_FEASIBLE | FX_FLAG_RETURNED, d_stage,
+                                                          base + o_part, D(o_ego), D(o_obst), D(o_occ), D(o_col));
     for (size_t k = 0; k < NS; k++) {   // plane k % 4 of agent k / 4: from its block to its place in that column of the call
-        const Parts &pt = at[k / 4];
-        const size_t Kn = (size_t)q[k / 4].K * (size_t)q[k / 4].n;
-        const RiskCopySeg g{D(o_col) + pt.col_at + (k % 4) * Kn, D(o_cat) + (k % 4) * T + pt.col_at / 4, (int64_t)Kn};
-        memcpy(stage.data() + t_seg + sizeof(RiskCopySeg) * k, &g, sizeof(g));
+        const size_t Kn = (size_t)q[k / 4].K * (size_t)q[k / 4].n, col_at = ag[k / 4].col_at;
+        const RiskCopySeg g{D(o_col) + col_at + (k % 4) * Kn, D(o_cat) + (k % 4) * T + col_at / 4, (int64_t)Kn};
+        memcpy(st.bytes.data() + t_seg + sizeof(RiskCopySeg) * k, &g, sizeof(g));
     }
-    HIP_TRY(hipMemcpyAsync(base + o_stage, stage.data(), stage.size(), hipMemcpyHostToDevice, c->stream));
     RiskCostBatchArgs t{};
-    t.rows = reinterpret_cast<const RiskBatchRow *>(base + o_stage + t_rows);
-    t.item0 = reinterpret_cast<const int64_t *>(base + o_stage + t_item0);
-    t.fin0 = reinterpret_cast<const int32_t *>(base + o_stage + t_fin0);
-    t.agent_row = reinterpret_cast<const int32_t *>(base + o_stage + t_arow);
-    t.cost = reinterpret_cast<const RiskCostArgs *>(base + o_stage + t_cost);
-    t.blk0 = reinterpret_cast<const int32_t *>(base + o_stage + t_blk0);
-    t.n_agents = n_agents, t.n_cost = (int32_t)NC, t.blocks = (int32_t)blocks;
-    t.seg = reinterpret_cast<const RiskCopySeg *>(base + o_stage + t_seg);
-    t.seg_blk0 = reinterpret_cast<const int32_t *>(base + o_stage + t_sblk);
+    t.t = batch_table_put(st, t_at, rows, tab, d_stage);
+    t.cost = reinterpret_cast<const RiskCostArgs *>(d_stage + t_cost);
+    t.blk0 = reinterpret_cast<const int32_t *>(d_stage + t_blk0);
+    t.n_cost = (int32_t)NC, t.blocks = (int32_t)blocks;
+    t.seg = reinterpret_cast<const RiskCopySeg *>(d_stage + t_seg);
+    t.seg_blk0 = reinterpret_cast<const int32_t *>(d_stage + t_sblk);
     t.n_seg = (int32_t)NS, t.seg_blocks = (int32_t)seg_blocks;
+    HIP_TRY(hipMemcpyAsync(d_stage, st.bytes.data(), st.bytes.size(), hipMemcpyHostToDevice, c->stream));
     long long *d_idx = reinterpret_cast<long long *>(base + o_idx);
-    HIP_TRY(fx_launch_risk_costs_batch(&t, rounds.data(), n_rounds, d_idx, d_idx + A, r->ev.e0, r->ev.e1, c->stream));
+    HIP_TRY(fx_launch_risk_costs_batch(&t, tab.rounds.data(), (int)tab.rounds.size(), d_idx, d_idx + A, r->ev.e0, r->ev.e1, c->stream));
     auto down = [&](double *dst, size_t o, size_t count) {
         return (dst && count) ? hipMemcpyAsync(dst, base + o, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
     };
@@ -1357,22 +1221,16 @@ extern "C" int32_t fx_eval_risk_costs_batch(FxContext *c, int32_t n_agents, cons
     const std::unique_ptr<double[]> h_out(n_out ? new double[n_out] : nullptr);
     HIP_TRY(down(h_out.get(), o_out, n_out));
     std::vector<long long> idx(A + NC, -1);
-    HIP_TRY(hipMemcpyAsync(idx.data(), d_idx, sizeof(long long) * (A + NC), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipEventElapsedTime(&r->last_ms, r->ev.e0, r->ev.e1));
-    r->last_rounds = n_rounds;
+    FX_TRY(risk_end(c, r, d_idx, idx.data(), A + NC, &r->last_ms));
+    r->last_rounds = (int32_t)tab.rounds.size();
     for (size_t i = 0; i < A; i++) {
-        const Parts &pt = at[i];
+        const RiskBatchAgent &b = ag[i];
         const size_t nn = (size_t)q[i].n;
-        if (pt.ci >= 0 && h_out)
+        if (b.ci >= 0 && h_out)
             for (int k = 0; k < 7; k++)
-                if (pr[k] && nn) memcpy(pr[k] + pt.out_at, h_out.get() + 7 * pt.cout_at + k * nn, sizeof(double) * nn);
-        // (sparse set: the arg-mins ran over positions, which grow with the candidate index -- the same winner, the same tie rule)
-        long long ri = idx[i], ci = pt.ci >= 0 ? idx[A + (size_t)pt.ci] : -1;
-        if (q[i].sparse && ri >= 0) ri = (long long)q[i].set.ids[ri];
-        if (q[i].sparse && ci >= 0) ci = (long long)q[i].set.ids[ci];
-        if (out->min_risk_index) out->min_risk_index[i] = (int64_t)ri;
-        if (out->min_cost_index) out->min_cost_index[i] = (int64_t)ci;
+                if (pr[k] && nn) memcpy(pr[k] + b.out_at, h_out.get() + 7 * b.cout_at + k * nn, sizeof(double) * nn);
+        if (out->min_risk_index) out->min_risk_index[i] = risk_winner(q[i], idx[i]);
+        if (out->min_cost_index) out->min_cost_index[i] = risk_winner(q[i], b.ci >= 0 ? idx[A + (size_t)b.ci] : -1);
     }
     return FX_OK;
 }

@@ -419,110 +419,82 @@ extern "C" hipError_t fx_launch_predprob(const PredProbArgs *args, long long *ou
     return hipSuccess;
 }
 
-// the same pass over several agents in one call: per round ONE item launch over the flat items of all its
-// rows and ONE finish launch, then one arg-min launch with a workgroup per agent.  t: the device tables; rounds: the host's account
-// of them (fx_api_risk.hip builds both).  ev_start / ev_stop bracket all launches.
-extern "C" hipError_t fx_launch_predprob_batch(const PredProbBatchArgs *t, const PredProbRound *rounds, int n_rounds, long long *out_idx,
+// The launches of a pass over several agents in one call (DESIGN.md sections 18 to 21), the one sequence of the four launchers below:
+// per round ONE item launch over the flat items of all its rows and ONE finish launch, then what `tail` launches once behind the
+// last round.  t: the device tables; rounds: the host's account of them (fx_api_risk.hip builds both).  ev_start / ev_stop
+// bracket all launches.
+template <class Row, class ItemKernel, class FinishKernel, class Tail>
+static hipError_t launch_rounds(const BatchTable<Row> &t, const FxItemRound *rounds, int n_rounds, ItemKernel item, FinishKernel finish,
+                                hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream, Tail tail) {
+    hipError_t e;
+    if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
+    for (int r = 0; r < n_rounds; r++) {
+        const FxItemRound &q = rounds[r];
+        if (q.items > 0) hipLaunchKernelGGL(item, dim3((unsigned)q.items), dim3(64), 0, stream, t.rows + q.row0, t.item0 + q.row0, q.n_rows);
+        hipLaunchKernelGGL(finish, dim3((unsigned)q.fin_blocks), dim3(256), 0, stream, t.rows + q.row0, t.fin0 + q.row0, q.n_rows);
+    }
+    tail();
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
+// the prediction-probability pass (section 18): behind the rounds one arg-min launch with a workgroup per agent -- 2 R + 1 launches
+extern "C" hipError_t fx_launch_predprob_batch(const PredProbBatchArgs *t, const FxItemRound *rounds, int n_rounds, long long *out_idx,
                                                hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream) {
-    hipError_t e;
-    if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
-    for (int r = 0; r < n_rounds; r++) {
-        const PredProbRound &q = rounds[r];
-        if (q.items > 0)
-            hipLaunchKernelGGL(fxpp::fx_predprob_batch_item_kernel, dim3((unsigned)q.items), dim3(64), 0, stream, t->rows + q.row0,
-                               t->item0 + q.row0, q.n_rows);
-        hipLaunchKernelGGL(fxpp::fx_predprob_batch_finish_kernel, dim3((unsigned)q.fin_blocks), dim3(256), 0, stream, t->rows + q.row0,
-                           t->fin0 + q.row0, q.n_rows);
-    }
-    hipLaunchKernelGGL(fxpp::fx_predprob_batch_argmin_kernel, dim3((unsigned)t->n_agents), dim3(1024), 0, stream, t->rows, t->agent_row, out_idx);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
-    return hipSuccess;
+    return launch_rounds(*t, rounds, n_rounds, fxpp::fx_predprob_batch_item_kernel, fxpp::fx_predprob_batch_finish_kernel, ev_start, ev_stop,
+                         stream, [&] {
+        hipLaunchKernelGGL(fxpp::fx_predprob_batch_argmin_kernel, dim3((unsigned)t->n_agents), dim3(1024), 0, stream, t->rows, t->agent_row, out_idx);
+    });
 }
 
-// the responsibility pass over several agents in one call (fx_risk_kernel.h): per round ONE item launch over
-// the flat items of all its rows and ONE finish launch; behind the last round the cost kernel, the re-sum and the arg-min once each
-// over all listed agents -- 2 R + 3 launches.  t: the device tables; rounds: the host's account of them (fx_api_risk.hip builds
-// both).  ev_start / ev_stop bracket all launches.
-extern "C" hipError_t fx_launch_risk_batch(const RiskBatchArgs *t, const RiskBatchRound *rounds, int n_rounds, long long *out_idx,
+// the responsibility pass (fx_risk_kernel.h; section 19): behind the rounds the cost kernel, the re-sum and the arg-min once each
+// over all listed agents -- 2 R + 3 launches
+extern "C" hipError_t fx_launch_risk_batch(const RiskBatchArgs *a, const FxItemRound *rounds, int n_rounds, long long *out_idx,
                                            hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream) {
-    hipError_t e;
-    if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
-    for (int r = 0; r < n_rounds; r++) {
-        const RiskBatchRound &q = rounds[r];
-        if (q.items > 0)
-            hipLaunchKernelGGL(fxrisk::fx_risk_batch_item_kernel, dim3((unsigned)q.items), dim3(64), 0, stream, t->rows + q.row0,
-                               t->item0 + q.row0, q.n_rows);
-        hipLaunchKernelGGL(fxrisk::fx_risk_batch_finish_kernel, dim3((unsigned)q.fin_blocks), dim3(256), 0, stream, t->rows + q.row0,
-                           t->fin0 + q.row0, q.n_rows);
-    }
-    if (t->blocks > 0) {
-        hipLaunchKernelGGL(fxrisk::fx_risk_batch_cost_kernel, dim3((unsigned)t->blocks), dim3(256), 0, stream, t->cost, t->blk0, t->n_agents);
-        hipLaunchKernelGGL(fxrisk::fx_risk_batch_sum_kernel, dim3((unsigned)t->blocks), dim3(256), 0, stream, t->sum, t->blk0, t->n_agents);
-    }
-    hipLaunchKernelGGL(fxrisk::fx_risk_batch_argmin_kernel, dim3((unsigned)t->n_agents), dim3(1024), 0, stream, t->sum, out_idx);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
-    return hipSuccess;
+    return launch_rounds(a->t, rounds, n_rounds, fxrisk::fx_risk_batch_item_kernel, fxrisk::fx_risk_batch_finish_kernel, ev_start, ev_stop,
+                         stream, [&] {
+        const int32_t n = a->t.n_agents;
+        if (a->blocks > 0) {
+            hipLaunchKernelGGL(fxrisk::fx_risk_batch_cost_kernel, dim3((unsigned)a->blocks), dim3(256), 0, stream, a->cost, a->blk0, n);
+            hipLaunchKernelGGL(fxrisk::fx_risk_batch_sum_kernel, dim3((unsigned)a->blocks), dim3(256), 0, stream, a->sum, a->blk0, n);
+        }
+        hipLaunchKernelGGL(fxrisk::fx_risk_batch_argmin_kernel, dim3((unsigned)n), dim3(1024), 0, stream, a->sum, out_idx);
+    });
 }
 
-// the plain risk pass over several agents in one call, each with an id list or none (fx_risk_kernel.h): per
-// round ONE item launch over the flat items of all its rows and ONE finish launch, then one arg-min launch with a workgroup per
-// agent -- 2 R + 1 launches.  t: the device tables; rounds: the host's account of them (fx_api_risk.hip builds both).
-// ev_start / ev_stop bracket all launches.
-extern "C" hipError_t fx_launch_risk_list_batch(const RiskListBatchArgs *t, const RiskBatchRound *rounds, int n_rounds, long long *out_idx,
+// the plain risk pass, each agent with an id list or none (section 20): behind the rounds one arg-min launch with a workgroup per
+// agent -- 2 R + 1 launches
+extern "C" hipError_t fx_launch_risk_list_batch(const RiskListBatchArgs *t, const FxItemRound *rounds, int n_rounds, long long *out_idx,
                                                 hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream) {
-    hipError_t e;
-    if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
-    for (int r = 0; r < n_rounds; r++) {
-        const RiskBatchRound &q = rounds[r];
-        if (q.items > 0)
-            hipLaunchKernelGGL(fxrisk::fx_risk_list_batch_item_kernel, dim3((unsigned)q.items), dim3(64), 0, stream, t->rows + q.row0,
-                               t->item0 + q.row0, q.n_rows);
-        hipLaunchKernelGGL(fxrisk::fx_risk_list_batch_finish_kernel, dim3((unsigned)q.fin_blocks), dim3(256), 0, stream, t->rows + q.row0,
-                           t->fin0 + q.row0, q.n_rows);
-    }
-    hipLaunchKernelGGL(fxrisk::fx_risk_list_batch_argmin_kernel, dim3((unsigned)t->n_agents), dim3(1024), 0, stream, t->rows, t->agent_row,
-                       out_idx);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
-    return hipSuccess;
+    return launch_rounds(*t, rounds, n_rounds, fxrisk::fx_risk_list_batch_item_kernel, fxrisk::fx_risk_list_batch_finish_kernel, ev_start,
+                         ev_stop, stream, [&] {
+        hipLaunchKernelGGL(fxrisk::fx_risk_list_batch_argmin_kernel, dim3((unsigned)t->n_agents), dim3(1024), 0, stream, t->rows, t->agent_row,
+                           out_idx);
+    });
 }
 
-// the detail and cost passes over several agents in one call, each with an id list or none and with cost parameters or none
-// (fx_risk_kernel.h): per round ONE item launch over the flat items of all its rows and ONE finish launch
-// (fx_risk_batch_finish_kernel, which serves as it stands), then the risk arg-min with a workgroup per agent
-// (fx_risk_list_batch_argmin_kernel, as it stands) and, where an agent has cost parameters, the cost kernel and the cost arg-min
-// once each over those agents, and, where the caller asked for a per-obstacle column, one launch that lays the agents' column blocks
-// into the call's concatenated columns -- 2 R + 4 launches at most.  out_idx [n_agents] the risk arg-min,
-// cost_idx [n_cost] the cost arg-min.  t: the device tables; rounds: the host's account of them (fx_api_risk.hip builds both).
-// ev_start / ev_stop bracket all launches.
-extern "C" hipError_t fx_launch_risk_costs_batch(const RiskCostBatchArgs *t, const RiskBatchRound *rounds, int n_rounds, long long *out_idx,
+// the detail and cost passes, each agent with an id list or none and with cost parameters or none (section 21; the finish kernel
+// is the responsibility pass's and the risk arg-min the plain pass's, as they stand): behind the rounds the risk arg-min with a
+// workgroup per agent and, where an agent has cost parameters, the cost kernel and the cost arg-min once each over those agents,
+// and, where the caller asked for a per-obstacle column, one launch that lays the agents' column blocks into the call's
+// concatenated columns -- 2 R + 4 launches at most.  out_idx [n_agents] the risk arg-min, cost_idx [n_cost] the cost arg-min.
+extern "C" hipError_t fx_launch_risk_costs_batch(const RiskCostBatchArgs *a, const FxItemRound *rounds, int n_rounds, long long *out_idx,
                                                  long long *cost_idx, hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream) {
-    hipError_t e;
-    if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
-    for (int r = 0; r < n_rounds; r++) {
-        const RiskBatchRound &q = rounds[r];
-        if (q.items > 0)
-            hipLaunchKernelGGL(fxrisk::fx_risk_costs_batch_item_kernel, dim3((unsigned)q.items), dim3(64), 0, stream, t->rows + q.row0,
-                               t->item0 + q.row0, q.n_rows);
-        hipLaunchKernelGGL(fxrisk::fx_risk_batch_finish_kernel, dim3((unsigned)q.fin_blocks), dim3(256), 0, stream, t->rows + q.row0,
-                           t->fin0 + q.row0, q.n_rows);
-    }
-    hipLaunchKernelGGL(fxrisk::fx_risk_list_batch_argmin_kernel, dim3((unsigned)t->n_agents), dim3(1024), 0, stream, t->rows, t->agent_row,
-                       out_idx);
-    if (t->n_cost > 0) {
-        if (t->blocks > 0)
-            hipLaunchKernelGGL(fxrisk::fx_risk_costs_batch_cost_kernel, dim3((unsigned)t->blocks), dim3(256), 0, stream, t->cost, t->blk0,
-                               t->n_cost);
-        hipLaunchKernelGGL(fxrisk::fx_risk_costs_batch_argmin_kernel, dim3((unsigned)t->n_cost), dim3(1024), 0, stream, t->cost, cost_idx);
-    }
-    if (t->seg_blocks > 0)
-        hipLaunchKernelGGL(fxrisk::fx_risk_costs_batch_gather_kernel, dim3((unsigned)t->seg_blocks), dim3(256), 0, stream, t->seg, t->seg_blk0,
-                           t->n_seg);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
-    return hipSuccess;
+    return launch_rounds(a->t, rounds, n_rounds, fxrisk::fx_risk_costs_batch_item_kernel, fxrisk::fx_risk_batch_finish_kernel, ev_start,
+                         ev_stop, stream, [&] {
+        hipLaunchKernelGGL(fxrisk::fx_risk_list_batch_argmin_kernel, dim3((unsigned)a->t.n_agents), dim3(1024), 0, stream, a->t.rows,
+                           a->t.agent_row, out_idx);
+        if (a->n_cost > 0) {
+            if (a->blocks > 0)
+                hipLaunchKernelGGL(fxrisk::fx_risk_costs_batch_cost_kernel, dim3((unsigned)a->blocks), dim3(256), 0, stream, a->cost, a->blk0,
+                                   a->n_cost);
+            hipLaunchKernelGGL(fxrisk::fx_risk_costs_batch_argmin_kernel, dim3((unsigned)a->n_cost), dim3(1024), 0, stream, a->cost, cost_idx);
+        }
+        if (a->seg_blocks > 0)
+            hipLaunchKernelGGL(fxrisk::fx_risk_costs_batch_gather_kernel, dim3((unsigned)a->seg_blocks), dim3(256), 0, stream, a->seg,
+                               a->seg_blk0, a->n_seg);
+    });
 }
 
 // batched candidate read-back (fx_gather_kernel.h): one workgroup per listed candidate

@@ -53,7 +53,7 @@ inline int64_t fx_item_batch(size_t per_candidate_bytes, int64_t n) {
     return (int64_t)(std::min(tiles, call) * 64);
 }
 
-// The rounds of such a pass over SEVERAL agents in one call (fx_eval_prediction_prob_batch): the scratch of one round holds
+// The rounds of such a pass over SEVERAL agents in one call (the four batched entries of fx_api_risk.hip): the scratch of one round holds
 // segments of candidates of one or more agents, at most `limit` bytes of it.  agents: per agent its n candidates and one
 // candidate's share of the scratch in bytes (0: the agent needs none).  The rule:
 //   * agents in call order, each agent's candidates ascending and contiguous;
@@ -85,6 +85,53 @@ inline std::vector<FxItemSegment> fx_item_rounds(const FxItemAgent *agents, int 
         }
     }
     return segs;
+}
+
+// The table of such a call: what its kernels and launches need to know of each row -- one row per segment, in the segments'
+// order -- and of each round.  per_tile: a row's items per tile of 64 candidates (0: the row runs no item); agents: as given to
+// fx_item_rounds, for the scratch share of a row's agent.
+//   * a row's nb is its count rounded up to whole tiles; a round's rows are [row0, row0 + n_rows), consecutive and in call order;
+//   * item0 / fin0: the row's first item / first finish workgroup in its round's launches, from 0 at the round's first row; a row
+//     has (nb / 64) x per_tile items and ceil(count / 256) finish workgroups of 256, and a round has the sums -- so a row without
+//     items shares item0 with the row behind it (the kernels' row search finds that one);
+//   * scratch: bytes of the largest round, every row's segment whole tiles; agent_row: a row of the agent (its last), -1 without one.
+// A round whose items or finish workgroups exceed a launch's 2^31 - 1 is refused.  Pure: no HIP call (tests/item_rounds.cpp).
+struct FxItemRound {
+    int32_t row0, n_rows;
+    int64_t items;          // of all its rows
+    int32_t fin_blocks;
+};
+struct FxItemTable {
+    std::vector<int64_t> nb, item0;   // [rows]
+    std::vector<int32_t> fin0;        // [rows]
+    std::vector<FxItemRound> rounds;
+    std::vector<int32_t> agent_row;   // [n_agents]
+    size_t scratch = 0;
+};
+inline int fx_item_table(const std::vector<FxItemSegment> &segs, const FxItemAgent *agents, int n_agents, const int64_t *per_tile,
+                         FxItemTable &t) {
+    const size_t R = segs.size();
+    t = FxItemTable{};
+    t.nb.resize(R), t.item0.resize(R), t.fin0.resize(R);
+    t.rounds.assign(R ? (size_t)segs.back().round + 1 : 0, FxItemRound{0, 0, 0, 0});
+    t.agent_row.assign((size_t)n_agents, -1);
+    for (size_t k = 0; k < R; k++) {
+        const FxItemSegment &g = segs[k];
+        const int64_t tiles = (g.count + 63) / 64;
+        FxItemRound &rd = t.rounds[g.round];
+        if (rd.n_rows == 0) rd.row0 = (int32_t)k;
+        rd.n_rows++;
+        t.nb[k] = tiles * 64, t.item0[k] = rd.items, t.fin0[k] = rd.fin_blocks;
+        rd.items += tiles * per_tile[k];
+        const int64_t fin = (int64_t)rd.fin_blocks + (g.count + 255) / 256;
+        if (fin > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld workgroups of candidates", (long long)fin);
+        rd.fin_blocks = (int32_t)fin;
+        t.scratch = std::max(t.scratch, g.scratch_off + (size_t)t.nb[k] * agents[g.agent].per_candidate_bytes);
+        t.agent_row[g.agent] = (int32_t)k;
+    }
+    for (const FxItemRound &rd : t.rounds)
+        if (rd.items > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "a round of %lld items", (long long)rd.items);
+    return FX_OK;
 }
 
 // wait for everything on the context's stream; what stays unknown is what a caller's own stream may hold (FxContext.tail_work)

@@ -127,19 +127,17 @@ struct PredProbRow {
     int64_t item0;             // first item of the row in the round's flat index; its items: (nb / 64) x chunks x K, tile fastest
     int32_t fin0;              // first workgroup of the row in the round's finish launch; it has ceil(count / 256)
 };
-// where the tables of a call lie, device pointers; the host's copy says what a round launches
-struct PredProbBatchArgs {
-    const PredProbRow *rows;   // [n_rows], all rounds
+// Where the tables of a batched call lie, device pointers (host only: the launchers read it): what the four passes over several
+// agents share.  The rounds are FxItemRound (fx_pass.h).
+template <class Row>
+struct BatchTable {
+    const Row *rows;           // [n_rows], all rounds
     const int64_t *item0;      // [n_rows] the rows' item0, compact: a wave looks its row up with one load
     const int32_t *fin0;       // [n_rows] the rows' fin0
-    const int32_t *agent_row;  // [n_agents] a row of the agent (any of them: the arg-min reads total, n and flags), -1 without one
+    const int32_t *agent_row;  // [n_agents] a row of the agent (any of them: an arg-min reads what is the agent's in it), -1 without one
     int32_t n_agents;
 };
-struct PredProbRound {         // host only
-    int32_t row0, n_rows;
-    int64_t items;             // of all its rows
-    int32_t fin_blocks;
-};
+typedef BatchTable<PredProbRow> PredProbBatchArgs;
 
 // The responsibility pass over several agents in one call (fx_eval_responsibility_cost_batch): the table of
 // the prediction-probability batch with the walk's arguments in the rows.  One row per (round, agent with candidates in it), the
@@ -155,39 +153,26 @@ struct RiskBatchRow {
     double *ego, *obst, *occ;  // [C] of the agent: what the finish kernel writes
     double *col;               // [4][K][C] of the agent
 };
-// where the tables of a call lie, device pointers; the host's copy says what the launches behind the rounds cover
+// the table and what the launches behind the rounds cover (the arg-min reads `sum`, not agent_row)
 struct RiskBatchArgs {
-    const RiskBatchRow *rows;  // [n_rows], all rounds
-    const int64_t *item0;      // [n_rows] the rows' item0, compact: a wave looks its row up with one load
-    const int32_t *fin0;       // [n_rows] the rows' fin0
+    BatchTable<RiskBatchRow> t;
     const RiskCostArgs *cost;  // [n_agents] of the cost kernel, ids null: every row is evaluated
     const RespSumArgs *sum;    // [n_agents] of the re-sum and the arg-min
     const int32_t *blk0;       // [n_agents] first workgroup of 256 of the agent in the cost and re-sum launches; it has ceil(C / 256)
-    int32_t n_agents, blocks;  // blocks: of all agents
-};
-struct RiskBatchRound {        // host only
-    int32_t row0, n_rows;
-    int64_t items;             // of all its rows
-    int32_t fin_blocks;
+    int32_t blocks;            // of all agents
 };
 
 // The plain risk pass over several agents in one call, each with an id list or none (fx_eval_risk_batch):
 // the rows are RiskBatchRow as above -- its layout is the existing batch kernels' -- with, per agent, w.ids its list in the block
 // (positions in its sparse set where the step stored no bundle) or null, w.n the list's length or C, first / count list positions,
 // it.need = VALID | FEASIBLE | RETURNED, it.part [K][chunks][2][nb], ego / obst the agent's rows of the call's concatenated
-// outputs, occ and col null.  The rounds are RiskBatchRound.
-struct RiskListBatchArgs {
-    const RiskBatchRow *rows;  // [n_rows], all rounds
-    const int64_t *item0;      // [n_rows] the rows' item0, compact
-    const int32_t *fin0;       // [n_rows] the rows' fin0
-    const int32_t *agent_row;  // [n_agents] a row of the agent (any of them: the arg-min reads ego, obst, w.n and w.ids), -1 without one
-    int32_t n_agents;
-};
+// outputs, occ and col null.  Its arg-min reads ego, obst, w.n and w.ids of the agent's row.
+typedef BatchTable<RiskBatchRow> RiskListBatchArgs;
 
 // The detail and cost passes over several agents in one call, each with an id list or none and with cost parameters or none
 // (fx_eval_risk_costs_batch): the rows are RiskBatchRow with the lists of section 20 in w.ids and the
 // detail pass's parts -- it.part [K][chunks][7][nb], occ the agent's rows of the call's concatenated outputs, col the agent's
-// [4][K][n] -- and the rounds RiskBatchRound.  The cost pass runs over the agents that have cost parameters alone.
+// [4][K][n].  The cost pass runs over the agents that have cost parameters alone.
 // The caller's columns are concatenated per column -- agent i's [K_i][n_i] at the sum of K_b n_b of the agents before it -- while
 // items_finish_body and cost_body index an agent's four columns as ONE block [4][K][n]: a segment is one plane of one agent.
 struct RiskCopySeg {
@@ -196,13 +181,10 @@ struct RiskCopySeg {
     int64_t n;                 // K n of the agent
 };
 struct RiskCostBatchArgs {
-    const RiskBatchRow *rows;  // [n_rows], all rounds
-    const int64_t *item0;      // [n_rows] the rows' item0, compact
-    const int32_t *fin0;       // [n_rows] the rows' fin0
-    const int32_t *agent_row;  // [n_agents] a row of the agent, -1 without one
+    BatchTable<RiskBatchRow> t;
     const RiskCostArgs *cost;  // [n_cost] of the agents with cost parameters, in call order; ids the agent's list or null
     const int32_t *blk0;       // [n_cost] first workgroup of 256 of the agent in the cost launch; it has ceil(n / 256)
-    int32_t n_agents, n_cost, blocks;   // blocks: of all agents with cost parameters
+    int32_t n_cost, blocks;    // blocks: of all agents with cost parameters
     const RiskCopySeg *seg;    // [n_seg] the agents' column planes on their way into the call's concatenated columns, or null
     const int32_t *seg_blk0;   // [n_seg] first workgroup of the segment in the gather launch; it has ceil(n / 1024)
     int32_t n_seg, seg_blocks; // seg_blocks 0: the caller asked for no column

@@ -1,13 +1,19 @@
-// item_rounds.cpp -- the round rule of the passes that work in items over several agents (csrc/fx_pass.h, fx_item_rounds) as a
-// stand-alone host program (tests/test_item_rounds.py builds it with hipcc --cuda-host-only and holds its answers to the rule's
-// statement).  Input, one case per line: limit n_agents (n per_candidate_bytes)*.  Output per case: one line
+// item_rounds.cpp -- the round rule of the passes that work in items over several agents (csrc/fx_pass.h, fx_item_rounds) and the
+// table of such a call (fx_item_table) as a stand-alone host program (tests/test_item_rounds.py builds it with hipcc
+// --cuda-host-only and holds its answers to the rules' statements).  Input, one case per line:
+//   limit n_agents (n per_candidate_bytes items_per_tile)*
+// Output per case, two lines:
 //   case <segments> <fx_item_batch of the first agent, 0 without one> (agent round first count scratch_off)*
+//   table <0, or fx_item_table's refusal> <scratch> <rounds> (row0 n_rows items fin_blocks)* <rows> (nb item0 fin0)* <agents> (agent_row)*
+// (a refused table: "table <code>" alone).  Every row of an agent gets the agent's items per tile.
 #include <cstdio>
 #include <iostream>
 #include <sstream>
 #include <string>
 
 #include "fx_pass.h"
+
+thread_local char g_err[512] = "";   // (the library's error text: fx_api.hip has it in the product)
 
 int main() {
     std::string line;
@@ -17,11 +23,12 @@ int main() {
         int n_agents;
         if (!(in >> limit >> n_agents)) continue;
         std::vector<FxItemAgent> agents((size_t)n_agents);
-        for (auto &a : agents) {
+        std::vector<long long> per_tile((size_t)n_agents);
+        for (size_t a = 0; a < agents.size(); a++) {
             long long n;
             unsigned long long per;
-            in >> n >> per;
-            a = FxItemAgent{(int64_t)n, (size_t)per};
+            in >> n >> per >> per_tile[a];
+            agents[a] = FxItemAgent{(int64_t)n, (size_t)per};
         }
         const std::vector<FxItemSegment> segs = fx_item_rounds(agents.data(), n_agents, (size_t)limit);
         long long batch = 0;   // (fx_item_batch works on the library's own limit: comparable where the case uses it)
@@ -29,6 +36,20 @@ int main() {
         printf("case %zu %lld", segs.size(), batch);
         for (const FxItemSegment &s : segs)
             printf(" %d %d %lld %lld %zu", (int)s.agent, (int)s.round, (long long)s.first, (long long)s.count, s.scratch_off);
+        printf("\n");
+        std::vector<int64_t> row_items(segs.size());
+        for (size_t k = 0; k < segs.size(); k++) row_items[k] = (int64_t)per_tile[(size_t)segs[k].agent];
+        FxItemTable t;
+        const int rc = fx_item_table(segs, agents.data(), n_agents, row_items.data(), t);
+        printf("table %d", rc);
+        if (!rc) {
+            printf(" %zu %zu", t.scratch, t.rounds.size());
+            for (const FxItemRound &r : t.rounds) printf(" %d %d %lld %d", (int)r.row0, (int)r.n_rows, (long long)r.items, (int)r.fin_blocks);
+            printf(" %zu", t.nb.size());
+            for (size_t k = 0; k < t.nb.size(); k++) printf(" %lld %lld %d", (long long)t.nb[k], (long long)t.item0[k], (int)t.fin0[k]);
+            printf(" %zu", t.agent_row.size());
+            for (int32_t r : t.agent_row) printf(" %d", (int)r);
+        }
         printf("\n");
     }
     return 0;

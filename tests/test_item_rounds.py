@@ -9,7 +9,13 @@ cases, and every answer is held to the rule's statement -- not to a second imple
   * no round is closed while the next tile still fits.
 
 The table of such a call (fx_item_table: what each row and each round of its launches covers) is answered by the same program on
-the same cases and held to its statement in the same way; two more cases stand at the capacity of a launch."""
+the same cases and held to its statement in the same way; two more cases stand at the capacity of a launch.
+
+The kernels find the row of an item or of a finish workgroup by "one load per 64 rows and a ballot" (row_of, batch_row_of): the
+last row whose first index lies at or before it.  The program applies that rule, as a plain loop, to EVERY flat index of every
+round's two launches and reports how many land outside the row whose extent holds them; tables of 64, 65, 129 and 130 agents --
+with agents without candidates, or rows without items, at the positions 0, 63, 64 and last -- carry it past the 64-row boundary,
+in one round and at a limit that puts more than 64 rows into one round: the host half of what the row search relies on."""
 import os
 import subprocess
 
@@ -41,6 +47,30 @@ CASES = {
 }
 
 
+# ---- beyond one wave of agents: (limit, agents) of 64, 65, 129 and 130 agents of one or two tiles each ----
+WAVE_COUNTS = (64, 65, 129, 130)
+
+
+def _many(A, holes, per_zero, rounds):
+    """A agents of 30 ... 129 candidates; `holes`: the agents at the positions 0, 63, 64 and last have no candidate; per_zero: they
+    need no scratch (their rows run no item); rounds "one": the library's limit; "several": what the tiles of the first 70 agents
+    take (of the first 25 below 129 agents, where 65 rows in one round leave nothing for another)"""
+    special = {0, 63, 64, A - 1}
+    agents = [(0 if holes and i in special else 30 + 11 * (i % 10), 0 if per_zero and i in special else 8 * (1 + i % 4) * 30) for i in range(A)]
+    if rounds == "one":
+        return LIB_LIMIT, agents
+    return sum(tiles(n) * 64 * per for n, per in agents[:70 if A >= 129 else 25]), agents
+
+
+def tiles(count):
+    return -(-count // 64)
+
+
+WAVE_CASES = {f"{A} agents, {what}, {rounds}": _many(A, what == "agents without candidates", what == "rows without items", rounds)
+              for A in WAVE_COUNTS for what in ("agents without candidates", "rows without items") for rounds in ("one", "several")}
+CASES.update(WAVE_CASES)
+
+
 def items_per_tile(a, per):
     """what the table function is told of every row of agent a (chunks x obstacles in the library): 0 exactly where the agent takes
     no scratch, otherwise a small count that differs from agent to agent"""
@@ -65,10 +95,11 @@ def program_output(tmp_path_factory):
     cases.update({name: (limit, [(n, per, ipt) for n, per in agents]) for name, (limit, agents, ipt) in CAPACITY.items()})
     text = "\n".join(" ".join(str(x) for x in [limit, len(agents)] + [v for a in agents for v in a]) for limit, agents in cases.values())
     out = subprocess.run([exe], input=text + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
-    assert len(out) == 2 * len(cases)
+    assert len(out) == 3 * len(cases)
     lines = [[int(x) for x in line.split()[1:]] for line in out]
-    assert all(line.startswith("case ") for line in out[0::2]) and all(line.startswith("table ") for line in out[1::2])
-    return dict(zip(cases, zip(lines[0::2], lines[1::2])))
+    assert all(line.startswith("case ") for line in out[0::3]) and all(line.startswith("table ") for line in out[1::3])
+    assert all(line.startswith("lookup ") for line in out[2::3])
+    return dict(zip(cases, zip(lines[0::3], lines[1::3], lines[2::3])))
 
 
 @pytest.fixture(scope="module")
@@ -97,10 +128,6 @@ def parse_table(v):
     agent_row = v[at + 1:]
     assert len(agent_row) == v[at]
     return scratch, rounds, rows, agent_row
-
-
-def tiles(count):
-    return -(-count // 64)
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -207,3 +234,46 @@ def test_a_round_beyond_a_launch_is_refused(program_output):
     scratch, rounds, rows, agent_row = parse_table(program_output["2^31 - 4096 items"][1])
     assert rounds == [(0, 1, (1 << 31) - 4096, 1024)] and rows == [(4096 * 64, 0, 0)] and agent_row == [0]
     assert scratch == 4096 * 64 * 8
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_row_search_finds_the_row_of_every_index(program_output, answers, name):
+    """the kernels' rule -- the last row that starts at or before the index -- on every item and every finish workgroup of every
+    round: the row whose [item0, item0 + items) / [fin0, fin0 + fin_blocks) holds the index; item0 and fin0 ascend within a round"""
+    _, agents = CASES[name]
+    scratch, rounds, rows, agent_row = parse_table(program_output[name][1])
+    items, items_wrong, fins, fins_wrong, unsorted = program_output[name][2]
+    assert (items, fins) == (sum(r[2] for r in rounds), sum(r[3] for r in rounds))       # every index of every launch was looked up
+    assert (items_wrong, fins_wrong, unsorted) == (0, 0, 0)
+    assert fins == sum(-(-s[3] // 256) for s in answers[name][1])
+
+
+def test_wave_cases_are_what_their_names_say(program_output, answers):
+    """the tables of 64 ... 130 agents do cross the 64-row boundary: a round of more than 64 rows wherever there are that many
+    agents with candidates, further rounds of fewer behind it at the small limit, rows without items that share item0 with the row
+    behind them at the positions 63 and 64, and items on both sides of the boundary"""
+    for name, (limit, agents) in WAVE_CASES.items():
+        A = len(agents)
+        scratch, rounds, rows, agent_row = parse_table(program_output[name][1])
+        segs = answers[name][1]
+        with_rows = sum(n > 0 for n, _ in agents)
+        assert len(agent_row) == A and [r >= 0 for r in agent_row] == [n > 0 for n, _ in agents]
+        # agent_row names the agent's (last) row: rows are in call order, so the rows of the agents in front lie before it
+        assert [segs[r][0] for r in agent_row if r >= 0] == [a for a, (n, _) in enumerate(agents) if n > 0]
+        widest = max(r[1] for r in rounds)
+        if name.endswith("one"):
+            assert len(rounds) == 1 and widest == with_rows
+        else:
+            assert len(rounds) >= 2 and min(r[1] for r in rounds) < 64
+        assert (widest > 64) == (with_rows > 64 and (name.endswith("one") or A >= 129)), (name, widest)
+        if "rows without items" in name:
+            r0 = rounds[0]
+            special = [a for a in (0, 63, 64, A - 1) if a < r0[1]]      # (rows of round 0: one per agent, in call order)
+            for a in special:
+                assert agents[a][1] == 0 and segs[a][0] == a
+                nxt = rows[a + 1][1] if a + 1 < r0[1] else r0[2]
+                assert rows[a][1] == nxt, (name, a)                   # shares item0 with the row behind it (or ends the launch)
+            if widest > 64:
+                assert 0 < rows[63][1] and (r0[1] <= 66 or any(rows[k][1] > rows[65][1] for k in range(66, r0[1])))
+        items = program_output[name][2][0]
+        assert items == sum(tiles(s[3]) * items_per_tile(s[0], agents[s[0]][1]) for s in segs) > 0

@@ -26,21 +26,11 @@ pytestmark = pytest.mark.gpu
 
 COSTED, NEED = 0x10, 0xB
 KEYS = ("resp", "total", "ego_risk", "obst_risk")
-MODES = [BASE, BASE, BASE, dict(BASE, fast_prob_mahalanobis=True), dict(BASE, harm_mode="ref_speed", ignore_angle=True)]
+from tests.risk_scenes import MODES  # noqa: E402
 REACH = [True, False, True, False, True]
 
 
-def _ego(a):
-    return dict(ego_length=4.508 + 0.1 * a, ego_width=1.61 + 0.02 * a, ego_mass=1239.0 + 50.0 * a)
-
-
-def _weight(a):
-    return 0.5 + 0.1 * a
-
-
-def _cost(resp):
-    from frenetix_motion_planner_amd import risk
-    return risk.risk_cost_params([0, 0, 0, 0, 1], responsibility=resp)
+from tests.risk_scenes import ego as _ego, resp_cost as _cost, weight as _weight  # noqa: E402,F401
 
 
 def _scene(eng, a, shape, inp, modes=BASE, reach=True):

@@ -35,33 +35,7 @@ def step():
     eng.close()
 
 
-def _err(got, want):
-    return float((np.abs(got - want) / np.maximum(np.abs(want), 1.0)).max()) if np.size(want) else 0.0
-
-
-def _reach_sets(planes, keys, sub, dt):
-    """Synthetic reach sets on the candidates' own points (both outcomes occur), on the first obstacles: unequal vertex counts, a
-    concave L, time_t 0.3 (step 1), a time_t = 0 part around everything, an obstacle whose only part is masked."""
-    sets = {}
-    for n, oid in enumerate(keys[:4]):
-        parts = []
-        if n == 0:
-            parts.append({0.0: np.array([[-1e4, -1e4], [1e4, -1e4], [1e4, 1e4], [-1e4, 1e4]])})
-        for ti, t in enumerate((0.3, 1.0, 2.2) if n < 3 else ()):
-            st = int(rcr.time_steps([t], dt)[0])
-            pts = np.stack([planes["x"][sub, st], planes["y"][sub, st]], axis=1)
-            c = np.median(pts, axis=0) + np.array([0.137 * (n + 1), -0.071 * (ti + 1)])
-            r = 0.25 * max(np.ptp(pts[:, 0]), np.ptp(pts[:, 1]), 0.4) + 0.05 * ti
-            if n == 1 and ti == 1:
-                poly = np.array([[-r, -r], [r, -r], [r, 0.0], [0.0, 0.0], [0.0, r], [-r, r]]) + c
-            else:
-                a = 0.3 * n + 2 * np.pi * np.arange(4 + ti + n) / (4 + ti + n)
-                poly = c + r * np.stack([np.cos(a), np.sin(a)], axis=1)
-            parts.append({t: poly})
-        if n == 3:
-            parts.append({-0.1: np.array([[-1e4, -1e4], [1e4, -1e4], [1e4, 1e4], [-1e4, 1e4]])})
-        sets[oid] = parts
-    return sets
+from tests.risk_scenes import err as _err, reach_sets as _reach_sets  # noqa: E402,F401
 
 
 @pytest.mark.parametrize("K,modes", CASES, ids=lambda v: str(v) if isinstance(v, int) else "-".join(

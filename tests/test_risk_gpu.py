@@ -1,18 +1,13 @@
 """Trajectory risk on the device (fx_risk_kernel.h) against the NumPy restatement of calc_risk, on the device's own read-back
 planes, for every supported harm / probability variant; the arg-min exactly.  DESIGN.md section 11."""
-import json
-import os
-
 import numpy as np
 import pytest
 
 from tests import risk_restatement as rr
+from tests.risk_scenes import BASE, HARM  # noqa: F401  (imported by other modules from here)
 
 pytestmark = pytest.mark.gpu
 
-HARM = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "harm_parameters.json")))
-BASE = dict(harm_mode="log_reg", ignore_angle=False, sym_angle=True, reduced_angle_areas=True, crash_angle_simplified=True,
-            fast_prob_mahalanobis=False)
 EGO = dict(ego_length=4.508, ego_width=1.61, ego_mass=1239.0)
 
 
@@ -29,30 +24,7 @@ def step():
     eng.close()
 
 
-def _predictions(planes, flags, rng, n_obs=8, types=None, zero_cov=True):
-    """Obstacles that walk along (shifted) ego candidates, so that many (candidate, obstacle, step) triples pass the 5 m gate,
-    with covariances whose correlations cover every branch of the bivariate normal (0, < 0.3, < 0.75, < 0.925, >= 0.925),
-    zero covariances and predictions shorter than the horizon."""
-    from frenetix_motion_planner_amd import _abi
-    C, S = planes["x"].shape
-    ok = np.nonzero((flags & 0xB) == 0xB)[0]
-    preds, typ = {}, {}
-    rhos = [0.0, 0.2, -0.6, 0.8, -0.95, 0.99, 0.5, -0.1]
-    kinds = types or ["car", "truck", "pedestrian", "bicycle", "car", "bus", "motorcycle", "car"]
-    for k in range(n_obs):
-        c = ok[rng.integers(len(ok))]
-        P = S - 1 if k % 3 else S - 7
-        off = rng.normal(0, 1.0, 2)
-        pos = np.stack([planes["x"][c, :P] + off[0], planes["y"][c, :P] + off[1]], axis=1)
-        r = rhos[k % len(rhos)]
-        sx, sy = 0.3 + 0.1 * k, 0.5
-        cov = np.tile(np.array([[sx * sx, r * sx * sy], [r * sx * sy, sy * sy]]), (P, 1, 1)) * np.linspace(1, 3, P)[:, None, None]
-        if k == 2 and zero_cov:   # (all-zero covariances become 0.1 I in the default mode; np.linalg.inv refuses them)
-            cov[:4] = 0.0
-        preds[100 + k] = dict(pos_list=pos, cov_list=cov, orientation_list=planes["theta"][c, :P] + rng.normal(0, 0.5),
-                              v_list=np.abs(planes["v"][c, :P] + rng.normal(0, 2)), shape=dict(length=4.0 + 0.3 * k, width=1.8))
-        typ[100 + k] = kinds[k % len(kinds)]
-    return preds, typ
+from tests.risk_scenes import predictions as _predictions  # noqa: E402,F401  (imported by other modules under this name)
 
 
 VARIANTS = [dict(BASE, ignore_angle=i, sym_angle=s, reduced_angle_areas=r) for i in (False, True) for s in (False, True)

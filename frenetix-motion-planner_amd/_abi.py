@@ -199,3 +199,7 @@ class FxRiskOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ego_risk", "obst_risk", "obst_harm_occ", "ego_risk_max", "obst_risk_max", "ego_harm_max",
                                           "obst_harm_max", "bayes", "equality", "maximin", "ego", "responsibility", "total",
                                           "boundary_harm", "min_risk_index", "min_cost_index")]
+
+# lanes per listed candidate that fx_set_materialise_lanes accepts (0 stands for 1); fx_materialise_candidates_batch and
+# fx_last_materialise_info take plain integers and addresses
+FX_MATERIALISE_LANES = (1, 8, 32)

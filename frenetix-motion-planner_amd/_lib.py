@@ -43,6 +43,7 @@ def exported_symbols():
         "fx_set_risk_obstacles_agent", "fx_eval_risk_agent", "fx_last_risk_ms",
         "fx_set_reach_sets_agent", "fx_eval_risk_costs_agent",
         "fx_materialise_candidates_agent", "fx_read_materialised_agent", "fx_read_package_materialised", "fx_last_materialise_ms",
+        "fx_set_materialise_lanes", "fx_materialise_candidates_batch", "fx_last_materialise_info",
         "fx_sort_candidates_agent", "fx_sort_candidates_batch", "fx_read_ranked_agent", "fx_sort_views", "fx_last_sort_ms",
         "fx_eval_prediction_prob_agent", "fx_last_predprob_ms", "fx_eval_prediction_prob_batch",
         "fx_eval_responsibility_cost_agent", "fx_eval_responsibility_cost_batch",
@@ -151,6 +152,9 @@ def lib():
         "fx_read_materialised_agent": ([vp, C.c_int32, C.c_int64] + [vp] * 8, C.c_int32),
         "fx_read_package_materialised": ([vp, C.c_int32, C.c_int64, C.c_double, C.POINTER(_abi.FxPackage), vp], C.c_int32),
         "fx_last_materialise_ms": ([vp], C.c_double),
+        "fx_set_materialise_lanes": ([vp, C.c_int32], C.c_int32),
+        "fx_materialise_candidates_batch": ([vp, C.c_int32, vp, vp, vp], C.c_int32),   # (arrays: plain addresses)
+        "fx_last_materialise_info": ([vp, pi32, pi32, pi32], C.c_int32),
         "fx_sort_candidates_agent": ([vp, C.c_int32, C.c_uint32, C.c_uint32, pi64, pi64], C.c_int32),
         "fx_sort_candidates_batch": ([vp, C.c_uint32, C.c_uint32, pi64, pi64], C.c_int32),
         "fx_read_ranked_agent": ([vp, C.c_int32, C.c_int64, C.c_int64, vp, vp, vp], C.c_int32),   # (arrays: plain addresses)

@@ -57,7 +57,8 @@ extern "C" hipError_t fx_launch_topk(const DevProblem *d_probs, int n_agents, in
 extern "C" hipError_t fx_launch_gather_candidates(const GatherArgs *args, const int64_t *d_ids, int64_t n, unsigned long long *d_out,
                                                   hipStream_t stream);
 extern "C" hipError_t fx_launch_eval_list(const DevProblem *d_prob, const int64_t *d_ids, int64_t n, size_t lds_bytes, bool obst, bool extra,
-                                          hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream);
+                                          const EvalListRow *d_rows, int n_rows, int lanes, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                          hipStream_t stream);
 
 // state updates up to this many bytes are staged by a copy kernel reading the mapped pinned block, larger ones by the DMA engine
 #define FX_STAGE_KERNEL_MAX ((size_t)1 << 20)

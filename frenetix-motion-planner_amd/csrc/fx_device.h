@@ -304,6 +304,13 @@ struct GatherArgs {
     uint32_t parts;            // FX_GATHER_*
 };
 
+// one row of fx_eval_list_rows_kernel's table (fx_eval_list_kernel.h): a listed agent's clone and its list,
+// both in device memory; the list's length is the clone's C
+struct EvalListRow {
+    const DevProblem *clone;
+    const int64_t *ids;
+};
+
 // arguments of the sort kernels (fx_sort_kernel.h).  One agent's planes and where its segment starts in the
 // sort's own per-candidate arrays; `agents` is indexed by agent0 + blockIdx.y.
 struct FxSortAgent {

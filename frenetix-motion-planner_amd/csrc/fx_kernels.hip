@@ -506,10 +506,34 @@ extern "C" hipError_t fx_launch_gather_candidates(const GatherArgs *args, const 
 }
 
 // list form of the generic kernel (fx_eval_list_kernel.h): the n = clone.C listed candidates of ONE agent into its sparse block;
-// d_prob is the clone of the agent's problem, lds_bytes as for fx_launch_eval
+// d_prob is the clone of the agent's problem, lds_bytes as for fx_launch_eval.
+// With d_rows: the rows form (fx_eval_list_rows_kernel) -- n_rows rows of one variant (lanes, obst, extra),
+// n the longest of their lists and lds_bytes the largest of their needs; d_prob and d_ids are not read.  Either event may be null:
+// a call's first launch takes the start event and its last one the stop event.
+template <int G, bool O, bool E>
+static hipError_t fx_launch_eval_list_rows(const EvalListRow *d_rows, int n_rows, int64_t n, size_t lds_bytes, hipEvent_t ev_start,
+                                           hipEvent_t ev_stop, hipStream_t stream) {
+    if (const hipError_t e = fx_allow_dynamic_lds<&fx_eval_list_rows_kernel<G, O, E>>(lds_bytes); e != hipSuccess) return e;
+    constexpr int CPB = FX_BLOCK / G;
+    hipExtLaunchKernelGGL((fx_eval_list_rows_kernel<G, O, E>), dim3((unsigned)((n + CPB - 1) / CPB), (unsigned)n_rows), dim3(FX_BLOCK), lds_bytes,
+                          stream, ev_start, ev_stop, 0, d_rows);
+    return hipGetLastError();
+}
 extern "C" hipError_t fx_launch_eval_list(const DevProblem *d_prob, const int64_t *d_ids, int64_t n, size_t lds_bytes, bool obst, bool extra,
-                                          hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream) {
+                                          const EvalListRow *d_rows, int n_rows, int lanes, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                          hipStream_t stream) {
     if (n <= 0) return hipSuccess;
+    if (d_rows) {
+        if (n_rows <= 0) return hipSuccess;
+        if (extra && lanes != 1) return hipErrorInvalidValue;   // (windowed terms need the whole horizon in one lane)
+#define FX_ROWS(G, O, E) return fx_launch_eval_list_rows<G, O, E>(d_rows, n_rows, n, lds_bytes, ev_start, ev_stop, stream)
+        if (lanes == 1 && extra) { if (obst) FX_ROWS(1, true, true); FX_ROWS(1, false, true); }
+        if (lanes == 1) { if (obst) FX_ROWS(1, true, false); FX_ROWS(1, false, false); }
+        if (lanes == 8) { if (obst) FX_ROWS(8, true, false); FX_ROWS(8, false, false); }
+        if (lanes == 32) { if (obst) FX_ROWS(32, true, false); FX_ROWS(32, false, false); }
+#undef FX_ROWS
+        return hipErrorInvalidValue;
+    }
     const dim3 grid((unsigned)((n + FX_BLOCK - 1) / FX_BLOCK)), block(FX_BLOCK);
 #define FX_LAUNCH(O, E)                                                                                         \
     do {                                                                                                        \

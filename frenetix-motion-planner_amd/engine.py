@@ -798,6 +798,13 @@ class FrenetEngine(StepRegistry):
         n, n_cost = len(ids), len(inp.cost_names)
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         check(lib().fx_materialise_candidates_agent(self._ctx, int(agent), n, ptr(ids)))
+        return self._read_materialised(ids, agent)
+
+    def _read_materialised(self, ids, agent: int) -> dict:
+        """the rows of `ids` from the agent's sparse set (fx_read_materialised_agent), every part"""
+        inp = self._inputs[agent]
+        n, n_cost = len(ids), len(inp.cost_names)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         have_r = inp._bound is not None and inp._bound["n"] > 0
         planes, co, tl = np.empty((n, _abi.FX_NUM_PLANES, inp.n_samples)), np.empty((n, 13)), np.empty(n, np.int32)
         raw = np.empty((n, n_cost))
@@ -818,10 +825,40 @@ class FrenetEngine(StepRegistry):
         w._costmap = True   # (a set's rows carry their raw costs whatever the step stored)
         return w
 
+    def set_materialise_lanes(self, lanes: int):
+        """Lanes per listed candidate of the list kernel (fx_set_materialise_lanes): 0 or 1 one lane (the
+        default), 8 or 32 the horizon split over that many adjacent lanes; anything else is refused and the setting stays.
+        Applies to `materialise` and `materialise_batch`; an agent with a windowed cost term runs at one lane whatever is set."""
+        check(lib().fx_set_materialise_lanes(self._ctx, int(lanes)))
+
+    def materialise_batch(self, ids, agents=None) -> list:
+        """`materialise` for several agents of the last step in one call (fx_materialise_candidates_batch): ids[j] is the list of
+        agents[j] (None: agent j); an empty list clears that agent's set.  One wait, one upload and one launch per kernel variant
+        present, whatever the agent count; every agent gets the set its own `materialise` would have made.  Returns one
+        `materialise` dict per listed agent, read back per agent."""
+        agents = list(range(len(ids))) if agents is None else [int(a) for a in agents]
+        if len(agents) != len(ids):
+            raise ValueError(f"{len(ids)} lists for {len(agents)} agents")
+        lists = [np.ascontiguousarray(x, dtype=np.int64).reshape(-1) for x in ids]
+        n = len(agents)
+        ag = np.asarray(agents, np.int32)
+        n_ids = np.asarray([len(x) for x in lists], np.int64)
+        addr = np.asarray([x.ctypes.data if len(x) else 0 for x in lists], np.uint64)
+        check(lib().fx_materialise_candidates_batch(self._ctx, n, ag.ctypes.data if n else None, n_ids.ctypes.data if n else None,
+                                                    addr.ctypes.data if n else None))
+        return [self._read_materialised(x, a) for x, a in zip(lists, agents)]
+
     @property
     def last_materialise_ms(self) -> float:
-        """device time of the last `materialise` call's list kernel"""
+        """device time of the last `materialise` or `materialise_batch` call's list kernels"""
         return float(lib().fx_last_materialise_ms(self._ctx))
+
+    @property
+    def last_materialise_info(self) -> dict:
+        """the last materialise call (fx_last_materialise_info): lanes (the widest split among its rows), launches, rows"""
+        v = [C.c_int32(0) for _ in range(3)]
+        check(lib().fx_last_materialise_info(self._ctx, *[C.byref(x) for x in v]))
+        return dict(lanes=int(v[0].value), launches=int(v[1].value), rows=int(v[2].value))
 
     # -- stable cost order of all candidates, on the device (DESIGN.md section 15) --
     def sort_candidates(self, agent: int = 0, require: int = _abi.FX_FLAG_COSTED, exclude: int = 0):

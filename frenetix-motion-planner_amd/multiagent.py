@@ -99,6 +99,9 @@ BATCHED_RISK_DEFAULT = False
 # AgentBatchHip(batched_risk_costs=None): the planners' "min_risk_cost" fallbacks of a whole batch in one call (DESIGN.md section
 # 21); off like the others, whatever that section's measurement says
 BATCHED_RISK_COSTS_DEFAULT = False
+# AgentBatchHip(batched_materialise=None): the keep lists of a batch's select-only planners (sparse_bundle_k > 0) re-walked in one
+# call; off like the others, whatever that section's measurement says
+BATCHED_MATERIALISE_DEFAULT = False
 
 
 class AgentBatchHip:
@@ -112,8 +115,15 @@ class AgentBatchHip:
     def __init__(self, agents: List[FrenetPlannerInterfaceHip], max_candidates: int, device: int = 0, max_ref_knots: int = 4096,
                  max_obstacles: int = 64, engine=None, parts=None, slots=None, winner_exchange=None, pipeline_groups: Optional[int] = None,
                  batched_passes: Optional[bool] = None, batched_responsibility: Optional[bool] = None,
-                 batched_risk: Optional[bool] = None, batched_risk_costs: Optional[bool] = None):
-        """batched_risk_costs: independent of batched_risk and made at the same place -- ONE engine.risk_costs_batch over the
+                 batched_risk: Optional[bool] = None, batched_risk_costs: Optional[bool] = None,
+                 batched_materialise: Optional[bool] = None):
+        """batched_materialise: the planners with sparse_bundle_k > 0 whose step ran select-only get their keep lists -- the
+        winner plus the step's top-k row, what _consume_result builds -- re-walked in ONE engine.materialise_batch call per engine
+        group and step, behind the batched launch, and each receives its rows through plan_consume, which then materialises
+        nothing itself; the same bits.  None: BATCHED_MATERIALISE_DEFAULT.  device_sort keep lists beyond
+        64, escalated levels, split agents and engines without the method keep the per-agent path; what a planner adds to its set
+        later (risk fallbacks, log_risk) goes through its step's own materialise.
+        batched_risk_costs: independent of batched_risk and made at the same place -- ONE engine.risk_costs_batch over the
         agents whose planner left a "min_risk_cost" fallback of its step waiting (ReactivePlannerHip.risk_cost_request: every
         VALID & FEASIBLE & RETURNED candidate, the planner's weights and responsibility mode), between plan_consume and
         plan_finish -- the same bits.  None: BATCHED_RISK_COSTS_DEFAULT.  Escalated levels, split agents,
@@ -186,6 +196,7 @@ class AgentBatchHip:
         self.batched_responsibility = BATCHED_RESPONSIBILITY_DEFAULT if batched_responsibility is None else bool(batched_responsibility)
         self.batched_risk = BATCHED_RISK_DEFAULT if batched_risk is None else bool(batched_risk)
         self.batched_risk_costs = BATCHED_RISK_COSTS_DEFAULT if batched_risk_costs is None else bool(batched_risk_costs)
+        self.batched_materialise = BATCHED_MATERIALISE_DEFAULT if batched_materialise is None else bool(batched_materialise)
         self.launches = 0
         self.escalations = 0
         self.last_batch_ms = 0.0
@@ -256,6 +267,27 @@ class AgentBatchHip:
             passes[j] = r
         return passes
 
+    def _materialise_passes(self, eng, planners, inputs, results) -> list:
+        """Behind a batched launch of `planners` (in the launch's agent order, with their inputs and results) on `eng`: the keep
+        lists of the select-only ones in one call; per planner (ids, rows) for plan_consume, or None: the planner's own path."""
+        passes = [None] * len(planners)
+        if not self.batched_materialise or not hasattr(eng, "materialise_batch"):
+            return passes
+        js = [j for j, p in enumerate(planners)
+              if p is not None and results[j] is not None and p.batched_materialise_pass(inputs[j], eng)]
+        rows_of, lists = {}, []   # (one top-k read per distinct k)
+        for j in js:
+            k = min(int(planners[j].config.sparse_bundle_k), 64)
+            if k not in rows_of:
+                rows_of[k] = eng.topk(k)[1]
+            lists.append(planners[j].sparse_keep_list(inputs[j], results[j], rows_of[k][j], k))
+        js, lists = [j for j, x in zip(js, lists) if len(x)], [x for x in lists if len(x)]
+        if not js:
+            return passes
+        for j, x, rows in zip(js, lists, eng.materialise_batch(lists, agents=js)):
+            passes[j] = (x, rows)
+        return passes
+
     def _responsibility_passes(self, eng, planners, inputs) -> list:
         """Behind a batched launch of `planners` (in the launch's agent order, with their inputs) on `eng`: the responsibility pass
         of those that weight the term and whose preparation returns parameters, in one call; per planner its dict for
@@ -306,10 +338,12 @@ class AgentBatchHip:
                 results, packages = eng.plan_batch_packaged([inp for _, inp in planning], yaws)
             passes = self._prediction_passes(eng, [a.planner for a, _ in planning])
             rpasses = self._responsibility_passes(eng, [a.planner for a, _ in planning], [inp for _, inp in planning])
-            def consume(defer, a, inp, j, eng=eng, results=results, packages=packages, passes=passes, rpasses=rpasses):
+            mpasses = self._materialise_passes(eng, [a.planner for a, _ in planning], [inp for _, inp in planning], results)
+            def consume(defer, a, inp, j, eng=eng, results=results, packages=packages, passes=passes, rpasses=rpasses, mpasses=mpasses):
                 return a.planner.plan_consume(inp, results[j], eng, j, package=packages[j],
                                               **({"prediction_pass": passes[j]} if passes[j] is not None else {}),
                                               **({"responsibility_pass": rpasses[j]} if rpasses[j] is not None else {}),
+                                              **({"materialise_pass": mpasses[j]} if mpasses[j] is not None else {}),
                                               **({"defer_risk": True} if defer else {}))
 
             self._conclude(eng, [(a, j, lambda defer, a=a, inp=inp, j=j, consume=consume: consume(defer, a, inp, j))
@@ -354,11 +388,14 @@ class AgentBatchHip:
                                                        for j, (a, _, k) in enumerate(planning)])
         rpasses = self._responsibility_passes(self.engine, [a.planner if self.parts[k][1] == 1 and results[j] is not None else None
                                                             for j, (a, _, k) in enumerate(planning)], [inp for _, inp, _ in planning])
+        mpasses = self._materialise_passes(self.engine, [a.planner if self.parts[k][1] == 1 else None for a, _, k in planning],
+                                           [inp for _, inp, _ in planning], results)
 
-        def consume(defer, a, inp, res, j, packages=packages, passes=passes, rpasses=rpasses):
+        def consume(defer, a, inp, res, j, packages=packages, passes=passes, rpasses=rpasses, mpasses=mpasses):
             return (a.planner.plan_consume(inp, res, self.engine, j, package=packages[j] if packages is not None else False,
                                            **({"prediction_pass": passes[j]} if passes is not None and passes[j] is not None else {}),
                                            **({"responsibility_pass": rpasses[j]} if rpasses is not None and rpasses[j] is not None else {}),
+                                           **({"materialise_pass": mpasses[j]} if mpasses is not None and mpasses[j] is not None else {}),
                                            **({"defer_risk": True} if defer else {}))
                     if res is not None else None)
 
@@ -387,7 +424,7 @@ class AgentBatchHip:
                 res1 = self.engine.plan_batch([one for _, one in again])
                 self.launches += 1
                 for j1, (a, one) in enumerate(again):
-                    conclude(a, one, res1[j1], j1, None, None, None)
+                    conclude(a, one, res1[j1], j1, None, None, None, None)
         for a, _, _ in passive:
             sel, _ = a.finish_step(None, global_timestep)
             out[a.id] = sel[0] if sel is not None else None
@@ -410,8 +447,8 @@ class MultiAgentSimulation:
                  use_road_boundary: bool = False, max_candidates: Optional[int] = None, engine_factory=None,
                  pipeline_groups: Optional[int] = None, freeze_gc: bool = False, batched_passes: Optional[bool] = None,
                  batched_responsibility: Optional[bool] = None, batched_risk: Optional[bool] = None,
-                 batched_risk_costs: Optional[bool] = None):
-        """batched_passes, batched_responsibility, batched_risk, batched_risk_costs: see AgentBatchHip.
+                 batched_risk_costs: Optional[bool] = None, batched_materialise: Optional[bool] = None):
+        """batched_passes, batched_responsibility, batched_risk, batched_risk_costs, batched_materialise: see AgentBatchHip.
         engine_factory: callable returning an engine object (tests inject a stand-in); default = FrenetEngine.
         pipeline_groups: see AgentBatchHip (None = automatic; with an engine_factory: that many injected engines, default one).
         freeze_gc: take what exists once the simulation is set up out of the garbage collector's generations (gc.freeze(): a
@@ -452,7 +489,7 @@ class MultiAgentSimulation:
                                    parts=[(part, n_parts) for _, part, n_parts in my_items], slots=self.my_slots,
                                    winner_exchange=self._exchange_winners if self.split else None, batched_passes=batched_passes,
                                    batched_responsibility=batched_responsibility, batched_risk=batched_risk,
-                                   batched_risk_costs=batched_risk_costs)
+                                   batched_risk_costs=batched_risk_costs, batched_materialise=batched_materialise)
         self.S = self.batch.agents[0].planner.N + 1 if mine else int(self.config.planning_horizon / self.config.dt) + 1
         self.time_step = 0
         # planned trajectories of ALL agents, identical on every rank after the exchange: [agents][S][FIELDS]

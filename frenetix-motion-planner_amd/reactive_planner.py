@@ -97,6 +97,9 @@ class PlannerConfig:
     # the packaging, log_risk and the risk fallbacks then work on that set, every other sample answers as a select-only sample
     # does.  0: the step stores everything, as ever.
     sparse_bundle_k: int = 0
+    # lanes per listed candidate of that re-walk: 1, or 8 / 32 for the list kernel on split lanes; set on
+    # the planner's engine (set_materialise_lanes) when sparse_bundle_k > 0.  The rows are the same bits at every setting.
+    sparse_lanes: int = 1
     # the cost order of all candidates sorted on the device and read by rank where the engine offers it
     # (`ranked`): all_traj pages through ranks, sparse_bundle_k may exceed 64, and the host road-boundary walk goes on past
     # `survivors` in pages of SURVIVOR_PAGE until the survivor pool ends, as the reference's does (planner.py:362-390).  Where the
@@ -133,6 +136,9 @@ class ReactivePlannerHip:
         self.msg_logger = msg_logger or logging.getLogger("Message_logger")
         self._device = device
         self._engine = engine
+        if self.config.sparse_lanes not in _abi.FX_MATERIALISE_LANES:
+            raise ValueError(f"PlannerConfig.sparse_lanes = {self.config.sparse_lanes}: one of {_abi.FX_MATERIALISE_LANES}")
+        self._lanes_set = not (self.config.sparse_bundle_k > 0 and self.config.sparse_lanes != 1)   # (nothing to set)
         self.road_boundary_check = road_boundary_check
         self.fallback_selector: Optional[Callable] = None   # last-level selection among colliding candidates (set_fallback_selector)
         self._risk_model = None             # set_risk_model: (risk.json, harm_parameters.json, obstacle types, ego mass)
@@ -198,6 +204,10 @@ class ReactivePlannerHip:
             cap = self.max_candidates_per_step()
             self._engine = FrenetEngine(max_candidates=max(cap, 4096), max_steps=self.N, max_ref_knots=4096,
                                         max_obstacles=MAX_OBSTACLES, max_pred_steps=max(64, self.N + 2), device=self._device)
+        if not self._lanes_set:
+            self._lanes_set = True
+            if hasattr(self._engine, "set_materialise_lanes"):
+                self._engine.set_materialise_lanes(self.config.sparse_lanes)
         return self._engine
 
     def max_candidates_per_step(self) -> int:
@@ -786,7 +796,7 @@ class ReactivePlannerHip:
         return self._inputs_for_level(self._sampling_min, stop_point_s)
 
     def plan_consume(self, inputs: PlanInputs, res: dict, engine, agent: int = 0, package=False, prediction_pass=None,
-                     responsibility_pass=None, defer_risk: bool = False):
+                     responsibility_pass=None, defer_risk: bool = False, materialise_pass=None):
         """Take this planner's share of a batched launch (first sampling level); returns the chosen trajectory
         (materialised -- the batch engine's buffers are reused) or None when the level has to escalate.
         package: the winner as the batched call already packaged it (engine.plan_batch_packaged; None = nothing found);
@@ -796,13 +806,14 @@ class ReactivePlannerHip:
         the planners' risk evaluations in one call -- a "min_risk" fallback of this level then returns None here and waits:
         risk_request says what to evaluate, hand_risk_result takes the result, plan_finish selects.  A "min_risk_cost" fallback
         of this level waits in the same way (risk_cost_request, hand_risk_cost_result); without a handed result plan_finish
-        makes the planner's own call."""
+        makes the planner's own call.  materialise_pass: (ids, rows) -- this agent's keep list (sparse_keep_list) and its dict of
+        an engine.materialise_batch call over this launch; None: the planner materialises its keep list itself."""
         if package is False:
             package = engine.package(agent, self.x_0.yaw_rate) if getattr(engine, "packaging", False) and inputs.write_bundle else None
         self._risk_defer = bool(defer_risk)
         try:
             best = self._consume_result(inputs, res, engine, agent, package, self._sampling_min, prediction_pass=prediction_pass,
-                                        responsibility_pass=responsibility_pass)
+                                        responsibility_pass=responsibility_pass, materialise_pass=materialise_pass)
         finally:
             self._risk_defer = False
         if best is not None:
@@ -943,8 +954,23 @@ class ReactivePlannerHip:
             self.msg_logger.warning("No optimal trajectory available. Select lowest risk trajectory!")
         return chosen
 
+    def batched_materialise_pass(self, inputs: PlanInputs, engine) -> bool:
+        """this planner's keep list of a step with `inputs` can be materialised by a batch's one call: a select-only step whose
+        keep list is the winner and top-k rows (not ranks beyond the top-k's bound, which _consume_result reads per agent)"""
+        k = int(self.config.sparse_bundle_k)
+        by_rank = bool(self.config.device_sort) and hasattr(engine, "ranked")
+        return k > 0 and not inputs.write_bundle and not (by_rank and k > 64)
+
+    @staticmethod
+    def sparse_keep_list(inputs: PlanInputs, res: dict, topk_row, k: int) -> np.ndarray:
+        """the winner and the first k entries of the step's top-k row, as local indices, ascending and without duplicates: the
+        set _consume_result materialises"""
+        keep = [int(res["best_index"])] if res["best_index"] >= 0 else []
+        keep += [int(g) for g in topk_row[:k] if g >= 0]
+        return np.unique(np.asarray(keep, np.int64) - inputs.shard_begin)
+
     def _consume_result(self, inputs: PlanInputs, res: dict, engine, agent: int, package=None, samp_lvl=None, prediction_pass=None,
-                        responsibility_pass=None):
+                        responsibility_pass=None, materialise_pass=None):
         if self.last_step is not None:
             self.last_step.invalidate()
         self._risk_pending = self._risk_handed = self._stopping_choice = None   # (they belong to the step before)
@@ -972,7 +998,9 @@ class ReactivePlannerHip:
         by_rank = bool(self.config.device_sort) and hasattr(engine, "ranked")
         if self._draw_traj_set or self.save_all_traj:
             self.all_traj = _LazySortedList(step, by_rank)
-        if self.config.sparse_bundle_k > 0 and not inputs.write_bundle:
+        if materialise_pass is not None:
+            step.install_materialised(*materialise_pass)   # (the batch's one call made this agent's set and read its rows)
+        elif self.config.sparse_bundle_k > 0 and not inputs.write_bundle:
             # the winner and the step's best survivors, re-walked into the agent's sparse set: what the code below reads of them
             keep = [int(res["best_index"])] if res["best_index"] >= 0 else []
             if by_rank and self.config.sparse_bundle_k > 64:   # (beyond the top-k's bound: the first ranks of the survivor pool)

@@ -502,6 +502,13 @@ class PlanStepResult:
         self._mat = self.engine.materialise(ids, self.agent)
         self._mat_ids = ids
 
+    def install_materialised(self, ids, rows):
+        """the rows of `ids` (ascending, without duplicates) as a call outside made them for this step's agent
+        (engine.materialise_batch): what materialise(ids) would have installed"""
+        self._check()
+        self._mat = rows
+        self._mat_ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+
     def _mat_row(self, index):
         """row of candidate `index` among the materialised ones, None when it is not listed"""
         ids = self._mat_ids

@@ -491,8 +491,30 @@ int32_t fx_read_materialised_agent(FxContext *ctx, int32_t agent, int64_t n, con
 /* the package of fx_read_package for candidate `index` (local) of the sparse set: found = 1, pkg->index global, block as there */
 int32_t fx_read_package_materialised(FxContext *ctx, int32_t agent, int64_t index, double yaw_rate0, FxPackage *pkg,
                                      double *block /*[FX_PKG_ROWS][S] or NULL*/);
-/* device time of the context's last list-kernel launch (events attached to the kernel), ms; -1 before the first.  Waits for it. */
+/* device time of the context's last materialise call, from the start of its first list-kernel launch to the end of its last
+ * (events attached to the kernels), ms; -1 before the first.  Waits for it. */
 double fx_last_materialise_ms(FxContext *ctx);
+/* ---- the list pass on split lanes and for a whole agent batch -- DESIGN.md section 22; additive, the ABI version stays ----
+ *      fx_set_materialise_lanes: lanes per listed candidate of the list kernel.  0 or 1 (the default): one lane walks a
+ *      candidate's whole horizon; 8 or 32: the horizon is cut into that many chunks walked by adjacent lanes, the decomposition
+ *      of the plan step's generic kernel at that many lanes, so a row equals the row that kernel stores bit for bit.  Anything
+ *      else: FX_ERR_INVALID_ARGUMENT, and the setting stays.  It applies to fx_materialise_candidates_agent and to the batch
+ *      call; an agent with a windowed cost term (acceleration, jerk, path_length, orientation_offset, distance_to_obstacles,
+ *      lane_center_offset) runs at one lane whatever is set.  fx_set_tuning does not touch it. */
+int32_t fx_set_materialise_lanes(FxContext *ctx, int32_t lanes);
+/*      fx_materialise_candidates_batch: fx_materialise_candidates_agent for n_agents agents in one call -- agents[j] (NULL:
+ *      agent j) with the list ids[j] of n_ids[j] candidates -- with one wait for the stream, one upload (row table, clones and
+ *      lists) and one launch per kernel variant (lanes, obstacle stage, windowed terms) present among the agents, four at most.
+ *      Each agent receives the set the per-agent call would have made, in its own block; the readers and the risk passes do not
+ *      tell the two apart.  n_ids[j] == 0 clears that agent's set.  Everything is checked before anything is written or
+ *      launched, and a refused call leaves every previous set readable and takes no memory: the per-agent refusals of each
+ *      agent, and FX_ERR_INVALID_ARGUMENT for n_agents < 0 or more agents than the last upload holds, an agent outside it or
+ *      listed twice, NULL n_ids or ids with n_agents > 0.  n_agents == 0 returns FX_OK and touches nothing. */
+int32_t fx_materialise_candidates_batch(FxContext *ctx, int32_t n_agents, const int32_t *agents /* NULL: 0 ... n_agents - 1 */,
+                                        const int64_t *n_ids, const int64_t *const *ids);
+/*      the last materialise call of the context: the widest lane split among its rows, its list-kernel launches and its rows
+ *      (agents with a non-empty list); zeros before the first and behind a call that only cleared.  Any pointer may be NULL. */
+int32_t fx_last_materialise_info(FxContext *ctx, int32_t *lanes, int32_t *launches, int32_t *rows);
 
 /* ---- stable cost order of ALL candidates of a plan step, sorted beside it and read back by rank -- DESIGN.md section 15 ----
  *      TrajectoryBundle.sort (trajectories.py:524-561) on the device: a stable radix sort of one agent's candidates by cost, ties

@@ -51,7 +51,7 @@ struct FxSparseOutputs {
 static void fx_sparse_clone(DevProblem &d, const DevProblem &src, int64_t m, int64_t ld, int n_blocks, char *base, const FxSparseOutputs &o,
                             unsigned long long *counters, double *part_cost, int64_t *part_idx) {
     d = src;
-    d.mode = (src.mode | FX_MODE_WRITE_BUNDLE | FX_MODE_WRITE_COSTMAP) & ~(FX_MODE_INT_DEFER_OBST | FX_MODE_INT_REC_LDS | FX_MODE_INT_STORE_WT);
+    d.mode = (src.mode | FX_MODE_WRITE_BUNDLE | FX_MODE_WRITE_COSTMAP) & ~(FX_MODE_INT_DEFER_OBST | FX_MODE_INT_REC_LDS | FX_MODE_INT_STORE_WT | FX_MODE_INT_CHUNK_INDEX);
     d.C = m; d.ld = ld; d.n_blocks = n_blocks;
     d.planes = reinterpret_cast<double *>(base + o.o_planes);
     d.coeffs = reinterpret_cast<double *>(base + o.o_coeffs);

@@ -62,6 +62,12 @@ int32_t fx_upload_batch(FxContext *c, int32_t n_agents, const FxProblem *probs) 
     const char *pad = getenv("FX_LDS_PAD");
     c->force.lds_pad = pad ? (size_t)atol(pad) : 0;
     c->force.tail_max_c = tail_max_c;
+    // (experiment: FX_OBST_WG = 0 / 1 forces the obstacle kernel's single-wave items / workgroups; read with the upload, as the two
+    // above, so that an evaluation puts no environment look-up in front of its first launch)
+    const char *wg_env = getenv("FX_OBST_WG");
+    c->force.obst_wg = wg_env ? (atoi(wg_env) ? 2 : 1) : 0;
+    const char *ci_env = getenv("FX_OBST_CHUNK_INDEX");   // (test hook: tests/test_chunk_placement.py)
+    c->force.obst_chunk_index = ci_env && atoi(ci_env) != 0;
     FxStepPlan &pl = c->plan;
     int rc = fx_plan_upload(n_agents, probs, c->force, c->caps, &pl, g_err, sizeof(g_err));
     if (rc) return rc;
@@ -253,7 +259,9 @@ int32_t fx_evaluate(FxContext *c) {
     if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
     if (!c->uploaded) return set_err(FX_ERR_NOT_READY, "fx_evaluate before fx_upload");
     if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it (its stream may never drain)");
-    HIP_TRY(hipSetDevice(c->device));
+    // (a planner's thread stays on its context's device from step to step: the device is set only where it is another one)
+    int cur_device = -1;
+    if (hipGetDevice(&cur_device) != hipSuccess || cur_device != c->device) HIP_TRY(hipSetDevice(c->device));
     if (c->probs_dirty || c->dirty_hi > c->dirty_lo) {
         // inputs rewritten by fx_update_state since the last evaluation: ONE copy of the front of the staging block (the
         // problems, then whatever changed behind them)
@@ -265,10 +273,6 @@ int32_t fx_evaluate(FxContext *c) {
         c->probs_dirty = false;
     }
     const FxStepPlan &pl = c->plan;
-    if (pl.split) {   // experiments: 0 / 1 force single-wave items / workgroups
-        const char *wg_env = getenv("FX_OBST_WG");
-        c->force.obst_wg = wg_env ? (atoi(wg_env) ? 2 : 1) : 0;
-    }
     FxLaunchPlan &L = c->launch = fx_plan_launches(pl, c->force, c->package_enabled);
     // timing (every timing_every-th step): FX_TIMING_KERNEL attaches start/stop events to the evaluation kernel
     // itself (hipExtLaunchKernel), so its duration is the kernel's, not launch latency; FX_TIMING_STREAM brackets

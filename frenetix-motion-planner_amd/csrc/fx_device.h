@@ -22,6 +22,9 @@ __host__ __device__ inline bool fx_split_wt(uint32_t mode) {
 // internal DevProblem.mode bit: the agent's obstacle record table rec[S][K][12] and its two step masks are staged in the dynamic
 // LDS of the lane-split evaluation kernels (the host has sized the launch's LDS for them: fx_api.hip)
 #define FX_MODE_INT_REC_LDS (1u << 28)
+// internal DevProblem.mode bit (test hook, FX_OBST_CHUNK_INDEX=1): the waves of an obstacle-kernel workgroup take the horizon's chunks
+// by index instead of through FX_OBST_CHUNK_MAP (fx_obstacle_kernel.h)
+#define FX_MODE_INT_CHUNK_INDEX (1u << 27)
 #define FX_HOT_STRIDE 10        // doubles per (step, obstacle) entry of the hot obstacle table (80 B)
 #define FX_HOT_PRE 4            // table elements per lane prefetched one step ahead (covers K <= 25 obstacles)
 #define FX_TP 14                // doubles per step of the time table in LDS: t .. t^5, then 2t, 3t^2, 4t^3, 5t^4, 6t, 12t^2, 20t^3, then the

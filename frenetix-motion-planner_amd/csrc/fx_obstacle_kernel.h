@@ -445,6 +445,13 @@ __device__ __forceinline__ void fx_obstacle_body(const DevProblem &P, const Obst
     FX_OSTAMP(15);
 }
 
+// Ten chunks on ten waves: which chunk a wave takes.  The hardware deals the waves of a ten-wave workgroup round-robin over the CU's
+// four SIMDs -- waves 0,4,8 / 1,5,9 / 2,6 / 3,7 share one -- and sets the CU's second workgroup one SIMD further: one SIMD carries six
+// waves, two five, one four (profiles/placement/census.txt).  The candidates of a tile diverge along the horizon, so the tile's
+// bounding disc and with it what survives the wave-level cull grow from chunk to chunk: the six earliest chunks go to the SIMDs with
+// three waves of the workgroup, the four latest to those with two.  wave -> chunk = 0 1 6 7 4 2 9 8 5 3, four bits per wave; wave 0
+// keeps chunk 0 and closes the tile, and the partials meet in LDS by chunk: results do not depend on the map.
+#define FX_OBST_CHUNK_MAP 0x3589247610ULL
 // HEAD: the launch has one agent and the leading arguments are its step header (ObstHead; probs .. h_K are the 12 preloaded dwords);
 // a batched launch runs the HEAD = false kernel, which reads every agent's problem first, as before.
 template <int CH, int WPS, bool WG = false, bool HEAD = false>
@@ -456,7 +463,8 @@ __global__ __launch_bounds__(WG ? 1024 : 64, WG ? FX_OBST_WG_WPE : WPS) void fx_
     const ObstHead H = HEAD ? ObstHead{h_obs_list, h_counters, h_obs_hot, h_C, h_S, h_K, h_mode} : ObstHead::of(P);
     const int NC = (H.S - 1 + CH - 1) / CH;
     const int tile = WG ? (int)blockIdx.x : (int)(blockIdx.x / NC);
-    const int chunk = WG ? (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(blockIdx.x - tile * NC);
+    int chunk = WG ? (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(blockIdx.x - tile * NC);
+    if (WG && NC == 10 && blockDim.x == 640 && !(H.mode & FX_MODE_INT_CHUNK_INDEX)) chunk = (int)((FX_OBST_CHUNK_MAP >> (4 * chunk)) & 15ULL);
     fx_obstacle_body<CH, WG, false>(P, H, lds_all, tile, chunk);
 }
 

@@ -29,6 +29,7 @@ struct FxForce {
     size_t lds_pad = 0;            // FX_LDS_PAD: occupancy cap through LDS
     int64_t tail_max_c = 8192;     // FX_TAIL_MAX_C: candidates per agent up to which the step's last workgroup counts the collisions (fx_plan_upload)
     int obst_wg = 0;               // FX_OBST_WG: 1 single-wave items, 2 workgroups
+    bool obst_chunk_index = false; // FX_OBST_CHUNK_INDEX=1: the obstacle workgroup's waves take their chunks by index (FX_MODE_INT_CHUNK_INDEX)
 };
 
 // the context's capacities (fx_create_batch)
@@ -319,6 +320,7 @@ inline int fx_plan_upload(int n_agents, const FxProblem *probs, const FxForce &f
         all_deferred = all_deferred && r.deferred;
         if (r.deferred) {   // the obstacle kernel writes this agent's arg-min partials: one per tile of 64 candidates
             r.mode |= FX_MODE_INT_DEFER_OBST;
+            if (f.obst_chunk_index) r.mode |= FX_MODE_INT_CHUNK_INDEX;
             const int n_tiles = (int)((C + 63) / 64), NC = (S - 1 + CH - 1) / CH;
             const int NC_alloc = std::max(NC, (S - 1 + 2) / 3);   // (the one-launch step picks its own steps per item: 3, 5 or 8)
             r.n_blocks = n_tiles;

@@ -8,6 +8,7 @@ import ctypes as C
 FX_ABI_VERSION = 15
 FX_READ_CHUNK_BYTES = 8 << 20   # fx_read_candidates_agent: bytes per chunk (ids + packed records)
 FX_LON_VELOCITY_KEEPING, FX_LON_STOP_POINT = 0, 1
+FX_RESCORE_MAX_VECTORS = 32768  # fx_rescore_agent: weight vectors per call
 
 FX_OK = 0
 FX_ERR_INVALID_ARGUMENT = -1

@@ -48,6 +48,7 @@ def exported_symbols():
         "fx_eval_prediction_prob_agent", "fx_last_predprob_ms", "fx_eval_prediction_prob_batch",
         "fx_eval_responsibility_cost_agent", "fx_eval_responsibility_cost_batch",
         "fx_eval_risk_batch", "fx_eval_risk_costs_batch",
+        "fx_rescore_agent", "fx_last_rescore_ms", "fx_device_costmap_view",
     ]
 
 
@@ -160,6 +161,12 @@ def lib():
         "fx_read_ranked_agent": ([vp, C.c_int32, C.c_int64, C.c_int64, vp, vp, vp], C.c_int32),   # (arrays: plain addresses)
         "fx_sort_views": ([vp, C.c_int32, C.POINTER(vp), pi64], C.c_int32),
         "fx_last_sort_ms": ([vp], C.c_double),
+        "fx_rescore_agent": ([vp, C.c_int32, C.c_int32, vp, vp, vp, vp], C.c_int32),   # (arrays: plain addresses)
+        "fx_last_rescore_ms": ([vp], C.c_double),
+        "fx_device_costmap_view": ([vp, C.c_int32, C.POINTER(vp), pi64, pi32], C.c_int32),
+        # (launcher hook of the tests and tools/bench_rescore.py, not part of fxplan.h: 0 the rule, 1 candidate per lane, 2 vector per lane)
+        "fx_rescore_set_regime": ([C.c_int32], None),
+        "fx_rescore_regime": ([C.c_int64, C.c_int32], C.c_int32),
         "fx_eval_prediction_prob_agent": ([vp, C.c_int32, C.POINTER(_abi.FxPredProbParams), C.c_int64, pi64,
                                            C.POINTER(_abi.FxPredProbOutputs)], C.c_int32),
         "fx_last_predprob_ms": ([vp], C.c_double),

@@ -1,8 +1,9 @@
 // fx_api_sort.hip -- the stable cost order of all candidates of the last plan step, sorted on the device beside it and read back by
 // rank (header: include/fxplan.h; kernels: fx_sort_kernel.h).  Nothing here runs in a plan step, and nothing a
 // plan step, the top-k, a sparse set or the risk passes wrote or published is touched: the pass reads the cost and flag planes and
-// writes its own block.
+// writes its own block.  Behind it, the re-score of the last step under other cost weights, a pass of the same kind.
 #include "fx_pass.h"
+#include "fx_rescore_plan.h"
 
 extern "C" hipError_t fx_launch_sort(const FxSortArgs *args, int n_agents, int64_t max_C, hipEvent_t ev_start, hipEvent_t ev_stop,
                                      hipStream_t stream);
@@ -184,5 +185,109 @@ int32_t fx_sort_views(FxContext *c, int32_t agent, void **d_index, int64_t *n_po
 
 // device time of the context's last sort (events around its launch sequence), ms; -1 before the first
 double fx_last_sort_ms(FxContext *c) { return (c && c->sort) ? c->sort->ev.elapsed_ms() : -1.0; }
+
+}  // extern "C"
+
+// ---- the last plan step re-scored under many cost-weight vectors at once (kernels: fx_rescore_kernel.h; launch
+// rule: fx_rescore_plan.h).  Like the sort it reads planes of the step -- the raw cost rows and the flag words -- and writes a block of
+// its own. ----
+// (weak: a host-only program that links these files against launcher stubs of its own need not define it)
+extern "C" __attribute__((weak)) hipError_t fx_launch_rescore(const FxRescoreArgs *a, const FxRescorePlan *p, hipEvent_t ev_start,
+                                                              hipEvent_t ev_stop, hipStream_t stream);
+
+struct FxRescoreState {
+    explicit FxRescoreState(FxContext *c) : block(&c->dev_bytes) {}
+    FxDeviceBlock block;   // staged weights | partials | winners | costs | totals, every part 256-byte aligned (FxBlockLayout)
+    FxEventPair ev;
+};
+
+void fx_rescore_release(FxRescoreState *s) { delete s; }
+
+// (launcher hook of the tests and of tools/bench_rescore.py, not part of fxplan.h: 0 the rule of fx_rescore_plan, FX_RESCORE_LANE /
+// FX_RESCORE_VECTOR that regime whatever the number of vectors -- the results do not depend on it)
+static std::atomic<int> fx_rescore_regime_forced{0};
+
+extern "C" {
+
+void fx_rescore_set_regime(int32_t regime) {
+    fx_rescore_regime_forced.store((regime == FX_RESCORE_LANE || regime == FX_RESCORE_VECTOR) ? regime : 0, std::memory_order_relaxed);
+}
+// the regime a call of n candidates and n_vec vectors takes
+int32_t fx_rescore_regime(int64_t n, int32_t n_vec) {
+    return fx_rescore_plan(n, n_vec, fx_rescore_regime_forced.load(std::memory_order_relaxed)).regime;
+}
+
+int32_t fx_device_costmap_view(FxContext *c, int32_t agent, void **costmap, int64_t *ld, int32_t *n_cost) {
+    FX_TRY(check_agent(c, agent));
+    const FxAgentSlot &s = c->slots[agent];
+    if (!(s.mode & FX_MODE_WRITE_COSTMAP)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_COSTMAP");
+    if (costmap) *costmap = c->d_costmap + (size_t)FX_NUM_COSTS * s.cand_off;
+    if (ld) *ld = s.ld;
+    if (n_cost) *n_cost = s.n_cost;
+    return FX_OK;
+}
+
+int32_t fx_rescore_agent(FxContext *c, int32_t agent, int32_t n_vec, const double *w, int64_t *winner, double *cost, double *totals) {
+    // every refusal stands in front of the first allocation, copy or launch
+    FX_TRY(check_agent(c, agent));
+    if (!fx_inputs_current(c))
+        return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
+    const FxAgentSlot &s = c->slots[agent];
+    if (!(s.mode & FX_MODE_WRITE_COSTMAP)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_COSTMAP");
+    if (n_vec < 1) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_rescore_agent: n_vec %d", n_vec);
+    if (!w || !winner || !cost) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_rescore_agent: NULL argument");
+    if (n_vec > FX_RESCORE_MAX_VECTORS) return set_err(FX_ERR_CAPACITY, "%d weight vectors: at most %d per call", n_vec, FX_RESCORE_MAX_VECTORS);
+    const DevProblem &hp = c->h_probs[agent];
+    const int n_cost = hp.n_cost;
+    for (size_t k = 0; k < (size_t)n_vec * n_cost; k++)
+        if (!(w[k] != 0.0) || !std::isfinite(w[k]))
+            return set_err(FX_ERR_INVALID_ARGUMENT, "weight %d of vector %lld is %g: weights are finite and not zero (a zero weight is another cost list)",
+                           (int)(k % n_cost), (long long)(k / n_cost), w[k]);
+    if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
+    if (!fx_launch_rescore) return set_err(FX_ERR_HIP, "built without the re-score launcher");
+    const FxRescorePlan plan = fx_rescore_plan(s.C, n_vec, fx_rescore_regime_forced.load(std::memory_order_relaxed));
+    if (plan.n_part > 0x7fffffffLL) return set_err(FX_ERR_CAPACITY, "%lld candidates: %lld workgroups", (long long)s.C, (long long)plan.n_part);
+
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->rescore) c->rescore.reset(new FxRescoreState(c));
+    FxRescoreState *st = c->rescore.get();
+    const size_t W = (size_t)n_vec, parts = fx_rescore_partials(plan, n_vec), n = (size_t)s.C;
+    FxBlockLayout lay;
+    const size_t o_w = lay.take(sizeof(double) * W * n_cost), o_pc = lay.take(sizeof(double) * parts), o_pi = lay.take(sizeof(long long) * parts);
+    const size_t o_win = lay.take(sizeof(long long) * W), o_cost = lay.take(sizeof(double) * W);
+    const size_t o_tot = totals ? lay.take(sizeof(double) * W * n) : 0;
+    // (a block that grows is freed: what was queued on it runs out first)
+    if (lay.size() > st->block.size() && st->block) HIP_TRY(hipStreamSynchronize(c->stream));
+    FX_TRY(st->block.ensure(lay.size()));
+    FX_TRY(st->ev.ensure());
+    st->ev.timed = false;
+    char *b = st->block;
+
+    FxRescoreArgs a{};
+    a.costmap = c->d_costmap + (size_t)FX_NUM_COSTS * s.cand_off;
+    a.flags = c->d_flags + s.cand_off;
+    a.n = s.C, a.ld = s.ld, a.n_cost = n_cost, a.n_vec = n_vec;
+    a.n_pred = -1;
+    for (int m = 0; m < n_cost; m++)
+        if (hp.cost_id[m] == FX_COST_PREDICTION) a.n_pred = m;
+    // (a deferred step without a prediction term closed nothing in the obstacle kernel: its costs are the walk's own sums)
+    a.deferred = ((hp.mode & FX_MODE_INT_DEFER_OBST) && a.n_pred >= 0) ? 1 : 0;
+    a.w = reinterpret_cast<const double *>(b + o_w);
+    a.part_cost = reinterpret_cast<double *>(b + o_pc), a.part_idx = reinterpret_cast<long long *>(b + o_pi);
+    a.winner = reinterpret_cast<long long *>(b + o_win), a.cost = reinterpret_cast<double *>(b + o_cost);
+    a.totals = totals ? reinterpret_cast<double *>(b + o_tot) : nullptr;
+    c->in_flight = true; c->tail_work = true;
+    if (n_cost > 0) HIP_TRY(hipMemcpyAsync(b + o_w, w, sizeof(double) * W * n_cost, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(fx_launch_rescore(&a, &plan, st->ev.e0, st->ev.e1, c->stream));
+    st->ev.timed = true;
+    static_assert(sizeof(long long) == sizeof(int64_t), "the winners are copied as they are");
+    HIP_TRY(hipMemcpyAsync(winner, a.winner, sizeof(int64_t) * W, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(cost, a.cost, sizeof(double) * W, hipMemcpyDeviceToHost, c->stream));
+    if (totals && n > 0) HIP_TRY(hipMemcpyAsync(totals, a.totals, sizeof(double) * W * n, hipMemcpyDeviceToHost, c->stream));
+    return fx_drain(c);
+}
+
+// device time of the context's last re-score (events around its launches), ms; -1 before the first
+double fx_last_rescore_ms(FxContext *c) { return (c && c->rescore) ? c->rescore->ev.elapsed_ms() : -1.0; }
 
 }  // extern "C"

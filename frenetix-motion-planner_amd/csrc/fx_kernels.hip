@@ -95,6 +95,7 @@ extern "C" hipError_t fx_launch_package(const DevProblem *d_probs, int n_agents,
 #define FX_TOPK_SLICES 64
 #define FX_TOPK_R 32
 #include "fx_topk_kernel.h"   // fx_topk_*_kernel
+#include "fx_rescore_kernel.h"   // fxrs::fx_rescore_*_kernel
 
 // Copy a small device buffer (the all-gathered survivors) into pinned host memory and publish a sequence word:
 // the host polls instead of paying for a D2H copy + stream synchronisation.
@@ -583,4 +584,33 @@ extern "C" hipError_t fx_launch_sort_gather(const int64_t *d_order, int64_t n, c
         hipLaunchKernelGGL(fx_sort_gather_kernel, dim3((unsigned)((n + FX_SORT_BLOCK - 1) / FX_SORT_BLOCK)), dim3(FX_SORT_BLOCK), 0, stream,
                            d_order, n, cost, flags, C, out_cost, out_flags);
     return hipGetLastError();
+}
+
+// A finished step re-scored under a->n_vec weight vectors (fx_rescore_kernel.h).  p: fx_rescore_plan of the
+// call -- the regime, the partials per vector and the grids; the partials' buffers hold a->n_vec x p->n_part entries.  The totals, where
+// asked for, come from the lane kernel in both regimes (coalesced stores): beside the vector kernel it runs without its reduction.
+// ev_start / ev_stop bracket all launches.
+extern "C" hipError_t fx_launch_rescore(const FxRescoreArgs *a, const FxRescorePlan *p, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                        hipStream_t stream) {
+    hipError_t e;
+    if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
+    fxrs::Dims d{a->n, a->ld, a->n_cost, a->n_pred, a->deferred, a->n_vec, p->vec_chunk, p->n_part, p->per};
+    const dim3 grid((unsigned)p->n_part, (unsigned)p->grid_y);
+    if (p->regime == FX_RESCORE_LANE) {
+        hipLaunchKernelGGL(fxrs::fx_rescore_lane_kernel<true>, grid, dim3(FX_RESCORE_TILE), 0, stream, a->costmap, a->flags, a->w, d, a->part_cost,
+                           a->part_idx, a->totals);
+    } else {
+        hipLaunchKernelGGL(fxrs::fx_rescore_vector_kernel, grid, dim3(64), 0, stream, a->costmap, a->flags, a->w, d, a->part_cost, a->part_idx);
+        if (a->totals && a->n > 0) {
+            const FxRescorePlan t = fx_rescore_plan(a->n, a->n_vec, FX_RESCORE_LANE);
+            d.vec_chunk = t.vec_chunk;
+            hipLaunchKernelGGL(fxrs::fx_rescore_lane_kernel<false>, dim3((unsigned)t.n_part, (unsigned)t.grid_y), dim3(FX_RESCORE_TILE), 0, stream,
+                               a->costmap, a->flags, a->w, d, nullptr, nullptr, a->totals);
+        }
+    }
+    hipLaunchKernelGGL(fxrs::fx_rescore_finish_kernel, dim3((unsigned)p->finish_blocks), dim3(256), 0, stream, a->part_cost, a->part_idx, p->n_part,
+                       a->n_vec, a->winner, a->cost);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
+    return hipSuccess;
 }

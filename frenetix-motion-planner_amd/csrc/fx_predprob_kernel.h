@@ -29,6 +29,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "fx_cost_sum.h"
 #include "fx_risk_kernel.h"
 
 namespace fxpp {
@@ -89,17 +90,16 @@ __device__ __forceinline__ void finish_body(const PredProbArgs &a, const int64_t
             for (int k = 0; k < K; k++) a.prob_obs[(size_t)k * n + j] = NAN;   // (the step keeps no per-obstacle sums)
     }
     // weighted sum in the cost list's order (fx_eval_kernel.h finish_candidate): sum = -0.0; sum += w * c per term;
-    // total = 0.0 + sum.  A deferred step (fx_obstacle_kernel.h) added the terms behind the prediction as ONE addend, tail.
-    double sum = -0.0, tail = 0.0;
+    // total = 0.0 + sum.  A deferred step (fx_obstacle_kernel.h) added the terms behind the prediction as ONE addend, tail
+    // (fx_cost_sum.h: the sum the re-score kernels share).
+    FxCostSum s;
     for (int m = 0; m < a.n_cost; m++) {
         const double cm = m == a.n_pred ? pred : a.costmap[(size_t)m * a.ld + c];
-        const double t = a.cost_w[m] * cm;
-        if (a.deferred && m > a.n_pred) tail += t;
-        else sum += t;
+        s = fx_cost_sum_add(a, s, m, a.cost_w[m], cm);
     }
-    if (a.deferred && a.n_pred + 1 < a.n_cost) sum += tail;
+    s = fx_cost_sum_join(a, s);
     a.prob[j] = pred;
-    a.total[j] = 0.0 + sum;
+    a.total[j] = fx_cost_sum_total(s);
 }
 __global__ __launch_bounds__(256) void fx_predprob_finish_kernel(const PredProbArgs a, const int64_t j0) {
     finish_body(a, j0, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);

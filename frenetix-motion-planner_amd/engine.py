@@ -150,6 +150,40 @@ def build_boundary_bins(ref_xy, segments, max_len: float, reach: float):
     check(rc)
 
 
+def rescore_weights(weights, cost_names) -> np.ndarray:
+    """The [W][n_cost] float64 array FrenetEngine.rescore hands to the library (no device needed).  `weights`: an [W][n_cost] array
+    (or one [n_cost] vector) in `cost_names` order, or name -> weight dicts (one, or a sequence) whose non-zero names are exactly
+    `cost_names` -- a zero entry is a term upstream does not register (cost_function.py:55-60), so it may be listed, and a step
+    whose list lacks a non-zero name, or has one the dict lacks, is another cost function: ValueError.  Every weight is finite and
+    not zero (ValueError); negative weights are legal.  cost_names None: no step to compare with, arrays pass as they are."""
+    if isinstance(weights, dict):
+        weights = [weights]
+    if not isinstance(weights, np.ndarray) and len(weights) > 0 and all(isinstance(d, dict) for d in weights):
+        if cost_names is None:
+            raise ValueError("weight dicts need a plan step whose cost_names they are held to")
+        rows = []
+        for k, d in enumerate(weights):
+            mine = sorted(n for n, v in d.items() if v != 0)
+            if mine != sorted(cost_names):
+                raise ValueError(f"weight set {k}: non-zero terms {mine} are not the step's {sorted(cost_names)}")
+            rows.append([d[n] for n in cost_names])
+        w = np.array(rows, dtype=np.float64).reshape(len(rows), len(cost_names))
+    else:
+        try:
+            w = np.array(weights, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"weights: an [W][n_cost] array or name -> weight dicts ({e})") from e
+        if w.ndim == 1 and w.size > 0:
+            w = w[None, :]
+    if w.ndim != 2 or w.shape[0] < 1:
+        raise ValueError(f"weights of shape {w.shape}: [W][n_cost] with W >= 1")
+    if cost_names is not None and w.shape[1] != len(cost_names):
+        raise ValueError(f"weights of shape {w.shape}: the step has {len(cost_names)} cost terms {list(cost_names)}")
+    if not np.all(np.isfinite(w)) or np.any(w == 0.0):
+        raise ValueError("weights must be finite and not zero (a zero weight is another cost list: plan a step with it)")
+    return np.ascontiguousarray(w)
+
+
 class WinnerPackage:
     """The chosen trajectory as the library packaged it (fx_read_package): `block` [FX_PKG_ROWS][S] = the 14 planes, yaw rate,
     steering angle, shifted heading; coefficients, raw partial costs, cost, flag word, horizon, global index."""
@@ -903,6 +937,35 @@ class FrenetEngine(StepRegistry):
     def last_sort_ms(self) -> float:
         """device time of the last sort's launches"""
         return float(lib().fx_last_sort_ms(self._ctx))
+
+    # -- the last step re-scored under other cost weights, on the device (DESIGN.md section 23) --
+    def rescore(self, weights, agent: int = 0, totals: bool = False) -> dict:
+        """The agent's last step under W other weight vectors in one call (fx_rescore_agent): which candidate wins, and at what cost,
+        had the step run with each of them.  `weights`: [W][n_cost] in the step's `PlanInputs.cost_names` order, or a sequence of
+        name -> weight dicts whose non-zero names are exactly the step's (`rescore_weights`); finite and not zero, negative is legal.
+        Returns dict(winner [W] int64: local candidate indices, -1 where nothing is eligible; cost [W]: +inf there; totals [W][C]
+        or None: every candidate's weighted cost, NaN without FX_FLAG_COSTED).  The bits are those of a plan step run with these
+        weights.  It is the device selection only: nothing of the step is rewritten, and no host walk follows."""
+        names = self._inputs[agent].cost_names if 0 <= agent < len(self._inputs) else None
+        w = rescore_weights(weights, names)
+        n_vec = w.shape[0]
+        n = self._inputs[agent].n_candidates if names is not None else 0
+        winner, cost = np.empty(n_vec, np.int64), np.empty(n_vec)
+        tot = np.empty((n_vec, n)) if totals else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        check(lib().fx_rescore_agent(self._ctx, int(agent), n_vec, ptr(w), ptr(winner), ptr(cost), ptr(tot)))
+        return dict(winner=winner, cost=cost, totals=tot)
+
+    @property
+    def last_rescore_ms(self) -> float:
+        """device time of the last re-score's launches"""
+        return float(lib().fx_last_rescore_ms(self._ctx))
+
+    def costmap_view(self, agent: int = 0):
+        """(device pointer of the agent's raw cost rows f64 [n_cost][ld], ld, n_cost) of a step that stored them (fx_device_costmap_view)"""
+        p, ld, n_cost = C.c_void_p(), C.c_int64(0), C.c_int32(0)
+        check(lib().fx_device_costmap_view(self._ctx, int(agent), C.byref(p), C.byref(ld), C.byref(n_cost)))
+        return p.value, int(ld.value), int(n_cost.value)
 
     def plane(self, name_or_index, agent: int = 0) -> np.ndarray:
         """[S, C] one plane of every candidate."""

@@ -521,6 +521,19 @@ class ReactivePlannerHip:
             raise ValueError("no plan step yet")
         return self._risk_costs_on(self.last_step, ids)
 
+    def rescore(self, weight_sets):
+        """The last plan step under other cost weights (FrenetEngine.rescore): [(index, cost)] per weight
+        set -- name -> weight dicts over the step's own non-zero terms, or rows in its cost_names order -- the candidate the
+        device selection would have chosen had the step run with them, -1 / inf where no candidate is selectable and
+        collision-free.  It is the device selection only: the host road-boundary walk and the occlusion walk of plan() are not
+        run, and nothing of the step, of optimal_trajectory or of the planner's own cost weights changes.  Needs a step that
+        stored its cost map (not sparse_bundle_k > 0)."""
+        if self.last_step is None:
+            raise ValueError("no plan step yet")
+        step = self.last_step
+        r = step.engine.rescore(weight_sets, agent=step.agent)
+        return [(int(i), float(c)) for i, c in zip(r["winner"], r["cost"])]
+
     def _risk_costs_on(self, step, ids):
         params, cp = self._risk_cost_setup(step)
         if ids is not None:

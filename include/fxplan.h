@@ -544,6 +544,31 @@ int32_t fx_sort_views(FxContext *ctx, int32_t agent, void **d_index, int64_t *n_
 /* device time of the context's last sort (events around its launches), ms; -1 before the first.  Waits for it. */
 double fx_last_sort_ms(FxContext *ctx);
 
+/* ---- a finished plan step re-scored under many cost-weight vectors at once, beside the step -- DESIGN.md section 23; additive
+ *      within ABI 15 ----
+ *      update_externals(cost_weights=...) (planner.py:204-205, reactive_planner_cpp.py:88-94) asked of a step that has already run:
+ *      which candidate wins under these other weights?  w[n_vec][n_cost] are weight vectors over the step's own cost list (its
+ *      non-zero terms in ascending id order).  total(c) under a vector is what the step would have stored as cost[c] had it run with
+ *      it -- the same multiplications and additions in the same order, for a step whose obstacle stage ran as its own kernel the
+ *      order of that kernel -- and NaN for a candidate without FX_FLAG_COSTED.  winner[v] is the lexicographic (total, index) minimum
+ *      over the candidates with FX_FLAG_SELECTABLE and neither FX_FLAG_COLLISION nor FX_FLAG_BOUNDARY, NaN totals skipped: a LOCAL
+ *      index in [0, C) as fx_read_ranked_agent answers them, also for a sharded agent; cost[v] its total.  Nothing eligible:
+ *      winner[v] = -1, cost[v] = +inf.  totals, where not NULL, receives total(c) of every candidate, [n_vec][C].
+ *      The call reads the raw cost rows and the flag plane of the step and writes a block of its own, allocated on the first call and
+ *      grow-only; it launches on the context's stream and waits.  It is the device selection only: no host road-boundary walk.
+ *      Checked before anything is allocated, copied or launched: FX_ERR_NOT_READY before the first evaluated step, when the inputs
+ *      were rewritten since it, and for a step without FX_MODE_WRITE_COSTMAP; FX_ERR_INVALID_ARGUMENT for NULL ctx, w, winner or cost,
+ *      an agent out of range, n_vec < 1 and a weight that is zero or not finite (cost_function.py:55-60 registers only non-zero
+ *      weights: a zero weight is another cost list, whose summation form the step decides; negative weights are legal);
+ *      FX_ERR_CAPACITY above 32 768 vectors per call. */
+int32_t fx_rescore_agent(FxContext *ctx, int32_t agent, int32_t n_vec, const double *w /*[n_vec][n_cost]*/, int64_t *winner /*[n_vec]*/,
+                         double *cost /*[n_vec]*/, double *totals /*[n_vec][C] or NULL*/);
+/* device time of the context's last re-score (events around its launches), ms; -1 before the first.  Waits for it. */
+double fx_last_rescore_ms(FxContext *ctx);
+/* device pointer of one agent's raw cost rows, f64 [n_cost][ld] -- the cost-map counterpart of fx_device_views.  FX_ERR_NOT_READY for a
+ * step that stored no cost map (FX_MODE_WRITE_COSTMAP).  Any pointer may be NULL. */
+int32_t fx_device_costmap_view(FxContext *ctx, int32_t agent, void **costmap, int64_t *ld, int32_t *n_cost);
+
 /* ---- road boundary (replaces create_road_boundary_obstacle + trajectories_collision_static_obstacles,
  *      planner.py:362-381,550-565; commonroad-drivability-checker, not in the reference tree) ----
  * fx_build_boundary_bins: host-side geometry, no GPU.  Splits the n_seg boundary segments seg[n_seg][4] =

@@ -49,6 +49,7 @@ def exported_symbols():
         "fx_eval_responsibility_cost_agent", "fx_eval_responsibility_cost_batch",
         "fx_eval_risk_batch", "fx_eval_risk_costs_batch",
         "fx_rescore_agent", "fx_last_rescore_ms", "fx_device_costmap_view",
+        "fx_rescore_agent_rows", "fx_rescore_batch",
     ]
 
 
@@ -162,6 +163,8 @@ def lib():
         "fx_sort_views": ([vp, C.c_int32, C.POINTER(vp), pi64], C.c_int32),
         "fx_last_sort_ms": ([vp], C.c_double),
         "fx_rescore_agent": ([vp, C.c_int32, C.c_int32, vp, vp, vp, vp], C.c_int32),   # (arrays: plain addresses)
+        "fx_rescore_agent_rows": ([vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp], C.c_int32),
+        "fx_rescore_batch": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
         "fx_last_rescore_ms": ([vp], C.c_double),
         "fx_device_costmap_view": ([vp, C.c_int32, C.POINTER(vp), pi64, pi32], C.c_int32),
         # (launcher hook of the tests and tools/bench_rescore.py, not part of fxplan.h: 0 the rule, 1 candidate per lane, 2 vector per lane)

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "fx_pass.h"
+#include "fx_rescore_batch_plan.h"   // fx_resp_term_at: where the responsibility term stands in a cost list
 #include "fx_risk_args.h"
 
 extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const RiskItemArgs *items, double *out_ego, double *out_obst, double *col,
@@ -568,11 +569,9 @@ static int resp_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskPara
 static void resp_sum_fill(const RiskPass &q, const FxRespCostParams *resp, RespSumArgs &rs) {
     const DevProblem &hp = q.c->h_probs[q.agent];
     rs.n_pred = -1;
-    rs.at = hp.n_cost;   // in front of the first name behind "responsibility" in the sorted list
-    for (int m = hp.n_cost - 1; m >= 0; m--) {
+    rs.at = fx_resp_term_at(hp.cost_id, hp.n_cost);   // in front of the first name behind "responsibility" in the sorted list
+    for (int m = hp.n_cost - 1; m >= 0; m--)
         if (hp.cost_id[m] == FX_COST_PREDICTION) rs.n_pred = m;
-        if (hp.cost_id[m] > FX_COST_PREDICTION) rs.at = m;
-    }
     rs.n = q.n, rs.flags = q.flags, rs.need = FX_FLAG_COSTED;
     rs.costmap = q.sparse ? q.set.costmap : q.c->d_costmap + (size_t)FX_NUM_COSTS * q.s->cand_off;
     rs.ld = q.ld;

@@ -3,6 +3,7 @@
 // plan step, the top-k, a sparse set or the risk passes wrote or published is touched: the pass reads the cost and flag planes and
 // writes its own block.  Behind it, the re-score of the last step under other cost weights, a pass of the same kind.
 #include "fx_pass.h"
+#include "fx_rescore_batch_plan.h"
 #include "fx_rescore_plan.h"
 
 extern "C" hipError_t fx_launch_sort(const FxSortArgs *args, int n_agents, int64_t max_C, hipEvent_t ev_start, hipEvent_t ev_stop,
@@ -194,11 +195,17 @@ double fx_last_sort_ms(FxContext *c) { return (c && c->sort) ? c->sort->ev.elaps
 // (weak: a host-only program that links these files against launcher stubs of its own need not define it)
 extern "C" __attribute__((weak)) hipError_t fx_launch_rescore(const FxRescoreArgs *a, const FxRescorePlan *p, hipEvent_t ev_start,
                                                               hipEvent_t ev_stop, hipStream_t stream);
+extern "C" __attribute__((weak)) hipError_t fx_launch_rescore_batch(const FxRescoreBatchArgs *a, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                                                    hipStream_t stream);
 
 struct FxRescoreState {
     explicit FxRescoreState(FxContext *c) : block(&c->dev_bytes) {}
-    FxDeviceBlock block;   // staged weights | partials | winners | costs | totals, every part 256-byte aligned (FxBlockLayout)
+    FxDeviceBlock block;   // staged weights | partials | winners | costs | totals, every part 256-byte aligned (FxBlockLayout); the table
+                           // calls below lay it out as staging | partials | winners and costs | totals
     FxEventPair ev;
+    // the table calls (fx_rescore_agent_rows, fx_rescore_batch): what goes up in one copy -- descriptors | offsets | weights |
+    // external rows -- and the winners and costs that come back in one; pinned, grow-only
+    FxPinned<char> up, down;
 };
 
 void fx_rescore_release(FxRescoreState *s) { delete s; }
@@ -289,5 +296,190 @@ int32_t fx_rescore_agent(FxContext *c, int32_t agent, int32_t n_vec, const doubl
 
 // device time of the context's last re-score (events around its launches), ms; -1 before the first
 double fx_last_rescore_ms(FxContext *c) { return (c && c->rescore) ? c->rescore->ev.elapsed_ms() : -1.0; }
+
+}  // extern "C"
+
+// ---- the re-score over EFFECTIVE cost lists and for several agents in one call (kernels:
+// fx_rescore_batch_kernel.h; table: fx_rescore_batch_plan.h).  An agent's effective list is the step's own list with two optional rows
+// from outside the step: pred [C] in place of the prediction's row, resp [C] one more term at fx_resp_term_at.  Both entry points
+// run the one path below: checks, one staging buffer up, three launches at most, winners and costs back in one copy. ----
+struct RescoreEntryCall {
+    int32_t agent, n_vec, n_eff, n_pred, at;   // at: position of the responsibility term in the effective list, -1 without one
+    const double *w, *pred, *resp;
+};
+
+// what fx_rescore_agent refuses, for one listed agent, and the effective list; who: "" or "agent 3: "
+static int rescore_entry_check(FxContext *c, const char *who, RescoreEntryCall &q) {
+    const FxAgentSlot &s = c->slots[q.agent];
+    if (!(s.mode & FX_MODE_WRITE_COSTMAP)) return set_err(FX_ERR_NOT_READY, "%splan step ran without FX_MODE_WRITE_COSTMAP", who);
+    if (q.n_vec < 1) return set_err(FX_ERR_INVALID_ARGUMENT, "%sn_vec %d", who, q.n_vec);
+    if (q.n_vec > FX_RESCORE_MAX_VECTORS)
+        return set_err(FX_ERR_CAPACITY, "%s%d weight vectors: at most %d per agent", who, q.n_vec, FX_RESCORE_MAX_VECTORS);
+    const DevProblem &hp = c->h_probs[q.agent];
+    q.n_pred = -1;
+    for (int m = 0; m < hp.n_cost; m++)
+        if (hp.cost_id[m] == FX_COST_PREDICTION) q.n_pred = m;
+    if (q.pred && q.n_pred < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "%sa prediction row for a cost list without a prediction term", who);
+    q.at = q.resp ? fx_resp_term_at(hp.cost_id, hp.n_cost) : -1;
+    q.n_eff = hp.n_cost + (q.resp ? 1 : 0);
+    if (!q.w) return set_err(FX_ERR_INVALID_ARGUMENT, "%sthe weights are NULL", who);
+    for (size_t k = 0; k < (size_t)q.n_vec * q.n_eff; k++)
+        if (!(q.w[k] != 0.0) || !std::isfinite(q.w[k]))
+            return set_err(FX_ERR_INVALID_ARGUMENT,
+                           "%sweight %d of vector %lld is %g: weights are finite and not zero (a zero weight is another cost list)", who,
+                           (int)(k % q.n_eff), (long long)(k / q.n_eff), q.w[k]);
+    return FX_OK;
+}
+
+// the checked entries of a call; winner / cost [sum of n_vec] in call order; totals [n_vec][C] only for a call of one entry
+static int rescore_entries(FxContext *c, const std::vector<RescoreEntryCall> &calls, int64_t *winner, double *cost, double *totals) {
+    if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
+    if (!fx_launch_rescore_batch) return set_err(FX_ERR_HIP, "built without the batched re-score launcher");
+    const int E = (int)calls.size(), forced = fx_rescore_regime_forced.load(std::memory_order_relaxed);
+    std::vector<FxRescoreBatchItem> items((size_t)E);
+    for (int i = 0; i < E; i++) items[i] = FxRescoreBatchItem{c->slots[calls[i].agent].C, calls[i].n_vec};
+    FxRescoreBatchPlan t;
+    int bad = 0;
+    if (fx_rescore_batch_plan(items.data(), E, forced, t, &bad))   // (the vector counts were checked: what is left is a grid)
+        return set_err(FX_ERR_CAPACITY, "agent %d: the call's flat grid exceeds %lld workgroups", calls[bad].agent, (long long)FX_RESCORE_GRID_MAX);
+    // the totals of a vector-regime entry: one more table entry, the lane kernel without its reduction (as fx_launch_rescore)
+    const bool tot_entry = totals && E == 1 && t.rows[0].plan.regime == FX_RESCORE_VECTOR && items[0].n > 0;
+    FxRescorePlan tot_plan;
+    if (tot_entry) {
+        tot_plan = fx_rescore_plan(items[0].n, items[0].n_vec, FX_RESCORE_LANE);
+        if (tot_plan.n_part * tot_plan.grid_y > FX_RESCORE_GRID_MAX)
+            return set_err(FX_ERR_CAPACITY, "agent %d: the totals' grid exceeds %lld workgroups", calls[0].agent, (long long)FX_RESCORE_GRID_MAX);
+    }
+
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->rescore) c->rescore.reset(new FxRescoreState(c));
+    FxRescoreState *st = c->rescore.get();
+    // what goes up: descriptors | offsets | weights | external rows
+    FxBlockLayout up;
+    const size_t n_desc = (size_t)E + (tot_entry ? 1 : 0);
+    const size_t u_desc = up.take(sizeof(FxRescoreEntry) * n_desc), u_off = up.take(sizeof(int64_t) * (2 * (size_t)E + 1));
+    std::vector<size_t> u_w((size_t)E), u_pred((size_t)E, 0), u_resp((size_t)E, 0);
+    for (int i = 0; i < E; i++) {
+        const size_t n = (size_t)items[i].n;
+        u_w[i] = up.take(sizeof(double) * (size_t)calls[i].n_vec * calls[i].n_eff);
+        if (calls[i].pred) u_pred[i] = up.take(sizeof(double) * n);
+        if (calls[i].resp) u_resp[i] = up.take(sizeof(double) * n);
+    }
+    const size_t V = (size_t)t.vectors, parts = (size_t)t.partials;
+    FxBlockLayout lay;
+    const size_t o_up = lay.take(up.size()), o_pc = lay.take(sizeof(double) * parts), o_pi = lay.take(sizeof(long long) * parts);
+    const size_t o_out = lay.take((sizeof(long long) + sizeof(double)) * V);   // winners, then costs: one part, one copy back
+    const size_t o_tot = totals ? lay.take(sizeof(double) * (size_t)items[0].n_vec * (size_t)items[0].n) : 0;
+    // (a block that grows is freed: what was queued on it runs out first)
+    if (lay.size() > st->block.size() && st->block) HIP_TRY(hipStreamSynchronize(c->stream));
+    FX_TRY(st->block.ensure(lay.size()));
+    if (up.size() > st->up.size() || (sizeof(long long) + sizeof(double)) * V > st->down.size()) HIP_TRY(hipStreamSynchronize(c->stream));
+    FX_TRY(st->up.ensure(up.size(), hipHostMallocDefault));
+    FX_TRY(st->down.ensure((sizeof(long long) + sizeof(double)) * V, hipHostMallocDefault));
+    FX_TRY(st->ev.ensure());
+    st->ev.timed = false;
+    char *b = st->block, *h = st->up;
+    char *d_up = b + o_up;
+    long long *d_win = reinterpret_cast<long long *>(b + o_out);
+    double *d_cost = reinterpret_cast<double *>(b + o_out + sizeof(long long) * V);
+
+    FxRescoreEntry *desc = reinterpret_cast<FxRescoreEntry *>(h + u_desc);
+    int64_t *off = reinterpret_cast<int64_t *>(h + u_off);
+    for (int i = 0; i < E; i++) {
+        const RescoreEntryCall &q = calls[i];
+        const FxRescoreBatchRow &r = t.rows[i];
+        const FxAgentSlot &s = c->slots[q.agent];
+        const DevProblem &hp = c->h_probs[q.agent];
+        const size_t n = (size_t)s.C;
+        FxRescoreEntry e{};
+        const double *costmap = c->d_costmap + (size_t)FX_NUM_COSTS * s.cand_off;
+        int k = 0;
+        for (int m = 0; m <= hp.n_cost; m++) {
+            if (m == q.at) e.row[k++] = reinterpret_cast<const double *>(d_up + u_resp[i]);
+            if (m == hp.n_cost) break;
+            e.row[k++] = (m == q.n_pred && q.pred) ? reinterpret_cast<const double *>(d_up + u_pred[i]) : costmap + (size_t)m * s.ld;
+        }
+        e.flags = c->d_flags + s.cand_off;
+        e.w = reinterpret_cast<const double *>(d_up + u_w[i]);
+        e.part_cost = reinterpret_cast<double *>(b + o_pc) + r.part0, e.part_idx = reinterpret_cast<long long *>(b + o_pi) + r.part0;
+        e.winner = d_win + r.out0, e.cost = d_cost + r.out0;
+        e.totals = (totals && r.plan.regime == FX_RESCORE_LANE) ? reinterpret_cast<double *>(b + o_tot) : nullptr;
+        e.n = s.C, e.n_part = r.plan.n_part, e.per = r.plan.per;
+        e.wg0 = r.wg0, e.fin0 = r.fin0;
+        e.n_cost = q.n_eff, e.n_pred = q.n_pred;   // (the responsibility term stands behind the prediction: its position stays)
+        // (a deferred step without a prediction term closed nothing in the obstacle kernel: its costs are the walk's own sums)
+        e.deferred = ((hp.mode & FX_MODE_INT_DEFER_OBST) && q.n_pred >= 0) ? 1 : 0;
+        e.n_vec = q.n_vec, e.vec_chunk = r.plan.vec_chunk;
+        desc[r.slot] = e;
+        off[r.slot] = r.wg0, off[E + r.slot] = r.fin0;
+        memcpy(h + u_w[i], q.w, sizeof(double) * (size_t)q.n_vec * q.n_eff);
+        if (q.pred && n > 0) memcpy(h + u_pred[i], q.pred, sizeof(double) * n);
+        if (q.resp && n > 0) memcpy(h + u_resp[i], q.resp, sizeof(double) * n);
+    }
+    FxRescoreBatchArgs a{};
+    a.entries = reinterpret_cast<const FxRescoreEntry *>(d_up + u_desc);
+    a.wg0 = reinterpret_cast<const int64_t *>(d_up + u_off);
+    a.n_lane = t.n_lane, a.n_vector = t.n_vector;
+    a.lane_wgs = t.lane_wgs, a.vector_wgs = t.vector_wgs, a.finish_blocks = t.finish_blocks, a.n_waves = t.vectors;
+    if (tot_entry) {
+        FxRescoreEntry e = desc[0];
+        e.totals = reinterpret_cast<double *>(b + o_tot);
+        e.part_cost = nullptr, e.part_idx = nullptr;
+        e.n_part = tot_plan.n_part, e.per = tot_plan.per, e.vec_chunk = tot_plan.vec_chunk, e.wg0 = 0;
+        desc[E] = e;
+        off[2 * E] = 0;
+        a.tot_entries = a.entries + E, a.tot_wg0 = a.wg0 + 2 * E, a.n_tot = 1, a.tot_wgs = tot_plan.n_part * tot_plan.grid_y;
+    }
+    c->in_flight = true; c->tail_work = true;
+    HIP_TRY(hipMemcpyAsync(d_up, h, up.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(fx_launch_rescore_batch(&a, st->ev.e0, st->ev.e1, c->stream));
+    st->ev.timed = true;
+    static_assert(sizeof(long long) == sizeof(int64_t), "the winners are copied as they are");
+    HIP_TRY(hipMemcpyAsync(st->down.get(), b + o_out, (sizeof(long long) + sizeof(double)) * V, hipMemcpyDeviceToHost, c->stream));
+    if (totals && items[0].n > 0)
+        HIP_TRY(hipMemcpyAsync(totals, b + o_tot, sizeof(double) * (size_t)items[0].n_vec * (size_t)items[0].n, hipMemcpyDeviceToHost, c->stream));
+    FX_TRY(fx_drain(c));
+    memcpy(winner, st->down.get(), sizeof(int64_t) * V);
+    memcpy(cost, st->down.get() + sizeof(long long) * V, sizeof(double) * V);
+    return FX_OK;
+}
+
+extern "C" {
+
+int32_t fx_rescore_agent_rows(FxContext *c, int32_t agent, int32_t n_vec, const double *w, const double *pred, const double *resp,
+                              int64_t *winner, double *cost, double *totals) {
+    // every refusal stands in front of the first allocation, copy or launch
+    FX_TRY(check_agent(c, agent));
+    if (!fx_inputs_current(c))
+        return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
+    if (!w || !winner || !cost) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_rescore_agent_rows: NULL argument");
+    std::vector<RescoreEntryCall> calls(1, RescoreEntryCall{agent, n_vec, 0, -1, -1, w, pred, resp});
+    FX_TRY(rescore_entry_check(c, "", calls[0]));
+    return rescore_entries(c, calls, winner, cost, totals);
+}
+
+int32_t fx_rescore_batch(FxContext *c, int32_t n_agents, const int32_t *agents, const int32_t *n_vec, const double *w,
+                         const double *const *pred, const double *const *resp, int64_t *winner, double *cost) {
+    if (n_agents < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_rescore_batch: n_agents %d", n_agents);
+    if (n_agents == 0) return FX_OK;   // (no agent: nothing is touched, the context included)
+    if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
+    if (!n_vec || !w || !winner || !cost) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_rescore_batch: NULL argument");
+    FX_TRY(check_agent(c, 0));
+    if (!fx_inputs_current(c))
+        return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
+    std::vector<RescoreEntryCall> calls((size_t)n_agents);
+    std::vector<char> listed((size_t)c->n_agents, 0);
+    for (int i = 0; i < n_agents; i++) {
+        const int32_t agent = agents ? agents[i] : i;
+        if (agent < 0 || agent >= c->n_agents) return set_err(FX_ERR_INVALID_ARGUMENT, "agent %d out of range", agent);
+        if (listed[agent]++) return set_err(FX_ERR_INVALID_ARGUMENT, "agent %d listed twice", agent);
+        calls[i] = RescoreEntryCall{agent, n_vec[i], 0, -1, -1, w, pred ? pred[i] : nullptr, resp ? resp[i] : nullptr};
+        char who[32];
+        snprintf(who, sizeof(who), "agent %d: ", agent);
+        FX_TRY(rescore_entry_check(c, who, calls[i]));
+        w += (size_t)calls[i].n_vec * calls[i].n_eff;
+    }
+    return rescore_entries(c, calls, winner, cost, nullptr);
+}
 
 }  // extern "C"

@@ -96,6 +96,7 @@ extern "C" hipError_t fx_launch_package(const DevProblem *d_probs, int n_agents,
 #define FX_TOPK_R 32
 #include "fx_topk_kernel.h"   // fx_topk_*_kernel
 #include "fx_rescore_kernel.h"   // fxrs::fx_rescore_*_kernel
+#include "fx_rescore_batch_kernel.h"   // fxrs::fx_rescore_batch_*_kernel
 
 // Copy a small device buffer (the all-gathered survivors) into pinned host memory and publish a sequence word:
 // the host polls instead of paying for a D2H copy + stream synchronisation.
@@ -610,6 +611,32 @@ extern "C" hipError_t fx_launch_rescore(const FxRescoreArgs *a, const FxRescoreP
     }
     hipLaunchKernelGGL(fxrs::fx_rescore_finish_kernel, dim3((unsigned)p->finish_blocks), dim3(256), 0, stream, a->part_cost, a->part_idx, p->n_part,
                        a->n_vec, a->winner, a->cost);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
+    return hipSuccess;
+}
+
+// A table of entries -- agents with their own weight vectors and effective cost lists -- re-scored in one call
+// (fx_rescore_batch_kernel.h): the lane-regime entries' launch and the vector-regime entries' launch, each only
+// where it has entries, and one finish launch with a wave per (entry, vector) -- three launches at most whatever the number of
+// entries.  a->tot_entries: the entries whose totals the lane kernel writes without its reduction (vector-regime entries of the
+// per-agent call that asked for totals), one more launch where there are any.  ev_start / ev_stop bracket all launches.
+extern "C" hipError_t fx_launch_rescore_batch(const FxRescoreBatchArgs *a, hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream) {
+    hipError_t e;
+    if (ev_start && (e = hipEventRecord(ev_start, stream)) != hipSuccess) return e;
+    const int n_all = a->n_lane + a->n_vector;
+    if (a->n_lane > 0 && a->lane_wgs > 0)
+        hipLaunchKernelGGL(fxrs::fx_rescore_batch_lane_kernel<true>, dim3((unsigned)a->lane_wgs), dim3(FX_RESCORE_TILE), 0, stream, a->entries,
+                           a->wg0, a->n_lane);
+    if (a->n_vector > 0 && a->vector_wgs > 0)
+        hipLaunchKernelGGL(fxrs::fx_rescore_batch_vector_kernel, dim3((unsigned)a->vector_wgs), dim3(64), 0, stream, a->entries + a->n_lane,
+                           a->wg0 + a->n_lane, a->n_vector);
+    if (a->n_tot > 0 && a->tot_wgs > 0)
+        hipLaunchKernelGGL(fxrs::fx_rescore_batch_lane_kernel<false>, dim3((unsigned)a->tot_wgs), dim3(FX_RESCORE_TILE), 0, stream, a->tot_entries,
+                           a->tot_wg0, a->n_tot);
+    if (a->finish_blocks > 0)
+        hipLaunchKernelGGL(fxrs::fx_rescore_batch_finish_kernel, dim3((unsigned)a->finish_blocks), dim3(256), 0, stream, a->entries, a->wg0 + n_all,
+                           n_all, a->n_waves);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
     return hipSuccess;

@@ -150,12 +150,29 @@ def build_boundary_bins(ref_xy, segments, max_len: float, reach: float):
     check(rc)
 
 
-def rescore_weights(weights, cost_names) -> np.ndarray:
+def effective_cost_names(cost_names, resp: bool = False):
+    """The names of an agent's effective cost list: the step's own `cost_names`, with "responsibility" at
+    its sorted place -- in front of the first name behind "prediction", else at the end (fx_resp_term_at) -- when a responsibility
+    row is given.  None stays None."""
+    if cost_names is None:
+        return None
+    names = list(cost_names)
+    if resp:
+        if "responsibility" in names:
+            raise ValueError("the step's cost list already has a responsibility term")
+        at = next((k for k, n in enumerate(names) if _abi.COST_ID[n] > _abi.COST_ID["prediction"]), len(names))
+        names.insert(at, "responsibility")
+    return names
+
+
+def rescore_weights(weights, cost_names, resp: bool = False) -> np.ndarray:
     """The [W][n_cost] float64 array FrenetEngine.rescore hands to the library (no device needed).  `weights`: an [W][n_cost] array
     (or one [n_cost] vector) in `cost_names` order, or name -> weight dicts (one, or a sequence) whose non-zero names are exactly
     `cost_names` -- a zero entry is a term upstream does not register (cost_function.py:55-60), so it may be listed, and a step
     whose list lacks a non-zero name, or has one the dict lacks, is another cost function: ValueError.  Every weight is finite and
-    not zero (ValueError); negative weights are legal.  cost_names None: no step to compare with, arrays pass as they are."""
+    not zero (ValueError); negative weights are legal.  cost_names None: no step to compare with, arrays pass as they are.
+    resp: the weights are held to `effective_cost_names(cost_names, True)` -- one more entry, "responsibility"."""
+    cost_names = effective_cost_names(cost_names, resp)
     if isinstance(weights, dict):
         weights = [weights]
     if not isinstance(weights, np.ndarray) and len(weights) > 0 and all(isinstance(d, dict) for d in weights):
@@ -182,6 +199,16 @@ def rescore_weights(weights, cost_names) -> np.ndarray:
     if not np.all(np.isfinite(w)) or np.any(w == 0.0):
         raise ValueError("weights must be finite and not zero (a zero weight is another cost list: plan a step with it)")
     return np.ascontiguousarray(w)
+
+
+def _rescore_row(row, n: int, what: str):
+    """a row [n] of FrenetEngine.rescore from outside the step, as the library reads it; None stays None"""
+    if row is None:
+        return None
+    row = np.ascontiguousarray(row, dtype=np.float64)
+    if row.shape != (n,):
+        raise ValueError(f"{what} of shape {row.shape} for {n} candidates")
+    return row
 
 
 class WinnerPackage:
@@ -938,23 +965,61 @@ class FrenetEngine(StepRegistry):
         """device time of the last sort's launches"""
         return float(lib().fx_last_sort_ms(self._ctx))
 
-    # -- the last step re-scored under other cost weights, on the device (DESIGN.md section 23) --
-    def rescore(self, weights, agent: int = 0, totals: bool = False) -> dict:
+    # -- the last step re-scored under other cost weights, on the device (DESIGN.md sections 23 and 24) --
+    def rescore(self, weights, agent: int = 0, totals: bool = False, pred=None, resp=None) -> dict:
         """The agent's last step under W other weight vectors in one call (fx_rescore_agent): which candidate wins, and at what cost,
         had the step run with each of them.  `weights`: [W][n_cost] in the step's `PlanInputs.cost_names` order, or a sequence of
         name -> weight dicts whose non-zero names are exactly the step's (`rescore_weights`); finite and not zero, negative is legal.
         Returns dict(winner [W] int64: local candidate indices, -1 where nothing is eligible; cost [W]: +inf there; totals [W][C]
         or None: every candidate's weighted cost, NaN without FX_FLAG_COSTED).  The bits are those of a plan step run with these
-        weights.  It is the device selection only: nothing of the step is rewritten, and no host walk follows."""
-        names = self._inputs[agent].cost_names if 0 <= agent < len(self._inputs) else None
-        w = rescore_weights(weights, names)
+        weights.  It is the device selection only: nothing of the step is rewritten, and no host walk follows.
+        pred [C] / resp [C] (fx_rescore_agent_rows): rows of a pass that ran beside the step -- pred in place
+        of the step's prediction row, resp one more term, "responsibility", at its sorted place; the weights then follow
+        `effective_cost_names`."""
+        inp = self._inputs[agent] if 0 <= agent < len(self._inputs) else None
+        names = inp.cost_names if inp is not None else None
+        w = rescore_weights(weights, names, resp is not None)
         n_vec = w.shape[0]
-        n = self._inputs[agent].n_candidates if names is not None else 0
+        n = inp.n_candidates if inp is not None else 0
         winner, cost = np.empty(n_vec, np.int64), np.empty(n_vec)
         tot = np.empty((n_vec, n)) if totals else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        check(lib().fx_rescore_agent(self._ctx, int(agent), n_vec, ptr(w), ptr(winner), ptr(cost), ptr(tot)))
+        if pred is None and resp is None:
+            check(lib().fx_rescore_agent(self._ctx, int(agent), n_vec, ptr(w), ptr(winner), ptr(cost), ptr(tot)))
+        else:
+            pred, resp = (_rescore_row(r, n, what) for r, what in ((pred, "pred"), (resp, "resp")))
+            check(lib().fx_rescore_agent_rows(self._ctx, int(agent), n_vec, ptr(w), ptr(pred), ptr(resp), ptr(winner), ptr(cost), ptr(tot)))
         return dict(winner=winner, cost=cost, totals=tot)
+
+    def rescore_batch(self, weights_per_agent, agents=None, pred=None, resp=None) -> list:
+        """`rescore` for several agents of the context in ONE call (fx_rescore_batch): three launches at most
+        and one copy each way whatever the number of agents, every agent's result the bits of its own call.  weights_per_agent: per
+        listed agent what `rescore` takes; agents: their indices in any order (None: 0 .. len - 1); pred / resp: per listed agent
+        a row [C] or None (None: no agent has one).  Returns one dict(winner [W_a], cost [W_a]) per listed agent."""
+        n_agents = len(weights_per_agent)
+        agents = list(range(n_agents)) if agents is None else [int(a) for a in agents]
+        pred = [None] * n_agents if pred is None else list(pred)
+        resp = [None] * n_agents if resp is None else list(resp)
+        if not (len(agents) == len(pred) == len(resp) == n_agents):
+            raise ValueError(f"{n_agents} weight sets for {len(agents)} agents, {len(pred)} pred and {len(resp)} resp rows")
+        if n_agents == 0:
+            return []
+        ws, rows = [], []
+        for i, a in enumerate(agents):
+            inp = self._inputs[a] if 0 <= a < len(self._inputs) else None
+            ws.append(rescore_weights(weights_per_agent[i], inp.cost_names if inp is not None else None, resp[i] is not None))
+            n = inp.n_candidates if inp is not None else 0
+            rows.append(tuple(_rescore_row(r, n, what) for r, what in ((pred[i], "pred"), (resp[i], "resp"))))
+        n_vec = np.array([w.shape[0] for w in ws], np.int32)
+        w = np.ascontiguousarray(np.concatenate([x.ravel() for x in ws]))
+        ids = np.array(agents, np.int32)
+        total = int(n_vec.sum())
+        winner, cost = np.empty(total, np.int64), np.empty(total)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        table = lambda k: None if all(r[k] is None for r in rows) else (C.c_void_p * n_agents)(*[None if r[k] is None else r[k].ctypes.data for r in rows])
+        check(lib().fx_rescore_batch(self._ctx, n_agents, ptr(ids), ptr(n_vec), ptr(w), table(0), table(1), ptr(winner), ptr(cost)))
+        ends = np.cumsum(n_vec)
+        return [dict(winner=winner[e - k:e], cost=cost[e - k:e]) for e, k in zip(ends, n_vec)]
 
     @property
     def last_rescore_ms(self) -> float:

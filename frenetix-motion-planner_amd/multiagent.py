@@ -430,6 +430,33 @@ class AgentBatchHip:
             out[a.id] = sel[0] if sel is not None else None
         return out
 
+    def rescore(self, weight_sets_by_agent_id: dict, rows: str = "step") -> dict:
+        """ReactivePlannerHip.rescore for several agents of the batch: ONE engine.rescore_batch per engine context that holds a
+        listed agent's step.  weight_sets_by_agent_id: agent id -> what the planner's rescore takes; rows
+        as there.  Returns agent id -> [(index, cost)] per weight set.  An agent that is not of this batch, or that has no current
+        plan step, is refused by name before any call."""
+        by_id = {a.id: a for a in self.agents}
+        steps = {}
+        for aid in weight_sets_by_agent_id:
+            a = by_id.get(aid)
+            if a is None:
+                raise ValueError(f"agent {aid} is not of this batch")
+            step = a.planner.last_step
+            if step is None or step._stale:
+                raise ValueError(f"agent {aid} has no current plan step")
+            steps[aid] = (step, a.planner.rescore_rows(step, rows))
+        out, engines = {}, []
+        for step, _ in steps.values():
+            if not any(step.engine is e for e in engines):
+                engines.append(step.engine)
+        for eng in engines:
+            ids = [aid for aid, (step, _) in steps.items() if step.engine is eng]
+            res = eng.rescore_batch([weight_sets_by_agent_id[aid] for aid in ids], agents=[steps[aid][0].agent for aid in ids],
+                                    pred=[steps[aid][1][0] for aid in ids], resp=[steps[aid][1][1] for aid in ids])
+            for aid, r in zip(ids, res):
+                out[aid] = [(int(i), float(c)) for i, c in zip(r["winner"], r["cost"])]
+        return {aid: out[aid] for aid in weight_sets_by_agent_id}
+
     def close(self):
         for e in self.engines:
             e.close()

@@ -521,18 +521,41 @@ class ReactivePlannerHip:
             raise ValueError("no plan step yet")
         return self._risk_costs_on(self.last_step, ids)
 
-    def rescore(self, weight_sets):
+    def rescore(self, weight_sets, rows: str = "step"):
         """The last plan step under other cost weights (FrenetEngine.rescore): [(index, cost)] per weight
         set -- name -> weight dicts over the step's own non-zero terms, or rows in its cost_names order -- the candidate the
         device selection would have chosen had the step run with them, -1 / inf where no candidate is selectable and
         collision-free.  It is the device selection only: the host road-boundary walk and the occlusion walk of plan() are not
         run, and nothing of the step, of optimal_trajectory or of the planner's own cost weights changes.  Needs a step that
-        stored its cost map (not sparse_bundle_k > 0)."""
+        stored its cost map (not sparse_bundle_k > 0).
+        rows "override" (DESIGN.md section 24): the cost the planner ranks by is partly summed beside the step
+        (prediction_cost="collision_probability", cost_weights["responsibility"]) -- the re-score then takes the rows of the
+        step's installed cost override (`rescore_rows`), and the weight dicts name `responsibility` too where the override has
+        that term.  A step without an override: ValueError."""
         if self.last_step is None:
             raise ValueError("no plan step yet")
         step = self.last_step
-        r = step.engine.rescore(weight_sets, agent=step.agent)
+        pred, resp = self.rescore_rows(step, rows)
+        r = step.engine.rescore(weight_sets, agent=step.agent, pred=pred, resp=resp)
         return [(int(i), float(c)) for i, c in zip(r["winner"], r["cost"])]
+
+    @staticmethod
+    def rescore_rows(step, rows: str = "step"):
+        """(pred, resp) of a re-score of `step`: (None, None) for rows "step"; for rows "override" the prediction array of the
+        step's installed cost override, where it holds one for the costed candidates, and the raw `responsibility` extra (None
+        where the override has none)."""
+        if rows == "step":
+            return None, None
+        if rows != "override":
+            raise ValueError(f"rows {rows!r}: 'step' or 'override'")
+        ov = step._override
+        if ov is None:
+            raise ValueError("the step has no cost override installed: rows='override' re-scores the rows of one")
+        step._load_arrays()
+        costed = (step._flags & _abi.FX_FLAG_COSTED) != 0
+        pred = ov[1] if costed.any() and not np.isnan(ov[1][costed]).all() else None
+        resp = step._extras["responsibility"][0] if "responsibility" in step._extras else None
+        return pred, resp
 
     def _risk_costs_on(self, step, ids):
         params, cp = self._risk_cost_setup(step)

@@ -563,6 +563,26 @@ double fx_last_sort_ms(FxContext *ctx);
  *      FX_ERR_CAPACITY above 32 768 vectors per call. */
 int32_t fx_rescore_agent(FxContext *ctx, int32_t agent, int32_t n_vec, const double *w /*[n_vec][n_cost]*/, int64_t *winner /*[n_vec]*/,
                          double *cost /*[n_vec]*/, double *totals /*[n_vec][C] or NULL*/);
+/* fx_rescore_agent over the agent's EFFECTIVE cost list: the step's own list with up to two rows from outside
+ * the step, as a cost that is partly summed beside the step has them.  pred [C], where not NULL, stands in place of the step's
+ * prediction row (the prob of fx_eval_prediction_prob_agent, say); FX_ERR_INVALID_ARGUMENT for a list without FX_COST_PREDICTION.
+ * resp [C], where not NULL, is ONE MORE term, where fx_eval_responsibility_cost_agent sums it: in front of the first entry whose id
+ * is above FX_COST_PREDICTION, else at the end.  A weight vector then has n_eff = n_cost (+ 1 with resp) weights in that order, and
+ * total(c) is the same sum over the effective list -- for a step whose obstacle stage ran as its own kernel the inserted term joins
+ * the addend of the terms behind the prediction.  A NaN in either row is a NaN total, skipped like any other.  Everything else --
+ * eligibility, ties, -1 / +inf, local indices, refusals, the block -- is fx_rescore_agent's; with both rows NULL so is every bit. */
+int32_t fx_rescore_agent_rows(FxContext *ctx, int32_t agent, int32_t n_vec, const double *w /*[n_vec][n_eff]*/,
+                              const double *pred /*[C] or NULL*/, const double *resp /*[C] or NULL*/, int64_t *winner /*[n_vec]*/,
+                              double *cost /*[n_vec]*/, double *totals /*[n_vec][C] or NULL*/);
+/* fx_rescore_agent_rows for n_agents agents of the context in one call: three launches at most, one copy up, one back, whatever the
+ * number of agents, and for every agent the bits of its own call.  agents [n_agents] (NULL: 0 .. n_agents - 1) in any order;
+ * n_vec [n_agents] vectors per listed agent; w the agents' [n_vec[i]][n_eff_i] weights one behind the other; pred / resp
+ * [n_agents] pointers to rows [C_i], any of them NULL, or NULL for none; winner / cost the agents' [n_vec[i]] answers one behind
+ * the other.  No totals.  Refused before anything is allocated, copied or launched, naming the agent: what fx_rescore_agent_rows
+ * refuses for it, an agent out of range or listed twice (FX_ERR_INVALID_ARGUMENT), more than 32 768 vectors for one agent or a
+ * flat grid above 2^31 - 1 workgroups (FX_ERR_CAPACITY).  n_agents == 0 returns FX_OK and touches nothing. */
+int32_t fx_rescore_batch(FxContext *ctx, int32_t n_agents, const int32_t *agents, const int32_t *n_vec, const double *w,
+                         const double *const *pred, const double *const *resp, int64_t *winner, double *cost);
 /* device time of the context's last re-score (events around its launches), ms; -1 before the first.  Waits for it. */
 double fx_last_rescore_ms(FxContext *ctx);
 /* device pointer of one agent's raw cost rows, f64 [n_cost][ld] -- the cost-map counterpart of fx_device_views.  FX_ERR_NOT_READY for a

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
-"""Parse `-Rpass-analysis=kernel-resource-usage` remarks (stdin or file) into one line per kernel: VGPRs, SGPRs, spills, occupancy, LDS."""
+"""Parse `-Rpass-analysis=kernel-resource-usage` remarks (stdin or file) into one line per kernel: VGPRs, SGPRs, spills, occupancy, LDS.
+--mangled: the kernels under their mangled names (one word each: what profiles/*/kernel_resources_*.txt hold and the tests compare)."""
 import re, sys, subprocess
+MANGLED = "--mangled" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--mangled"]
 txt = open(sys.argv[1]).read() if len(sys.argv) > 1 else sys.stdin.read()
 cur = None
 rows = {}
@@ -24,6 +27,6 @@ except Exception:
     dem = names
 for n, d in zip(names, dem):
     r = rows[n]
-    short = re.sub(r"\(.*", "", d).replace("void ", "")
+    short = n if MANGLED else re.sub(r"\(.*", "", d).replace("void ", "")
     print(f"{short:60s} VGPR {r.get('VGPRs', -1):4d} SGPR {r.get('SGPRs', -1):3d} spillV {r.get('VGPRs Spill', 0):3d} spillS {r.get('SGPRs Spill', 0):3d} scratch {r.get('ScratchSize [bytes/lane]', 0):4d} "
           f"occ {r.get('Occupancy [waves/SIMD]', -1)} lds {r.get('LDS Size [bytes/block]', 0)}")

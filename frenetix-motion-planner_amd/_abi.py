@@ -96,6 +96,21 @@ class FxStateUpdate(C.Structure):
     ]
 
 
+FX_HYPOTHESES_MAX = 4096        # fx_eval_hypotheses_agent: hypotheses per call
+
+
+class FxHypothesis(C.Structure):
+    """one prediction set of fx_eval_hypotheses_agent: FxStateUpdate's five obstacle arrays with the K and P of the upload"""
+    _fields_ = [("obs_pos", C.c_void_p), ("obs_cov_inv", C.c_void_p), ("obs_npred", C.c_void_p), ("obs_hull", C.c_void_p),
+                ("obs_nhull", C.c_void_p)]
+
+
+class FxHypothesisOutputs(C.Structure):
+    """winner [H] i64, cost [H], n_collisions [H] i64 or NULL, pred / total [H][C] or NULL, collision [H][C] u8 or NULL"""
+    _fields_ = [("winner", C.c_void_p), ("cost", C.c_void_p), ("n_collisions", C.c_void_p), ("pred", C.c_void_p), ("total", C.c_void_p),
+                ("collision", C.c_void_p)]
+
+
 FX_PKG_ROWS = FX_NUM_PLANES + 3
 PKG_ROW_YAW_RATE, PKG_ROW_STEERING, PKG_ROW_ORIENTATION = FX_NUM_PLANES, FX_NUM_PLANES + 1, FX_NUM_PLANES + 2
 

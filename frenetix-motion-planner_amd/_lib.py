@@ -50,6 +50,7 @@ def exported_symbols():
         "fx_eval_risk_batch", "fx_eval_risk_costs_batch",
         "fx_rescore_agent", "fx_last_rescore_ms", "fx_device_costmap_view",
         "fx_rescore_agent_rows", "fx_rescore_batch",
+        "fx_eval_hypotheses_agent", "fx_last_hypotheses_ms", "fx_last_hypotheses_info",
     ]
 
 
@@ -170,6 +171,11 @@ def lib():
         # (launcher hook of the tests and tools/bench_rescore.py, not part of fxplan.h: 0 the rule, 1 candidate per lane, 2 vector per lane)
         "fx_rescore_set_regime": ([C.c_int32], None),
         "fx_rescore_regime": ([C.c_int64, C.c_int32], C.c_int32),
+        "fx_eval_hypotheses_agent": ([vp, C.c_int32, C.c_int32, C.POINTER(_abi.FxHypothesis), C.POINTER(_abi.FxHypothesisOutputs)], C.c_int32),
+        "fx_last_hypotheses_ms": ([vp], C.c_double),
+        "fx_last_hypotheses_info": ([vp, pi32, pi32, pi32], C.c_int32),
+        # (hook of the tests and tools/bench_hypotheses.py, not part of fxplan.h: bytes of tables plus scratch per round, 0 = FX_ITEM_SCRATCH_BYTES)
+        "fx_hypotheses_set_scratch_limit": ([C.c_size_t], None),
         "fx_eval_prediction_prob_agent": ([vp, C.c_int32, C.POINTER(_abi.FxPredProbParams), C.c_int64, pi64,
                                            C.POINTER(_abi.FxPredProbOutputs)], C.c_int32),
         "fx_last_predprob_ms": ([vp], C.c_double),

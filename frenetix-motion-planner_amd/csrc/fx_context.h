@@ -6,6 +6,7 @@
 //   fx_api_risk.hip      trajectory risk and risk costs beside the plan step
 //   fx_api_materialise.hip  listed candidates of a step re-walked into a sparse set, its read-back and package
 //   fx_api_sort.hip      stable cost order of all candidates beside the step, read back by rank; the step re-scored under other weights
+//                        and re-evaluated under other prediction sets
 #pragma once
 
 #include <algorithm>
@@ -84,6 +85,7 @@ void fx_risk_release(struct FxRiskState *r);       // (fx_api_risk.hip)
 void fx_sparse_release(struct FxSparseState *s);   // (fx_api_materialise.hip)
 void fx_sort_release(struct FxSortState *s);       // (fx_api_sort.hip)
 void fx_rescore_release(struct FxRescoreState *s);   // (fx_api_sort.hip)
+void fx_hyp_release(struct FxHypState *s);           // (fx_api_sort.hip)
 
 struct FxContext {
     int device = 0;
@@ -198,6 +200,7 @@ struct FxContext {
     std::unique_ptr<FxSparseState, void (*)(FxSparseState *)> sparse{nullptr, fx_sparse_release};   // sparse sets of listed candidates
     std::unique_ptr<FxSortState, void (*)(FxSortState *)> sort{nullptr, fx_sort_release};           // cost order of all candidates
     std::unique_ptr<FxRescoreState, void (*)(FxRescoreState *)> rescore{nullptr, fx_rescore_release};   // re-score under other weights
+    std::unique_ptr<FxHypState, void (*)(FxHypState *)> hyp{nullptr, fx_hyp_release};                   // the obstacle stage under other predictions
 };
 
 // An agent's sparse set as its consumers see it (fx_api_materialise.hip): the structure-of-arrays rows of

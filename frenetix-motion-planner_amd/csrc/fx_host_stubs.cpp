@@ -8,4 +8,4 @@ FX_STUB(fx_launch_eval) FX_STUB(fx_launch_eval_grid) FX_STUB(fx_launch_obstacle)
 FX_STUB(fx_launch_select) FX_STUB(fx_launch_math_test) FX_STUB(fx_launch_publish) FX_STUB(fx_launch_stage) FX_STUB(fx_launch_package)
 FX_STUB(fx_launch_topk) FX_STUB(fx_launch_probe_read) FX_STUB(fx_launch_risk) FX_STUB(fx_launch_gather_candidates) FX_STUB(fx_launch_eval_list) FX_STUB(fx_launch_selftest)
 FX_STUB(fx_launch_sort) FX_STUB(fx_launch_sort_gather) FX_STUB(fx_launch_predprob) FX_STUB(fx_launch_predprob_batch) FX_STUB(fx_launch_risk_batch)
-FX_STUB(fx_launch_risk_list_batch) FX_STUB(fx_launch_risk_costs_batch) FX_STUB(fx_launch_rescore) FX_STUB(fx_launch_rescore_batch)
+FX_STUB(fx_launch_risk_list_batch) FX_STUB(fx_launch_risk_costs_batch) FX_STUB(fx_launch_rescore) FX_STUB(fx_launch_rescore_batch) FX_STUB(fx_launch_hypotheses)

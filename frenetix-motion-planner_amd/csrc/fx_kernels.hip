@@ -97,6 +97,7 @@ extern "C" hipError_t fx_launch_package(const DevProblem *d_probs, int n_agents,
 #include "fx_topk_kernel.h"   // fx_topk_*_kernel
 #include "fx_rescore_kernel.h"   // fxrs::fx_rescore_*_kernel
 #include "fx_rescore_batch_kernel.h"   // fxrs::fx_rescore_batch_*_kernel
+#include "fx_hypotheses_kernel.h"   // fxhy::fx_hyp_*_kernel
 
 // Copy a small device buffer (the all-gathered survivors) into pinned host memory and publish a sequence word:
 // the host polls instead of paying for a D2H copy + stream synchronisation.
@@ -640,4 +641,21 @@ extern "C" hipError_t fx_launch_rescore_batch(const FxRescoreBatchArgs *a, hipEv
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (ev_stop && (e = hipEventRecord(ev_stop, stream)) != hipSuccess) return e;
     return hipSuccess;
+}
+
+// The obstacle stage of a finished step over the a->n_hyp prediction sets of one ROUND (fx_hypotheses_kernel.h; DESIGN.md section 25;
+// rounds: fx_hypotheses_plan.h): items, finish, selection -- three launches.  lds_bytes = CH * K * 48 of an item's wave.  The caller
+// records its events around the rounds of a call.
+extern "C" hipError_t fx_launch_hypotheses(const FxHypArgs *a, size_t lds_bytes, hipStream_t stream) {
+    const dim3 grid((unsigned)(a->n_tiles * a->NC), (unsigned)a->n_hyp);
+#define FX_LAUNCH(CHv)                                                                                                       \
+    if (a->CH == CHv) {                                                                                                      \
+        if (const hipError_t e_ = fx_allow_dynamic_lds<&fxhy::fx_hyp_item_kernel<CHv>>(lds_bytes); e_ != hipSuccess) return e_; \
+        hipLaunchKernelGGL(fxhy::fx_hyp_item_kernel<CHv>, grid, dim3(64), lds_bytes, stream, *a);                              \
+    } else
+    FX_LAUNCH(2) FX_LAUNCH(3) FX_LAUNCH(5) return hipErrorInvalidValue;
+#undef FX_LAUNCH
+    hipLaunchKernelGGL(fxhy::fx_hyp_finish_kernel, dim3((unsigned)a->n_part, (unsigned)a->n_hyp), dim3(FX_HYP_FINISH_TILE), 0, stream, *a);
+    hipLaunchKernelGGL(fxhy::fx_hyp_select_kernel, dim3((unsigned)a->n_hyp), dim3(1024), 0, stream, *a);
+    return hipGetLastError();
 }

@@ -1026,6 +1026,65 @@ class FrenetEngine(StepRegistry):
         """device time of the last re-score's launches"""
         return float(lib().fx_last_rescore_ms(self._ctx))
 
+    # -- the last step's obstacle stage under other prediction sets, on the device (DESIGN.md section 25) --
+    def hypotheses(self, prediction_sets, agent: int = 0, pred: bool = False, totals: bool = False, collisions: bool = False) -> dict:
+        """The agent's last step under H other prediction sets in one call (fx_eval_hypotheses_agent): what a plan step with each of
+        them would have selected, the walk not run again.  `prediction_sets`: a sequence of packed predictions
+        (`problem.pack_predictions`, or `problem.hypothesis_arrays` of one); a set that has not the upload's K and P is padded
+        with absent obstacles and re-strided by `hypothesis_arrays` (more obstacles than the upload: ValueError).
+        Returns dict(winner [H] int64: local candidate indices, -1 where nothing is eligible; cost [H]: +inf there;
+        n_collisions [H] int64; pred [H][C] / totals [H][C] / collisions [H][C] bool, each None unless asked for).  For a step
+        whose obstacle stage ran as its own kernel the bits are those of a plan step with these predictions; for one that ran
+        it inside the walk those of the same step forced to set_obstacle_stage(2, last_hypotheses_info["steps_per_item"]).  It
+        is the device selection only: nothing of the step is rewritten, and no host walk follows."""
+        from .problem import hypothesis_arrays
+        inp = self._inputs[agent] if 0 <= agent < len(self._inputs) else None
+        sets = list(prediction_sets) if isinstance(prediction_sets, (list, tuple)) else [prediction_sets]
+        n_hyp = len(sets)
+        K, P = (int(inp.obstacles["K"]), int(inp.obstacles["P"])) if inp is not None else (0, 0)
+        keep, hyp = [], (_abi.FxHypothesis * max(n_hyp, 1))()
+
+        def arr(a, typ, size):
+            a = np.ascontiguousarray(a, dtype=typ)
+            if a.size != size:
+                raise ValueError(f"hypothesis array of {a.size} values, the upload's K={K}, P={P} need {size}")
+            keep.append(a)
+            return a.ctypes.data
+
+        for h, s in enumerate(sets):
+            if K > 0:   # (an upload without obstacles: the library refuses the call, whatever the sets hold)
+                if int(s["K"]) != K or int(s["P"]) != P or not np.size(s.get("hull", ())):
+                    s = hypothesis_arrays(s, K, P)
+                hyp[h].obs_pos, hyp[h].obs_cov_inv = arr(s["pos"], np.float64, 2 * K * P), arr(s["cov_inv"], np.float64, 4 * K * P)
+                hyp[h].obs_npred = arr(s["npred"], np.int32, K)
+                hyp[h].obs_hull, hyp[h].obs_nhull = arr(s["hull"], np.float64, 6 * K * (P - 1)), arr(s["nhull"], np.int32, K)
+        n = inp.n_candidates if inp is not None else 0
+        H = max(n_hyp, 1)
+        winner, cost, n_col = np.empty(H, np.int64), np.empty(H), np.empty(H, np.int64)
+        o_pred = np.empty((H, n)) if pred else None
+        o_tot = np.empty((H, n)) if totals else None
+        o_col = np.empty((H, n), np.uint8) if collisions else None
+        out = _abi.FxHypothesisOutputs()
+        out.winner, out.cost, out.n_collisions = winner.ctypes.data, cost.ctypes.data, n_col.ctypes.data
+        out.pred = None if o_pred is None else o_pred.ctypes.data
+        out.total = None if o_tot is None else o_tot.ctypes.data
+        out.collision = None if o_col is None else o_col.ctypes.data
+        check(lib().fx_eval_hypotheses_agent(self._ctx, int(agent), n_hyp, hyp, C.byref(out)))
+        return dict(winner=winner, cost=cost, n_collisions=n_col, pred=o_pred, totals=o_tot,
+                    collisions=None if o_col is None else o_col.astype(bool))
+
+    @property
+    def last_hypotheses_ms(self) -> float:
+        """device time of the last hypotheses call's launches"""
+        return float(lib().fx_last_hypotheses_ms(self._ctx))
+
+    @property
+    def last_hypotheses_info(self) -> dict:
+        """steps per item, rounds of hypotheses and kernel launches of the last hypotheses call"""
+        v = [C.c_int32(0) for _ in range(3)]
+        check(lib().fx_last_hypotheses_info(self._ctx, *[C.byref(x) for x in v]))
+        return dict(steps_per_item=v[0].value, rounds=v[1].value, launches=v[2].value)
+
     def costmap_view(self, agent: int = 0):
         """(device pointer of the agent's raw cost rows f64 [n_cost][ld], ld, n_cost) of a step that stored them (fx_device_costmap_view)"""
         p, ld, n_cost = C.c_void_p(), C.c_int64(0), C.c_int32(0)

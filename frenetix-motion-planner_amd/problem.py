@@ -258,6 +258,31 @@ def pack_predictions(predictions: Optional[Dict], n_samples: int, build_hulls):
     return dict(K=K, P=P, pos=_f64(pos), cov_inv=_f64(cov_inv), npred=npred, hull=_f64(hull), nhull=nhull)
 
 
+def hypothesis_arrays(packed: Dict, K: int, P: int) -> Dict:
+    """A `pack_predictions` result as one hypothesis of FrenetEngine.hypotheses (fx_eval_hypotheses_agent): the
+    five obstacle arrays with the K and P of the upload.  Fewer obstacles than K are padded with absent ones (npred = 0, nhull = 0),
+    the rows are re-strided from the packed P to P -- predictions and hulls beyond P are cut, as an upload with that P never holds
+    them -- and a set without hulls gets none.  More obstacles than K: ValueError."""
+    K, P = int(K), int(P)
+    k0, p0 = int(packed["K"]), int(packed["P"])
+    if K < 1 or P < 2:
+        raise ValueError(f"hypothesis_arrays: K={K}, P={P} (the upload has at least one obstacle and two predictions)")
+    if k0 > K:
+        raise ValueError(f"{k0} predicted obstacles in a hypothesis for an upload of K={K}")
+    pos, cov_inv, hull = np.zeros((K, P, 2)), np.zeros((K, P, 4)), np.zeros((K, P - 1, 6))
+    npred, nhull = np.zeros(K, np.int32), np.zeros(K, np.int32)
+    if k0 > 0:
+        n = min(p0, P)
+        pos[:k0, :n] = np.asarray(packed["pos"], np.float64).reshape(k0, p0, 2)[:, :n]
+        cov_inv[:k0, :n] = np.asarray(packed["cov_inv"], np.float64).reshape(k0, p0, 4)[:, :n]
+        npred[:k0] = np.asarray(packed["npred"], np.int32).reshape(k0)
+        h = packed.get("hull")
+        if h is not None and np.size(h) and n > 1:
+            hull[:k0, :n - 1] = np.asarray(h, np.float64).reshape(k0, p0 - 1, 6)[:, :n - 1]
+            nhull[:k0] = np.minimum(np.asarray(packed["nhull"], np.int32).reshape(k0), P - 1)
+    return dict(K=K, P=P, pos=pos, cov_inv=cov_inv, npred=npred, hull=hull, nhull=nhull)
+
+
 def pack_road_boundary(segments, cs: CoordinateSystem, vehicle: "VehicleParams", d_reach: float, max_len: float = 4.0):
     """Road boundary segments [n][4] = (ax, ay, bx, by) -> what the engine takes (planner.py:362-381, 550-565).
 

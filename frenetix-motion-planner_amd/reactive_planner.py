@@ -539,6 +539,21 @@ class ReactivePlannerHip:
         r = step.engine.rescore(weight_sets, agent=step.agent, pred=pred, resp=resp)
         return [(int(i), float(c)) for i, c in zip(r["winner"], r["cost"])]
 
+    def what_if(self, prediction_sets):
+        """The last plan step under other predictions (FrenetEngine.hypotheses): [(index, cost, n_collisions)]
+        per predictions dict -- the form set_predictions takes, packed with the planner's own packer -- the candidate the device
+        selection would have chosen had the step run with them, -1 / inf where no candidate is selectable and collision-free.  A
+        dict may hold fewer obstacles than the step's upload (the rest are absent), not more.  It is the device selection only:
+        the host road-boundary walk and the occlusion walk of plan() are not run, and nothing of the step, of optimal_trajectory
+        or of the planner's own predictions changes.  Needs a step that stored its bundle and cost map (not sparse_bundle_k > 0)."""
+        if self.last_step is None:
+            raise ValueError("no plan step yet")
+        from .engine import build_obstacle_hulls
+        step = self.last_step
+        sets = [pack_predictions(p, self.N + 1, build_obstacle_hulls) for p in prediction_sets]
+        r = step.engine.hypotheses(sets, agent=step.agent)
+        return [(int(i), float(c), int(k)) for i, c, k in zip(r["winner"], r["cost"], r["n_collisions"])]
+
     @staticmethod
     def rescore_rows(step, rows: str = "step"):
         """(pred, resp) of a re-score of `step`: (None, None) for rows "step"; for rows "override" the prediction array of the

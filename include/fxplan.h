@@ -589,6 +589,57 @@ double fx_last_rescore_ms(FxContext *ctx);
  * step that stored no cost map (FX_MODE_WRITE_COSTMAP).  Any pointer may be NULL. */
 int32_t fx_device_costmap_view(FxContext *ctx, int32_t agent, void **costmap, int64_t *ld, int32_t *n_cost);
 
+/* ---- a finished plan step re-evaluated under many prediction sets at once, beside the step -- DESIGN.md section 25; additive
+ *      within ABI 15 ----
+ *      The walk of a step does not read the predictions; its obstacle stage -- the `prediction` cost and the collision walk -- reads
+ *      only x, y, theta, the flag words and the obstacle tables.  One call answers, for n_hyp hypotheses, what a plan step with those
+ *      predictions would have selected.  A hypothesis is the five obstacle arrays of FxStateUpdate WITH THE K AND P OF THE UPLOAD,
+ *      exactly what fx_update_state accepts; an absent obstacle has obs_npred = 0 and obs_nhull = 0.  Everything else is the step's:
+ *      ego state, sampling, cost list and weights, dto_pos, lanelets, hot_origin.
+ *      The rule.  Let CH be the steps per item the obstacle kernel has, or would have, for this step (fx_step_info_ex's split_CH; a forced
+ *      fx_set_obstacle_stage(.., steps_per_item) is honoured).  pred[h][c] is the raw prediction entry fx_obstacle_kernel would store;
+ *      collision[h][c] the collision decision on the hypothesis' hulls; total[h][c] the weighted sum of the step's raw cost rows with
+ *      pred[h][c] in the prediction entry, in the order of a step whose obstacle stage ran as its own kernel (NaN without
+ *      FX_FLAG_COSTED; a list without FX_COST_PREDICTION sums as the step did); winner[h] the lexicographic (total, index) minimum
+ *      over the candidates with FX_FLAG_SELECTABLE, without collision[h][c] and without FX_FLAG_BOUNDARY, NaN totals skipped -- a
+ *      LOCAL index, -1 with cost +inf where nothing is eligible; n_collisions[h] the selectable colliding candidates ordered before
+ *      the winner by (total, index), all of them where nothing is eligible.
+ *      For a step whose obstacle stage ran in its own kernel the step's own arrays reproduce the step bit for bit, and any
+ *      hypothesis equals a real step run with those arrays.  For a step that ran the stage INSIDE the walk the answer is, bit for
+ *      bit, that of the same step forced to fx_set_obstacle_stage(ctx, 2, CH); against the fused step's own cost it agrees only up
+ *      to the association of at most S - 1 non-negative addends -- the walk's lane-split associations are not emulated.
+ *      It is the device selection only: no host road-boundary walk, no occlusion walk.  Synchronous; any agent of a batch context.
+ *      The call packs one table per hypothesis into one staging buffer, copies it up once, enqueues at most three launches per
+ *      round of hypotheses and copies the answers back; its block is allocated on first use, grow-only, counted in fx_device_bytes.
+ *      Checked before anything is allocated, copied or enqueued: FX_ERR_NOT_READY before the first finished step, when the inputs
+ *      were rewritten since it, and for a step without FX_MODE_WRITE_BUNDLE or without FX_MODE_WRITE_COSTMAP;
+ *      FX_ERR_INVALID_ARGUMENT for n_hyp < 1, a NULL array in a hypothesis, NULL out, winner or cost, an agent out of range, an
+ *      upload with K = 0, and a step the obstacle kernel does not serve (needs K <= 64, no road boundary, no windowed cost term);
+ *      FX_ERR_CAPACITY above FX_HYPOTHESES_MAX hypotheses per call. */
+#define FX_HYPOTHESES_MAX 4096
+typedef struct FxHypothesis {
+    const double *obs_pos;       /* [K][P][2] */
+    const double *obs_cov_inv;   /* [K][P][4] */
+    const int32_t *obs_npred;    /* [K] */
+    const double *obs_hull;      /* [K][P-1][6] */
+    const int32_t *obs_nhull;    /* [K] */
+} FxHypothesis;
+typedef struct FxHypothesisOutputs {
+    int64_t *winner;         /* [n_hyp] */
+    double *cost;            /* [n_hyp] */
+    int64_t *n_collisions;   /* [n_hyp] or NULL */
+    double *pred;            /* [n_hyp][C] or NULL: 0 without FX_FLAG_COSTED, as the step's cost map */
+    double *total;           /* [n_hyp][C] or NULL */
+    uint8_t *collision;      /* [n_hyp][C] or NULL */
+} FxHypothesisOutputs;
+int32_t fx_eval_hypotheses_agent(FxContext *ctx, int32_t agent, int32_t n_hyp, const FxHypothesis *hyp /*[n_hyp]*/,
+                                 const FxHypothesisOutputs *out);
+/* device time of the context's last hypotheses call (events around its launches), ms; -1 before the first.  Waits for it. */
+double fx_last_hypotheses_ms(FxContext *ctx);
+/* the last call's steps per item (CH), rounds of hypotheses and kernel launches; any pointer may be NULL.  FX_ERR_NOT_READY before
+ * the first call. */
+int32_t fx_last_hypotheses_info(FxContext *ctx, int32_t *steps_per_item, int32_t *rounds, int32_t *launches);
+
 /* ---- road boundary (replaces create_road_boundary_obstacle + trajectories_collision_static_obstacles,
  *      planner.py:362-381,550-565; commonroad-drivability-checker, not in the reference tree) ----
  * fx_build_boundary_bins: host-side geometry, no GPU.  Splits the n_seg boundary segments seg[n_seg][4] =

@@ -199,7 +199,7 @@ static int exchange_signal(FxContext *c, int32_t total) {
 int32_t fx_step_exchange(FxContext *c, FxResult *res, double *cost, int64_t *index) {
     if (!c || !res || !cost || !index) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_step_exchange: NULL argument");
     if (!c->comm) return set_err(FX_ERR_NOT_READY, "fx_step_exchange before fx_comm_init");
-    if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
+    FX_TRY(fx_check_not_timed_out(c));
     const int A = c->comm_agents;
     int rc_local = FX_OK;
     char err_local[sizeof(g_err)];
@@ -248,7 +248,7 @@ int32_t fx_step_exchange_topk(FxContext *c, int32_t k, FxResult *res, double *co
     if (!c || !res || !cost || !index) return set_err(FX_ERR_INVALID_ARGUMENT, "fx_step_exchange_topk: NULL argument");
     if (k < 1 || k > 64) return set_err(FX_ERR_INVALID_ARGUMENT, "k=%d outside [1,64]", k);
     if (!c->comm) return set_err(FX_ERR_NOT_READY, "fx_step_exchange_topk before fx_comm_init");
-    if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
+    FX_TRY(fx_check_not_timed_out(c));
     const int A = c->comm_agents;
     const size_t n = (size_t)A * 2 * k, total = n * c->comm_world;
     // what depends only on (communicator, k) is the same on every rank: these refusals happen everywhere or nowhere

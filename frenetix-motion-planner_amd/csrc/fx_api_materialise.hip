@@ -137,8 +137,7 @@ static int fx_sparse_plan(FxContext *c, int32_t agent, int64_t n, const int64_t 
 static int fx_sparse_ready(FxContext *c) {
     if (!fx_inputs_current(c))
         return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): the re-walk would use another state");
-    if (c->timed_out) return set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it");
-    return FX_OK;
+    return fx_check_not_timed_out(c);
 }
 
 // The rows form: every plan with candidates becomes a row of its variant's launch.  Everything was checked; from here on only the

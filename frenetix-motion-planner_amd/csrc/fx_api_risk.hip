@@ -17,27 +17,6 @@
 #include "fx_rescore_batch_plan.h"   // fx_resp_term_at: where the responsibility term stands in a cost list
 #include "fx_risk_args.h"
 
-extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const RiskItemArgs *items, double *out_ego, double *out_obst, double *col,
-                                     double *out_occ, const RiskCostArgs *cost, long long *out_idx, hipEvent_t ev_start,
-                                     hipEvent_t ev_stop, hipStream_t stream, const RespSumArgs *resp, long long *resp_idx);
-extern "C" hipError_t fx_launch_predprob(const PredProbArgs *args, long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
-                                         hipStream_t stream);
-// (weak, like the chunk rule below: a host-only program that links these files against launcher stubs of its own need not define
-// the launchers that came after it was written; fx_eval_prediction_prob_batch reports their absence)
-extern "C" __attribute__((weak)) hipError_t fx_launch_predprob_batch(const PredProbBatchArgs *t, const FxItemRound *rounds, int n_rounds,
-                                                                     long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
-                                                                     hipStream_t stream);
-extern "C" __attribute__((weak)) hipError_t fx_launch_risk_batch(const RiskBatchArgs *t, const FxItemRound *rounds, int n_rounds,
-                                                                 long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
-                                                                 hipStream_t stream);
-extern "C" __attribute__((weak)) hipError_t fx_launch_risk_list_batch(const RiskListBatchArgs *t, const FxItemRound *rounds, int n_rounds,
-                                                                      long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
-                                                                      hipStream_t stream);
-extern "C" __attribute__((weak)) hipError_t fx_launch_risk_costs_batch(const RiskCostBatchArgs *t, const FxItemRound *rounds, int n_rounds,
-                                                                       long long *out_idx, long long *cost_idx, hipEvent_t ev_start,
-                                                                       hipEvent_t ev_stop, hipStream_t stream);
-extern "C" __attribute__((weak)) int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K);   // (fx_kernels.hip: the rule, or what a test forces)
-
 namespace {
 // Gauss-Legendre nodes on [-1, 1], positive half: 6, 12 and 20 points (Genz 2004)
 const double kX6[3] = {0.9324695142031522, 0.6612093864662647, 0.2386191860831970};
@@ -280,6 +259,13 @@ static std::atomic<int> fx_risk_items_chunk_forced{0};
 extern "C" void fx_risk_items_set_chunk_steps(int32_t steps) { fx_risk_items_chunk_forced.store(steps > 0 ? steps : 0, std::memory_order_relaxed); }
 extern "C" int32_t fx_risk_items_chunk_steps(int64_t n, int32_t S, int32_t K) {
     return fx_item_chunk_steps(n, S, K, fx_risk_items_chunk_forced.load(std::memory_order_relaxed));
+}
+// The same for the prediction-probability items: what fx_launch_predprob (fx_kernels.hip) and the batched pass below size their
+// chunks by, or what fx_predprob_set_chunk_steps forces (tests: the results do not depend on it)
+static std::atomic<int> fx_predprob_chunk_forced{0};
+extern "C" void fx_predprob_set_chunk_steps(int32_t steps) { fx_predprob_chunk_forced.store(steps > 0 ? steps : 0, std::memory_order_relaxed); }
+extern "C" int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K) {
+    return fx_item_chunk_steps(n, S, K, fx_predprob_chunk_forced.load(std::memory_order_relaxed));
 }
 
 // What every pass does before it touches the device: the stream drained, the passes' one block at `bytes` or more, the events
@@ -549,8 +535,7 @@ extern "C" int32_t fx_eval_risk_costs_agent(FxContext *c, int32_t agent, const F
 static int resp_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskParams *params, const FxRespCostParams *resp, int64_t n_ids,
                       const int64_t *ids, bool have_out, FxRiskCostParams &cost) {
     FX_TRY(check_agent(c, agent));
-    if (!fx_inputs_current(c))   // (the condition of fx_eval_prediction_prob_agent: the planes and cost rows are the last evaluated step's)
-        return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
+    FX_TRY(fx_check_inputs_current(c));   // (the condition of fx_eval_prediction_prob_agent: the planes and cost rows are the last evaluated step's)
     if (!(c->slots[agent].mode & FX_MODE_WRITE_COSTMAP)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_COSTMAP");
     FX_TRY(risk_check(q, c, agent, (params && resp) ? params : nullptr, n_ids, ids, have_out, true));
     if (!(resp->weight != 0.0) || resp->weight != resp->weight) return set_err(FX_ERR_INVALID_ARGUMENT, "responsibility weight %g", resp->weight);
@@ -568,10 +553,8 @@ static int resp_check(RiskPass &q, FxContext *c, int32_t agent, const FxRiskPara
 // what the re-sum reads of a checked agent's cost list, but for the pointers into the pass's block
 static void resp_sum_fill(const RiskPass &q, const FxRespCostParams *resp, RespSumArgs &rs) {
     const DevProblem &hp = q.c->h_probs[q.agent];
-    rs.n_pred = -1;
+    rs.n_pred = fx_prediction_term(hp);
     rs.at = fx_resp_term_at(hp.cost_id, hp.n_cost);   // in front of the first name behind "responsibility" in the sorted list
-    for (int m = hp.n_cost - 1; m >= 0; m--)
-        if (hp.cost_id[m] == FX_COST_PREDICTION) rs.n_pred = m;
     rs.n = q.n, rs.flags = q.flags, rs.need = FX_FLAG_COSTED;
     rs.costmap = q.sparse ? q.set.costmap : q.c->d_costmap + (size_t)FX_NUM_COSTS * q.s->cand_off;
     rs.ld = q.ld;
@@ -626,8 +609,7 @@ static int predprob_check(RiskPass &q, FxContext *c, int32_t agent, const FxPred
     FX_TRY(check_agent(c, agent));
     // (the planes and the cost map are the last EVALUATED step's: inputs rewritten since belong to a step that has not run -- the
     // condition of the sort and of the sparse set, fx_api_sort.hip / fx_api_materialise.hip)
-    if (!fx_inputs_current(c))   // (check_agent has established `evaluated`)
-        return set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
+    FX_TRY(fx_check_inputs_current(c));   // (check_agent has established `evaluated`)
     if (!(c->slots[agent].mode & FX_MODE_WRITE_COSTMAP)) return set_err(FX_ERR_NOT_READY, "plan step ran without FX_MODE_WRITE_COSTMAP");
     FxRiskParams rp{};   // what risk_check and step_probability read of it: the MVN mode and the ego's footprint
     rp.prob_mode = FX_RISK_PROB_MVN;
@@ -638,10 +620,7 @@ static int predprob_check(RiskPass &q, FxContext *c, int32_t agent, const FxPred
     q.prm = nullptr;   // (rp is a local; this pass reads the footprint from its own parameters)
     if (params->source != FX_PRED_SOURCE_PROBABILITY && params->source != FX_PRED_SOURCE_STEP)
         return set_err(FX_ERR_INVALID_ARGUMENT, "source %d", params->source);
-    const DevProblem &hp = c->h_probs[agent];
-    n_pred = -1;
-    for (int m = 0; m < hp.n_cost; m++)
-        if (hp.cost_id[m] == FX_COST_PREDICTION) n_pred = m;
+    n_pred = fx_prediction_term(c->h_probs[agent]);
     if (n_pred < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "the cost list has no FX_COST_PREDICTION");
     return FX_OK;
 }
@@ -693,18 +672,16 @@ extern "C" int32_t fx_eval_prediction_prob_agent(FxContext *c, int32_t agent, co
 // risk_block; risk_fill_rows; risk_cost_fill; risk_end and risk_winner.  None of them makes a runtime call per agent.
 
 // The front of a call: the refusals in the order the entries report them.  missing: what of the call's own arguments is NULL, or
-// null; no_launcher: the launcher the library was linked without, or null; name_agent: the refusal of a context without an
-// evaluated step names the first agent; current: the call needs the inputs of the last evaluation (fx_inputs_current).  check is
+// null; name_agent: the refusal of a context without an evaluated step names the first agent; current: the call needs the inputs of the last evaluation (fx_inputs_current).  check is
 // the per-agent entry's check of agent `agent`, the i-th of the call, into q[i]; its refusal is reported as "agent <agent>: ...".
 // n_agents == 0 returns FX_OK with nothing touched: the caller returns then too.
 template <class Check>
-static int batch_front(FxContext *c, const char *missing, int32_t n_agents, const int32_t *agents, const char *no_launcher, bool name_agent,
-                       bool current, std::vector<RiskPass> &q, Check check) {
+static int batch_front(FxContext *c, const char *missing, int32_t n_agents, const int32_t *agents, bool name_agent, bool current,
+                       std::vector<RiskPass> &q, Check check) {
     if (!c) return set_err(FX_ERR_INVALID_ARGUMENT, "context is NULL");
     if (missing) return set_err(FX_ERR_INVALID_ARGUMENT, "%s", missing);
     if (n_agents < 0) return set_err(FX_ERR_INVALID_ARGUMENT, "n_agents %d", n_agents);
     if (n_agents == 0) return FX_OK;
-    if (no_launcher) return set_err(FX_ERR_HIP, "built without the batched %s launcher", no_launcher);
     const int32_t agent0 = agents ? agents[0] : 0;
     if (!c->evaluated)
         return name_agent ? set_err(FX_ERR_NOT_READY, "agent %d: no evaluated plan step", agent0) : set_err(FX_ERR_NOT_READY, "no evaluated plan step");
@@ -872,8 +849,7 @@ extern "C" int32_t fx_eval_prediction_prob_batch(FxContext *c, int32_t n_agents,
                                                  const FxPredProbBatchOutputs *out) {
     std::vector<RiskPass> q;
     std::vector<int> n_pred;   // (sized in the check: the front has accepted n_agents by then)
-    const int rc = batch_front(c, (!params || !out) ? "params or out is NULL" : nullptr, n_agents, agents,
-                               (fx_launch_predprob_batch && fx_predprob_chunk_steps) ? nullptr : "prediction-probability", false, false, q,
+    const int rc = batch_front(c, (!params || !out) ? "params or out is NULL" : nullptr, n_agents, agents, false, false, q,
                                [&](RiskPass &p, size_t i, int32_t agent) {
         n_pred.resize(q.size());
         return predprob_check(p, c, agent, params + i, 0, nullptr, true, n_pred[i]);
@@ -960,8 +936,8 @@ extern "C" int32_t fx_eval_responsibility_cost_batch(FxContext *c, int32_t n_age
     std::vector<RiskPass> q;
     std::vector<FxRiskCostParams> cost;   // (sized in the check: the front has accepted n_agents by then)
     const bool have_out = out && out->resp && out->total && out->ego_risk && out->obst_risk && out->best_index && out->best_cost;
-    const int rc = batch_front(c, (!params || !resp || !out) ? "params, resp or out is NULL" : nullptr, n_agents, agents,
-                               fx_launch_risk_batch ? nullptr : "responsibility", true, false, q, [&](RiskPass &p, size_t i, int32_t agent) {
+    const int rc = batch_front(c, (!params || !resp || !out) ? "params, resp or out is NULL" : nullptr, n_agents, agents, true, false, q,
+                               [&](RiskPass &p, size_t i, int32_t agent) {
         cost.resize(q.size());
         return resp_check(p, c, agent, params + i, resp + i, 0, nullptr, have_out, cost[i]);   // (without ids it refuses a step that stored no bundle)
     });
@@ -1060,8 +1036,7 @@ extern "C" int32_t fx_eval_risk_batch(FxContext *c, int32_t n_agents, const int3
     std::vector<RiskPass> q;
     const char *const missing = (!params || !out) ? "params or out is NULL"
                                 : (!out->ego_risk || !out->obst_risk || !out->min_risk_index) ? "an output pointer is NULL" : nullptr;
-    const int rc = batch_front(c, missing, n_agents, agents, fx_launch_risk_list_batch ? nullptr : "risk", true, true, q,
-                               [&](RiskPass &p, size_t i, int32_t agent) {
+    const int rc = batch_front(c, missing, n_agents, agents, true, true, q, [&](RiskPass &p, size_t i, int32_t agent) {
         return risk_check(p, c, agent, params + i, batch_n_ids(n_ids, i), batch_ids(n_ids, ids, i), true, false);
     });
     if (rc || n_agents == 0) return rc;
@@ -1118,8 +1093,8 @@ extern "C" int32_t fx_eval_risk_costs_batch(FxContext *c, int32_t n_agents, cons
                                             const FxRiskCostParams *const *cost, const int64_t *n_ids, const int64_t *const *ids,
                                             const FxRiskCostBatchOutputs *out) {
     std::vector<RiskPass> q;
-    const int rc = batch_front(c, (!params || !out) ? "params or out is NULL" : nullptr, n_agents, agents,
-                               fx_launch_risk_costs_batch ? nullptr : "risk-cost", true, true, q, [&](RiskPass &p, size_t i, int32_t agent) {
+    const int rc = batch_front(c, (!params || !out) ? "params or out is NULL" : nullptr, n_agents, agents, true, true, q,
+                               [&](RiskPass &p, size_t i, int32_t agent) {
         const int rc_i = risk_check(p, c, agent, params + i, batch_n_ids(n_ids, i), batch_ids(n_ids, ids, i), true, true);
         return (!rc_i && cost && cost[i]) ? risk_cost_check(p, cost[i]) : rc_i;
     });

@@ -1,12 +1,13 @@
-// fx_context.h -- what the translation units of the C-ABI share: the context, its helpers, the launchers' declarations.
+// fx_context.h -- what the translation units of the C-ABI share: the context and its helpers (the launchers: fx_launch.h).
 //   fx_api.hip           context life cycle, settings, measurement hooks
 //   fx_api_step.hip      upload, evaluation (launch policy: fx_policy.h), results, state updates, winner package, batched plan calls
 //   fx_api_exchange.hip  survivor exchange inside the library (RCCL)
 //   fx_api_host.hip      host geometry of the callers either side of the path, read-back
 //   fx_api_risk.hip      trajectory risk and risk costs beside the plan step
 //   fx_api_materialise.hip  listed candidates of a step re-walked into a sparse set, its read-back and package
-//   fx_api_sort.hip      stable cost order of all candidates beside the step, read back by rank; the step re-scored under other weights
-//                        and re-evaluated under other prediction sets
+//   fx_api_sort.hip      stable cost order of all candidates beside the step, read back by rank
+//   fx_api_rescore.hip   the step re-scored under other cost weights, one agent or a batch; the device view of the raw cost rows
+//   fx_api_hypotheses.hip  the step's obstacle stage re-evaluated under other prediction sets
 #pragma once
 
 #include <algorithm>
@@ -27,39 +28,8 @@
 #include <fcntl.h>
 #include <unistd.h>
 
+#include "fx_launch.h"
 #include "fx_owner.h"
-
-extern "C" hipError_t fx_launch_eval(const DevProblem *d_probs, int n_agents, int max_blocks, size_t lds_bytes, int G,
-                                     bool bundle, bool obst, bool extra, int wpe, hipEvent_t ev_start, hipEvent_t ev_stop,
-                                     FuseArgs fuse, hipStream_t stream);
-extern "C" hipError_t fx_launch_eval_grid(const DevProblem *d_probs, int n_agents, int max_blocks, int block_size,
-                                          size_t lds_bytes, int G, bool bundle, bool obst, int wpe, bool wsplit,
-                                          hipEvent_t ev_start, hipEvent_t ev_stop, FuseArgs fuse, hipStream_t stream);
-extern "C" hipError_t fx_launch_obstacle(const DevProblem *d_probs, int n_agents, int max_items, size_t lds_bytes, int CH,
-                                         hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream, int wg_waves, int max_tiles,
-                                         const DevProblem *head);
-extern "C" hipError_t fx_step_kernel_capacity(int CH, size_t lds_bytes, int *blocks_out);
-extern "C" hipError_t fx_launch_step(const DevProblem *d_probs, int n_agents, int blocks, size_t lds_bytes, int CH, hipEvent_t ev_start,
-                                     hipEvent_t ev_stop, FuseArgs fuse, StepArgs sa, hipStream_t stream);
-extern "C" hipError_t fx_launch_select(const DevProblem *d_probs, int n_agents, int64_t max_candidates, unsigned long long *host_result,
-                                       unsigned long long seq, double *dev_winner, double *host_pkg, int pkg_stride, int pkg_plane_rows,
-                                       hipStream_t stream, const DevProblem *head);
-extern "C" hipError_t fx_launch_math_test(int n, const double *x, double *at, double *sn, double *cs, hipStream_t stream);
-extern "C" hipError_t fx_launch_selftest(int op, int n, const SelftestArgs *args, hipStream_t stream);
-extern "C" hipError_t fx_launch_publish(const double *src, int n, double *host_dst, unsigned long long *host_seq,
-                                        unsigned long long seq, hipStream_t stream);
-extern "C" hipError_t fx_launch_stage(const void *src_mapped, void *dst, size_t bytes, hipStream_t stream);
-extern "C" hipError_t fx_launch_package(const DevProblem *d_probs, int n_agents, const double *winner, double *host_pkg, int stride,
-                                        int plane_rows, unsigned long long seq, hipStream_t stream);
-extern "C" hipError_t fx_launch_topk(const DevProblem *d_probs, int n_agents, int64_t max_candidates, int k, double *scr_cost, long long *scr_idx,
-                                     double *out_cost, long long *out_idx, hipStream_t stream);
-
-
-extern "C" hipError_t fx_launch_gather_candidates(const GatherArgs *args, const int64_t *d_ids, int64_t n, unsigned long long *d_out,
-                                                  hipStream_t stream);
-extern "C" hipError_t fx_launch_eval_list(const DevProblem *d_prob, const int64_t *d_ids, int64_t n, size_t lds_bytes, bool obst, bool extra,
-                                          const EvalListRow *d_rows, int n_rows, int lanes, hipEvent_t ev_start, hipEvent_t ev_stop,
-                                          hipStream_t stream);
 
 // state updates up to this many bytes are staged by a copy kernel reading the mapped pinned block, larger ones by the DMA engine
 #define FX_STAGE_KERNEL_MAX ((size_t)1 << 20)
@@ -84,8 +54,8 @@ struct FxAgentSlot {
 void fx_risk_release(struct FxRiskState *r);       // (fx_api_risk.hip)
 void fx_sparse_release(struct FxSparseState *s);   // (fx_api_materialise.hip)
 void fx_sort_release(struct FxSortState *s);       // (fx_api_sort.hip)
-void fx_rescore_release(struct FxRescoreState *s);   // (fx_api_sort.hip)
-void fx_hyp_release(struct FxHypState *s);           // (fx_api_sort.hip)
+void fx_rescore_release(struct FxRescoreState *s);   // (fx_api_rescore.hip)
+void fx_hyp_release(struct FxHypState *s);           // (fx_api_hypotheses.hip)
 
 struct FxContext {
     int device = 0;
@@ -402,8 +372,6 @@ inline void hot_origin_of(const double *knots, int M, double s0, double *origin)
     origin[1] = knots[(size_t)ko * FX_REF_FIELDS + 5];
 }
 
-
-extern "C" hipError_t fx_launch_probe_read(const void *src, void *dst, int blocks, hipStream_t stream);
 // Host writes into device memory (large BAR) -- OPT-IN (FX_STAGE=bar).  On boxes where the whole VRAM is mapped into the process a
 // state update needs no staging launch: the host copies the rewritten range of its pinned block into the device arena itself --
 // posted PCIe writes, ~50 GB/s and no round trip (tools/micro/bar_write.hip, bar_bw.hip; ~3 us of a host-fed step).  Round 5 ran it

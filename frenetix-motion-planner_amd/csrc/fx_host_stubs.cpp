@@ -1,11 +1,16 @@
-// Sanitizer build of the library's HOST code only (make asan; tools/asan_host.sh): the kernel launchers of fx_kernels.hip are
-// replaced by stubs that report hipErrorNotSupported -- nothing on a CPU box launches a kernel; what runs under ASan / UBSan is
-// the host logic of fx_api.hip that needs no GPU (fx_pack_predictions, fx_invert_cov2, fx_build_obstacle_hulls*, fx_cs_to_curvilinear*,
-// fx_build_boundary_bins, fx_wait_word, argument validation) and the CPython extension _fxhost (fx_host_ext.c).
-#include <hip/hip_runtime_api.h>
-#define FX_STUB(name) extern "C" hipError_t name(...) { return hipErrorNotSupported; }
-FX_STUB(fx_launch_eval) FX_STUB(fx_launch_eval_grid) FX_STUB(fx_launch_obstacle) FX_STUB(fx_step_kernel_capacity) FX_STUB(fx_launch_step)
-FX_STUB(fx_launch_select) FX_STUB(fx_launch_math_test) FX_STUB(fx_launch_publish) FX_STUB(fx_launch_stage) FX_STUB(fx_launch_package)
-FX_STUB(fx_launch_topk) FX_STUB(fx_launch_probe_read) FX_STUB(fx_launch_risk) FX_STUB(fx_launch_gather_candidates) FX_STUB(fx_launch_eval_list) FX_STUB(fx_launch_selftest)
-FX_STUB(fx_launch_sort) FX_STUB(fx_launch_sort_gather) FX_STUB(fx_launch_predprob) FX_STUB(fx_launch_predprob_batch) FX_STUB(fx_launch_risk_batch)
-FX_STUB(fx_launch_risk_list_batch) FX_STUB(fx_launch_risk_costs_batch) FX_STUB(fx_launch_rescore) FX_STUB(fx_launch_rescore_batch) FX_STUB(fx_launch_hypotheses)
+// Stubs of everything fx_kernels.hip defines for the host files, made from the one list of their names (FX_LAUNCHERS, fx_launch.h),
+// for programs that link the library's HOST code without its device code: the sanitizer build (make asan; tools/asan_host.sh), where
+// nothing launches a kernel and a stub reports hipErrorNotSupported, and the stand-alone test programs (tests/context_owners.cpp,
+// tests/batch_staging.cpp, tests/materialise_staging.cpp), which build this file with -DFX_STUB_RESULT=hipSuccess.
+// The stubs are WEAK definitions: a test program overrides a launcher by defining it, and takes the stubs for all the others.
+#include "fx_launch.h"
+
+#ifndef FX_STUB_RESULT
+#define FX_STUB_RESULT hipErrorNotSupported
+#endif
+
+// (the header declares the launchers with their parameters: a stub is defined under a name of its own and carries the launcher's symbol)
+#define FX_STUB(name)                                                                    \
+    extern "C" __attribute__((weak)) hipError_t stub_##name(...) __asm__(#name);         \
+    extern "C" hipError_t stub_##name(...) { return FX_STUB_RESULT; }
+FX_LAUNCHERS(FX_STUB)

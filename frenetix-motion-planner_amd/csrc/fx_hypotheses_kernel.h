@@ -1,5 +1,5 @@
 // fx_hypotheses_kernel.h -- the obstacle stage of a finished plan step run again over many prediction sets at once, beside the step:
-// nothing a step wrote is rewritten (host: fx_api_sort.hip; launch rule: fx_hypotheses_plan.h).
+// nothing a step wrote is rewritten (host: fx_api_hypotheses.hip; launch rule: fx_hypotheses_plan.h).
 //
 // Per hypothesis h (one set of obstacle tables) and candidate c with FX_FLAG_COSTED the kernels answer what a plan step with those
 // predictions, its obstacle stage run by fx_obstacle_kernel at CH steps per item, stores and selects:

@@ -1,5 +1,5 @@
 // fx_kernels.hip -- the one translation unit of libfxplan.so with device code: it includes every kernel family (fx_*_kernel.h,
-// fx_select.h) and holds their launchers (declared in fx_context.h, called by fx_api*.hip) and a few kernels too small for a header
+// fx_select.h) and holds their launchers (declared in fx_launch.h, called by fx_api*.hip) and a few kernels too small for a header
 // of their own.  What runs when is decided by the callers (fx_policy.h); the evaluation pipeline is described in fx_eval_kernel.h.
 #include <hip/hip_ext.h>
 
@@ -15,6 +15,7 @@
 #include "fx_gather_kernel.h"
 #include "fx_sort_kernel.h"
 #include "fx_selftest_kernel.h"
+#include "fx_launch.h"   // every launcher below is held to its declaration
 #include "fx_pass.h"
 
 using fxk::wave_count;
@@ -396,13 +397,7 @@ extern "C" hipError_t fx_launch_risk(const RiskWalkArgs *walk, const RiskItemArg
 
 // collision probability as the prediction cost (fx_predprob_kernel.h) over the a.n listed candidates, in
 // batches of a.nb: per batch the (tile, chunk, obstacle) items and the finish kernel, then the arg-min of the total into out_idx.
-// Steps per chunk: fx_item_chunk_steps (fx_pass.h) -- or what fx_predprob_set_chunk_steps forces (tests: the results do not depend
-// on it).  ev_start / ev_stop bracket all launches.
-static std::atomic<int> fx_predprob_chunk_forced{0};
-extern "C" void fx_predprob_set_chunk_steps(int32_t steps) { fx_predprob_chunk_forced.store(steps > 0 ? steps : 0, std::memory_order_relaxed); }
-extern "C" int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K) {
-    return fx_item_chunk_steps(n, S, K, fx_predprob_chunk_forced.load(std::memory_order_relaxed));
-}
+// Steps per chunk: fx_predprob_chunk_steps (fx_api_risk.hip).  ev_start / ev_stop bracket all launches.
 extern "C" hipError_t fx_launch_predprob(const PredProbArgs *args, long long *out_idx, hipEvent_t ev_start, hipEvent_t ev_stop,
                                          hipStream_t stream) {
     const PredProbArgs &a = *args;

@@ -1,5 +1,5 @@
-// fx_pass.h -- the host scaffold of the passes that run beside the plan step (fx_api_risk.hip, fx_api_sort.hip,
-// fx_api_materialise.hip, the read-back of fx_api_host.hip), each piece written once.  Nothing here launches a kernel.  The block of
+// fx_pass.h -- the host scaffold of the passes that run beside the plan step (fx_api_risk.hip, fx_api_sort.hip, fx_api_rescore.hip,
+// fx_api_hypotheses.hip, fx_api_materialise.hip, the read-back of fx_api_host.hip), each piece written once.  Nothing here launches a kernel.  The block of
 // a pass is an FxDeviceBlock (fx_owner.h): grow-only, laid out by FxBlockLayout.
 #pragma once
 
@@ -32,7 +32,7 @@ struct FxEventPair {
 
 // Steps per chunk of an item decomposition -- one wave per (tile of 64 candidates, chunk of steps, obstacle) -- over n candidates,
 // S - 1 steps and K obstacles: as many as keep the call at FX_ITEM_WAVES items or more, at least one -- or `forced` > 0, a test's
-// choice.  The one rule of the prediction-probability launcher (fx_kernels.hip) and the risk items (fx_api_risk.hip).  Pure: no HIP call.
+// choice.  The one rule of the prediction-probability items and the risk items (both fx_api_risk.hip).  Pure: no HIP call.
 #define FX_ITEM_WAVES 4096
 inline int fx_item_chunk_steps(int64_t n, int S, int K, int forced) {
     const int steps = S - 1 > 0 ? S - 1 : 1;
@@ -143,6 +143,38 @@ inline int fx_drain(FxContext *c) {
 
 // the resident inputs and outputs are the last evaluation's: no upload (clears `evaluated`) and no state update since
 inline bool fx_inputs_current(const FxContext *c) { return c->evaluated && !c->probs_dirty && !(c->dirty_hi > c->dirty_lo); }
+
+// the two refusals of every pass that reads what the last evaluation left; each call site keeps its place among the pass's refusals
+inline int fx_check_inputs_current(const FxContext *c) {
+    return fx_inputs_current(c) ? FX_OK
+                                : set_err(FX_ERR_NOT_READY, "the inputs were rewritten since the last evaluation (fx_update_state): evaluate first");
+}
+inline int fx_check_not_timed_out(const FxContext *c) {
+    return c->timed_out ? set_err(FX_ERR_TIMEOUT, "an earlier wait on this context timed out: destroy it") : FX_OK;
+}
+
+// Room for a pass's block and, where it has them, its pinned staging buffers `up` and `down`.  All are grow-only, and one that grows
+// is freed first: where something that already exists must grow, what was queued on it runs out before -- one wait, in front of the
+// first `ensure`; tail_work stays as it is.
+inline int fx_pass_room(FxContext *c, FxDeviceBlock &block, size_t bytes, FxPinned<char> *up = nullptr, size_t up_bytes = 0,
+                        FxPinned<char> *down = nullptr, size_t down_bytes = 0) {
+    if ((block && bytes > block.size()) || (up && *up && up_bytes > up->size()) || (down && *down && down_bytes > down->size()))
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    FX_TRY(block.ensure(bytes));
+    if (up) FX_TRY(up->ensure(up_bytes, hipHostMallocDefault));
+    if (down) FX_TRY(down->ensure(down_bytes, hipHostMallocDefault));
+    return FX_OK;
+}
+
+// Position of the prediction term in an agent's cost list, -1 without one.  Whether a pass sums its costs in the deferred form
+// follows from it, but not in one way, so the caller forms that bit: the re-score follows the step (FX_MODE_INT_DEFER_OBST and a
+// prediction term: a deferred step without one closed nothing in the obstacle kernel), the hypotheses pass runs the obstacle stage
+// itself whatever the step did (a prediction term alone).
+inline int fx_prediction_term(const DevProblem &hp) {
+    for (int m = 0; m < hp.n_cost; m++)
+        if (hp.cost_id[m] == FX_COST_PREDICTION) return m;
+    return -1;
+}
 
 // a caller's list of n candidates of an agent with C of them: the list is there (fx_check_id_list), every entry is a candidate
 // (fx_check_id_range); fx_check_ids is both, for the callers that have nothing to check in between

@@ -1,5 +1,5 @@
 // fx_rescore_batch_kernel.h -- the re-score of fx_rescore_kernel.h for a table of ENTRIES in one call, over effective cost lists
-// (host: fx_api_sort.hip; table: fx_rescore_batch_plan.h).
+// (host: fx_api_rescore.hip; table: fx_rescore_batch_plan.h).
 //
 // An entry is one agent with its own weight vectors.  Its effective list is the step's own cost list with up to two rows from
 // outside the step: one given in place of the prediction's row, one more term (the responsibility).  The kernels read a candidate's

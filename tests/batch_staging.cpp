@@ -30,15 +30,7 @@
 #include "fx_risk_args.h"
 #include "fxplan.h"
 
-// (the headers above declare the launchers with their parameters: the stubs are defined under names of their own and carry the
-// launchers' symbols)
-#define FX_STUB(name) extern "C" hipError_t stub_##name(...) __asm__(#name); extern "C" hipError_t stub_##name(...) { return hipSuccess; }
-FX_STUB(fx_launch_eval) FX_STUB(fx_launch_eval_grid) FX_STUB(fx_launch_obstacle) FX_STUB(fx_step_kernel_capacity) FX_STUB(fx_launch_step)
-FX_STUB(fx_launch_select) FX_STUB(fx_launch_math_test) FX_STUB(fx_launch_publish) FX_STUB(fx_launch_stage) FX_STUB(fx_launch_package)
-FX_STUB(fx_launch_topk) FX_STUB(fx_launch_probe_read) FX_STUB(fx_launch_risk) FX_STUB(fx_launch_gather_candidates) FX_STUB(fx_launch_eval_list) FX_STUB(fx_launch_selftest)
-FX_STUB(fx_launch_sort) FX_STUB(fx_launch_sort_gather) FX_STUB(fx_launch_predprob)
-
-// ---- the four batched launchers: keep what they were given ----
+// ---- the four batched launchers: keep what they were given (every other launcher: the stubs of csrc/fx_host_stubs.cpp) ----
 static PredProbBatchArgs g_pp;
 static RiskBatchArgs g_resp;
 static RiskListBatchArgs g_list;
@@ -56,9 +48,6 @@ hipError_t fx_launch_risk_list_batch(const RiskListBatchArgs *t, const FxItemRou
 hipError_t fx_launch_risk_costs_batch(const RiskCostBatchArgs *t, const FxItemRound *rounds, int n_rounds, long long *, long long *, hipEvent_t,
                                       hipEvent_t, hipStream_t) { g_cost = *t; keep_rounds(rounds, n_rounds); return hipSuccess; }
 }
-
-// (fx_kernels.hip answers this with the one rule of fx_pass.h; the probability pass takes its steps per chunk from it)
-extern "C" int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K) { return fx_item_chunk_steps(n, S, K, 0); }
 
 // ---- the fake runtime (tests/context_owners.cpp), with the calls an evaluation and a pass beside it make ----
 enum Kind { DEVICE, PINNED, EVENT, STREAM };

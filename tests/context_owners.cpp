@@ -1,7 +1,7 @@
 // context_owners.cpp -- the context's memory behind its owner types (csrc/fx_owner.h), without a GPU: the library's host sources,
-// launcher stubs that succeed, and malloc-backed fakes of the HIP runtime entry points that create, upload and destroy call
-// (tests/test_context_owners.py builds it with the compiler's host pass and runs it; the definitions here take precedence over
-// the runtime library's).  The fakes keep a table of everything handed out -- kind, bytes, frees per pointer -- and can fail the
+// launcher stubs that succeed (csrc/fx_host_stubs.cpp), and malloc-backed fakes of the HIP runtime entry points that create, upload
+// and destroy call (tests/test_context_owners.py builds it with the compiler's host pass and runs it; the definitions here take
+// precedence over the runtime library's).  The fakes keep a table of everything handed out -- kind, bytes, frees per pointer -- and can fail the
 // k-th call.  Checked:
 //   1. create with one and with four agents, destroy: nothing live, every block freed exactly once;
 //   2. create with call k failing, for every k of a create: an error, *out == NULL, nothing live;
@@ -18,12 +18,6 @@
 #include <vector>
 
 #include "fxplan.h"
-
-#define FX_STUB(name) extern "C" hipError_t name(...) { return hipSuccess; }
-FX_STUB(fx_launch_eval) FX_STUB(fx_launch_eval_grid) FX_STUB(fx_launch_obstacle) FX_STUB(fx_step_kernel_capacity) FX_STUB(fx_launch_step)
-FX_STUB(fx_launch_select) FX_STUB(fx_launch_math_test) FX_STUB(fx_launch_publish) FX_STUB(fx_launch_stage) FX_STUB(fx_launch_package)
-FX_STUB(fx_launch_topk) FX_STUB(fx_launch_probe_read) FX_STUB(fx_launch_risk) FX_STUB(fx_launch_gather_candidates) FX_STUB(fx_launch_eval_list) FX_STUB(fx_launch_selftest)
-FX_STUB(fx_launch_sort) FX_STUB(fx_launch_sort_gather) FX_STUB(fx_launch_predprob)
 
 // ---- the fake runtime ----
 enum Kind { DEVICE, PINNED, EVENT, STREAM };

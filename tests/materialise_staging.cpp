@@ -31,16 +31,7 @@
 #include "fx_risk_args.h"
 #include "fxplan.h"
 
-// (the headers above declare the launchers with their parameters: the stubs are defined under names of their own and carry the
-// launchers' symbols)
-#define FX_STUB(name) extern "C" hipError_t stub_##name(...) __asm__(#name); extern "C" hipError_t stub_##name(...) { return hipSuccess; }
-FX_STUB(fx_launch_eval) FX_STUB(fx_launch_eval_grid) FX_STUB(fx_launch_obstacle) FX_STUB(fx_step_kernel_capacity) FX_STUB(fx_launch_step)
-FX_STUB(fx_launch_select) FX_STUB(fx_launch_math_test) FX_STUB(fx_launch_publish) FX_STUB(fx_launch_stage) FX_STUB(fx_launch_package)
-FX_STUB(fx_launch_topk) FX_STUB(fx_launch_probe_read) FX_STUB(fx_launch_risk) FX_STUB(fx_launch_gather_candidates) FX_STUB(fx_launch_selftest)
-FX_STUB(fx_launch_sort) FX_STUB(fx_launch_sort_gather) FX_STUB(fx_launch_predprob) FX_STUB(fx_launch_predprob_batch) FX_STUB(fx_launch_risk_batch)
-FX_STUB(fx_launch_risk_list_batch) FX_STUB(fx_launch_risk_costs_batch)
-
-// ---- the list launcher: keep what it was given ----
+// ---- the list launcher: keep what it was given (every other launcher: the stubs of csrc/fx_host_stubs.cpp) ----
 struct Launch {
     const DevProblem *prob;
     const int64_t *ids;
@@ -57,8 +48,6 @@ extern "C" hipError_t fx_launch_eval_list(const DevProblem *d_prob, const int64_
     g_launches.push_back(Launch{d_prob, d_ids, n, lds_bytes, obst, extra, d_rows, n_rows, lanes, ev_start != nullptr, ev_stop != nullptr});
     return hipSuccess;
 }
-
-extern "C" int32_t fx_predprob_chunk_steps(int64_t n, int32_t S, int32_t K) { return fx_item_chunk_steps(n, S, K, 0); }
 
 // ---- the fake runtime (tests/batch_staging.cpp), every call counted ----
 enum Kind { DEVICE, PINNED, EVENT, STREAM };

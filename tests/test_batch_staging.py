@@ -6,16 +6,11 @@ fx_eval_responsibility_cost_batch, fx_eval_risk_batch and fx_eval_risk_costs_bat
 order.  It holds agent_row[], the rows, item0[] / fin0[], blk0[] (by agent, and compact over the agents with cost parameters) and
 seg_blk0[] to their expected values, every table and every row's memory to ONE live device block, and fx_device_bytes to the
 fakes' table."""
-import os
 import subprocess
 
-from tests.test_context_owners import CSRC, HIPCC, HOST_SOURCES, ROOT
+from tests.test_context_owners import build_host_program
 
 
 def test_batch_staging(tmp_path):
-    exe = str(tmp_path / "batch_staging")
-    subprocess.run([HIPCC, "--cuda-host-only", "-std=c++17", "-O1", "-Wall", "-Wno-unused-function", "-Wno-unused-command-line-argument",
-                    "-I", CSRC, "-I", os.path.join(ROOT, "include")] + [os.path.join(CSRC, s) for s in HOST_SOURCES] +
-                   [os.path.join(ROOT, "tests", "batch_staging.cpp"), "-o", exe], check=True)
-    run = subprocess.run([exe], capture_output=True, text=True)
+    run = subprocess.run([build_host_program("batch_staging", tmp_path)], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.startswith("ok (129 agents, 8 batched launches)"), run.stdout[-4000:] + run.stderr[-2000:]

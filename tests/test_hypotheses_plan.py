@@ -59,7 +59,7 @@ def test_constants_follow_the_sources(answers):
     assert int(re.search(r"#define FX_HYPOTHESES_MAX (\d+)", hdr).group(1)) == consts["max"]
     assert consts["grid_y"] == 65_535 and consts["finish_tile"] == 256 and consts["launches_per_round"] == 3
     # the default limit of a round is the passes' FX_ITEM_SCRATCH_BYTES
-    api = open(os.path.join(CSRC, "fx_api_sort.hip")).read()
+    api = open(os.path.join(CSRC, "fx_api_hypotheses.hip")).read()
     assert "limit_forced ? limit_forced : FX_ITEM_SCRATCH_BYTES" in api
     assert re.search(r"#define FX_ITEM_SCRATCH_BYTES \(\(size_t\)64 << 20\)", open(os.path.join(CSRC, "fx_pass.h")).read())
 

@@ -11,6 +11,7 @@ import numpy as np
 from frenetix_motion_planner_amd import _abi, _lib, commonroad_xml as crx, multiagent
 from frenetix_motion_planner_amd.reactive_planner import PlannerConfig
 from tests.oracle_engine import PackagingOracleEngine
+from tests.test_launchers import stubbed_launchers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "frenetix-motion-planner_amd", "csrc")
@@ -35,25 +36,25 @@ def test_symbols_are_exported_and_declared():
 
 
 def test_one_list_launcher_and_no_new_one():
-    """tests/context_owners.cpp and tests/batch_staging.cpp link every host source against a fixed list of launcher stubs: every
-    launcher the host sources call is one those two files and fx_host_stubs.cpp define, the list launcher under its one name"""
-    stubs = set(re.findall(r"FX_STUB\((fx_launch_\w+)\)", open(os.path.join(CSRC, "fx_host_stubs.cpp")).read()))
+    """tests/context_owners.cpp and tests/batch_staging.cpp link every host source against the launcher stubs of fx_host_stubs.cpp
+    and their own definitions: every launcher the host sources call is one of those, the list launcher under its one name"""
+    stubs = stubbed_launchers()
     assert "fx_launch_eval_list" in stubs
     called = set()
     for src in os.listdir(CSRC):
         if src.startswith("fx_api") and src.endswith(".hip"):
             called |= set(re.findall(r"\b(fx_launch_\w+)\s*\(", open(os.path.join(CSRC, src)).read()))
-    declared = set(re.findall(r"\b(fx_launch_\w+)\s*\(", open(os.path.join(CSRC, "fx_context.h")).read()))
+    declared = set(re.findall(r"\b(fx_launch_\w+)\s*\(", open(os.path.join(CSRC, "fx_launch.h")).read()))
     assert "fx_launch_eval_list" in declared and len([n for n in declared if "eval_list" in n]) == 1
     # ... and it is the one launcher that takes the row table of the rows form
-    decl = re.search(r"hipError_t fx_launch_eval_list\(([^;]*)\);", open(os.path.join(CSRC, "fx_context.h")).read()).group(1)
+    decl = re.search(r"hipError_t fx_launch_eval_list\(([^;]*)\);", open(os.path.join(CSRC, "fx_launch.h")).read()).group(1)
     assert "const EvalListRow *d_rows, int n_rows, int lanes" in " ".join(decl.split())
     assert declared <= stubs and called <= stubs, (declared - stubs, called - stubs)
     used = set(re.findall(r"\b(fx_launch_\w+)\s*\(", open(os.path.join(CSRC, "fx_api_materialise.hip")).read()))
     assert used == {"fx_launch_eval_list"}
     for other in ("context_owners.cpp", "batch_staging.cpp"):
         text = open(os.path.join(ROOT, "tests", other)).read()
-        defined = set(re.findall(r"FX_STUB\((fx_launch_\w+)\)", text)) | set(re.findall(r"hipError_t (fx_launch_\w+)\(", text))
+        defined = stubs | set(re.findall(r"hipError_t (fx_launch_\w+)\(", text))
         assert used <= defined, (other, used - defined)
 
 

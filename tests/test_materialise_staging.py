@@ -6,19 +6,14 @@ and over a list given out of order, at 1 and at 32 lanes.  It holds the launches
 n_blocks and mode bits, every clone's outputs to the agent's ONE live device block, the uploaded lists to ascending and
 de-duplicated, fx_device_bytes to the fakes' table, a refused call to changing nothing, and the runtime calls of a repeated call
 to the same count for 3 agents as for 129."""
-import os
 import re
 import subprocess
 
-from tests.test_context_owners import CSRC, HIPCC, HOST_SOURCES, ROOT
+from tests.test_context_owners import build_host_program
 
 
 def test_materialise_staging(tmp_path):
-    exe = str(tmp_path / "materialise_staging")
-    subprocess.run([HIPCC, "--cuda-host-only", "-std=c++17", "-O1", "-Wall", "-Wno-unused-function", "-Wno-unused-command-line-argument",
-                    "-I", CSRC, "-I", os.path.join(ROOT, "include")] + [os.path.join(CSRC, s) for s in HOST_SOURCES] +
-                   [os.path.join(ROOT, "tests", "materialise_staging.cpp"), "-o", exe], check=True)
-    run = subprocess.run([exe], capture_output=True, text=True)
+    run = subprocess.run([build_host_program("materialise_staging", tmp_path)], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.startswith("ok (129 agents, "), run.stdout[-4000:] + run.stderr[-2000:]
     # one wait, one upload, and per launch nothing the fakes see (the launcher is a stub here): the count DESIGN.md section 22 gives
     calls = int(re.search(r"(\d+) runtime calls per repeated call", run.stdout).group(1))

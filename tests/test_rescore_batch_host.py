@@ -13,6 +13,7 @@ from frenetix_motion_planner_amd import _abi, _lib
 from frenetix_motion_planner_amd.engine import effective_cost_names, rescore_weights
 from tests import rescore_planes as rp
 from tests import rescore_rows as rr
+from tests.test_launchers import stubbed_launchers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["distance_to_reference_path", "lateral_jerk", "longitudinal_jerk", "prediction", "velocity_offset"]
@@ -24,9 +25,7 @@ def test_entry_points_are_exported_and_declared():
     for sym in ("fx_rescore_agent_rows", "fx_rescore_batch"):
         assert hasattr(L, sym) and re.search(rf"\b{sym}\s*\(", hdr) and sym in _lib.exported_symbols()
     assert L.fx_abi_version() == _abi.FX_ABI_VERSION == 15      # additive: the version stays
-    stubs = open(os.path.join(rp.CSRC, "fx_host_stubs.cpp")).read()
-    host = open(os.path.join(rp.CSRC, "fx_api_sort.hip")).read()
-    assert "FX_STUB(fx_launch_rescore_batch)" in stubs and re.search(r"__attribute__\(\(weak\)\) hipError_t fx_launch_rescore_batch\(", host)
+    assert "fx_launch_rescore_batch" in stubbed_launchers()   # (and declared once, nowhere weak: tests/test_launchers.py)
 
 
 def test_refusals_that_need_no_device():
@@ -75,11 +74,11 @@ def test_weights_over_the_effective_names():
 
 
 def test_one_statement_of_where_the_term_stands():
-    """the rule lives in fx_resp_term_at; the responsibility pass (fx_api_risk.hip) and the re-score (fx_api_sort.hip) both call it"""
+    """the rule lives in fx_resp_term_at; the responsibility pass (fx_api_risk.hip) and the re-score (fx_api_rescore.hip) both call it"""
     src = {f: open(os.path.join(rp.CSRC, f)).read() for f in os.listdir(rp.CSRC) if f.endswith((".h", ".hip"))}
     stated = [f for f, t in src.items() if re.search(r"cost_id\[m\] > FX_COST_PREDICTION", t)]
     assert stated == ["fx_rescore_batch_plan.h"]
-    for f in ("fx_api_risk.hip", "fx_api_sort.hip"):
+    for f in ("fx_api_risk.hip", "fx_api_rescore.hip"):
         assert "fx_resp_term_at(hp.cost_id, hp.n_cost)" in src[f], f
 
 

@@ -111,6 +111,10 @@ class FxHypothesisOutputs(C.Structure):
                 ("collision", C.c_void_p)]
 
 
+# fx_eval_hypotheses_batch(ctx, n_agents, agents [n_agents] i32 or NULL, n_hyp [n_agents] i32, hyp: the agents' hypotheses one behind
+# the other, out: the agents' answers and blocks one behind the other)
+FX_EVAL_HYPOTHESES_BATCH_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(FxHypothesis), C.POINTER(FxHypothesisOutputs)]
+
 FX_PKG_ROWS = FX_NUM_PLANES + 3
 PKG_ROW_YAW_RATE, PKG_ROW_STEERING, PKG_ROW_ORIENTATION = FX_NUM_PLANES, FX_NUM_PLANES + 1, FX_NUM_PLANES + 2
 

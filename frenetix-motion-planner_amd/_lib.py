@@ -50,7 +50,7 @@ def exported_symbols():
         "fx_eval_risk_batch", "fx_eval_risk_costs_batch",
         "fx_rescore_agent", "fx_last_rescore_ms", "fx_device_costmap_view",
         "fx_rescore_agent_rows", "fx_rescore_batch",
-        "fx_eval_hypotheses_agent", "fx_last_hypotheses_ms", "fx_last_hypotheses_info",
+        "fx_eval_hypotheses_agent", "fx_last_hypotheses_ms", "fx_last_hypotheses_info", "fx_eval_hypotheses_batch",
     ]
 
 
@@ -172,6 +172,7 @@ def lib():
         "fx_rescore_set_regime": ([C.c_int32], None),
         "fx_rescore_regime": ([C.c_int64, C.c_int32], C.c_int32),
         "fx_eval_hypotheses_agent": ([vp, C.c_int32, C.c_int32, C.POINTER(_abi.FxHypothesis), C.POINTER(_abi.FxHypothesisOutputs)], C.c_int32),
+        "fx_eval_hypotheses_batch": (_abi.FX_EVAL_HYPOTHESES_BATCH_ARGS, C.c_int32),
         "fx_last_hypotheses_ms": ([vp], C.c_double),
         "fx_last_hypotheses_info": ([vp, pi32, pi32, pi32], C.c_int32),
         # (hook of the tests and tools/bench_hypotheses.py, not part of fxplan.h: bytes of tables plus scratch per round, 0 = FX_ITEM_SCRATCH_BYTES)

@@ -99,6 +99,7 @@ extern "C" hipError_t fx_launch_package(const DevProblem *d_probs, int n_agents,
 #include "fx_rescore_kernel.h"   // fxrs::fx_rescore_*_kernel
 #include "fx_rescore_batch_kernel.h"   // fxrs::fx_rescore_batch_*_kernel
 #include "fx_hypotheses_kernel.h"   // fxhy::fx_hyp_*_kernel
+#include "fx_hypotheses_batch_kernel.h"   // fxhy::fx_hyp_batch_*_kernel
 
 // Copy a small device buffer (the all-gathered survivors) into pinned host memory and publish a sequence word:
 // the host polls instead of paying for a D2H copy + stream synchronisation.
@@ -652,5 +653,26 @@ extern "C" hipError_t fx_launch_hypotheses(const FxHypArgs *a, size_t lds_bytes,
 #undef FX_LAUNCH
     hipLaunchKernelGGL(fxhy::fx_hyp_finish_kernel, dim3((unsigned)a->n_part, (unsigned)a->n_hyp), dim3(FX_HYP_FINISH_TILE), 0, stream, *a);
     hipLaunchKernelGGL(fxhy::fx_hyp_select_kernel, dim3((unsigned)a->n_hyp), dim3(1024), 0, stream, *a);
+    return hipGetLastError();
+}
+
+// The same for the rows of one ROUND of a call over several agents (fx_hypotheses_batch_kernel.h; rounds:
+// fx_hypotheses_batch_plan.h): items, finish, selection over flat grids -- three launches whatever the number of agents.
+// a->lds_bytes = CH * (largest K of the round's rows) * 48.  The caller records its events around the rounds of a call.
+extern "C" hipError_t fx_launch_hypotheses_batch(const FxHypBatchArgs *a, hipStream_t stream) {
+    if (a->n_rows < 1 || a->items < 1 || a->fin_blocks < 1 || a->pairs < 1 || a->items > FX_HYP_GRID_MAX || a->fin_blocks > FX_HYP_GRID_MAX ||
+        a->pairs > FX_HYP_GRID_MAX)
+        return hipErrorInvalidValue;
+#define FX_LAUNCH(CHv)                                                                                                                  \
+    if (a->CH == CHv) {                                                                                                                 \
+        if (const hipError_t e_ = fx_allow_dynamic_lds<&fxhy::fx_hyp_batch_item_kernel<CHv>>(a->lds_bytes); e_ != hipSuccess) return e_; \
+        hipLaunchKernelGGL(fxhy::fx_hyp_batch_item_kernel<CHv>, dim3((unsigned)a->items), dim3(64), a->lds_bytes, stream, a->rows, a->item0, \
+                           a->n_rows);                                                                                                  \
+    } else
+    FX_LAUNCH(2) FX_LAUNCH(3) FX_LAUNCH(5) return hipErrorInvalidValue;
+#undef FX_LAUNCH
+    hipLaunchKernelGGL(fxhy::fx_hyp_batch_finish_kernel, dim3((unsigned)a->fin_blocks), dim3(FX_HYP_FINISH_TILE), 0, stream, a->rows, a->fin0,
+                       a->n_rows);
+    hipLaunchKernelGGL(fxhy::fx_hyp_batch_select_kernel, dim3((unsigned)a->pairs), dim3(1024), 0, stream, a->rows, a->sel0, a->n_rows);
     return hipGetLastError();
 }

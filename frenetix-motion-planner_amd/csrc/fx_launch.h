@@ -5,6 +5,7 @@
 #pragma once
 
 #include "fx_device.h"
+#include "fx_hypotheses_batch_plan.h"
 #include "fx_hypotheses_plan.h"
 #include "fx_rescore_batch_plan.h"
 #include "fx_rescore_plan.h"
@@ -17,7 +18,8 @@ struct FxItemRound;   // (fx_pass.h: the host's account of a round of a batched 
     X(fx_launch_math_test) X(fx_launch_selftest) X(fx_launch_publish) X(fx_launch_stage) X(fx_launch_probe_read) X(fx_launch_package) \
     X(fx_launch_topk) X(fx_launch_gather_candidates) X(fx_launch_eval_list) X(fx_launch_sort) X(fx_launch_sort_gather)               \
     X(fx_launch_risk) X(fx_launch_predprob) X(fx_launch_predprob_batch) X(fx_launch_risk_batch) X(fx_launch_risk_list_batch)         \
-    X(fx_launch_risk_costs_batch) X(fx_launch_rescore) X(fx_launch_rescore_batch) X(fx_launch_hypotheses)
+    X(fx_launch_risk_costs_batch) X(fx_launch_rescore) X(fx_launch_rescore_batch) X(fx_launch_hypotheses) \
+    X(fx_launch_hypotheses_batch)
 
 extern "C" {
 
@@ -68,6 +70,7 @@ hipError_t fx_launch_risk_costs_batch(const RiskCostBatchArgs *a, const FxItemRo
 hipError_t fx_launch_rescore(const FxRescoreArgs *a, const FxRescorePlan *p, hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream);
 hipError_t fx_launch_rescore_batch(const FxRescoreBatchArgs *a, hipEvent_t ev_start, hipEvent_t ev_stop, hipStream_t stream);
 hipError_t fx_launch_hypotheses(const FxHypArgs *a, size_t lds_bytes, hipStream_t stream);
+hipError_t fx_launch_hypotheses_batch(const FxHypBatchArgs *a, hipStream_t stream);
 
 // The other way round: host code (fx_api_risk.hip) that fx_launch_predprob calls -- the steps per chunk of its items, the rule of
 // fx_pass.h or what a test forces.  No launcher, so not in the list: every host-only build links its definition.

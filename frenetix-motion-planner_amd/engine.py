@@ -1073,6 +1073,71 @@ class FrenetEngine(StepRegistry):
         return dict(winner=winner, cost=cost, n_collisions=n_col, pred=o_pred, totals=o_tot,
                     collisions=None if o_col is None else o_col.astype(bool))
 
+    def hypotheses_batch(self, prediction_sets_per_agent, agents=None, pred: bool = False, totals: bool = False,
+                         collisions: bool = False) -> list:
+        """`hypotheses` for several agents of the context in ONE call (fx_eval_hypotheses_batch): three
+        launches per round and one copy each way whatever the number of agents, every agent's result the bits of its own call.
+        prediction_sets_per_agent: per listed agent what `hypotheses` takes, each agent's sets brought to that agent's K and P by
+        `hypothesis_arrays` exactly as `hypotheses` does it; agents: their indices in any order (None: 0 .. len - 1).  Returns one
+        dict per listed agent as `hypotheses` returns it (winner [H_a], cost [H_a], n_collisions [H_a], pred / totals /
+        collisions [H_a][C_a] or None); the arrays are views of the call's concatenated ones.  It is the device selection only:
+        nothing of the steps is rewritten, and no host walk follows."""
+        from .problem import hypothesis_arrays
+        per_agent = list(prediction_sets_per_agent)
+        n_agents = len(per_agent)
+        agents = list(range(n_agents)) if agents is None else [int(a) for a in agents]
+        if len(agents) != n_agents:
+            raise ValueError(f"{n_agents} lists of prediction sets for {len(agents)} agents")
+        if n_agents == 0:
+            return []
+        per_agent = [list(s) if isinstance(s, (list, tuple)) else [s] for s in per_agent]
+        n_hyp = np.array([len(s) for s in per_agent], np.int32)
+        keep, hyp = [], (_abi.FxHypothesis * max(int(n_hyp.sum()), 1))()
+
+        def arr(a, typ, size, K, P):
+            a = np.ascontiguousarray(a, dtype=typ)
+            if a.size != size:
+                raise ValueError(f"hypothesis array of {a.size} values, the upload's K={K}, P={P} need {size}")
+            keep.append(a)
+            return a.ctypes.data
+
+        at, n_cand = 0, []
+        for a, sets in zip(agents, per_agent):
+            inp = self._inputs[a] if 0 <= a < len(self._inputs) else None
+            K, P = (int(inp.obstacles["K"]), int(inp.obstacles["P"])) if inp is not None else (0, 0)
+            n_cand.append(inp.n_candidates if inp is not None else 0)
+            for s in sets:
+                if K > 0:   # (an upload without obstacles: the library refuses the call, whatever the sets hold)
+                    if int(s["K"]) != K or int(s["P"]) != P or not np.size(s.get("hull", ())):
+                        s = hypothesis_arrays(s, K, P)
+                    y = hyp[at]
+                    y.obs_pos, y.obs_cov_inv = arr(s["pos"], np.float64, 2 * K * P, K, P), arr(s["cov_inv"], np.float64, 4 * K * P, K, P)
+                    y.obs_npred = arr(s["npred"], np.int32, K, K, P)
+                    y.obs_hull, y.obs_nhull = arr(s["hull"], np.float64, 6 * K * (P - 1), K, P), arr(s["nhull"], np.int32, K, K, P)
+                at += 1
+        pairs = max(int(n_hyp.sum()), 1)
+        cells = int(sum(int(h) * n for h, n in zip(n_hyp, n_cand)))
+        winner, cost, n_col = np.empty(pairs, np.int64), np.empty(pairs), np.empty(pairs, np.int64)
+        o_pred = np.empty(cells) if pred else None
+        o_tot = np.empty(cells) if totals else None
+        o_col = np.empty(cells, np.uint8) if collisions else None
+        out = _abi.FxHypothesisOutputs()
+        out.winner, out.cost, out.n_collisions = winner.ctypes.data, cost.ctypes.data, n_col.ctypes.data
+        out.pred = None if o_pred is None else o_pred.ctypes.data
+        out.total = None if o_tot is None else o_tot.ctypes.data
+        out.collision = None if o_col is None else o_col.ctypes.data
+        ids = np.array(agents, np.int32)
+        check(lib().fx_eval_hypotheses_batch(self._ctx, n_agents, ids.ctypes.data_as(C.c_void_p), n_hyp.ctypes.data_as(C.c_void_p), hyp,
+                                             C.byref(out)))
+        res, p0, c0 = [], 0, 0
+        for h, n in zip((int(x) for x in n_hyp), n_cand):
+            block = lambda a: None if a is None else a[c0:c0 + h * n].reshape(h, n)
+            col = block(o_col)
+            res.append(dict(winner=winner[p0:p0 + h], cost=cost[p0:p0 + h], n_collisions=n_col[p0:p0 + h], pred=block(o_pred),
+                            totals=block(o_tot), collisions=None if col is None else col.view(np.bool_)))
+            p0, c0 = p0 + h, c0 + h * n
+        return res
+
     @property
     def last_hypotheses_ms(self) -> float:
         """device time of the last hypotheses call's launches"""

@@ -457,6 +457,37 @@ class AgentBatchHip:
                 out[aid] = [(int(i), float(c)) for i, c in zip(r["winner"], r["cost"])]
         return {aid: out[aid] for aid in weight_sets_by_agent_id}
 
+    def what_if(self, prediction_sets_by_agent_id: dict) -> dict:
+        """ReactivePlannerHip.what_if for several agents of the batch: ONE engine.hypotheses_batch per engine context that holds a
+        listed agent's step.  prediction_sets_by_agent_id: agent id -> the predictions dicts the planner's
+        what_if takes, packed with that planner's own packer as it packs them.  Returns agent id -> [(index, cost, n_collisions)]
+        per predictions dict.  An agent that is not of this batch, or that has no current plan step, is refused by name before any
+        call.  It is the device selection only: the host road-boundary walk and the occlusion walk of plan() are not run, and
+        nothing of the steps or of the planners' own predictions changes."""
+        from .engine import build_obstacle_hulls
+        from .problem import pack_predictions
+        by_id = {a.id: a for a in self.agents}
+        steps = {}
+        for aid in prediction_sets_by_agent_id:
+            a = by_id.get(aid)
+            if a is None:
+                raise ValueError(f"agent {aid} is not of this batch")
+            step = a.planner.last_step
+            if step is None or step._stale:
+                raise ValueError(f"agent {aid} has no current plan step")
+            steps[aid] = (step, a.planner)
+        out, engines = {}, []
+        for step, _ in steps.values():
+            if not any(step.engine is e for e in engines):
+                engines.append(step.engine)
+        for eng in engines:
+            ids = [aid for aid, (step, _) in steps.items() if step.engine is eng]
+            sets = [[pack_predictions(p, steps[aid][1].N + 1, build_obstacle_hulls) for p in prediction_sets_by_agent_id[aid]] for aid in ids]
+            res = eng.hypotheses_batch(sets, agents=[steps[aid][0].agent for aid in ids])
+            for aid, r in zip(ids, res):
+                out[aid] = [(int(i), float(c), int(k)) for i, c, k in zip(r["winner"], r["cost"], r["n_collisions"])]
+        return {aid: out[aid] for aid in prediction_sets_by_agent_id}
+
     def close(self):
         for e in self.engines:
             e.close()

@@ -634,10 +634,27 @@ typedef struct FxHypothesisOutputs {
 } FxHypothesisOutputs;
 int32_t fx_eval_hypotheses_agent(FxContext *ctx, int32_t agent, int32_t n_hyp, const FxHypothesis *hyp /*[n_hyp]*/,
                                  const FxHypothesisOutputs *out);
-/* device time of the context's last hypotheses call (events around its launches), ms; -1 before the first.  Waits for it. */
+/* fx_eval_hypotheses_agent for n_agents agents of the context in one call: three launches per round, one copy
+ * up, one back, whatever the number of agents, and for every listed agent every output bit for bit what fx_eval_hypotheses_agent
+ * returns for that agent with those hypotheses on the same resident step.  agents [n_agents] (NULL: 0 .. n_agents - 1) in any order;
+ * n_hyp [n_agents] hypotheses per listed agent; hyp the agents' [n_hyp[i]] hypotheses one behind the other, each with the K and P of
+ * its agent's upload.  out->winner, cost and n_collisions hold the agents' [n_hyp[i]] answers one behind the other, in call order;
+ * out->pred, total and collision, where not NULL, the agents' [n_hyp[i]][C_i] blocks one behind the other.  Every agent keeps the C,
+ * ld, S, K and P of its own slot; all use the context's steps per item (split_CH), which the per-agent call reads.  A round takes
+ * (agent, hypothesis) pairs in call order while its tables and scratch fit and no launch exceeds 2^31 - 1 workgroups; an agent's
+ * hypotheses may be cut across rounds.  The block is the per-agent call's.
+ * Refused before anything is allocated, copied or launched, naming the agent, the context left usable and fx_last_hypotheses_info
+ * as it was: what fx_eval_hypotheses_agent refuses for it (n_hyp[i] < 1 included), an agent out of range or listed twice, NULL
+ * n_hyp, hyp, out, winner or cost (FX_ERR_INVALID_ARGUMENT), more than FX_HYPOTHESES_MAX hypotheses for one agent or one hypothesis
+ * of one agent whose items exceed 2^31 - 1 workgroups (FX_ERR_CAPACITY).  n_agents == 0 returns FX_OK and touches nothing. */
+int32_t fx_eval_hypotheses_batch(FxContext *ctx, int32_t n_agents, const int32_t *agents /*[n_agents], NULL: 0 .. n_agents-1*/,
+                                 const int32_t *n_hyp /*[n_agents]*/, const FxHypothesis *hyp /*the agents' [n_hyp[i]] one behind the other*/,
+                                 const FxHypothesisOutputs *out);
+/* device time of the context's last hypotheses call of either kind (events around its launches), ms; -1 before the first.  Waits
+ * for it. */
 double fx_last_hypotheses_ms(FxContext *ctx);
-/* the last call's steps per item (CH), rounds of hypotheses and kernel launches; any pointer may be NULL.  FX_ERR_NOT_READY before
- * the first call. */
+/* the last call's (of either kind) steps per item (CH), rounds of hypotheses and kernel launches; any pointer may be NULL.
+ * FX_ERR_NOT_READY before the first call. */
 int32_t fx_last_hypotheses_info(FxContext *ctx, int32_t *steps_per_item, int32_t *rounds, int32_t *launches);
 
 /* ---- road boundary (replaces create_road_boundary_obstacle + trajectories_collision_static_obstacles,

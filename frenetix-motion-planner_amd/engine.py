@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _abi
 from ._lib import check, lib
-from .problem import PlanInputs
+from .problem import PlanInputs, hypothesis_arrays
 from .trajectories import StepRegistry
 
 
@@ -287,6 +287,111 @@ def device_count() -> int:
     return n.value
 
 
+# -- marshalling of FrenetEngine's pass wrappers: every rule once, for the per-agent and the batched entry of a pass (DESIGN.md
+#    section 26); the rules that need the last upload are the private methods at the head of their section of the class --
+_PI32, _PI64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+
+
+def _ptr(a, typ=C.c_void_p):
+    """an array as the library takes it, NULL for None (`typ`: the pointer type of an entry point declared with one)"""
+    return None if a is None else a.ctypes.data_as(typ)
+
+
+def _bind(out, arrays: dict):
+    """the fields of an output structure pointed at the arrays of their names; `out`"""
+    for k, a in arrays.items():
+        setattr(out, k, a.ctypes.data)
+    return out
+
+
+# candidate rows (candidates, materialise)
+def _rows_dict(planes, co, tl, raw, cost, flags, bst) -> dict:
+    """the dict of `FrenetEngine.candidates` over the row buffers of `_read_rows`; a part without a buffer is None"""
+    lon, lat, tau = (None, None, None) if co is None else (co[:, :6], co[:, 6:12], co[:, 12])
+    return dict(planes=planes, lon=lon, lat=lat, tau_lat=tau, traj_len=tl, raw_costs=raw, cost=cost, flags=flags, boundary_step=bst)
+
+
+# hypotheses
+def _pack_hypothesis(dst, s, K: int, P: int, keep: list):
+    """One prediction set `s` into the FxHypothesis `dst` of an upload with K obstacles and P predictions: re-strided by
+    `hypothesis_arrays` unless it has that K and P and hulls, every array held to its size; the arrays go to `keep`."""
+    if K <= 0:   # (an upload without obstacles: the library refuses the call, whatever the sets hold)
+        return
+    if int(s["K"]) != K or int(s["P"]) != P or not np.size(s.get("hull", ())):
+        s = hypothesis_arrays(s, K, P)
+    for field, typ, size in (("pos", np.float64, 2 * K * P), ("cov_inv", np.float64, 4 * K * P), ("npred", np.int32, K),
+                             ("hull", np.float64, 6 * K * (P - 1)), ("nhull", np.int32, K)):
+        a = np.ascontiguousarray(s[field], dtype=typ)
+        if a.size != size:
+            raise ValueError(f"hypothesis array of {a.size} values, the upload's K={K}, P={P} need {size}")
+        keep.append(a)
+        setattr(dst, "obs_" + field, a.ctypes.data)
+
+
+def _hypothesis_outputs(pairs: int, cells_shape, pred: bool, totals: bool, collisions: bool):
+    """(arrays by field name, the FxHypothesisOutputs bound to them) of a hypotheses call: winner, cost, n_collisions [pairs], and of
+    pred, total (f64) and collision (u8), each of `cells_shape`, the ones asked for -- the others None, and NULL to the library"""
+    res = dict(winner=np.empty(pairs, np.int64), cost=np.empty(pairs), n_collisions=np.empty(pairs, np.int64),
+               pred=np.empty(cells_shape) if pred else None, total=np.empty(cells_shape) if totals else None,
+               collision=np.empty(cells_shape, np.uint8) if collisions else None)
+    return res, _bind(_abi.FxHypothesisOutputs(), {k: a for k, a in res.items() if a is not None})
+
+
+# the risk family (risk, risk_detail, risk_costs, responsibility_cost, prediction_probability)
+_RISK_ROWS = ["ego_risk", "obst_risk", "obst_harm_occ"]                                   # [n]
+_RISK_COLS = ["ego_risk_max", "obst_risk_max", "ego_harm_max", "obst_harm_max"]           # [K, n] to the library, [n, K] views back
+_RISK_COST_ROWS = list(_abi.RISK_COST_NAMES) + ["total", "boundary_harm"]                 # [n], with cost parameters only
+_RESP_ROWS = ("resp", "total", "ego_risk", "obst_risk")
+
+
+def _broadcast_params(x, typ, n: int) -> list:
+    """one structure for all listed agents, or one per listed agent: the list"""
+    return [x] * n if isinstance(x, typ) else list(x)
+
+
+def _id_tables(ids, n: int):
+    """The id lists of a batched risk call (None: no agent has one; per agent None, every candidate, or an int array) -> (the lists
+    as int64 arrays, n_ids [n + 1] with a trailing 0 and the table of pointers as the library takes them, both NULL when no agent
+    has a list, what must stay alive behind them).  The caller holds len(lists) to its agent count."""
+    ids = [None] * n if ids is None else [None if x is None else np.ascontiguousarray(x, dtype=np.int64) for x in ids]
+    if all(x is None for x in ids):
+        return ids, (None, None), None
+    n_ids = np.array([0 if x is None else len(x) for x in ids] + [0], dtype=np.int64)
+    backs = [None if x is None else (x if len(x) else np.zeros(1, np.int64)) for x in ids]   # (an empty list is a list: never NULL)
+    idp = (_PI64 * len(ids))(*[C.cast(None, _PI64) if x is None else x.ctypes.data_as(_PI64) for x in backs])
+    return ids, (_ptr(n_ids, _PI64), idp), (n_ids, backs)
+
+
+def _check_responsibility_length(cp, K: int, who: str = ""):
+    lens = getattr(cp, "_lengths", {})
+    if lens.get("responsibility", K) != K:
+        raise ValueError(f"{who}responsibility has {lens['responsibility']} entries for {K} obstacles")
+
+
+def _check_risk_cost_lengths(cp, n: int, K: int, who: str = ""):
+    """the arrays behind the pointers of the cost parameters `cp` (None: none) cover what the library reads: [n] and [K]"""
+    lens = getattr(cp, "_lengths", {})
+    if lens.get("boundary_harm", n) != n:
+        raise ValueError(f"{who}boundary_harm has {lens['boundary_harm']} entries for {n} candidates")
+    _check_responsibility_length(cp, K, who)
+
+
+def _check_responsibility(cp, weight, K: int, who: str = ""):
+    """The refusals of `responsibility_cost`, in this order and before any library call.  The library refuses the last two as well:
+    here they are refused before the probability pass is launched."""
+    _check_responsibility_length(cp, K, who)
+    if not float(weight) or np.isnan(float(weight)):
+        raise ValueError(f"{who}responsibility weight {weight!r}: a non-zero number")
+    if cp.responsibility_mode not in (_abi.FX_RISK_RESP_ACTION_SPACE, _abi.FX_RISK_RESP_REACH_SET):
+        raise ValueError(f"{who}responsibility_mode {cp.responsibility_mode}: the action-space factors or 'reach_set'")
+
+
+def _resp_cost_params(cp, weight, pred):
+    """FxRespCostParams of one agent: pred None or its [n] prediction entries (no row: NULL, the step's own are summed)"""
+    return _abi.FxRespCostParams(float(weight), int(cp.responsibility_mode), cp.responsibility,
+                                 pred.ctypes.data if pred is not None and len(pred) else None)
+
+
 class FrenetEngine(StepRegistry):
     def __init__(self, max_candidates: int, max_steps: int = 30, max_ref_knots: int = 1024, max_obstacles: int = 32,
                  max_pred_steps: int = 64, device: int = 0, max_agents: int = 1):
@@ -296,6 +401,7 @@ class FrenetEngine(StepRegistry):
         self._resident_keys = None
         self.packaging = False
         self.sort_serials = {}   # agent -> sorts of that agent so far (PlanStepResult.ranked_ids: is the agent's device order still mine?)
+        self._risk_K = {}        # agent -> K of its `set_risk_obstacles` (shape of the risk passes' [n, K] columns)
         check(lib().fx_create_batch(C.byref(self._ctx), device, max_agents, int(max_candidates), int(max_steps),
                                     int(max_ref_knots), int(max_obstacles), int(max_pred_steps)))
         self.device = device
@@ -811,6 +917,33 @@ class FrenetEngine(StepRegistry):
         return dict(planes=planes if have_b else None, lon=co[:6].copy(), lat=co[6:12].copy(), tau_lat=float(co[12]), traj_len=tl.value,
                     raw_costs=raw[:len(inp.cost_names)] if have_c else None, cost=cost.value, flags=flags.value)
 
+    # -- the agents a pass beside the step means (the wrappers below) --
+    def _agent_input(self, agent: int):
+        """the agent's inputs of the last upload; None for an agent that is not there (the library refuses the call)"""
+        return self._inputs[agent] if 0 <= agent < len(self._inputs) else None
+
+    def _listed(self, agents, n: Optional[int] = None):
+        """(the listed agents, their int32 array or None for NULL) of a batched call.  agents None: to the risk family every agent of
+        the last upload, in order, and NULL is passed; to a pass with one argument per listed agent (n of them) 0 .. n - 1, passed."""
+        if agents is None and n is None:
+            return list(range(len(self._inputs))), None
+        listed = list(range(n)) if agents is None else [int(a) for a in agents]
+        return listed, np.array(listed, np.int32)
+
+    def _row_counts(self, listed, ids=None):
+        """(rows per listed agent: its id list, else all its candidates; their offsets [n + 1] in the call's concatenated arrays)"""
+        # (an agent the library will refuse counts no rows: the refusal comes before anything is written)
+        counts = [inp.n_candidates if inp is not None else 0 for inp in map(self._agent_input, listed)]
+        if ids is not None:
+            counts = [m if x is None else len(x) for m, x in zip(counts, ids)]
+        return counts, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+    def _info3(self, fn) -> list:
+        """the three int32 a fx_last_*_info entry point writes"""
+        v = [C.c_int32(0) for _ in range(3)]
+        check(fn(self._ctx, *[C.byref(x) for x in v]))
+        return [int(x.value) for x in v]
+
     def candidates(self, ids, agent: int = 0) -> dict:
         """candidate() for a list of indices in ONE call (fx_read_candidates_agent: a gather kernel behind the step, one copy and
         one synchronisation per chunk of _abi.FX_READ_CHUNK_BYTES): planes [n, 14, S], lon / lat [n, 6], tau_lat [n], traj_len [n],
@@ -818,33 +951,32 @@ class FrenetEngine(StepRegistry):
         None for the parts the step did not produce."""
         inp = self._inputs[agent]
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
-        n, n_cost = len(ids), len(inp.cost_names)
         # ascending indices: neighbouring workgroups of the gather then touch neighbouring lines; the rows are permuted back here
         order = None
-        if n > 1 and not bool((ids[1:] >= ids[:-1]).all()):
+        if len(ids) > 1 and not bool((ids[1:] >= ids[:-1]).all()):
             order = np.argsort(ids, kind="stable")
             ids = ids[order]
-        have_b, have_c = bool(inp.write_bundle), bool(inp.write_costmap) and n_cost > 0
-        have_r = inp._bound is not None and inp._bound["n"] > 0
-        planes = np.empty((n, _abi.FX_NUM_PLANES, inp.n_samples)) if have_b else None
-        co = np.empty((n, 13)) if have_b else None
-        tl = np.empty(n, np.int32) if have_b else None
-        raw = np.empty((n, n_cost)) if have_c else None
-        cost, flags = np.empty(n), np.empty(n, np.uint32)
-        bst = np.empty(n, np.int32) if have_r else None
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        check(lib().fx_read_candidates_agent(self._ctx, int(agent), n, ptr(ids), ptr(planes), ptr(co), ptr(tl), ptr(raw), ptr(cost),
-                                             ptr(flags), ptr(bst)))
+        rows = self._read_rows(lib().fx_read_candidates_agent, ids, agent, bool(inp.write_bundle),
+                               bool(inp.write_costmap) and len(inp.cost_names) > 0)
         if order is not None:
-            def back(a):
-                if a is None:
-                    return None
-                out = np.empty_like(a)
-                out[order] = a
-                return out
-            planes, co, tl, raw, cost, flags, bst = (back(a) for a in (planes, co, tl, raw, cost, flags, bst))
-        return dict(planes=planes, lon=co[:, :6] if have_b else None, lat=co[:, 6:12] if have_b else None,
-                    tau_lat=co[:, 12] if have_b else None, traj_len=tl, raw_costs=raw, cost=cost, flags=flags, boundary_step=bst)
+            back = np.argsort(order)   # (row order[i] of the result is row i of what was read)
+            rows = [None if a is None else a[back] for a in rows]
+        return _rows_dict(*rows)
+
+    def _read_rows(self, fn, ids, agent: int, have_b: bool, have_c: bool) -> list:
+        """The rows of `ids` read by `fn` (fx_read_candidates_agent, fx_read_materialised_agent): planes, coefficients [n, 13], traj_len
+        (None, and NULL to the library, without have_b), raw costs (without have_c), cost, flags, boundary steps (unless the step
+        ran the road-boundary stage)."""
+        inp = self._inputs[agent]
+        n, n_cost = len(ids), len(inp.cost_names)
+        have_r = inp._bound is not None and inp._bound["n"] > 0
+        rows = [np.empty((n, _abi.FX_NUM_PLANES, inp.n_samples)) if have_b else None, np.empty((n, 13)) if have_b else None,
+                np.empty(n, np.int32) if have_b else None, np.empty((n, n_cost)) if have_c else None, np.empty(n), np.empty(n, np.uint32),
+                np.empty(n, np.int32) if have_r else None]
+        p = [_ptr(a) for a in rows]
+        p[3] = p[3] if n_cost > 0 else None   # (no cost term: no raw rows, whatever the buffer)
+        check(fn(self._ctx, int(agent), n, _ptr(ids), *p))
+        return rows
 
     def materialise(self, ids, agent: int = 0) -> dict:
         """The dict of `candidates(ids)` with EVERY part filled, whatever the step stored: the listed
@@ -854,27 +986,14 @@ class FrenetEngine(StepRegistry):
         the next materialise of this agent or the next evaluation, upload or state update: `risk`, `risk_detail` and
         `risk_costs` of a step without a bundle accept ids inside it, `materialised_package` packages one of its rows.  Nothing
         the step wrote is touched (costs(), topk(), kept samples stay as they were), so no kept step is rescued here."""
-        inp = self._inputs[agent]
+        self._inputs[agent]   # (an agent that is not there: IndexError, before the library is asked)
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
-        n, n_cost = len(ids), len(inp.cost_names)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        check(lib().fx_materialise_candidates_agent(self._ctx, int(agent), n, ptr(ids)))
+        check(lib().fx_materialise_candidates_agent(self._ctx, int(agent), len(ids), _ptr(ids)))
         return self._read_materialised(ids, agent)
 
     def _read_materialised(self, ids, agent: int) -> dict:
         """the rows of `ids` from the agent's sparse set (fx_read_materialised_agent), every part"""
-        inp = self._inputs[agent]
-        n, n_cost = len(ids), len(inp.cost_names)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        have_r = inp._bound is not None and inp._bound["n"] > 0
-        planes, co, tl = np.empty((n, _abi.FX_NUM_PLANES, inp.n_samples)), np.empty((n, 13)), np.empty(n, np.int32)
-        raw = np.empty((n, n_cost))
-        cost, flags = np.empty(n), np.empty(n, np.uint32)
-        bst = np.empty(n, np.int32) if have_r else None
-        check(lib().fx_read_materialised_agent(self._ctx, int(agent), n, ptr(ids), ptr(planes), ptr(co), ptr(tl),
-                                               ptr(raw) if n_cost > 0 else None, ptr(cost), ptr(flags), ptr(bst)))
-        return dict(planes=planes, lon=co[:, :6], lat=co[:, 6:12], tau_lat=co[:, 12], traj_len=tl, raw_costs=raw, cost=cost, flags=flags,
-                    boundary_step=bst)
+        return _rows_dict(*self._read_rows(lib().fx_read_materialised_agent, ids, agent, True, True))
 
     def materialised_package(self, index: int, yaw_rate: float = 0.0, agent: int = 0):
         """The winner package of `package()` for candidate `index` of the agent's sparse set (fx_read_package_materialised)"""
@@ -897,16 +1016,14 @@ class FrenetEngine(StepRegistry):
         agents[j] (None: agent j); an empty list clears that agent's set.  One wait, one upload and one launch per kernel variant
         present, whatever the agent count; every agent gets the set its own `materialise` would have made.  Returns one
         `materialise` dict per listed agent, read back per agent."""
-        agents = list(range(len(ids))) if agents is None else [int(a) for a in agents]
+        agents, ag = self._listed(agents, len(ids))
         if len(agents) != len(ids):
             raise ValueError(f"{len(ids)} lists for {len(agents)} agents")
         lists = [np.ascontiguousarray(x, dtype=np.int64).reshape(-1) for x in ids]
         n = len(agents)
-        ag = np.asarray(agents, np.int32)
         n_ids = np.asarray([len(x) for x in lists], np.int64)
         addr = np.asarray([x.ctypes.data if len(x) else 0 for x in lists], np.uint64)
-        check(lib().fx_materialise_candidates_batch(self._ctx, n, ag.ctypes.data if n else None, n_ids.ctypes.data if n else None,
-                                                    addr.ctypes.data if n else None))
+        check(lib().fx_materialise_candidates_batch(self._ctx, n, *[_ptr(a) if n else None for a in (ag, n_ids, addr)]))
         return [self._read_materialised(x, a) for x, a in zip(lists, agents)]
 
     @property
@@ -917,9 +1034,7 @@ class FrenetEngine(StepRegistry):
     @property
     def last_materialise_info(self) -> dict:
         """the last materialise call (fx_last_materialise_info): lanes (the widest split among its rows), launches, rows"""
-        v = [C.c_int32(0) for _ in range(3)]
-        check(lib().fx_last_materialise_info(self._ctx, *[C.byref(x) for x in v]))
-        return dict(lanes=int(v[0].value), launches=int(v[1].value), rows=int(v[2].value))
+        return dict(zip(("lanes", "launches", "rows"), self._info3(lib().fx_last_materialise_info)))
 
     # -- stable cost order of all candidates, on the device (DESIGN.md section 15) --
     def sort_candidates(self, agent: int = 0, require: int = _abi.FX_FLAG_COSTED, exclude: int = 0):
@@ -946,12 +1061,12 @@ class FrenetEngine(StepRegistry):
         """Ranks [first, first + n) of the agent's last sort: indices within the shard (what candidates(), materialise() and the
         risk passes take).  with_cost: (ids, cost, flags), the costs and flag words as the step wrote them, bit for bit."""
         n = int(n)
-        room = min(max(n, 0), self._inputs[agent].n_candidates) if 0 <= agent < len(self._inputs) else 0   # (a longer range is refused)
+        inp = self._agent_input(agent)
+        room = min(max(n, 0), inp.n_candidates) if inp is not None else 0   # (a longer range is refused)
         ids = np.empty(room, np.int64)
         cost = np.empty(room) if with_cost else None
         flags = np.empty(room, np.uint32) if with_cost else None
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        check(lib().fx_read_ranked_agent(self._ctx, int(agent), int(first), n, ptr(ids), ptr(cost), ptr(flags)))
+        check(lib().fx_read_ranked_agent(self._ctx, int(agent), int(first), n, _ptr(ids), _ptr(cost), _ptr(flags)))
         return (ids, cost, flags) if with_cost else ids
 
     def sort_view(self, agent: int = 0):
@@ -966,6 +1081,13 @@ class FrenetEngine(StepRegistry):
         return float(lib().fx_last_sort_ms(self._ctx))
 
     # -- the last step re-scored under other cost weights, on the device (DESIGN.md sections 23 and 24) --
+    def _rescore_set(self, weights, agent: int, pred, resp):
+        """(weights [W][n_cost] held to the agent's effective cost list, its candidates, pred and resp row held to them)"""
+        inp = self._agent_input(agent)
+        w = rescore_weights(weights, inp.cost_names if inp is not None else None, resp is not None)
+        n = inp.n_candidates if inp is not None else 0
+        return w, n, _rescore_row(pred, n, "pred"), _rescore_row(resp, n, "resp")
+
     def rescore(self, weights, agent: int = 0, totals: bool = False, pred=None, resp=None) -> dict:
         """The agent's last step under W other weight vectors in one call (fx_rescore_agent): which candidate wins, and at what cost,
         had the step run with each of them.  `weights`: [W][n_cost] in the step's `PlanInputs.cost_names` order, or a sequence of
@@ -976,19 +1098,15 @@ class FrenetEngine(StepRegistry):
         pred [C] / resp [C] (fx_rescore_agent_rows): rows of a pass that ran beside the step -- pred in place
         of the step's prediction row, resp one more term, "responsibility", at its sorted place; the weights then follow
         `effective_cost_names`."""
-        inp = self._inputs[agent] if 0 <= agent < len(self._inputs) else None
-        names = inp.cost_names if inp is not None else None
-        w = rescore_weights(weights, names, resp is not None)
+        w, n, pred, resp = self._rescore_set(weights, agent, pred, resp)
         n_vec = w.shape[0]
-        n = inp.n_candidates if inp is not None else 0
         winner, cost = np.empty(n_vec, np.int64), np.empty(n_vec)
         tot = np.empty((n_vec, n)) if totals else None
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         if pred is None and resp is None:
-            check(lib().fx_rescore_agent(self._ctx, int(agent), n_vec, ptr(w), ptr(winner), ptr(cost), ptr(tot)))
+            check(lib().fx_rescore_agent(self._ctx, int(agent), n_vec, _ptr(w), _ptr(winner), _ptr(cost), _ptr(tot)))
         else:
-            pred, resp = (_rescore_row(r, n, what) for r, what in ((pred, "pred"), (resp, "resp")))
-            check(lib().fx_rescore_agent_rows(self._ctx, int(agent), n_vec, ptr(w), ptr(pred), ptr(resp), ptr(winner), ptr(cost), ptr(tot)))
+            check(lib().fx_rescore_agent_rows(self._ctx, int(agent), n_vec, _ptr(w), _ptr(pred), _ptr(resp), _ptr(winner), _ptr(cost),
+                                              _ptr(tot)))
         return dict(winner=winner, cost=cost, totals=tot)
 
     def rescore_batch(self, weights_per_agent, agents=None, pred=None, resp=None) -> list:
@@ -997,27 +1115,21 @@ class FrenetEngine(StepRegistry):
         listed agent what `rescore` takes; agents: their indices in any order (None: 0 .. len - 1); pred / resp: per listed agent
         a row [C] or None (None: no agent has one).  Returns one dict(winner [W_a], cost [W_a]) per listed agent."""
         n_agents = len(weights_per_agent)
-        agents = list(range(n_agents)) if agents is None else [int(a) for a in agents]
+        agents, ids = self._listed(agents, n_agents)
         pred = [None] * n_agents if pred is None else list(pred)
         resp = [None] * n_agents if resp is None else list(resp)
         if not (len(agents) == len(pred) == len(resp) == n_agents):
             raise ValueError(f"{n_agents} weight sets for {len(agents)} agents, {len(pred)} pred and {len(resp)} resp rows")
         if n_agents == 0:
             return []
-        ws, rows = [], []
-        for i, a in enumerate(agents):
-            inp = self._inputs[a] if 0 <= a < len(self._inputs) else None
-            ws.append(rescore_weights(weights_per_agent[i], inp.cost_names if inp is not None else None, resp[i] is not None))
-            n = inp.n_candidates if inp is not None else 0
-            rows.append(tuple(_rescore_row(r, n, what) for r, what in ((pred[i], "pred"), (resp[i], "resp"))))
-        n_vec = np.array([w.shape[0] for w in ws], np.int32)
-        w = np.ascontiguousarray(np.concatenate([x.ravel() for x in ws]))
-        ids = np.array(agents, np.int32)
+        sets = [self._rescore_set(weights_per_agent[i], a, pred[i], resp[i]) for i, a in enumerate(agents)]
+        n_vec = np.array([s[0].shape[0] for s in sets], np.int32)
+        w = np.ascontiguousarray(np.concatenate([s[0].ravel() for s in sets]))
         total = int(n_vec.sum())
         winner, cost = np.empty(total, np.int64), np.empty(total)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        table = lambda k: None if all(r[k] is None for r in rows) else (C.c_void_p * n_agents)(*[None if r[k] is None else r[k].ctypes.data for r in rows])
-        check(lib().fx_rescore_batch(self._ctx, n_agents, ptr(ids), ptr(n_vec), ptr(w), table(0), table(1), ptr(winner), ptr(cost)))
+        # (a table of the agents' rows, NULL for an agent without one; no agent has one: no table)
+        table = lambda k: None if all(s[k] is None for s in sets) else (C.c_void_p * n_agents)(*[_ptr(s[k]) for s in sets])
+        check(lib().fx_rescore_batch(self._ctx, n_agents, _ptr(ids), _ptr(n_vec), _ptr(w), table(2), table(3), _ptr(winner), _ptr(cost)))
         ends = np.cumsum(n_vec)
         return [dict(winner=winner[e - k:e], cost=cost[e - k:e]) for e, k in zip(ends, n_vec)]
 
@@ -1027,6 +1139,11 @@ class FrenetEngine(StepRegistry):
         return float(lib().fx_last_rescore_ms(self._ctx))
 
     # -- the last step's obstacle stage under other prediction sets, on the device --
+    def _hypothesis_shape(self, agent: int):
+        """(K, P, candidates) of the agent's upload; zeros for an agent that is not there"""
+        inp = self._agent_input(agent)
+        return (int(inp.obstacles["K"]), int(inp.obstacles["P"]), inp.n_candidates) if inp is not None else (0, 0, 0)
+
     def hypotheses(self, prediction_sets, agent: int = 0, pred: bool = False, totals: bool = False, collisions: bool = False) -> dict:
         """The agent's last step under H other prediction sets in one call (fx_eval_hypotheses_agent): what a plan step with each of
         them would have selected, the walk not run again.  `prediction_sets`: a sequence of packed predictions
@@ -1037,41 +1154,17 @@ class FrenetEngine(StepRegistry):
         whose obstacle stage ran as its own kernel the bits are those of a plan step with these predictions; for one that ran
         it inside the walk those of the same step forced to set_obstacle_stage(2, last_hypotheses_info["steps_per_item"]).  It
         is the device selection only: nothing of the step is rewritten, and no host walk follows."""
-        from .problem import hypothesis_arrays
-        inp = self._inputs[agent] if 0 <= agent < len(self._inputs) else None
         sets = list(prediction_sets) if isinstance(prediction_sets, (list, tuple)) else [prediction_sets]
         n_hyp = len(sets)
-        K, P = (int(inp.obstacles["K"]), int(inp.obstacles["P"])) if inp is not None else (0, 0)
+        K, P, n = self._hypothesis_shape(agent)
         keep, hyp = [], (_abi.FxHypothesis * max(n_hyp, 1))()
-
-        def arr(a, typ, size):
-            a = np.ascontiguousarray(a, dtype=typ)
-            if a.size != size:
-                raise ValueError(f"hypothesis array of {a.size} values, the upload's K={K}, P={P} need {size}")
-            keep.append(a)
-            return a.ctypes.data
-
         for h, s in enumerate(sets):
-            if K > 0:   # (an upload without obstacles: the library refuses the call, whatever the sets hold)
-                if int(s["K"]) != K or int(s["P"]) != P or not np.size(s.get("hull", ())):
-                    s = hypothesis_arrays(s, K, P)
-                hyp[h].obs_pos, hyp[h].obs_cov_inv = arr(s["pos"], np.float64, 2 * K * P), arr(s["cov_inv"], np.float64, 4 * K * P)
-                hyp[h].obs_npred = arr(s["npred"], np.int32, K)
-                hyp[h].obs_hull, hyp[h].obs_nhull = arr(s["hull"], np.float64, 6 * K * (P - 1)), arr(s["nhull"], np.int32, K)
-        n = inp.n_candidates if inp is not None else 0
+            _pack_hypothesis(hyp[h], s, K, P, keep)
         H = max(n_hyp, 1)
-        winner, cost, n_col = np.empty(H, np.int64), np.empty(H), np.empty(H, np.int64)
-        o_pred = np.empty((H, n)) if pred else None
-        o_tot = np.empty((H, n)) if totals else None
-        o_col = np.empty((H, n), np.uint8) if collisions else None
-        out = _abi.FxHypothesisOutputs()
-        out.winner, out.cost, out.n_collisions = winner.ctypes.data, cost.ctypes.data, n_col.ctypes.data
-        out.pred = None if o_pred is None else o_pred.ctypes.data
-        out.total = None if o_tot is None else o_tot.ctypes.data
-        out.collision = None if o_col is None else o_col.ctypes.data
+        r, out = _hypothesis_outputs(H, (H, n), pred, totals, collisions)
         check(lib().fx_eval_hypotheses_agent(self._ctx, int(agent), n_hyp, hyp, C.byref(out)))
-        return dict(winner=winner, cost=cost, n_collisions=n_col, pred=o_pred, totals=o_tot,
-                    collisions=None if o_col is None else o_col.astype(bool))
+        return dict(winner=r["winner"], cost=r["cost"], n_collisions=r["n_collisions"], pred=r["pred"], totals=r["total"],
+                    collisions=None if r["collision"] is None else r["collision"].astype(bool))
 
     def hypotheses_batch(self, prediction_sets_per_agent, agents=None, pred: bool = False, totals: bool = False,
                          collisions: bool = False) -> list:
@@ -1082,59 +1175,33 @@ class FrenetEngine(StepRegistry):
         dict per listed agent as `hypotheses` returns it (winner [H_a], cost [H_a], n_collisions [H_a], pred / totals /
         collisions [H_a][C_a] or None); the arrays are views of the call's concatenated ones.  It is the device selection only:
         nothing of the steps is rewritten, and no host walk follows."""
-        from .problem import hypothesis_arrays
         per_agent = list(prediction_sets_per_agent)
         n_agents = len(per_agent)
-        agents = list(range(n_agents)) if agents is None else [int(a) for a in agents]
+        agents, ids = self._listed(agents, n_agents)
         if len(agents) != n_agents:
             raise ValueError(f"{n_agents} lists of prediction sets for {len(agents)} agents")
         if n_agents == 0:
             return []
         per_agent = [list(s) if isinstance(s, (list, tuple)) else [s] for s in per_agent]
         n_hyp = np.array([len(s) for s in per_agent], np.int32)
-        keep, hyp = [], (_abi.FxHypothesis * max(int(n_hyp.sum()), 1))()
-
-        def arr(a, typ, size, K, P):
-            a = np.ascontiguousarray(a, dtype=typ)
-            if a.size != size:
-                raise ValueError(f"hypothesis array of {a.size} values, the upload's K={K}, P={P} need {size}")
-            keep.append(a)
-            return a.ctypes.data
-
+        pairs = int(n_hyp.sum())
+        keep, hyp = [], (_abi.FxHypothesis * max(pairs, 1))()
         at, n_cand = 0, []
         for a, sets in zip(agents, per_agent):
-            inp = self._inputs[a] if 0 <= a < len(self._inputs) else None
-            K, P = (int(inp.obstacles["K"]), int(inp.obstacles["P"])) if inp is not None else (0, 0)
-            n_cand.append(inp.n_candidates if inp is not None else 0)
+            K, P, n = self._hypothesis_shape(a)
+            n_cand.append(n)
             for s in sets:
-                if K > 0:   # (an upload without obstacles: the library refuses the call, whatever the sets hold)
-                    if int(s["K"]) != K or int(s["P"]) != P or not np.size(s.get("hull", ())):
-                        s = hypothesis_arrays(s, K, P)
-                    y = hyp[at]
-                    y.obs_pos, y.obs_cov_inv = arr(s["pos"], np.float64, 2 * K * P, K, P), arr(s["cov_inv"], np.float64, 4 * K * P, K, P)
-                    y.obs_npred = arr(s["npred"], np.int32, K, K, P)
-                    y.obs_hull, y.obs_nhull = arr(s["hull"], np.float64, 6 * K * (P - 1), K, P), arr(s["nhull"], np.int32, K, K, P)
+                _pack_hypothesis(hyp[at], s, K, P, keep)
                 at += 1
-        pairs = max(int(n_hyp.sum()), 1)
         cells = int(sum(int(h) * n for h, n in zip(n_hyp, n_cand)))
-        winner, cost, n_col = np.empty(pairs, np.int64), np.empty(pairs), np.empty(pairs, np.int64)
-        o_pred = np.empty(cells) if pred else None
-        o_tot = np.empty(cells) if totals else None
-        o_col = np.empty(cells, np.uint8) if collisions else None
-        out = _abi.FxHypothesisOutputs()
-        out.winner, out.cost, out.n_collisions = winner.ctypes.data, cost.ctypes.data, n_col.ctypes.data
-        out.pred = None if o_pred is None else o_pred.ctypes.data
-        out.total = None if o_tot is None else o_tot.ctypes.data
-        out.collision = None if o_col is None else o_col.ctypes.data
-        ids = np.array(agents, np.int32)
-        check(lib().fx_eval_hypotheses_batch(self._ctx, n_agents, ids.ctypes.data_as(C.c_void_p), n_hyp.ctypes.data_as(C.c_void_p), hyp,
-                                             C.byref(out)))
+        r, out = _hypothesis_outputs(max(pairs, 1), cells, pred, totals, collisions)
+        check(lib().fx_eval_hypotheses_batch(self._ctx, n_agents, _ptr(ids), _ptr(n_hyp), hyp, C.byref(out)))
         res, p0, c0 = [], 0, 0
         for h, n in zip((int(x) for x in n_hyp), n_cand):
             block = lambda a: None if a is None else a[c0:c0 + h * n].reshape(h, n)
-            col = block(o_col)
-            res.append(dict(winner=winner[p0:p0 + h], cost=cost[p0:p0 + h], n_collisions=n_col[p0:p0 + h], pred=block(o_pred),
-                            totals=block(o_tot), collisions=None if col is None else col.view(np.bool_)))
+            col = block(r["collision"])
+            res.append(dict(winner=r["winner"][p0:p0 + h], cost=r["cost"][p0:p0 + h], n_collisions=r["n_collisions"][p0:p0 + h],
+                            pred=block(r["pred"]), totals=block(r["total"]), collisions=None if col is None else col.view(np.bool_)))
             p0, c0 = p0 + h, c0 + h * n
         return res
 
@@ -1146,9 +1213,7 @@ class FrenetEngine(StepRegistry):
     @property
     def last_hypotheses_info(self) -> dict:
         """steps per item, rounds of hypotheses and kernel launches of the last hypotheses call"""
-        v = [C.c_int32(0) for _ in range(3)]
-        check(lib().fx_last_hypotheses_info(self._ctx, *[C.byref(x) for x in v]))
-        return dict(steps_per_item=v[0].value, rounds=v[1].value, launches=v[2].value)
+        return dict(zip(("steps_per_item", "rounds", "launches"), self._info3(lib().fx_last_hypotheses_info)))
 
     def costmap_view(self, agent: int = 0):
         """(device pointer of the agent's raw cost rows f64 [n_cost][ld], ld, n_cost) of a step that stored them (fx_device_costmap_view)"""
@@ -1173,7 +1238,7 @@ class FrenetEngine(StepRegistry):
         pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         t = {k: np.ascontiguousarray(v) for k, v in tables.items() if isinstance(v, np.ndarray)}
         self._risk_tables = t    # (kept alive for the call; the library copies them)
-        self._risk_K = {**getattr(self, "_risk_K", {}), agent: int(tables["K"])}   # (shape of risk_detail's columns)
+        self._risk_K = {**self._risk_K, agent: int(tables["K"])}   # (shape of risk_detail's columns)
         f = lambda n: t[n].ctypes.data_as(pd)
         i = lambda n: t[n].ctypes.data_as(pi)
         check(lib().fx_set_risk_obstacles_agent(self._ctx, agent, int(tables["K"]), int(tables["P"]), f("pos"), f("cov"), f("cov_inv"),
@@ -1186,7 +1251,7 @@ class FrenetEngine(StepRegistry):
         if ids is None:
             return self._inputs[agent].n_candidates, 0, None, None
         ids = np.ascontiguousarray(ids, dtype=np.int64)
-        return len(ids), len(ids), ids.ctypes.data_as(C.POINTER(C.c_int64)), ids
+        return len(ids), len(ids), _ptr(ids, _PI64), ids
 
     def risk(self, params, ids=None, agent: int = 0):
         """(ego_risk, obst_risk, min_risk_index) of the last plan step's candidates on the device (fx_eval_risk_agent).
@@ -1206,27 +1271,18 @@ class FrenetEngine(StepRegistry):
         the call's concatenated ones.  params: one FxRiskParams for all or one per listed agent; ids: None (no agent has a list) or
         per listed agent None (every candidate) or an int array; agents None: every agent of the last upload, in order; the
         obstacles are each agent's `set_risk_obstacles`."""
-        listed = list(range(len(self._inputs))) if agents is None else [int(a) for a in agents]
+        listed, al = self._listed(agents)
         n = len(listed)
-        params = [params] * n if isinstance(params, _abi.FxRiskParams) else list(params)
-        ids = [None] * n if ids is None else [None if x is None else np.ascontiguousarray(x, dtype=np.int64) for x in ids]
+        params = _broadcast_params(params, _abi.FxRiskParams, n)
+        ids, id_args, _alive = _id_tables(ids, n)
         if len(params) != n or len(ids) != n:
             raise ValueError(f"{len(params)} params and {len(ids)} id lists for {n} agents")
         prm = (_abi.FxRiskParams * max(n, 1))(*params)
-        pi64 = C.POINTER(C.c_int64)
-        n_ids = np.array([0 if x is None else len(x) for x in ids] + [0], dtype=np.int64)
-        backs = [None if x is None else (x if len(x) else np.zeros(1, np.int64)) for x in ids]   # (an empty list is a list: never NULL)
-        idp = (pi64 * max(n, 1))(*[C.cast(None, pi64) if x is None else x.ctypes.data_as(pi64) for x in backs])
-        # (an agent the library will refuse counts no rows: the refusal comes before anything is written)
-        counts = [(self._inputs[a].n_candidates if 0 <= a < len(self._inputs) else 0) if x is None else len(x) for a, x in zip(listed, ids)]
-        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        counts, off = self._row_counts(listed, ids)
         ego, obst = np.zeros(max(int(off[-1]), 1)), np.zeros(max(int(off[-1]), 1))
         idx = np.full(max(n, 1), -1, np.int64)
         out = _abi.FxRiskBatchOutputs(ego.ctypes.data, obst.ctypes.data, idx.ctypes.data)
-        al = np.ascontiguousarray(listed, dtype=np.int32)
-        any_list = any(x is not None for x in ids)
-        check(lib().fx_eval_risk_batch(self._ctx, n, al.ctypes.data_as(C.POINTER(C.c_int32)) if agents is not None else None, prm,
-                                       n_ids.ctypes.data_as(pi64) if any_list else None, idp if any_list else None, C.byref(out)))
+        check(lib().fx_eval_risk_batch(self._ctx, n, _ptr(al, _PI32), prm, *id_args, C.byref(out)))
         return [(ego[off[i]:off[i + 1]], obst[off[i]:off[i + 1]], int(idx[i])) for i in range(n)]
 
     def set_reach_sets(self, tables: dict, agent: int = 0):
@@ -1240,28 +1296,17 @@ class FrenetEngine(StepRegistry):
                                             i("part_step"), i("part_vert_off"), len(verts), verts.ctypes.data_as(pd)))
 
     def _risk_costs(self, params, cost_params, ids, agent):
-        K = getattr(self, "_risk_K", {}).get(agent, 0)
+        K = self._risk_K.get(agent, 0)
         n, n_ids, idp, ids = self._risk_ids(ids, agent)
-        if cost_params is not None:   # the arrays behind the structure's pointers must cover what the library reads
-            lens = getattr(cost_params, "_lengths", {})
-            if lens.get("boundary_harm", n) != n:
-                raise ValueError(f"boundary_harm has {lens['boundary_harm']} entries for {n} candidates")
-            if lens.get("responsibility", K) != K:
-                raise ValueError(f"responsibility has {lens['responsibility']} entries for {K} obstacles")
-        names = ["ego_risk", "obst_risk", "obst_harm_occ"]
-        cols = ["ego_risk_max", "obst_risk_max", "ego_harm_max", "obst_harm_max"]
-        cost_names = list(_abi.RISK_COST_NAMES) + ["total", "boundary_harm"] if cost_params is not None else []
-        res = {k: np.zeros(max(n, 1)) for k in names + cost_names}
-        res.update({k: np.zeros((K, max(n, 1))) for k in cols})
+        _check_risk_cost_lengths(cost_params, n, K)
+        res = {k: np.zeros(max(n, 1)) for k in _RISK_ROWS + (_RISK_COST_ROWS if cost_params is not None else [])}
+        res.update({k: np.zeros((K, max(n, 1))) for k in _RISK_COLS})
         idx = np.full(2, -1, np.int64)
-        out = _abi.FxRiskOutputs()
-        for k, a in res.items():
-            setattr(out, k, a.ctypes.data)
-        out.min_risk_index, out.min_cost_index = idx.ctypes.data, idx.ctypes.data + 8
+        out = _bind(_abi.FxRiskOutputs(), dict(res, min_risk_index=idx[:1], min_cost_index=idx[1:]))
         if n > 0:   # (an empty id list: nothing to evaluate, no arg-min)
             check(lib().fx_eval_risk_costs_agent(self._ctx, agent, C.byref(params), C.byref(cost_params) if cost_params is not None else None,
                                                  n_ids, idp, C.byref(out)))
-        res = {k: (a[:, :n].T if k in cols else a[:n]) for k, a in res.items()}   # [n, K] views of the obstacle-major columns
+        res = {k: (a[:, :n].T if k in _RISK_COLS else a[:n]) for k, a in res.items()}   # [n, K] views of the obstacle-major columns
         res["min_risk_index"] = int(idx[0])
         if cost_params is not None:
             res["min_cost_index"] = int(idx[1])
@@ -1280,51 +1325,32 @@ class FrenetEngine(StepRegistry):
         return self._risk_costs(params, cost_params, ids, agent)
 
     def _risk_costs_batch(self, params, cost_params, ids, agents) -> list:
-        listed = list(range(len(self._inputs))) if agents is None else [int(a) for a in agents]
+        listed, al = self._listed(agents)
         n = len(listed)
-        params = [params] * n if isinstance(params, _abi.FxRiskParams) else list(params)
-        costs = [cost_params] * n if cost_params is None or isinstance(cost_params, _abi.FxRiskCostParams) else list(cost_params)
-        ids = [None] * n if ids is None else [None if x is None else np.ascontiguousarray(x, dtype=np.int64) for x in ids]
+        params = _broadcast_params(params, _abi.FxRiskParams, n)
+        costs = [None] * n if cost_params is None else _broadcast_params(cost_params, _abi.FxRiskCostParams, n)
+        ids, id_args, _alive = _id_tables(ids, n)
         if len(params) != n or len(ids) != n or len(costs) != n:
             raise ValueError(f"{len(params)} params, {len(costs)} cost params and {len(ids)} id lists for {n} agents")
-        # (an agent the library will refuse counts no rows: the refusal comes before anything is written)
-        counts = [(self._inputs[a].n_candidates if 0 <= a < len(self._inputs) else 0) if x is None else len(x) for a, x in zip(listed, ids)]
-        Ks = [getattr(self, "_risk_K", {}).get(a, 0) for a in listed]
-        for a, m, K, cp in zip(listed, counts, Ks, costs):   # the arrays behind the structures' pointers must cover what the library reads
-            lens = getattr(cp, "_lengths", {}) if cp is not None else {}
-            if lens.get("boundary_harm", m) != m:
-                raise ValueError(f"agent {a}: boundary_harm has {lens['boundary_harm']} entries for {m} candidates")
-            if lens.get("responsibility", K) != K:
-                raise ValueError(f"agent {a}: responsibility has {lens['responsibility']} entries for {K} obstacles")
+        counts, off = self._row_counts(listed, ids)
+        Ks = [self._risk_K.get(a, 0) for a in listed]
+        for a, m, K, cp in zip(listed, counts, Ks, costs):
+            _check_risk_cost_lengths(cp, m, K, f"agent {a}: ")
         prm = (_abi.FxRiskParams * max(n, 1))(*params)
-        pi64, pcp = C.POINTER(C.c_int64), C.POINTER(_abi.FxRiskCostParams)
+        pcp = C.POINTER(_abi.FxRiskCostParams)
         cpp = (pcp * max(n, 1))(*[C.cast(None, pcp) if cp is None else C.pointer(cp) for cp in costs])
-        n_ids = np.array([0 if x is None else len(x) for x in ids] + [0], dtype=np.int64)
-        backs = [None if x is None else (x if len(x) else np.zeros(1, np.int64)) for x in ids]   # (an empty list is a list: never NULL)
-        idp = (pi64 * max(n, 1))(*[C.cast(None, pi64) if x is None else x.ctypes.data_as(pi64) for x in backs])
-        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         coff = np.concatenate([[0], np.cumsum([K * m for K, m in zip(Ks, counts)])]).astype(np.int64)
         any_cost = any(cp is not None for cp in costs)
-        names = ["ego_risk", "obst_risk", "obst_harm_occ"]
-        cols = ["ego_risk_max", "obst_risk_max", "ego_harm_max", "obst_harm_max"]
-        cost_names = list(_abi.RISK_COST_NAMES) + ["total", "boundary_harm"]
-        flat = {k: np.zeros(max(int(off[-1]), 1)) for k in names + (cost_names if any_cost else [])}
-        flat.update({k: np.zeros(max(int(coff[-1]), 1)) for k in cols})
+        flat = {k: np.zeros(max(int(off[-1]), 1)) for k in _RISK_ROWS + (_RISK_COST_ROWS if any_cost else [])}
+        flat.update({k: np.zeros(max(int(coff[-1]), 1)) for k in _RISK_COLS})
         idx = np.full((2, max(n, 1)), -1, np.int64)
-        out = _abi.FxRiskCostBatchOutputs()
-        for k, a in flat.items():
-            setattr(out, k, a.ctypes.data)
-        out.min_risk_index, out.min_cost_index = idx[0].ctypes.data, idx[1].ctypes.data
-        al = np.ascontiguousarray(listed, dtype=np.int32)
-        any_list = any(x is not None for x in ids)
-        check(lib().fx_eval_risk_costs_batch(self._ctx, n, al.ctypes.data_as(C.POINTER(C.c_int32)) if agents is not None else None, prm,
-                                             cpp if any_cost else None, n_ids.ctypes.data_as(pi64) if any_list else None,
-                                             idp if any_list else None, C.byref(out)))
+        out = _bind(_abi.FxRiskCostBatchOutputs(), dict(flat, min_risk_index=idx[0], min_cost_index=idx[1]))
+        check(lib().fx_eval_risk_costs_batch(self._ctx, n, _ptr(al, _PI32), prm, cpp if any_cost else None, *id_args, C.byref(out)))
         res = []
         for i in range(n):
             m, K = counts[i], Ks[i]
-            d = {k: flat[k][off[i]:off[i + 1]] for k in names + (cost_names if costs[i] is not None else [])}
-            d.update({k: flat[k][coff[i]:coff[i + 1]].reshape(K, m).T for k in cols})   # [n, K] views of the obstacle-major columns
+            d = {k: flat[k][off[i]:off[i + 1]] for k in _RISK_ROWS + (_RISK_COST_ROWS if costs[i] is not None else [])}
+            d.update({k: flat[k][coff[i]:coff[i + 1]].reshape(K, m).T for k in _RISK_COLS})   # [n, K] views of the obstacle-major columns
             d["min_risk_index"] = int(idx[0, i])
             if costs[i] is not None:
                 d["min_cost_index"] = int(idx[1, i])
@@ -1368,27 +1394,15 @@ class FrenetEngine(StepRegistry):
         Needs write_costmap, and the bundle or ids inside the agent's sparse set.  Nothing the step wrote is touched."""
         if prediction not in ("step", "probability"):
             raise ValueError(f"prediction {prediction!r}: 'step' or 'probability'")
-        K = getattr(self, "_risk_K", {}).get(agent, 0)
-        lens = getattr(cost_params, "_lengths", {})
-        if lens.get("responsibility", K) != K:
-            raise ValueError(f"responsibility has {lens['responsibility']} entries for {K} obstacles")
-        # (the library refuses these two as well: here they are refused before the probability pass below is launched)
-        if not float(weight) or np.isnan(float(weight)):
-            raise ValueError(f"responsibility weight {weight!r}: a non-zero number")
-        if cost_params.responsibility_mode not in (_abi.FX_RISK_RESP_ACTION_SPACE, _abi.FX_RISK_RESP_REACH_SET):
-            raise ValueError(f"responsibility_mode {cost_params.responsibility_mode}: the action-space factors or 'reach_set'")
+        _check_responsibility(cost_params, weight, self._risk_K.get(agent, 0))
         pred = None
         if prediction == "probability":
             pred = np.ascontiguousarray(self.prediction_probability(params.ego_length, params.ego_width, ids=ids, agent=agent)["prob"])
         n, n_ids, idp, ids = self._risk_ids(ids, agent)
-        rp = _abi.FxRespCostParams(float(weight), int(cost_params.responsibility_mode), cost_params.responsibility,
-                                   pred.ctypes.data if pred is not None and len(pred) else None)
-        res = {k: np.zeros(max(n, 1)) for k in ("resp", "total", "ego_risk", "obst_risk")}
+        rp = _resp_cost_params(cost_params, weight, pred)
+        res = {k: np.zeros(max(n, 1)) for k in _RESP_ROWS}
         best_index, best_cost = np.full(1, -1, np.int64), np.full(1, np.nan)
-        out = _abi.FxRespCostOutputs()
-        for k, a in res.items():
-            setattr(out, k, a.ctypes.data)
-        out.best_index, out.best_cost = best_index.ctypes.data, best_cost.ctypes.data
+        out = _bind(_abi.FxRespCostOutputs(), dict(res, best_index=best_index, best_cost=best_cost))
         if n > 0 or ids is None:   # (an empty id list: nothing to evaluate, no arg-min)
             check(lib().fx_eval_responsibility_cost_agent(self._ctx, int(agent), C.byref(params), C.byref(rp), n_ids, idp, C.byref(out)))
         res = {k: a[:n] for k, a in res.items()}
@@ -1404,7 +1418,7 @@ class FrenetEngine(StepRegistry):
         in order; obstacles and reach sets are each agent's `set_risk_obstacles` / `set_reach_sets`.  prediction "probability":
         ONE `prediction_probability_batch` over the same agents first (ego length and width of each params), each agent's prob
         as its prediction entry; a sequence of the two words, one per listed agent: that call over the "probability" ones."""
-        listed = list(range(len(self._inputs))) if agents is None else [int(a) for a in agents]
+        listed, al = self._listed(agents)
         n = len(listed)
         kinds = [prediction] * n if isinstance(prediction, str) else list(prediction)
         if len(kinds) != n or any(k not in ("step", "probability") for k in kinds):
@@ -1413,14 +1427,7 @@ class FrenetEngine(StepRegistry):
         if not (len(params) == len(cost_params) == len(weights) == n):
             raise ValueError(f"{len(params)} params, {len(cost_params)} cost_params and {len(weights)} weights for {n} agents")
         for a, cp, w in zip(listed, cost_params, weights):   # (the refusals of responsibility_cost, before any call)
-            K = getattr(self, "_risk_K", {}).get(a, 0)
-            lens = getattr(cp, "_lengths", {})
-            if lens.get("responsibility", K) != K:
-                raise ValueError(f"agent {a}: responsibility has {lens['responsibility']} entries for {K} obstacles")
-            if not w or np.isnan(w):
-                raise ValueError(f"agent {a}: responsibility weight {w!r}: a non-zero number")
-            if cp.responsibility_mode not in (_abi.FX_RISK_RESP_ACTION_SPACE, _abi.FX_RISK_RESP_REACH_SET):
-                raise ValueError(f"agent {a}: responsibility_mode {cp.responsibility_mode}: the action-space factors or 'reach_set'")
+            _check_responsibility(cp, w, self._risk_K.get(a, 0), f"agent {a}: ")
         preds = [None] * n
         js = [i for i in range(n) if kinds[i] == "probability"]
         if js:
@@ -1429,19 +1436,12 @@ class FrenetEngine(StepRegistry):
             for i, r in zip(js, pp):
                 preds[i] = np.ascontiguousarray(r["prob"])
         prm = (_abi.FxRiskParams * max(n, 1))(*params)
-        rps = (_abi.FxRespCostParams * max(n, 1))(*[
-            _abi.FxRespCostParams(weights[i], int(cost_params[i].responsibility_mode), cost_params[i].responsibility,
-                                  preds[i].ctypes.data if preds[i] is not None and len(preds[i]) else None) for i in range(n)])
-        # (an agent the library will refuse counts no rows: the refusal comes before anything is written)
-        counts = [self._inputs[a].n_candidates if 0 <= a < len(self._inputs) else 0 for a in listed]
-        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        res = {k: np.zeros(max(int(off[-1]), 1)) for k in ("resp", "total", "ego_risk", "obst_risk")}
+        rps = (_abi.FxRespCostParams * max(n, 1))(*[_resp_cost_params(cp, w, p) for cp, w, p in zip(cost_params, weights, preds)])
+        counts, off = self._row_counts(listed)
+        res = {k: np.zeros(max(int(off[-1]), 1)) for k in _RESP_ROWS}
         best_index, best_cost = np.full(max(n, 1), -1, np.int64), np.full(max(n, 1), np.nan)
-        out = _abi.FxRespCostBatchOutputs(*[res[k].ctypes.data for k in ("resp", "total", "ego_risk", "obst_risk")],
-                                          best_index.ctypes.data, best_cost.ctypes.data)
-        ids = np.ascontiguousarray(listed, dtype=np.int32)
-        check(lib().fx_eval_responsibility_cost_batch(self._ctx, n, ids.ctypes.data_as(C.POINTER(C.c_int32)) if agents is not None else None,
-                                                      prm, rps, C.byref(out)))
+        out = _bind(_abi.FxRespCostBatchOutputs(), dict(res, best_index=best_index, best_cost=best_cost))
+        check(lib().fx_eval_responsibility_cost_batch(self._ctx, n, _ptr(al, _PI32), prm, rps, C.byref(out)))
         return [dict({k: a[off[i]:off[i + 1]] for k, a in res.items()}, best_index=int(best_index[i]), best_cost=float(best_cost[i]),
                      prediction=preds[i]) for i in range(n)]
 
@@ -1458,17 +1458,13 @@ class FrenetEngine(StepRegistry):
         bundle or ids inside the agent's sparse set (`materialise`).  Nothing the step wrote is touched."""
         if source not in _abi.PRED_SOURCES:
             raise ValueError(f"source {source!r}: one of {sorted(_abi.PRED_SOURCES)}")
-        K = getattr(self, "_risk_K", {}).get(agent, 0)
         n, n_ids, idp, ids = self._risk_ids(ids, agent)
         params = _abi.FxPredProbParams(float(ego_length), float(ego_width), _abi.PRED_SOURCES[source])
         res = dict(prob=np.zeros(max(n, 1)), total=np.zeros(max(n, 1)))
         if per_obstacle:
-            res["prob_obs"] = np.zeros((K, max(n, 1)))
+            res["prob_obs"] = np.zeros((self._risk_K.get(agent, 0), max(n, 1)))
         best_index, best_cost = np.full(1, -1, np.int64), np.full(1, np.nan)
-        out = _abi.FxPredProbOutputs()
-        for k, a in res.items():
-            setattr(out, k, a.ctypes.data)
-        out.best_index, out.best_cost = best_index.ctypes.data, best_cost.ctypes.data
+        out = _bind(_abi.FxPredProbOutputs(), dict(res, best_index=best_index, best_cost=best_cost))
         if n > 0 or ids is None:   # (an empty id list: nothing to evaluate, no arg-min)
             check(lib().fx_eval_prediction_prob_agent(self._ctx, int(agent), C.byref(params), n_ids, idp, C.byref(out)))
         res = {k: (a[:, :n].T if k == "prob_obs" else a[:n]) for k, a in res.items()}
@@ -1483,20 +1479,16 @@ class FrenetEngine(StepRegistry):
         `set_risk_obstacles`.  The arrays are views of the call's concatenated ones."""
         if source not in _abi.PRED_SOURCES:
             raise ValueError(f"source {source!r}: one of {sorted(_abi.PRED_SOURCES)}")
-        listed = list(range(len(self._inputs))) if agents is None else [int(a) for a in agents]
+        listed, al = self._listed(agents)
         n = len(listed)
         ln, wd = np.broadcast_to(np.asarray(ego_lengths, np.float64), (n,)), np.broadcast_to(np.asarray(ego_widths, np.float64), (n,))
         params = (_abi.FxPredProbParams * max(n, 1))(*[_abi.FxPredProbParams(float(ln[i]), float(wd[i]), _abi.PRED_SOURCES[source])
                                                        for i in range(n)])
-        # (an agent the library will refuse counts no rows: the refusal comes before anything is written)
-        counts = [self._inputs[a].n_candidates if 0 <= a < len(self._inputs) else 0 for a in listed]
-        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        counts, off = self._row_counts(listed)
         prob, total = np.zeros(max(int(off[-1]), 1)), np.zeros(max(int(off[-1]), 1))
         best_index, best_cost = np.full(max(n, 1), -1, np.int64), np.full(max(n, 1), np.nan)
         out = _abi.FxPredProbBatchOutputs(prob.ctypes.data, total.ctypes.data, best_index.ctypes.data, best_cost.ctypes.data)
-        ids = np.ascontiguousarray(listed, dtype=np.int32)
-        check(lib().fx_eval_prediction_prob_batch(self._ctx, n, ids.ctypes.data_as(C.POINTER(C.c_int32)) if agents is not None else None,
-                                                  params, C.byref(out)))
+        check(lib().fx_eval_prediction_prob_batch(self._ctx, n, _ptr(al, _PI32), params, C.byref(out)))
         return [dict(prob=prob[off[i]:off[i + 1]], total=total[off[i]:off[i + 1]], best_index=int(best_index[i]),
                      best_cost=float(best_cost[i])) for i in range(n)]
 
